@@ -22,9 +22,15 @@ over it in this process, and `value` is the faster of the two if the direct one 
 RCCL only, nothing afterwards.
 
 Prints ONE JSON line on rank 0.  `roofline` is computed from HIP events recorded on the
-library's own stream around the sweep kernels; `cpu_baseline` times the CPU oracle's
-restatement of the reference visit (kind "port": the reference is Julia, not runnable
-here) on a bounded sample of the same data.
+library's own stream around the sweep kernels.
+
+A plain run sets up, warms up, times the --steps steps and prints the line; nothing else.  --full adds
+what is measured or checked beside the headline, each outside the timed region: the same steps replayed
+from hipGraphs, the sparse regime, exchange latencies on row shards, `cpu_baseline` (the CPU oracle's
+restatement of the reference visit, kind "port": the reference is Julia, not runnable here, on a bounded
+sample of the same data) with the timed sweep's parity against it, cfg1, the HBM traffic counted by
+rocprofv3 in child runs, and on the default workload the cfg3 path and the reference-shape path.
+--dump-outputs DIR writes what the last timed step left to its caller as DIR/<name>.npy (dump_rows).
 """
 import argparse
 import json
@@ -39,6 +45,30 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_SAMPLE_ROWS = 1 << 20  # residual rows --dump-outputs writes (8 MB in fp64)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_rows(n_total, k=DUMP_SAMPLE_ROWS, seed=20261016):
+    """Rows of the residual that --dump-outputs writes, in global row order: all of them up to k, else a fixed
+    seeded sample of k (the same for every run, build and number of ranks with the same --rows)."""
+    import numpy as np
+    if n_total <= k:
+        return np.arange(n_total, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n_total, size=k, replace=False))
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 or float64, DUMP_LIMIT_BYTES in all at most."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    bad = {k: str(v.dtype) for k, v in arrays.items() if v.dtype not in (np.float32, np.float64)}
+    assert not bad, bad
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def profiled_traffic(kernel, rows, cols, dtype, block):
@@ -399,7 +429,7 @@ def self_launch(argv, gpus):
     return rc if rc != 0 or lines else 1
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -433,10 +463,23 @@ def main():
     ap.add_argument("--no-cfg3", action="store_true", help="skip the cfg3 (100-lambda path, n=2e6, p=5000) timing and the 60-lambda path at the reference's benchmark shape")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not measure roofline.traffic with rocprofv3 --pmc child runs (the committed figure is used)")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what is not the headline (graph replay, sparse regime, exchange latencies, "
+                         "CPU baseline and parity, cfg1, live HBM traffic, cfg3 and reference-shape paths); the --no-* "
+                         "options above switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (beta, its max |h|, a fixed sample of the residual) "
+                         "as DIR/<name>.npy")
+    return ap
+
+
+def main():
+    a = arg_parser().parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
-        sys.exit(self_launch(sys.argv[1:], a.gpus))     # before anything below initialises HIP
+        # (the ranks start in ROOT: a relative --dump-outputs is resolved here; the last occurrence wins)
+        argv = sys.argv[1:] + (["--dump-outputs", os.path.abspath(a.dump_outputs)] if a.dump_outputs else [])
+        sys.exit(self_launch(argv, a.gpus))     # before anything below initialises HIP
 
     import numpy as np
     import coordinatedescent_jl_amd as cd
@@ -549,10 +592,23 @@ def main():
     dt = cp.max_over_ranks(time.perf_counter() - t0)
     ev_ms, launches, alg_bytes = f.profile_end()
     beta_timed, moved = x.dense().copy(), int(x.nnz)
+
+    def outputs(maxh):
+        """What a caller of the timed step holds after the last one: beta, the step's max |h|, and the residual
+        r = y - X beta at the rows of dump_rows, gathered over row shards.  Collective at N > 1."""
+        rows = dump_rows(a.rows)
+        mine = (rows >= row0) & (rows < row0 + n_local)
+        r = np.zeros(len(rows))
+        r[mine] = f.r[rows[mine] - row0]
+        if cp.world > 1:
+            r = np.frombuffer(cp.all_gather_bytes(r.tobytes()), dtype=np.float64).reshape(cp.world, -1).sum(axis=0)
+        return {"beta": x.dense(), "max_h": np.array([maxh], dtype=np.float64), "residual_sample": r.astype(dtype)}
+
+    dumped = outputs(maxh) if a.dump_outputs else None
     # the same K steps once more with every pass replayed from a captured hipGraph (north_star names it; measured
     # neutral on long columns: the stream is GPU-bound, not launch-bound).  Informational, never `value`; one GPU only.
     graph_trial = None
-    if cp.world == 1 and not a.graph:
+    if a.full and cp.world == 1 and not a.graph:
         try:
             f.set_use_graph(True)
             step()                          # the capture
@@ -570,7 +626,7 @@ def main():
     # the record one exchange carries in this sweep mode (4 doubles per coordinate; c, G, q per block)
     rec_doubles = {16: 273, 32: 801, 64: 2625}.get(a.block, 4 * a.block) if a.mode == "block" else 4
     exch_us = {}
-    if cp.world > 1 and exchange != "none(test-only)":
+    if a.full and cp.world > 1 and exchange != "none(test-only)":
         try:
             exch_us[exchange] = f.exchange_latency(rec_doubles, 200)  # back-to-back all-reduces, HIP events
         except Exception as e:                                        # informational: never costs the result line
@@ -586,7 +642,7 @@ def main():
     #                          lambda path / sigma loop; same iterates)
     sparse = None
     # one GPU only: on row shards nothing that is not needed for `value` runs before the result line is out
-    if not a.no_sparse and cp.world == 1:
+    if a.full and not a.no_sparse and cp.world == 1:
         gs = cd.ProxL1(0.5 * lmax)
         nsp = max(2, min(a.steps, 5))
 
@@ -714,7 +770,7 @@ def main():
             except Exception as e:
                 ok_loc, trial["error"] = False, str(e)[:200]
         all_ok = cp.sum_over_ranks(1.0 if ok_loc else 0.0) == cp.world
-        if all_ok:
+        if all_ok and a.full:
             try:
                 exch_us["p2p"] = f.exchange_latency(rec_doubles, 200)
             except Exception as e:
@@ -726,7 +782,10 @@ def main():
                           "ms_per_step": t_max / a.steps * 1e3 if all_ok else None,
                           "max_abs_dbeta_vs_rccl": err_max if all_ok else None})
         t_min = cp.min_over_ranks(t_loc)
-        if adopt_direct_exchange(a.exchange, connected, all_ok, err_max, t_max, dt):
+        adopted = adopt_direct_exchange(a.exchange, connected, all_ok, err_max, t_max, dt)
+        if a.dump_outputs and cp.sum_over_ranks(1.0 if adopted else 0.0) == cp.world:
+            dumped = outputs(maxh_p2p)          # `value` is the direct exchange's region: its last step's outputs
+        if adopted:
             dt_loc_min, dt_loc_max = t_min, t_max
             rccl_line = res
             res = result("p2p", t_max, maxh_p2p, *prof)
@@ -742,8 +801,11 @@ def main():
             f.p2p_enable(False)
         except Exception:
             pass
+    if dumped is not None and cp.rank == 0:
+        write_outputs(a.dump_outputs, dumped)
 
-    if cp.rank == 0 and cp.world == 1 and not a.no_cpu_baseline:
+    # --full: everything below measures or checks what is not the headline
+    if a.full and cp.rank == 0 and cp.world == 1 and not a.no_cpu_baseline:
         try:
             cb = cpu_baseline(f, n_local, g.lambda0)
             res["cpu_baseline"] = cb[1]
@@ -761,13 +823,13 @@ def main():
                 res["cpu_baseline_all_cores"] = mt[0]
         except Exception as e:
             res["cpu_baseline"] = {"error": str(e)[:200]}
-    if cp.rank == 0 and cp.world == 1 and not a.no_cfg1 and not a.no_cpu_baseline:
+    if a.full and cp.rank == 0 and cp.world == 1 and not a.no_cfg1 and not a.no_cpu_baseline:
         try:
             res["cfg1"] = cfg1_cpu_vs_gpu(device)
         except Exception as e:
             res["cfg1"] = {"error": str(e)[:200]}
     f.close()
-    if cp.rank == 0 and cp.world == 1 and not a.no_live_traffic and not a.no_cpu_baseline:
+    if a.full and cp.rank == 0 and cp.world == 1 and not a.no_live_traffic and not a.no_cpu_baseline:
         # the 80 GB are released: the two counter passes (child processes) have the device to themselves
         tail = ["--rows", str(a.rows), "--cols", str(a.cols), "--planted", str(a.planted), "--noise", str(a.noise),
                 "--dtype", a.dtype, "--mode", a.mode, "--block", str(a.block), "--lam-frac", str(a.lam_frac)]
@@ -780,12 +842,12 @@ def main():
         else:
             res["roofline"]["traffic_live_error"] = detail
     default_workload = (a.rows, a.cols, a.dtype) == (10_000_000, 1000, "f64")
-    if cp.rank == 0 and cp.world == 1 and default_workload and not a.no_cfg3 and not a.no_cpu_baseline:
+    if a.full and cp.rank == 0 and cp.world == 1 and default_workload and not a.no_cfg3 and not a.no_cpu_baseline:
         try:                               # the 80 GB of cfg2 are released: cfg3's 80 GB fit
             res["cfg3_path"] = cfg3_path(device)
         except Exception as e:
             res["cfg3_path"] = {"error": str(e)[:200]}
-    if cp.rank == 0 and cp.world == 1 and default_workload and not a.no_cfg3 and not a.no_cpu_baseline:
+    if a.full and cp.rank == 0 and cp.world == 1 and default_workload and not a.no_cfg3 and not a.no_cpu_baseline:
         try:
             res["ref_shape_path"] = ref_shape_path(device)
         except Exception as e:

@@ -18,7 +18,7 @@ def test_bench_options_do_not_collide_with_torchrun_abbreviations():
             "bench.py"]
     for o in opts:
         argv += [o] if o in ("--graph", "--no-cpu-baseline", "--no-sparse", "--no-rccl", "--no-exchange-trial",
-                             "--no-cfg1", "--no-cfg3", "--no-live-traffic") else [o, "1"]
+                             "--no-cfg1", "--no-cfg3", "--no-live-traffic", "--full") else [o, "1"]
     ns = get_args_parser().parse_args(argv)
     assert ns.training_script == "bench.py"
     assert ns.training_script_args == argv[argv.index("bench.py") + 1:]   # every option reached the script
@@ -117,3 +117,36 @@ def test_bench_gpus_n_without_a_launcher_starts_n_ranks_before_touching_the_gpu(
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.stderr.count("no HIP device") >= 2 or r.stderr.count("HipError") >= 2, r.stderr[-2000:]
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """`bench.py --gpus 1 --steps N --warmup W` measures the headline only; --full adds the rest; no dump unless asked."""
+    ap = _bench_module().arg_parser()
+    a = ap.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = ap.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_rows_are_a_fixed_sample_in_global_row_order():
+    bench = _bench_module()
+    np.testing.assert_array_equal(bench.dump_rows(1000), np.arange(1000))
+    rows = bench.dump_rows(10_000_000)
+    assert len(rows) == bench.DUMP_SAMPLE_ROWS and rows.dtype == np.int64
+    assert rows[0] >= 0 and rows[-1] < 10_000_000 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(rows, bench.dump_rows(10_000_000))      # same rows in every run
+    assert 8 * len(rows) + 8 * 1000 + 8 <= bench.DUMP_LIMIT_BYTES           # beta + max_h + fp64 sample fit
+
+
+def test_write_outputs_writes_float_npy_within_the_limit(tmp_path):
+    import pytest
+    bench = _bench_module()
+    d = str(tmp_path / "out")
+    bench.write_outputs(d, {"beta": np.arange(5.0), "r": np.ones(3, dtype=np.float32)})
+    assert sorted(os.listdir(d)) == ["beta.npy", "r.npy"]
+    np.testing.assert_array_equal(np.load(os.path.join(d, "beta.npy")), np.arange(5.0))
+    assert np.load(os.path.join(d, "r.npy")).dtype == np.float32
+    with pytest.raises(AssertionError):
+        bench.write_outputs(d, {"idx": np.arange(3)})
+    with pytest.raises(AssertionError):
+        bench.write_outputs(d, {"big": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})

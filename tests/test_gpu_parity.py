@@ -637,8 +637,9 @@ def test_bench_sharded_with_p2p_exchange_two_ranks_one_gpu():
 
 def test_bench_exchange_trial_code_path_two_ranks_one_gpu():
     """The guarded trial bench.py runs after an RCCL-timed region, exercised without RCCL (--no-rccl:
-    the timed region has no exchange, so only the trial's own fields are meaningful here)."""
-    ja, _ = _bench_two_ranks_one_gpu([])               # --exchange auto is the default
+    the timed region has no exchange, so only the trial's own fields are meaningful here).  The exchange latencies
+    are measured with --full only."""
+    ja, _ = _bench_two_ranks_one_gpu(["--full"])       # --exchange auto is the default
     t = ja["exchange_trial"]
     assert t["probe"]["rc"] == 0 and t["probe"]["line"].startswith("P2P_PROBE_OK") and t["probe"]["latency_us"] > 0
     assert t["selftest"] is True and t["completed_on_all_ranks"] is True and t["ms_per_step"] > 0
