@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kernels.hpp"
@@ -71,6 +72,35 @@ bool load_rccl(std::string& err) {
 constexpr int kNcclDouble = 8;  // ncclFloat64
 constexpr int kNcclSum = 0;
 
+// ---- ownership of the handle's device and pinned host memory -------------------------------------------------------
+// A HipBuf owns one allocation and frees it when it goes.  A failed alloc() leaves it empty and clears the runtime's last error
+// (the status it returns is the report: a later launch check must not see it again); alloc does nothing else (no memset, no
+// synchronisation, no NULL stream).  It reads as the T* it holds.  Moving never frees: a move assignment swaps.
+template <class T, bool kPinned>
+class HipBuf {
+  public:
+    HipBuf() = default;
+    HipBuf(HipBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    HipBuf& operator=(HipBuf&& o) noexcept { std::swap(p_, o.p_); return *this; }
+    ~HipBuf() { if (p_) (void)(kPinned ? hipHostFree(p_) : hipFree(p_)); }
+    // (of an empty owner) flags: hipHostMalloc's (pinned), hipExtMallocWithFlags' (device; 0 is plain hipMalloc)
+    hipError_t alloc(size_t bytes, unsigned flags = 0) {
+        void* q = nullptr;
+        const hipError_t e = kPinned ? hipHostMalloc(&q, bytes, flags)
+                                     : flags ? hipExtMallocWithFlags(&q, bytes, flags) : hipMalloc(&q, bytes);
+        if (e == hipSuccess) p_ = static_cast<T*>(q);
+        else (void)hipGetLastError();
+        return e;
+    }
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
+    template <class U> explicit operator U*() const { return (U*)p_; }
+  private:
+    T* p_ = nullptr;
+};
+template <class T> using DevBuf = HipBuf<T, false>;
+template <class T> using PinBuf = HipBuf<T, true>;
+
 }  // namespace
 
 // Gradient cache of the screened full passes (no reference counterpart; exact).  A visit of a coordinate
@@ -96,39 +126,39 @@ struct GradCache {
     std::vector<uint8_t> in_moved;
     std::vector<int32_t> slot;      // coordinate -> Gram column, -1 = not cached
     std::vector<std::vector<double>> G;
-    double* d_cross = nullptr;      // device: ceil(p / 64) records of 64 x 32 cross products
-    double* d_cross_part = nullptr; // device: the same per row-slab block (cross_J of them per column group)
+    DevBuf<double> d_cross;         // device: ceil(p / 64) records of 64 x 32 cross products
+    DevBuf<double> d_cross_part;    // device: the same per row-slab block (cross_J of them per column group)
     int cross_J = 1, cross_GX = 1;
-    int64_t* d_cols = nullptr;      // device: the B columns of a batch
+    DevBuf<int64_t> d_cols;         // device: the B columns of a batch
     std::vector<double> h_cross;
     // covariance-form visits: device mirrors of g, the Gram columns (slot-major, p doubles each) and the slot map
     bool cov = true;                // env CDH_GC_COV
-    double *d_g = nullptr, *d_G = nullptr, *h_g_pin = nullptr;
-    int32_t* d_slot = nullptr;
+    DevBuf<double> d_g, d_G;
+    PinBuf<double> h_g_pin; DevBuf<int32_t> d_slot;
     // whole full passes on the device (gc_pass_device): g lives in d_g between passes and comes back only when host
     // code asks for it.  g_host_ok / g_dev_ok say which copies are current (at least one always is while `valid`).
     bool g_host_ok = true, g_dev_ok = false;
-    double *d_a = nullptr, *d_g_snap = nullptr, *d_beta_snap = nullptr, *d_qs = nullptr;
-    int64_t* d_pass_idx = nullptr;        // the pass's visit list (0-based), as uploaded last
+    DevBuf<double> d_a, d_g_snap, d_beta_snap, d_qs;
+    DevBuf<int64_t> d_pass_idx;           // the pass's visit list (0-based), as uploaded last
     std::vector<int64_t> pass_idx_host;   // ... and what it holds
-    int32_t *d_pos_of = nullptr, *d_upos = nullptr;
-    uint8_t *d_setflag = nullptr, *d_forced = nullptr;   // (d_forced: the second half of d_setflag's allocation)
+    DevBuf<int32_t> d_pos_of; int32_t* d_upos = nullptr;
+    DevBuf<uint8_t> d_setflag; uint8_t* d_forced = nullptr;   // (d_forced: the second half of d_setflag's allocation)
     bool forced_dirty = false;
     int64_t n_forced_rounds = 0, n_cs_forced_rounds = 0, n_cs_crew_passes = 0, n_cs_crew_jobs = 0;
     // the scan's counters sit at the head of the buffer of unsettled positions (one copy brings both back); the results of
     // a pass come back through k_cov_pack's block
-    int32_t *d_scanbuf = nullptr, *h_scanbuf = nullptr;   // [CovScanOut: 4 int32][positions: cap]; h_: pinned
+    DevBuf<int32_t> d_scanbuf; PinBuf<int32_t> h_scanbuf;   // [CovScanOut: 4 int32][positions: cap]
     cdk::CovScanOut* d_scan = nullptr;    // = d_scanbuf
     cdk::CovScanOut* h_scan = nullptr;    // = h_scanbuf
     int32_t* h_upos = nullptr;            // = h_scanbuf + 4
-    double *d_pack = nullptr, *h_pack = nullptr;          // kPackHead + 2.5 cap doubles; h_: pinned
+    DevBuf<double> d_pack; PinBuf<double> h_pack;           // kPackHead + 2.5 cap doubles
     bool a_dev_ok = false;                // d_a mirrors c.a
     double yy = 0.0;                      // y'y over all shards (fp32 certificate margin), valid while yy_ok
     bool yy_ok = false;
     int64_t n_dev_passes = 0;
     int inject_rollback = 0, inject_count = 0;   // env CDH_GC_INJECT_ROLLBACK (tests)
     int64_t dev_slots_cap = 0, dev_slots = 0;   // columns the device store can hold / holds
-    std::vector<double*> d_G_retired;           // stores outgrown on the way (freed with the handle)
+    std::vector<DevBuf<double>> d_G_retired;    // stores outgrown on the way (freed with the handle)
     int64_t cov_since_ref = 0;      // covariance-form visits since g was last taken from X itself
     int64_t refresh_after = 0;      // ... after which it is (kGcCovRefresh; env CDH_GC_REFRESH for tests)
     std::vector<double> g_new;      // g as a covariance-form chunk left it, until the chunk is accepted
@@ -147,7 +177,7 @@ struct GradCache {
     int cs_helpers = 31;             // helper workgroups a launch that expects large visit lists brings (env CDH_CS_CREW; 0: none, table mode only)
     bool cs_shuffle_ok = true, cs_stalled = false;
     size_t cs_lds_budget = 0;
-    char *cs_dev = nullptr, *cs_pin = nullptr, *cs_pin_dev = nullptr;
+    DevBuf<char> cs_dev; PinBuf<char> cs_pin; char* cs_pin_dev = nullptr;
     CovSolveBufs cs_bufs{};
     CovSolveCtl* cs_ctl = nullptr;
     int32_t *cs_in_sup = nullptr, *cs_out_sup_idx = nullptr, *cs_out_moved_idx = nullptr, *cs_out_list = nullptr;
@@ -192,10 +222,10 @@ struct SmallPath {
     int64_t max_bytes = -1;          // env CDH_SMALL_MAX_BYTES: a fixed limit on n p sz instead of rent-or-buy (experiments)
     int64_t always_bytes = (int64_t)kSmallAlwaysBytes;   // env CDH_SMALL_ALWAYS_BYTES (tests: 0 makes every handle rent first)
     double rent_paid = 0.0;          // modelled seconds of streamed solves on the current X while G was not built (SmallRent)
-    int64_t* d_iota = nullptr;       // 0 .. p-1: the column lists of the Gram build
+    DevBuf<int64_t> d_iota;          // 0 .. p-1: the column lists of the Gram build
     bool G_valid = false;
-    double* d_G = nullptr;           // p x p
-    char *d_io = nullptr, *h_io = nullptr;    // [SmallCtl][support][beta]: what crosses the bus per solve, one block each way
+    DevBuf<double> d_G;              // p x p
+    DevBuf<char> d_io; PinBuf<char> h_io;     // [SmallCtl][support][beta]: what crosses the bus per solve, one block each way
     char* hd_io = nullptr;           // h_io as the device addresses it
     bool zero_copy = true;           // env CDH_SMALL_ZEROCOPY (default 1): the kernel works on h_io itself, nothing is copied
     SmallCtl *d_ctl = nullptr, *h_ctl = nullptr;   // views into d_io / h_io (pinned)
@@ -203,7 +233,7 @@ struct SmallPath {
     double *d_beta = nullptr, *h_beta = nullptr;
     int64_t n_solves = 0, n_gram = 0, n_precision = 0;
     bool c_valid = false;            // d_ca / h_c / yy hold X'y (X'Wy), diag(G) and y'y of the current y
-    double* d_ca = nullptr;          // interleaved (c_k, a_k), then y'y at [2p]
+    DevBuf<double> d_ca;             // interleaved (c_k, a_k), then y'y at [2p]
     std::vector<double> h_c;         // host copy of c (lambda_max of a cold start needs no device work)
     double yy = 0.0;
     int ncache = 0;                  // Gram columns the solve kernel can keep in LDS
@@ -216,20 +246,20 @@ struct cdh_handle_s {
     size_t esz = 8;
     hipStream_t stream = nullptr;
     // device
-    void *X = nullptr, *y = nullptr, *r = nullptr, *w = nullptr;
-    double *beta = nullptr, *omega = nullptr;
-    Ctrl* d_ctrl = nullptr;
-    int64_t* d_idx = nullptr;
-    double *d_hs = nullptr, *d_newval = nullptr;
-    int32_t* d_touched = nullptr;
-    double *d_partials = nullptr, *d_red = nullptr, *d_colout = nullptr;
-    int64_t* d_sup_idx = nullptr;
-    double* d_sup_val = nullptr;
+    DevBuf<void> X, y, r, w;
+    DevBuf<double> beta, omega;
+    DevBuf<Ctrl> d_ctrl;
+    DevBuf<int64_t> d_idx;
+    DevBuf<double> d_hs, d_newval;
+    DevBuf<int32_t> d_touched;
+    DevBuf<double> d_partials, d_red, d_colout;
+    DevBuf<int64_t> d_sup_idx;
+    DevBuf<double> d_sup_val;
     // pinned host staging
-    int64_t* h_idx = nullptr;
-    double *h_hs = nullptr, *h_newval = nullptr, *h_red = nullptr;
-    int32_t* h_touched = nullptr;
-    Ctrl* h_ctrl = nullptr;
+    PinBuf<int64_t> h_idx;
+    PinBuf<double> h_hs, h_newval, h_red;
+    PinBuf<int32_t> h_touched;
+    PinBuf<Ctrl> h_ctrl;
     // state
     int64_t cap = 0;          // visits per chunk
     size_t partials_doubles = 0;
@@ -281,21 +311,21 @@ struct cdh_handle_s {
     void* comm = nullptr;
     int rank = 0, nranks = 1;
     // optional direct exchange of the short records (p2p_exchange.hpp); off unless connected and enabled
-    unsigned long long* p2p_inbox = nullptr;
+    DevBuf<unsigned long long> p2p_inbox;
     cdk::P2PPeers p2p_peers{};
     std::vector<void*> p2p_mapped;
-    int* p2p_timeout = nullptr;  // pinned host flag written by a kernel whose bounded spin ran out
+    PinBuf<int> p2p_timeout;     // pinned host flag written by a kernel whose bounded spin ran out
     unsigned p2p_epoch = 0, p2p_spin_limit = cdk::kP2PSpinLimit;
     int p2p_ranks = 0;
     bool p2p_on = false, p2p_dead = false;
     bool lost_exchange = false;       // a multi-rank shard whose host transport was taken away: allreduce() refuses
-    unsigned* d_p2p_base = nullptr;   // epoch base of a replayed graph's exchanges (device memory)
+    DevBuf<unsigned> d_p2p_base;      // epoch base of a replayed graph's exchanges (device memory)
     bool capturing = false;           // run_chunk is recording a graph: exchanges take base + offset epochs
     unsigned cap_exchanges = 0, cap_rccl = 0;   // exchanges recorded in the graph being captured
     // bring-your-own transport (cdh_set_host_exchange): staged through pinned host memory
     cdh_host_allreduce_fn host_fn = nullptr;
     void* host_user = nullptr;
-    double* h_xchg = nullptr;
+    PinBuf<double> h_xchg;
     size_t h_xchg_doubles = 0;
     int64_t n_rccl_calls = 0, n_p2p_calls = 0, n_host_calls = 0;
     // profile
@@ -1146,42 +1176,12 @@ void free_all(cdh_handle h) {
     (void)hipSetDevice(h->device);
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
     for (void* m : h->p2p_mapped) (void)hipIpcCloseMemHandle(m);
-    if (h->p2p_inbox) (void)hipFree(h->p2p_inbox);
-    if (h->d_p2p_base) (void)hipFree(h->d_p2p_base);
-    if (h->gc.d_cross) (void)hipFree(h->gc.d_cross);
-    if (h->gc.d_cols) (void)hipFree(h->gc.d_cols);
-    if (h->gc.d_cross_part) (void)hipFree(h->gc.d_cross_part);
-    if (h->gc.d_g) (void)hipFree(h->gc.d_g);
-    if (h->gc.d_G) (void)hipFree(h->gc.d_G);
-    for (double* q : h->gc.d_G_retired) (void)hipFree(q);
-    if (h->gc.d_slot) (void)hipFree(h->gc.d_slot);
-    if (h->gc.h_g_pin) (void)hipHostFree(h->gc.h_g_pin);
-    if (h->small.d_G) (void)hipFree(h->small.d_G);
-    if (h->small.d_iota) (void)hipFree(h->small.d_iota);
-    if (h->small.d_io) (void)hipFree(h->small.d_io);
-    if (h->small.d_ca) (void)hipFree(h->small.d_ca);
-    if (h->small.h_io) (void)hipHostFree(h->small.h_io);
-    {
-        GradCache& c = h->gc;
-        void* dv[] = {c.d_a, c.d_g_snap, c.d_beta_snap, c.d_qs, c.d_pass_idx, c.d_pos_of, c.d_scanbuf, c.d_setflag, c.d_pack};
-        for (void* q : dv) if (q) (void)hipFree(q);
-        if (c.h_scanbuf) (void)hipHostFree(c.h_scanbuf);
-        if (c.h_pack) (void)hipHostFree(c.h_pack);
-        if (c.cs_dev) (void)hipFree(c.cs_dev);
-        if (c.cs_pin) (void)hipHostFree(c.cs_pin);
-    }
-    if (h->h_xchg) (void)hipHostFree(h->h_xchg);
-    if (h->p2p_timeout) (void)hipHostFree(h->p2p_timeout);
     for (auto& e : h->graphs) (void)hipGraphExecDestroy(e.exec);
-    void* dev[] = {h->X, h->y, h->r, h->w, h->beta, h->omega, h->d_ctrl, h->d_idx, h->d_hs, h->d_newval,
-                   h->d_touched, h->d_partials, h->d_red, h->d_colout, h->d_sup_idx, h->d_sup_val};
-    for (void* p : dev) if (p) (void)hipFree(p);
-    void* pin[] = {h->h_idx, h->h_hs, h->h_newval, h->h_red, h->h_touched, h->h_ctrl};
-    for (void* p : pin) if (p) (void)hipHostFree(p);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    const hipEvent_t ev[] = {h->ev0, h->ev1};
+    const hipStream_t stream = h->stream;
+    delete h;   // the owners free the device and pinned memory, before the stream goes
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 }  // namespace
@@ -1266,40 +1266,40 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
         h->lt_per_cu = std::max(0, std::min(4, env_int("CDH_LT_PER_CU", 0)));
         h->gram_units = wantg;
         const size_t colbytes = (size_t)h->ld * h->esz;
-        HIPCHK(h, hipMalloc(&h->X, colbytes * (size_t)p));
-        HIPCHK(h, hipMalloc(&h->y, colbytes));
-        HIPCHK(h, hipMalloc(&h->r, colbytes));
+        HIPCHK(h, h->X.alloc(colbytes * (size_t)p));
+        HIPCHK(h, h->y.alloc(colbytes));
+        HIPCHK(h, h->r.alloc(colbytes));
         HIPCHK(h, hipMemsetAsync(h->y, 0, colbytes, h->stream));
         HIPCHK(h, hipMemsetAsync(h->r, 0, colbytes, h->stream));
         if (loss == CDH_WLS) {
-            HIPCHK(h, hipMalloc(&h->w, colbytes));
+            HIPCHK(h, h->w.alloc(colbytes));
             HIPCHK(h, hipMemsetAsync(h->w, 0, colbytes, h->stream));
         }
-        HIPCHK(h, hipMalloc(&h->beta, sizeof(double) * p));
+        HIPCHK(h, h->beta.alloc(sizeof(double) * p));
         HIPCHK(h, hipMemsetAsync(h->beta, 0, sizeof(double) * p, h->stream));
-        HIPCHK(h, hipMalloc(&h->omega, sizeof(double) * p));
-        HIPCHK(h, hipMalloc(&h->d_ctrl, sizeof(Ctrl)));
-        HIPCHK(h, hipMalloc(&h->d_idx, sizeof(int64_t) * h->cap));
-        HIPCHK(h, hipMalloc(&h->d_hs, sizeof(double) * h->cap));
-        HIPCHK(h, hipMalloc(&h->d_newval, sizeof(double) * h->cap));
-        HIPCHK(h, hipMalloc(&h->d_touched, sizeof(int32_t) * h->cap));
+        HIPCHK(h, h->omega.alloc(sizeof(double) * p));
+        HIPCHK(h, h->d_ctrl.alloc(sizeof(Ctrl)));
+        HIPCHK(h, h->d_idx.alloc(sizeof(int64_t) * h->cap));
+        HIPCHK(h, h->d_hs.alloc(sizeof(double) * h->cap));
+        HIPCHK(h, h->d_newval.alloc(sizeof(double) * h->cap));
+        HIPCHK(h, h->d_touched.alloc(sizeof(int32_t) * h->cap));
         h->partials_doubles = std::max<size_t>({(size_t)kMaxStepGrid * kNSum,
                                                 (size_t)cus * kBlockGridPerCU * BlockRec<kMaxBlockB>::N,
                                                 (size_t)4096 * kColChunks * 2,
                                                 (size_t)cus * 2 * GramRec<4>::N,
                                                 (size_t)cus * std::max(h->gram32_per_cu, 4) * GramRec<2>::N,
                                                 (size_t)cus * 4 * GramRec<1>::N});
-        HIPCHK(h, hipMalloc(&h->d_partials, sizeof(double) * h->partials_doubles));
-        HIPCHK(h, hipMalloc(&h->d_red, sizeof(double) * 4096));
-        HIPCHK(h, hipMalloc(&h->d_colout, sizeof(double) * 2 * p));
-        HIPCHK(h, hipMalloc(&h->d_sup_idx, sizeof(int64_t) * p));
-        HIPCHK(h, hipMalloc(&h->d_sup_val, sizeof(double) * p));
-        HIPCHK(h, hipHostMalloc(&h->h_idx, sizeof(int64_t) * h->cap));
-        HIPCHK(h, hipHostMalloc(&h->h_hs, sizeof(double) * h->cap));
-        HIPCHK(h, hipHostMalloc(&h->h_newval, sizeof(double) * h->cap));
-        HIPCHK(h, hipHostMalloc(&h->h_touched, sizeof(int32_t) * h->cap));
-        HIPCHK(h, hipHostMalloc(&h->h_red, sizeof(double) * 64));
-        HIPCHK(h, hipHostMalloc(&h->h_ctrl, sizeof(Ctrl)));
+        HIPCHK(h, h->d_partials.alloc(sizeof(double) * h->partials_doubles));
+        HIPCHK(h, h->d_red.alloc(sizeof(double) * 4096));
+        HIPCHK(h, h->d_colout.alloc(sizeof(double) * 2 * p));
+        HIPCHK(h, h->d_sup_idx.alloc(sizeof(int64_t) * p));
+        HIPCHK(h, h->d_sup_val.alloc(sizeof(double) * p));
+        HIPCHK(h, h->h_idx.alloc(sizeof(int64_t) * h->cap));
+        HIPCHK(h, h->h_hs.alloc(sizeof(double) * h->cap));
+        HIPCHK(h, h->h_newval.alloc(sizeof(double) * h->cap));
+        HIPCHK(h, h->h_touched.alloc(sizeof(int32_t) * h->cap));
+        HIPCHK(h, h->h_red.alloc(sizeof(double) * 64));
+        HIPCHK(h, h->h_ctrl.alloc(sizeof(Ctrl)));
         // zero the pad rows of X once (uploads / the generator only write rows < n)
         if (h->ld > h->n) HIPCHK(h, hipMemsetAsync(h->X, 0, colbytes * (size_t)p, h->stream));
         h->ctrl.lambda0 = 0.0; h->ctrl.n_total = (double)n_total; h->ctrl.maxH = 0.0;
@@ -1391,8 +1391,10 @@ int32_t cdh_get_y(cdh_handle h, void* host_y) {
 static int32_t ensure_weights_buffer(cdh_handle h) {
     if (h->w) return CDH_OK;
     const size_t colbytes = (size_t)h->ld * h->esz;
-    HIPCHK(h, hipMalloc(&h->w, colbytes));
-    HIPCHK(h, hipMemsetAsync(h->w, 0, colbytes, h->stream));
+    DevBuf<void> w;
+    HIPCHK(h, w.alloc(colbytes));
+    HIPCHK(h, hipMemsetAsync(w, 0, colbytes, h->stream));
+    h->w = std::move(w);
     return CDH_OK;
 }
 
@@ -2079,19 +2081,17 @@ int32_t cdh_p2p_local_handle(cdh_handle h, void* out_64_bytes) {
     static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size is part of the ABI");
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->p2p_inbox) {
+        DevBuf<unsigned long long> inbox; DevBuf<unsigned> base; PinBuf<int> timeout;
         // polled by this GPU while peers write it: must not be served from a stale L2 line
-        void* q = nullptr;
-        if (hipExtMallocWithFlags(&q, kP2PInboxBytes, hipDeviceMallocUncached) != hipSuccess) {
-            (void)hipGetLastError();
-            HIPCHK(h, hipExtMallocWithFlags(&q, kP2PInboxBytes, hipDeviceMallocFinegrained));
-        }
-        h->p2p_inbox = (unsigned long long*)q;
-        HIPCHK(h, hipMemset(h->p2p_inbox, 0, kP2PInboxBytes));  // tag 0 = never written; epochs start at 1
-        HIPCHK(h, hipMalloc((void**)&h->d_p2p_base, sizeof(unsigned)));
-        HIPCHK(h, hipMemset(h->d_p2p_base, 0, sizeof(unsigned)));
-        HIPCHK(h, hipHostMalloc((void**)&h->p2p_timeout, sizeof(int), hipHostMallocDefault));
-        *h->p2p_timeout = 0;
+        if (inbox.alloc(kP2PInboxBytes, hipDeviceMallocUncached) != hipSuccess)
+            HIPCHK(h, inbox.alloc(kP2PInboxBytes, hipDeviceMallocFinegrained));
+        HIPCHK(h, hipMemset(inbox, 0, kP2PInboxBytes));  // tag 0 = never written; epochs start at 1
+        HIPCHK(h, base.alloc(sizeof(unsigned)));
+        HIPCHK(h, hipMemset(base, 0, sizeof(unsigned)));
+        HIPCHK(h, timeout.alloc(sizeof(int)));
+        *timeout = 0;
         HIPCHK(h, hipDeviceSynchronize());
+        h->p2p_inbox = std::move(inbox); h->d_p2p_base = std::move(base); h->p2p_timeout = std::move(timeout);
     }
     hipIpcMemHandle_t ipc;
     HIPCHK(h, hipIpcGetMemHandle(&ipc, h->p2p_inbox));
@@ -2146,8 +2146,9 @@ int32_t cdh_set_host_exchange(cdh_handle h, cdh_host_allreduce_fn fn, void* user
     if (h->comm || h->p2p_ranks) return fail(h, CDH_BAD_ARG, "the handle already has an exchange (RCCL / direct)");
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->h_xchg) {   // the longest record is the 2p column dots of _findLambdaMax / _stdX!
-        h->h_xchg_doubles = (size_t)std::max<int64_t>(4096, 2 * h->p);
-        HIPCHK(h, hipHostMalloc((void**)&h->h_xchg, sizeof(double) * h->h_xchg_doubles));
+        const size_t doubles = (size_t)std::max<int64_t>(4096, 2 * h->p);
+        HIPCHK(h, h->h_xchg.alloc(sizeof(double) * doubles));
+        h->h_xchg_doubles = doubles;
     }
     h->host_fn = fn; h->host_user = user; h->rank = rank; h->nranks = nranks;
     h->lost_exchange = false;

@@ -1252,20 +1252,15 @@ int32_t cs_alloc(cdh_handle h) {
                              cs_align(8 * tc * tc) + 2 * cs_align(8 * tc) + cs_align(4 * tc) + 3 * cs_align(4 * p) /* the Gram table */ +
                              cs_align(sizeof(CsCrew)) + cs_align(8 * p) /* the crew: jobs, g's snapshot */;
     const size_t pin_bytes = cs_align(sizeof(CovSolveCtl)) + 4 * cs_align(4 * p) + 2 * cs_align(8 * p);
+    DevBuf<char> dev; PinBuf<char> pin;
     void* dev_view = nullptr;
-    bool fits = hipMalloc((void**)&c.cs_dev, dev_bytes) == hipSuccess && hipHostMalloc((void**)&c.cs_pin, pin_bytes) == hipSuccess &&
-                hipHostGetDevicePointer(&dev_view, c.cs_pin, 0) == hipSuccess;
-    if (!fits) (void)hipGetLastError();
+    bool fits = dev.alloc(dev_bytes) == hipSuccess && pin.alloc(pin_bytes) == hipSuccess &&
+                hipHostGetDevicePointer(&dev_view, pin, 0) == hipSuccess;
+    if (!fits) (void)hipGetLastError();   // (a refused device view: a failed alloc has cleared its own)
     CHK(all_ranks_agree(h, fits, &fits));
-    if (!fits) {
-        if (c.cs_dev) (void)hipFree(c.cs_dev);
-        if (c.cs_pin) (void)hipHostFree(c.cs_pin);
-        c.cs_dev = nullptr; c.cs_pin = nullptr; c.cs_enabled = false;
-        return CDH_OK;
-    }
-    c.cs_pin_dev = static_cast<char*>(dev_view);
-    CovSolveBufs& b = c.cs_bufs;
-    char* d = c.cs_dev;
+    if (!fits) { c.cs_enabled = false; return CDH_OK; }
+    CovSolveBufs b = c.cs_bufs;
+    char* d = dev;
     auto take = [&](size_t bytes) { char* q = d; d += cs_align(bytes); return q; };
     b.p = h->p;
     b.gx = (double*)take(8 * p); b.bfold = (double*)take(8 * p); b.bsnap = (double*)take(8 * p); b.hs = (double*)take(8 * p);
@@ -1276,27 +1271,28 @@ int32_t cs_alloc(cdh_handle h) {
     b.vb = (int32_t*)take(4 * p); b.moved = (int32_t*)take(4 * p); b.holes = (int32_t*)take(4 * p); b.fills = (int32_t*)take(4 * p);
     b.gxp = (int32_t*)take(4 * p); b.upos = (int32_t*)take(4 * p); b.aidx = (int32_t*)take(4 * p); b.occ = (int32_t*)take(4 * p);
     b.setflag = (uint8_t*)take(p); b.inmoved = (uint8_t*)take(p); b.forced = (uint8_t*)take(p);
-    // (on the handle's own stream: the first operation on the NULL stream of a process creates its queue -- 10 ms measured)
-    HIPCHK(h, hipMemsetAsync(b.forced, 0, p, h->stream));
-    c.d_colmax = (double*)take(8 * p);
-    b.colmax = c.d_colmax;
+    double* const colmax = (double*)take(8 * p); b.colmax = colmax;
     b.Gc = (double*)take(8 * tc * tc); b.gxc = (double*)take(8 * tc); b.cidk = (int64_t*)take(8 * tc); b.gxe = (int32_t*)take(4 * tc);
     b.cidof = (int32_t*)take(4 * p); b.ucid = (int32_t*)take(4 * p); b.newc = (int32_t*)take(4 * p);
-    c.cs_ncid = 0; c.cs_table_reset = true;
     b.crew = (CsCrew*)take(sizeof(CsCrew)); b.g_snap = (double*)take(8 * p);
-    // the pinned block, as the host and as the device address it
+    char* const pin_dev = static_cast<char*>(dev_view);   // the pinned block as the device addresses it
     size_t o = cs_align(sizeof(CovSolveCtl));
-    auto pin = [&](size_t bytes) { const size_t at = o; o += cs_align(bytes); return at; };
-    const size_t o_in = pin(4 * p), o_si = pin(4 * p), o_mi = pin(4 * p), o_li = pin(4 * p), o_sv = pin(8 * p), o_mv = pin(8 * p);
-    c.cs_ctl = reinterpret_cast<CovSolveCtl*>(c.cs_pin);
+    auto at = [&](size_t bytes) { const size_t q = o; o += cs_align(bytes); return q; };
+    const size_t o_in = at(4 * p), o_si = at(4 * p), o_mi = at(4 * p), o_li = at(4 * p), o_sv = at(8 * p), o_mv = at(8 * p);
+    b.in_sup = reinterpret_cast<const int32_t*>(pin_dev + o_in);
+    b.out_sup_idx = reinterpret_cast<int32_t*>(pin_dev + o_si); b.out_moved_idx = reinterpret_cast<int32_t*>(pin_dev + o_mi);
+    b.out_list = reinterpret_cast<int32_t*>(pin_dev + o_li);
+    b.out_sup_val = reinterpret_cast<double*>(pin_dev + o_sv); b.out_moved_val = reinterpret_cast<double*>(pin_dev + o_mv);
+    // (on the handle's own stream: the first operation on the NULL stream of a process creates its queue -- 10 ms measured)
+    HIPCHK(h, hipMemsetAsync(b.forced, 0, p, h->stream));
+    c.cs_dev = std::move(dev); c.cs_pin = std::move(pin); c.cs_pin_dev = pin_dev;   // all there: the handle takes the group
+    c.cs_bufs = b; c.d_colmax = colmax;
+    c.cs_ncid = 0; c.cs_table_reset = true;
+    c.cs_ctl = (CovSolveCtl*)c.cs_pin;
     c.cs_in_sup = reinterpret_cast<int32_t*>(c.cs_pin + o_in);
     c.cs_out_sup_idx = reinterpret_cast<int32_t*>(c.cs_pin + o_si); c.cs_out_moved_idx = reinterpret_cast<int32_t*>(c.cs_pin + o_mi);
     c.cs_out_list = reinterpret_cast<int32_t*>(c.cs_pin + o_li);
     c.cs_out_sup_val = reinterpret_cast<double*>(c.cs_pin + o_sv); c.cs_out_moved_val = reinterpret_cast<double*>(c.cs_pin + o_mv);
-    b.in_sup = reinterpret_cast<const int32_t*>(c.cs_pin_dev + o_in);
-    b.out_sup_idx = reinterpret_cast<int32_t*>(c.cs_pin_dev + o_si); b.out_moved_idx = reinterpret_cast<int32_t*>(c.cs_pin_dev + o_mi);
-    b.out_list = reinterpret_cast<int32_t*>(c.cs_pin_dev + o_li);
-    b.out_sup_val = reinterpret_cast<double*>(c.cs_pin_dev + o_sv); b.out_moved_val = reinterpret_cast<double*>(c.cs_pin_dev + o_mv);
     c.cs_old.assign(p, 0.0);
     c.colmax_slots = 0;
     // dynamic LDS: the tracked coordinates' Gram block and, for shuffled sweeps, the shuffle's two p-sized arrays

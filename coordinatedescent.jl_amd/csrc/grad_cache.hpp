@@ -30,13 +30,6 @@ int32_t all_ranks_agree(cdh_handle h, bool mine, bool* all) {
 int32_t gc_size(cdh_handle h) {   // first use on this handle
     GradCache& c = h->gc;
     if (!c.g.empty()) return CDH_OK;
-    const size_t p = (size_t)h->p;
-    c.g.assign(p, 0.0); c.a.assign(p, 0.0); c.dbeta.assign(p, 0.0);
-    c.in_moved.assign(p, 0); c.slot.assign(p, -1);
-    c.beta_ref.assign(p, 0.0);
-    c.beta_ok = h->r_consistent;          // r == y - X * (the handle's iterate) right now?
-    if (c.beta_ok)
-        for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) c.beta_ref[(size_t)h->x.coord(s_)] = h->x.slot_value(s_);
     // one k_cross launch per batch: a block per (group of 64 columns, j of J), about two resident blocks per CU
     const int64_t launches = (h->p + kCrossA - 1) / kCrossA;      // column groups
     const int64_t nslabs = (h->nvec + kCrossSlab - 1) / kCrossSlab;
@@ -51,22 +44,21 @@ int32_t gc_size(cdh_handle h) {   // first use on this handle
     // column super-groups instead (benchmark/cd_bench.jl's shape: 8 blocks walked 79 column groups, 0.78 ms per batch of a
     // 120 MB X; 40 blocks: one group per wave)
     if (!gxe) c.cross_GX = (int)std::min<int64_t>(nsuper, std::max<int64_t>(c.cross_GX, (occ * h->cus) / c.cross_J));
-    // (a handle whose first sizing failed may be asked again: what a failed attempt got was freed below)
-    bool fits = hipMalloc((void**)&c.d_cross, sizeof(double) * (size_t)launches * kCrossRec) == hipSuccess &&
-                hipMalloc((void**)&c.d_cross_part, sizeof(double) * (size_t)launches * (size_t)c.cross_J * kCrossRec) == hipSuccess &&
-                hipMalloc((void**)&c.d_cols, sizeof(int64_t) * kCrossB) == hipSuccess;
-    if (!fits) (void)hipGetLastError();
+    // (a handle whose first sizing failed may be asked again: a failed attempt leaves nothing behind)
+    DevBuf<double> cross, cross_part; DevBuf<int64_t> cols;
+    bool fits = cross.alloc(sizeof(double) * (size_t)launches * kCrossRec) == hipSuccess &&
+                cross_part.alloc(sizeof(double) * (size_t)launches * (size_t)c.cross_J * kCrossRec) == hipSuccess &&
+                cols.alloc(sizeof(int64_t) * kCrossB) == hipSuccess;
     CHK(all_ranks_agree(h, fits, &fits));
-    if (!fits) {                      // no room for the cache's scratch (on some rank): the dots-only screens stay
-        if (c.d_cross) (void)hipFree(c.d_cross);
-        if (c.d_cross_part) (void)hipFree(c.d_cross_part);
-        if (c.d_cols) (void)hipFree(c.d_cols);
-        c.d_cross = nullptr; c.d_cross_part = nullptr; c.d_cols = nullptr;
-        c.mode = 0;
-        c.g.clear(); c.g.shrink_to_fit();
-        return CDH_OK;
-    }
+    if (!fits) { c.mode = 0; return CDH_OK; }   // no room for the cache's scratch (on some rank): the dots-only screens stay
+    c.d_cross = std::move(cross); c.d_cross_part = std::move(cross_part); c.d_cols = std::move(cols);
     c.h_cross.assign((size_t)launches * kCrossRec, 0.0);
+    const size_t p = (size_t)h->p;
+    c.g.assign(p, 0.0); c.a.assign(p, 0.0); c.dbeta.assign(p, 0.0);
+    c.in_moved.assign(p, 0); c.slot.assign(p, -1); c.beta_ref.assign(p, 0.0);
+    c.beta_ok = h->r_consistent;          // r == y - X * (the handle's iterate) right now?
+    if (c.beta_ok)
+        for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) c.beta_ref[(size_t)h->x.coord(s_)] = h->x.slot_value(s_);
     return CDH_OK;
 }
 
@@ -81,53 +73,57 @@ int32_t gc_dev_reserve(cdh_handle h, int64_t have) {
     const int64_t p = h->p;
     // no room on the device for the mirrors (on any rank) is not an error: the visits stay in residual form
     if (!c.d_g) {
-        bool fits = hipMalloc((void**)&c.d_g, sizeof(double) * (size_t)p) == hipSuccess &&
-                    hipMalloc((void**)&c.d_slot, sizeof(int32_t) * (size_t)p) == hipSuccess &&
+        DevBuf<double> g, a, g_snap, beta_snap, qs, pack; DevBuf<int32_t> slot, pos_of, scanbuf; DevBuf<int64_t> pass_idx;
+        DevBuf<uint8_t> setflag; PinBuf<double> g_pin, h_pack; PinBuf<int32_t> h_scanbuf;
+        bool fits = g.alloc(sizeof(double) * (size_t)p) == hipSuccess &&
+                    slot.alloc(sizeof(int32_t) * (size_t)p) == hipSuccess &&
                     // pinned staging for g on its way down and back (pageable copies are staged by the
                     // runtime, one hidden synchronisation each: two per chunk of visits)
-                    hipHostMalloc((void**)&c.h_g_pin, sizeof(double) * 2 * (size_t)p) == hipSuccess;
+                    g_pin.alloc(sizeof(double) * 2 * (size_t)p) == hipSuccess;
         // ... and what a whole full pass on the device needs (gc_pass_device): a, the snapshots, the per-coordinate
         // position / settled flag, the compacted visit list, the per-visit r'r, the scan's counters
-        fits = fits && hipMalloc((void**)&c.d_a, sizeof(double) * (size_t)p) == hipSuccess &&
-               hipMalloc((void**)&c.d_g_snap, sizeof(double) * (size_t)p) == hipSuccess &&
-               hipMalloc((void**)&c.d_beta_snap, sizeof(double) * (size_t)p) == hipSuccess &&
-               hipMalloc((void**)&c.d_qs, sizeof(double) * (size_t)h->cap) == hipSuccess &&
-               hipMalloc((void**)&c.d_pass_idx, sizeof(int64_t) * (size_t)h->cap) == hipSuccess &&
-               hipMalloc((void**)&c.d_pos_of, sizeof(int32_t) * (size_t)p) == hipSuccess &&
-               hipMalloc((void**)&c.d_scanbuf, sizeof(int32_t) * (size_t)(h->cap + 4)) == hipSuccess &&
-               hipMalloc((void**)&c.d_setflag, 2 * (size_t)p) == hipSuccess &&       // [settled flags][forced marks]
-               hipMalloc((void**)&c.d_pack, sizeof(double) * (size_t)(kPackHead + 3 * h->cap)) == hipSuccess &&
-               hipHostMalloc((void**)&c.h_scanbuf, sizeof(int32_t) * (size_t)(h->cap + 4)) == hipSuccess &&
-               hipHostMalloc((void**)&c.h_pack, sizeof(double) * (size_t)(kPackHead + 3 * h->cap)) == hipSuccess;
-        if (!fits) (void)hipGetLastError();
+        fits = fits && a.alloc(sizeof(double) * (size_t)p) == hipSuccess &&
+               g_snap.alloc(sizeof(double) * (size_t)p) == hipSuccess &&
+               beta_snap.alloc(sizeof(double) * (size_t)p) == hipSuccess &&
+               qs.alloc(sizeof(double) * (size_t)h->cap) == hipSuccess &&
+               pass_idx.alloc(sizeof(int64_t) * (size_t)h->cap) == hipSuccess &&
+               pos_of.alloc(sizeof(int32_t) * (size_t)p) == hipSuccess &&
+               scanbuf.alloc(sizeof(int32_t) * (size_t)(h->cap + 4)) == hipSuccess &&
+               setflag.alloc(2 * (size_t)p) == hipSuccess &&       // [settled flags][forced marks]
+               pack.alloc(sizeof(double) * (size_t)(kPackHead + 3 * h->cap)) == hipSuccess &&
+               h_scanbuf.alloc(sizeof(int32_t) * (size_t)(h->cap + 4)) == hipSuccess &&
+               h_pack.alloc(sizeof(double) * (size_t)(kPackHead + 3 * h->cap)) == hipSuccess;
         CHK(all_ranks_agree(h, fits, &fits));
         if (!fits) { c.cov = false; return CDH_OK; }
-        c.d_scan = reinterpret_cast<cdk::CovScanOut*>(c.d_scanbuf); c.d_upos = c.d_scanbuf + 4;
-        c.h_scan = reinterpret_cast<cdk::CovScanOut*>(c.h_scanbuf); c.h_upos = c.h_scanbuf + 4;
-        HIPCHK(h, hipMemsetAsync(c.d_qs, 0, sizeof(double) * (size_t)h->cap, h->stream));
-        HIPCHK(h, hipMemsetAsync(c.d_setflag, 0, 2 * (size_t)p, h->stream));
+        HIPCHK(h, hipMemsetAsync(qs, 0, sizeof(double) * (size_t)h->cap, h->stream));
+        HIPCHK(h, hipMemsetAsync(setflag, 0, 2 * (size_t)p, h->stream));
+        c.d_g = std::move(g); c.d_slot = std::move(slot); c.h_g_pin = std::move(g_pin); c.d_a = std::move(a);
+        c.d_g_snap = std::move(g_snap); c.d_beta_snap = std::move(beta_snap); c.d_qs = std::move(qs);
+        c.d_pass_idx = std::move(pass_idx); c.d_pos_of = std::move(pos_of); c.d_scanbuf = std::move(scanbuf);
+        c.d_setflag = std::move(setflag); c.d_pack = std::move(pack); c.h_scanbuf = std::move(h_scanbuf); c.h_pack = std::move(h_pack);
+        c.d_scan = (cdk::CovScanOut*)c.d_scanbuf; c.d_upos = c.d_scanbuf + 4;
+        c.h_scan = (cdk::CovScanOut*)c.h_scanbuf; c.h_upos = c.h_scanbuf + 4;
         c.d_forced = c.d_setflag + p; c.forced_dirty = false;
         c.g_dev_ok = false; c.a_dev_ok = false;
     }
     if (have > c.dev_slots_cap) {   // grow the store (at least 64 columns more, doubling once it holds 128: a path that ends at 800 columns
-                                    // reallocates 5 times, not 14 -- each is a hipMalloc, a copy and a hipFree, milliseconds apiece on a
+                                    // reallocates 5 times, not 14 -- each is an allocation, a copy and a free, milliseconds apiece on a
                                     // fresh handle; at most kGcMaxBytes), keeping what is there
         const int64_t most = (int64_t)(kGcMaxBytes / sizeof(double)) / std::max<int64_t>(p, 1);
         const int64_t cap = std::min<int64_t>(std::max<int64_t>((have + 63) / 64 * 64 + 64, c.dev_slots_cap >= 128 ? 2 * c.dev_slots_cap : 0), most);
         if (cap < have) { c.cov = false; return CDH_OK; }   // does not fit (the same on every rank): residual form
-        double* bigger = nullptr;
-        bool fits = hipMalloc((void**)&bigger, sizeof(double) * (size_t)cap * (size_t)p) == hipSuccess;
-        if (!fits) (void)hipGetLastError();
+        DevBuf<double> bigger;
+        bool fits = bigger.alloc(sizeof(double) * (size_t)cap * (size_t)p) == hipSuccess;
         CHK(all_ranks_agree(h, fits, &fits));
-        if (!fits) { if (bigger) (void)hipFree(bigger); c.cov = false; return CDH_OK; }
+        if (!fits) { c.cov = false; return CDH_OK; }
         if (c.d_G && c.dev_slots > 0)
             HIPCHK(h, hipMemcpyAsync(bigger, c.d_G, sizeof(double) * (size_t)c.dev_slots * (size_t)p, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        // (the store it replaces is released with the handle: hipFree synchronises the device and, after large allocations have gone,
+        // (the store it replaces is released with the handle: a device free synchronises the device and, after large allocations have gone,
         // can take tens of milliseconds -- seen as one 66 ms solve in the first path of a process that had freed 80 GB; the stores a
         // handle outgrows add up to less than the one it ends with)
-        if (c.d_G) c.d_G_retired.push_back(c.d_G);
-        c.d_G = bigger; c.dev_slots_cap = cap;
+        if (c.d_G) c.d_G_retired.push_back(std::move(c.d_G));
+        c.d_G = std::move(bigger); c.dev_slots_cap = cap;
     }
     return CDH_OK;
 }

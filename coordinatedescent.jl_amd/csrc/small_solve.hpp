@@ -511,13 +511,15 @@ int32_t small_prepare(cdh_handle h) {     // buffers, X'y and diag(G) of the cur
     if (!sp.d_io) {
         CHK(gc_size(h));                  // k_cross's scratch (d_cross, d_cross_part, d_cols) is the gradient cache's
         if (!c.d_cross) { sp.enabled = false; return CDH_OK; }
-        bool fits = hipMalloc((void**)&sp.d_G, sizeof(double) * (size_t)h->p * (size_t)h->p) == hipSuccess &&
-                    hipMalloc((void**)&sp.d_ca, sizeof(double) * (2 * (size_t)h->p + 1)) == hipSuccess &&
+        DevBuf<double> G, ca; DevBuf<char> d_io; PinBuf<char> h_io;
+        bool fits = G.alloc(sizeof(double) * (size_t)h->p * (size_t)h->p) == hipSuccess &&
+                    ca.alloc(sizeof(double) * (2 * (size_t)h->p + 1)) == hipSuccess &&
                     // one block for everything that crosses the bus per solve: [SmallCtl][support: p int32][beta: p doubles]
-                    hipMalloc((void**)&sp.d_io, small_io_bytes(h->p)) == hipSuccess &&
-                    hipHostMalloc((void**)&sp.h_io, small_io_bytes(h->p)) == hipSuccess;
-        if (!fits) { (void)hipGetLastError(); sp.enabled = false; return CDH_OK; }
-        sp.d_ctl = reinterpret_cast<SmallCtl*>(sp.d_io); sp.h_ctl = reinterpret_cast<SmallCtl*>(sp.h_io);
+                    d_io.alloc(small_io_bytes(h->p)) == hipSuccess &&
+                    h_io.alloc(small_io_bytes(h->p)) == hipSuccess;
+        if (!fits) { sp.enabled = false; return CDH_OK; }
+        sp.d_G = std::move(G); sp.d_ca = std::move(ca); sp.d_io = std::move(d_io); sp.h_io = std::move(h_io);
+        sp.d_ctl = (SmallCtl*)sp.d_io; sp.h_ctl = (SmallCtl*)sp.h_io;
         void* dev_view = nullptr;          // the pinned block as the device addresses it (zero-copy solves)
         if (hipHostGetDevicePointer(&dev_view, sp.h_io, 0) == hipSuccess) sp.hd_io = static_cast<char*>(dev_view);
         else (void)hipGetLastError();
@@ -555,9 +557,11 @@ int32_t small_prepare(cdh_handle h) {     // buffers, X'y and diag(G) of the cur
     if (!sp.d_iota) {                 // the column lists of all batches, uploaded once: the batches then run back to back
         std::vector<int64_t> iota((size_t)h->p);
         for (int64_t k = 0; k < h->p; ++k) iota[(size_t)k] = k;
-        if (hipMalloc((void**)&sp.d_iota, sizeof(int64_t) * (size_t)h->p) != hipSuccess) { (void)hipGetLastError(); sp.enabled = false; return CDH_OK; }
-        HIPCHK(h, hipMemcpyAsync(sp.d_iota, iota.data(), sizeof(int64_t) * (size_t)h->p, hipMemcpyHostToDevice, h->stream));
+        DevBuf<int64_t> d_iota;
+        if (d_iota.alloc(sizeof(int64_t) * (size_t)h->p) != hipSuccess) { sp.enabled = false; return CDH_OK; }
+        HIPCHK(h, hipMemcpyAsync(d_iota, iota.data(), sizeof(int64_t) * (size_t)h->p, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
+        sp.d_iota = std::move(d_iota);
     }
     for (int64_t b0 = 0; b0 < h->p; b0 += kCrossB) {
         const int nbc = (int)std::min<int64_t>(kCrossB, h->p - b0);

@@ -1342,20 +1342,34 @@ def test_covariance_chunks_roll_back_when_a_skipped_certificate_breaks(loss):
     assert rollbacks > 0
 
 
-def test_handles_with_every_optional_buffer_are_created_and_destroyed_repeatedly():
+def _device_memory():
+    """(free, total) bytes of device 0, as the HIP runtime libcdhip.so uses reports them (hipMemGetInfo)."""
+    import ctypes as C
+    free, total = C.c_size_t(), C.c_size_t()
+    assert cd._lib.lib().hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+    return free.value, total.value
+
+
+def test_handles_with_every_optional_buffer_are_created_and_destroyed_repeatedly(monkeypatch):
     """Graph replay + gradient cache (Gram columns, device mirrors, pinned staging) + observation weights +
-    a host exchange on the same process, 40 handles in a row: destruction releases everything (a leak or a
-    double free shows up as a HIP error or a crash long before 40), and the 40th solve equals the first."""
+    a host exchange + the direct exchange's inbox + the one-launch solve + the device pass loop with its table and
+    helpers on the same process, 40 rounds of handles in a row: destruction releases everything (a double free
+    shows up as a HIP error or a crash long before 40, a leak as device memory that does not come back after the
+    second round), and the 40th solve equals the first."""
     rng, X, Y = _problem(81, 2000, 300, 8)
     w = rng.uniform(0.5, 2.0, size=2000)
     o = cd.CDOptions(maxIter=2000, optTol=1e-11, randomize=False)
-    first = None
+    _, Xc, Yc = _problem(82, 3000, 400, 10)
+    lams_c = np.exp(np.linspace(np.log(0.3), np.log(0.03), 8))
+    first = first_s = first_c = None
+    free = []
     for it in range(40):
         f = cd.CDLeastSquaresLoss(Y, X)
         f.set_use_graph(True)
         f.set_gradient_cache(3)
         if it % 4 == 3:
             f.set_host_exchange(lambda buf: None, 0, 1)          # a one-rank "transport": the seam with nothing behind it
+        assert len(f.p2p_local_handle()) == 64                   # the direct exchange's inbox, never connected
         x = cd.SparseIterate(300)
         for lam in (0.3, 0.15, 0.08):
             cd.coordinateDescent_(x, f, cd.ProxL1(lam), o)
@@ -1367,11 +1381,61 @@ def test_handles_with_every_optional_buffer_are_created_and_destroyed_repeatedly
         xw = cd.SparseIterate(300)
         cd.coordinateDescent_(xw, fw, cd.ProxL1(0.1), o)
         fw.close()
+        with monkeypatch.context() as m:                         # the one-launch solve (read when a handle is made)
+            m.setenv("CDH_SMALL_PATH", "1")
+            fs = cd.CDLeastSquaresLoss(Y, X)
+        xs = cd.SparseIterate(300)
+        cd.coordinateDescent_(xs, fs, cd.ProxL1(0.1), o)
+        assert fs.onchip_stats()["solves"] == 1
+        first_s = xs.dense().copy() if first_s is None else first_s
+        np.testing.assert_allclose(xs.dense(), first_s, rtol=0, atol=1e-12)
+        fs.close()
+        with monkeypatch.context() as m:                         # the device pass loop's table and helpers, as smoke() reaches them
+            m.setenv("CDH_CS_UCAP", "8")
+            fc = cd.CDLeastSquaresLoss(Yc, Xc)
+        fc.set_gradient_cache(3)
+        fc.set_onchip_solve(False)
+        xc = cd.SparseIterate(400)
+        for lam in lams_c:
+            cd.coordinateDescent_(xc, fc, cd.ProxL1(lam), o)
+        ls = fc.device_loop_stats()
+        assert ls["table"]["passes"] > 0 and ls["crew"]["passes"] > 0, ls
+        first_c = xc.dense().copy() if first_c is None else first_c
+        np.testing.assert_allclose(xc.dense(), first_c, rtol=0, atol=1e-12)
+        fc.close()
+        free.append(_device_memory()[0])
+    # the first two rounds may leave what the runtime keeps for good (queues, scratch, code objects); after that, nothing
+    assert abs(free[-1] - free[1]) <= 2 << 20, [(b - free[1]) >> 10 for b in free]
     xo = O.SparseIterate(300)
     fo = O.CDLeastSquaresLoss(Y, X)
     for lam in (0.3, 0.15, 0.08):
         O.coordinateDescent_(xo, fo, O.ProxL1(lam), O.CDOptions(maxIter=2000, optTol=1e-11, randomize=False))
     np.testing.assert_allclose(first, xo.dense(), rtol=0, atol=BETA_TOL)
+
+
+def test_create_that_cannot_have_its_matrix_fails_whole():
+    """cdh_create of an X twice the size of the device's memory: CDH_OOM, the message names the allocation that
+    failed, and whatever the attempt had got before it is released again; the next handle is made and solves as
+    usual (the failed allocation is not reported a second time by its first launch)."""
+    import ctypes as C
+    L = cd._lib.lib()
+    _, X, Y = _problem(83, 500, 20, 4)
+    cd.CDLeastSquaresLoss(Y, X).close()                          # the process's first handle: runtime set-up out of the way
+    free0, total = _device_memory()
+    n = 1 << 20
+    p = 2 * total // (8 * n) + 1
+    h = C.c_void_p()
+    st = L.cdh_create(C.byref(h), cd._lib.CDH_F64, cd._lib.CDH_LS, n, n, 0, p, 0)
+    msg = (L.cdh_last_error(None) or b"").decode()
+    assert st == cd._lib.CDH_OOM and not h.value, (st, msg)
+    assert "X.alloc(" in msg, msg
+    free1, _ = _device_memory()
+    assert abs(free1 - free0) <= 2 << 20, (free0, free1)
+    f = cd.CDLeastSquaresLoss(Y, X)
+    x = cd.SparseIterate(20)
+    cd.coordinateDescent_(x, f, cd.ProxL1(0.1), cd.CDOptions(maxIter=2000, optTol=1e-10, randomize=False))
+    assert f.last_stats["converged"]
+    f.close()
 
 
 @pytest.mark.parametrize("loss", ["ls", "sqrt"])
