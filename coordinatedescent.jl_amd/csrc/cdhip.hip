@@ -26,8 +26,9 @@ namespace {
 
 std::string g_create_error;
 
+constexpr int kStepGridPerCU = 8;    // blocks per CU of k_step (and the axpy kernels that share its grid)
 constexpr int kMaxStepGrid = 2048;   // blocks of k_step (8 per CU on 256 CUs)
-constexpr int kBlockGridPerCU = 4;   // upper bound of k_blockstep blocks per CU (partials sizing)
+constexpr int kBlockGridPerCU = 3;   // blocks per CU of k_blockstep
 constexpr int kColChunks = 64;       // row chunks per column in k_col_dots
 constexpr int kMaxBlockB = 8;
 constexpr int kShortRounds = 16;     // below this many rounds of 64-vector chunks per launch: short chunks
@@ -132,7 +133,7 @@ struct GradCache {
     DevBuf<int64_t> d_cols;         // device: the B columns of a batch
     std::vector<double> h_cross;
     // covariance-form visits: device mirrors of g, the Gram columns (slot-major, p doubles each) and the slot map
-    bool cov = true;                // env CDH_GC_COV
+    bool cov = true;                // covariance-form visits (Knobs::gc_cov; off for good where the store does not fit)
     DevBuf<double> d_g, d_G;
     PinBuf<double> h_g_pin; DevBuf<int32_t> d_slot;
     // whole full passes on the device (gc_pass_device): g lives in d_g between passes and comes back only when host
@@ -156,11 +157,10 @@ struct GradCache {
     double yy = 0.0;                      // y'y over all shards (fp32 certificate margin), valid while yy_ok
     bool yy_ok = false;
     int64_t n_dev_passes = 0;
-    int inject_rollback = 0, inject_count = 0;   // env CDH_GC_INJECT_ROLLBACK (tests)
+    int inject_count = 0;           // device passes so far, for Knobs::gc_inject_rollback (tests)
     int64_t dev_slots_cap = 0, dev_slots = 0;   // columns the device store can hold / holds
     std::vector<DevBuf<double>> d_G_retired;    // stores outgrown on the way (freed with the handle)
-    int64_t cov_since_ref = 0;      // covariance-form visits since g was last taken from X itself
-    int64_t refresh_after = 0;      // ... after which it is (kGcCovRefresh; env CDH_GC_REFRESH for tests)
+    int64_t cov_since_ref = 0;      // covariance-form visits since g was last taken from X itself (re-read after Knobs::gc_refresh)
     std::vector<double> g_new;      // g as a covariance-form chunk left it, until the chunk is accepted
     double q = 0.0;                 // r'r of the (virtual) residual g describes: sqrt-lasso thresholds and updates
     double q_exact = 0.0;           // ... as last summed from r itself (the carried value is refreshed once it has fallen far below it)
@@ -171,10 +171,9 @@ struct GradCache {
     int64_t n_validate = 0, n_batches = 0, n_columns = 0, n_certified = 0, n_exact = 0, n_passes = 0, n_cov = 0,
             n_reconcile = 0;
     // the device-resident pass loop (cov_solve.hpp): its scratch, the pinned block it reads from and writes into, the bound's M_k
-    bool cs_enabled = true;          // env CDH_COV_SOLVE (default 1)
+    bool cs_enabled = true;          // Knobs::cov_solve, cdh_set_device_loop
     bool cs_big = false;             // a visit list has outgrown the loop's LDS block on this handle: launches use the instantiation with the table and the helpers
-    int cs_ucap_limit = 0;           // env CDH_CS_UCAP (tests): visit lists longer than this leave the LDS block
-    int cs_helpers = 31;             // helper workgroups a launch that expects large visit lists brings (env CDH_CS_CREW; 0: none, table mode only)
+    int cs_helpers = 31;             // helper workgroups a launch that expects large visit lists brings (Knobs::cs_crew, cdh_set_device_loop; 0: none)
     bool cs_shuffle_ok = true, cs_stalled = false;
     size_t cs_lds_budget = 0;
     DevBuf<char> cs_dev; PinBuf<char> cs_pin; char* cs_pin_dev = nullptr;
@@ -190,7 +189,7 @@ struct GradCache {
     int64_t n_cs_launches = 0, n_cs_passes = 0, n_cs_folds = 0, n_cs_exact = 0, n_cs_table_passes = 0, n_cs_table_rows = 0;
     int32_t cs_ncid = 0, cs_tepoch = 0;      // the kernel's Gram table: coordinates it holds, the epoch of its carried gradients
     bool cs_table_reset = true;
-    int64_t cs_ticks[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cs_cycles = 0, cs_ticks_total = 0;
+    int64_t cs_ticks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 // The one-launch solve of problems that fit on chip (small_solve.hpp): the full Gram matrix of the resident X, the
@@ -218,16 +217,13 @@ struct SmallCtl {
 };
 
 struct SmallPath {
-    bool enabled = true;             // env CDH_SMALL_PATH (default 1), cdh_set_small_path
-    int64_t max_bytes = -1;          // env CDH_SMALL_MAX_BYTES: a fixed limit on n p sz instead of rent-or-buy (experiments)
-    int64_t always_bytes = (int64_t)kSmallAlwaysBytes;   // env CDH_SMALL_ALWAYS_BYTES (tests: 0 makes every handle rent first)
+    bool enabled = true;             // Knobs::small_path, cdh_set_small_path
     double rent_paid = 0.0;          // modelled seconds of streamed solves on the current X while G was not built (SmallRent)
     DevBuf<int64_t> d_iota;          // 0 .. p-1: the column lists of the Gram build
     bool G_valid = false;
     DevBuf<double> d_G;              // p x p
     DevBuf<char> d_io; PinBuf<char> h_io;     // [SmallCtl][support][beta]: what crosses the bus per solve, one block each way
-    char* hd_io = nullptr;           // h_io as the device addresses it
-    bool zero_copy = true;           // env CDH_SMALL_ZEROCOPY (default 1): the kernel works on h_io itself, nothing is copied
+    char* hd_io = nullptr;           // h_io as the device addresses it: the kernel works on h_io itself, nothing is copied
     SmallCtl *d_ctl = nullptr, *h_ctl = nullptr;   // views into d_io / h_io (pinned)
     int32_t *d_sup = nullptr, *h_sup = nullptr;
     double *d_beta = nullptr, *h_beta = nullptr;
@@ -239,6 +235,52 @@ struct SmallPath {
     int ncache = 0;                  // Gram columns the solve kernel can keep in LDS
     unsigned lds_bytes = 0;
 };
+
+// ---- environment knobs ----------------------------------------------------------------------------------------------
+// Every CDH_* variable the library reads (LAB_NOTES.md "Tuning knobs"), read by read_knobs() in cdh_create and kept on the
+// handle: a change of the environment reaches the handles created after it, never a live one.  Defaults are the measured
+// best.  Where a setting seeds state that the ABI or a fallback changes later (the cache's mode, the device loop, the
+// one-launch solve), the handle's state starts from it; the rest is read from here.
+constexpr int64_t kGcCovRefresh = 200000;   // covariance-form visits after which g is re-read from X
+struct Knobs {
+    int lt = 2;                      // CDH_LT: k_gramstep's operand loads transposed through LDS: 0 off, 1 on, 2 by size
+    int ks = 0;                      // CDH_KS: chunk length of that path: 0 by shard length, 1 short, 2 long
+    int gradient_cache = 1;          // CDH_GRADIENT_CACHE: the cache's initial mode (0 - 3)
+    bool gc_cov = true;              // CDH_GC_COV: covariance-form visits
+    int64_t gc_refresh = kGcCovRefresh;    // CDH_GC_REFRESH (tests)
+    int gc_inject_rollback = 0;      // CDH_GC_INJECT_ROLLBACK (tests): every N-th device pass of the cache is declared failed
+    int64_t gc_rows_per_nnz = 0;     // CDH_GC_ROWS_PER_NNZ (tests): a fixed rows-per-non-zero rule (0: by path, gc_rows_per_nnz)
+    bool cov_solve = true;           // CDH_COV_SOLVE: the device-resident pass loop
+    int cs_crew = 31;                // CDH_CS_CREW: its helper workgroups (0: none)
+    int cs_ucap = 0;                 // CDH_CS_UCAP (tests): visit lists longer than this leave the loop's LDS block
+    bool small_path = true;          // CDH_SMALL_PATH: the one-launch solve
+    int64_t small_max_bytes = -1;    // CDH_SMALL_MAX_BYTES: a fixed limit on n p sz instead of rent-or-buy (-1: none)
+    int64_t small_always_bytes = (int64_t)kSmallAlwaysBytes;   // CDH_SMALL_ALWAYS_BYTES (tests: 0 makes every handle rent first)
+    bool force_rccl = false;         // CDH_FORCE_RCCL (set): cdh_comm_init builds a 1-rank communicator too
+    unsigned p2p_spin_limit = cdk::kP2PSpinLimit;   // CDH_P2P_SPIN_LIMIT: bound of the direct exchange's wait
+};
+
+// the only reader of the environment in the library
+Knobs read_knobs() {
+    auto num = [](const char* nm, long long dflt) { const char* v = getenv(nm); return v ? atoll(v) : dflt; };
+    Knobs k;
+    k.lt = (int)num("CDH_LT", k.lt);
+    k.ks = (int)num("CDH_KS", k.ks);
+    k.gradient_cache = (int)std::max(0LL, std::min(3LL, num("CDH_GRADIENT_CACHE", k.gradient_cache)));
+    k.gc_cov = num("CDH_GC_COV", 1) != 0;
+    k.gc_refresh = std::max(1LL, num("CDH_GC_REFRESH", k.gc_refresh));
+    k.gc_inject_rollback = (int)std::max(0LL, num("CDH_GC_INJECT_ROLLBACK", 0));
+    if (getenv("CDH_GC_ROWS_PER_NNZ")) k.gc_rows_per_nnz = std::max(1LL, num("CDH_GC_ROWS_PER_NNZ", 1));
+    k.cov_solve = num("CDH_COV_SOLVE", 1) != 0;
+    k.cs_crew = (int)std::max(0LL, std::min((long long)kCsCrewMax, num("CDH_CS_CREW", k.cs_crew)));
+    k.cs_ucap = (int)std::max(0LL, num("CDH_CS_UCAP", 0));
+    k.small_path = num("CDH_SMALL_PATH", 1) != 0;
+    k.small_max_bytes = num("CDH_SMALL_MAX_BYTES", k.small_max_bytes);
+    k.small_always_bytes = num("CDH_SMALL_ALWAYS_BYTES", k.small_always_bytes);
+    k.force_rccl = getenv("CDH_FORCE_RCCL") != nullptr;
+    k.p2p_spin_limit = (unsigned)std::max(1LL, num("CDH_P2P_SPIN_LIMIT", k.p2p_spin_limit));
+    return k;
+}
 
 struct cdh_handle_s {
     int dtype = CDH_F64, loss = CDH_LS, device = 0;
@@ -301,12 +343,9 @@ struct cdh_handle_s {
     std::vector<GraphEntry> graphs;  // captured chunk launch sequences
     bool graph_broken = false;       // a capture failed on this handle: launch node by node from now on
     bool domain_error = false;
-    int step_grid = 1, block_grid = 1, gram_per_cu = 2, cus = 1, gram32_per_cu = 1;
-    int lt_per_cu = 0;  // experiments: blocks per CU of the LDS-transposed variants (0 = by tile size)
+    int step_grid = 1, block_grid = 1, cus = 1;
     int64_t gram_units = 1;
-    bool nt = true;  // non-temporal loads for the X column streams
-    int ks = 0;      // chunk length of the LDS-transposed path: 0 by shard length, 1 short, 2 long (env CDH_KS)
-    int lt = 2;      // coalesced operand loads transposed through LDS: 0 off, 1 on, 2 by size (default)
+    Knobs knobs;     // the environment as cdh_create found it
     // comm
     void* comm = nullptr;
     int rank = 0, nranks = 1;
@@ -315,7 +354,7 @@ struct cdh_handle_s {
     cdk::P2PPeers p2p_peers{};
     std::vector<void*> p2p_mapped;
     PinBuf<int> p2p_timeout;     // pinned host flag written by a kernel whose bounded spin ran out
-    unsigned p2p_epoch = 0, p2p_spin_limit = cdk::kP2PSpinLimit;
+    unsigned p2p_epoch = 0;
     int p2p_ranks = 0;
     bool p2p_on = false, p2p_dead = false;
     bool lost_exchange = false;       // a multi-rank shard whose host transport was taken away: allreduce() refuses
@@ -440,10 +479,10 @@ inline unsigned epoch_after(unsigned e) { return e >= kEpochWrap ? ((e & 1u) ? 2
 cdk::P2PCall next_p2p_call(cdh_handle h) {
     if (h->capturing) {
         h->cap_exchanges += 1;
-        return cdk::P2PCall{h->p2p_peers, h->rank, h->p2p_ranks, h->cap_exchanges, h->p2p_spin_limit, h->p2p_timeout, h->d_p2p_base};
+        return cdk::P2PCall{h->p2p_peers, h->rank, h->p2p_ranks, h->cap_exchanges, h->knobs.p2p_spin_limit, h->p2p_timeout, h->d_p2p_base};
     }
     h->p2p_epoch = epoch_after(h->p2p_epoch);
-    return cdk::P2PCall{h->p2p_peers, h->rank, h->p2p_ranks, h->p2p_epoch, h->p2p_spin_limit, h->p2p_timeout, nullptr};
+    return cdk::P2PCall{h->p2p_peers, h->rank, h->p2p_ranks, h->p2p_epoch, h->knobs.p2p_spin_limit, h->p2p_timeout, nullptr};
 }
 
 // The one exchange seam of the row-sharded path: sum `count` doubles at dbuf (device) over all ranks,
@@ -578,12 +617,11 @@ constexpr int kGcMaxFetch = 64;     // more uncached movers than this: re-refere
 constexpr int kGcMaxSupport = 512;  // supports beyond this are not worth Gram columns
 constexpr size_t kGcMaxBytes = (size_t)1 << 30;
 constexpr int64_t kGcCovWindow = 2048;      // positions one covariance-form chunk of a full pass may span
-constexpr int64_t kGcCovRefresh = 200000;   // covariance-form visits after which g is re-read from X
 constexpr int64_t kGcRowsPerNnz = 400;   // rows the problem must have per non-zero for the HOST-side fold and re-check to pay ...
 constexpr int64_t kGcRowsPerNnzDev = 32; // ... and when the passes run on the device (round 3: g, the fold and the re-check never leave it)
 inline int64_t gc_rows_per_nnz(const cdh_handle_s* h) {
     const GradCache& c = h->gc;
-    if (const char* e = getenv("CDH_GC_ROWS_PER_NNZ")) return std::max<int64_t>(1, atoll(e));   // experiments
+    if (h->knobs.gc_rows_per_nnz > 0) return h->knobs.gc_rows_per_nnz;   // tests
     return (c.cov && (c.d_scan || c.g.empty())) ? kGcRowsPerNnzDev : kGcRowsPerNnz;   // (before the first sizing: assume the device path)
 }
 
@@ -771,12 +809,8 @@ template <typename T, int B> int32_t launch_block_chunk(cdh_handle h, int m) {
     int nprev = 0;
     for (int pos0 = 0; pos0 < m; pos0 += B) {
         const int nb = std::min(B, m - pos0);
-        if (h->nt)
-            hipLaunchKernelGGL((k_blockstep<T, B, true>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
-                               h->ld, h->nvec, (T*)h->r, h->d_idx, h->d_hs, pos0, nb, nprev, h->d_partials);
-        else
-            hipLaunchKernelGGL((k_blockstep<T, B, false>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
-                               h->ld, h->nvec, (T*)h->r, h->d_idx, h->d_hs, pos0, nb, nprev, h->d_partials);
+        hipLaunchKernelGGL((k_blockstep<T, B>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
+                           h->ld, h->nvec, (T*)h->r, h->d_idx, h->d_hs, pos0, nb, nprev, h->d_partials);
         if (!sharded(h)) {
             hipLaunchKernelGGL((k_block_finalize<B, true>), dim3(1), dim3(1024), 0, h->stream,
                                h->d_partials, G, nb, h->d_ctrl, h->beta, h->omega, h->d_idx, h->d_hs,
@@ -803,12 +837,14 @@ template <typename T, int B> int32_t launch_block_chunk(cdh_handle h, int m) {
 // bounded by their 68-78 KB operand tiles to 2 blocks -- B = 32 launched with 3 per CU ran its
 // third of the grid as a second, half-empty round: 933 -> 861 us per block at 1e7 rows), never
 // more than the partial buffer was sized for
-inline int gram_blocks_per_cu(cdh_handle h, int NG, bool lt) {
-    if (lt) return h->lt_per_cu > 0 ? h->lt_per_cu : 2;
-    return NG == 4 ? std::min(h->gram32_per_cu, 2) : NG == 2 ? h->gram32_per_cu : h->gram_per_cu;
+constexpr int kGramGridPerCU = 2;     // fragment path, B = 16 and 64
+constexpr int kGram32GridPerCU = 3;   // fragment path, B = 32
+constexpr int kLtGridPerCU = 2;       // LDS-transposed path, every width
+constexpr int gram_blocks_per_cu(int NG, bool lt) {
+    return lt ? kLtGridPerCU : NG == 2 ? kGram32GridPerCU : kGramGridPerCU;
 }
 inline int NGgrid(cdh_handle h, int NG, bool lt = false) {
-    return balanced_grid(h->gram_units, (int64_t)h->cus * gram_blocks_per_cu(h, NG, lt));
+    return balanced_grid(h->gram_units, (int64_t)h->cus * gram_blocks_per_cu(NG, lt));
 }
 
 // wide blocks (B = 16 / 32 / 64): MFMA-accumulated Gram kernel + two-stage reduction
@@ -819,19 +855,20 @@ template <typename T, int NG> int32_t launch_gram_chunk(cdh_handle h, int m) {
     // LDS-transposed (fully coalesced) operand loads: measured -5 % at >= 5e6 rows for every
     // width; with short chunks also -10 % for B = 32 at 6.25e5 .. 1.25e6 rows and neutral for
     // B = 64.  B = 16 takes it on long columns only.  fp32 B = 64 would spill: fragment path.
-    const bool use_lt = (h->lt == 1 || (h->lt == 2 && (NG >= 2 || h->n >= 2000000))) && !(NG == 4 && sizeof(T) == 4);
+    const int lt = h->knobs.lt;
+    const bool use_lt = (lt == 1 || (lt == 2 && (NG >= 2 || h->n >= 2000000))) && !(NG == 4 && sizeof(T) == 4);
     int G = NGgrid(h, NG, use_lt);
     // short columns (a launch is fewer than kShortRounds rounds of 64-vector chunks): chunks of
     // one sub-chunk, so a partly filled last round costs a quarter (B = 64) or half (B = 32) as much
     const int64_t rounds64 = ((h->nvec + 63) / 64) / ((int64_t)G * kGramWaves);
-    const bool short_chunks = use_lt && (h->ks == 1 || (h->ks == 0 && rounds64 < kShortRounds));
+    const bool short_chunks = use_lt && (h->knobs.ks == 1 || (h->knobs.ks == 0 && rounds64 < kShortRounds));
     // ... and as many blocks as there are chunks of THAT length to hand out, four per block (round 3: the grid was sized for
     // 64-vector chunks, which at 24 KB columns -- benchmark/cd_bench.jl's n = 3000 -- left 6 blocks to walk 94 short chunks,
     // four apiece and one after the other: 31 us per launch whatever it read)
     {
         const int64_t cvn = use_lt ? (int64_t)(64 / NG) * (short_chunks ? 1 : NG) : 64;
         const int64_t nchunks = (h->nvec + cvn - 1) / cvn;
-        G = balanced_grid((nchunks + kGramWaves - 1) / kGramWaves, (int64_t)h->cus * gram_blocks_per_cu(h, NG, use_lt));
+        G = balanced_grid((nchunks + kGramWaves - 1) / kGramWaves, (int64_t)h->cus * gram_blocks_per_cu(NG, use_lt));
     }
     if ((size_t)G * R::N > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partial buffer too small for this grid");
     int nprev = 0;
@@ -843,18 +880,16 @@ template <typename T, int NG> int32_t launch_gram_chunk(cdh_handle h, int m) {
         };
         if (use_lt) {
             if constexpr (NG == 1) {
-                go(k_gramstep<T, 1, true, true>);
+                go(k_gramstep<T, 1, true>);
             } else if constexpr (NG == 4 && sizeof(T) == 4) {
                 // (never reached: use_lt is false for fp32 B = 64 -- its LDS-transposed variants spilled 160 - 280 bytes per lane
                 // and are not instantiated)
-                go(k_gramstep<T, NG, true>);
+                go(k_gramstep<T, NG>);
             } else {
-                if (short_chunks) go(k_gramstep<T, NG, true, true, 1>); else go(k_gramstep<T, NG, true, true>);
+                if (short_chunks) go(k_gramstep<T, NG, true, 1>); else go(k_gramstep<T, NG, true>);
             }
-        } else if (h->nt) {
-            go(k_gramstep<T, NG, true>);
         } else {
-            go(k_gramstep<T, NG, false>);
+            go(k_gramstep<T, NG>);
         }
         hipLaunchKernelGGL(k_gram_reduce, dim3((R::N + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream, h->d_partials, G, R::N, h->d_red);
         CHK(allreduce(h, h->d_red, R::N));
@@ -872,13 +907,10 @@ template <typename T> int32_t launch_coord_chunk(cdh_handle h, int m) {
     const int G = h->step_grid;
     for (int pos = 0; pos < m; ++pos) {
         if (h->has_w)
-            hipLaunchKernelGGL((k_step<T, true, true>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
+            hipLaunchKernelGGL((k_step<T, true>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
                                h->ld, h->nvec, (const T*)h->w, (T*)h->r, h->d_idx, h->d_hs, pos, h->d_partials);
-        else if (h->nt)
-            hipLaunchKernelGGL((k_step<T, false, true>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
-                               h->ld, h->nvec, (const T*)nullptr, (T*)h->r, h->d_idx, h->d_hs, pos, h->d_partials);
         else
-            hipLaunchKernelGGL((k_step<T, false, false>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
+            hipLaunchKernelGGL((k_step<T, false>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
                                h->ld, h->nvec, (const T*)nullptr, (T*)h->r, h->d_idx, h->d_hs, pos, h->d_partials);
         if (!sharded(h)) {
             hipLaunchKernelGGL(k_finalize<true>, dim3(1), dim3(kBlock), 0, h->stream, h->d_partials, G,
@@ -945,7 +977,7 @@ int32_t run_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH) {
     if (h->use_graph && !h->graph_broken && !h->host_fn && !h->p2p_dead && m >= (blocked ? 2 * h->blockB : 8)) {
         const uint64_t key = ((uint64_t)m << 20) | ((uint64_t)(blocked ? h->blockB : 0) << 8) |
                              (h->comm ? 32u : 0u) | (h->p2p_on ? 16u : 0u) |
-                             (h->chunk_dup ? 4u : 0u) | (h->has_w ? 2u : 0u) | (h->nt ? 1u : 0u);
+                             (h->chunk_dup ? 4u : 0u) | (h->has_w ? 2u : 0u);
         cdh_handle_s::GraphEntry* entry = nullptr;
         for (auto& e : h->graphs) if (e.key == key) entry = &e;
         if (!entry) {
@@ -1237,34 +1269,18 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
         hipDeviceProp_t prop;
         HIPCHK(h, hipGetDeviceProperties(&prop, device));
         const int cus = std::max(1, prop.multiProcessorCount);
-        // tuning knobs (experiments only; defaults are the measured best)
-        auto env_int = [](const char* nm, int dflt) { const char* v = getenv(nm); return v ? atoi(v) : dflt; };
-        h->nt = env_int("CDH_NT", 1) != 0;
-        h->lt = env_int("CDH_LT", 2);
-        h->ks = env_int("CDH_KS", 0);
-        h->gc.mode = std::max(0, std::min(3, env_int("CDH_GRADIENT_CACHE", 1)));
-        h->gc.cov = env_int("CDH_GC_COV", 1) != 0;
-        h->gc.cs_enabled = env_int("CDH_COV_SOLVE", 1) != 0;
-        h->gc.cs_helpers = std::max(0, std::min(kCsCrewMax, env_int("CDH_CS_CREW", 31)));
-        h->gc.cs_ucap_limit = std::max(0, env_int("CDH_CS_UCAP", 0));
-        h->small.enabled = env_int("CDH_SMALL_PATH", 1) != 0;
-        if (const char* e = getenv("CDH_SMALL_MAX_BYTES")) h->small.max_bytes = std::atoll(e);
-        h->small.zero_copy = env_int("CDH_SMALL_ZEROCOPY", 1) != 0;
-        if (const char* e = getenv("CDH_SMALL_ALWAYS_BYTES")) h->small.always_bytes = std::atoll(e);
-        h->gc.inject_rollback = std::max(0, env_int("CDH_GC_INJECT_ROLLBACK", 0));
-        h->gc.refresh_after = std::max(1, env_int("CDH_GC_REFRESH", (int)kGcCovRefresh));
-        const int step_per_cu = std::max(1, env_int("CDH_STEP_GRID_PER_CU", 8));
-        const int block_per_cu = std::max(1, std::min(kBlockGridPerCU, env_int("CDH_BLOCK_GRID_PER_CU", 3)));
+        h->knobs = read_knobs();
+        h->gc.mode = h->knobs.gradient_cache;
+        h->gc.cov = h->knobs.gc_cov;
+        h->gc.cs_enabled = h->knobs.cov_solve;
+        h->gc.cs_helpers = h->knobs.cs_crew;
+        h->small.enabled = h->knobs.small_path;
         const int64_t want = (h->nvec + (int64_t)kBlock * kUnroll - 1) / ((int64_t)kBlock * kUnroll);
-        h->step_grid = balanced_grid(want, std::min<int64_t>((int64_t)kMaxStepGrid, (int64_t)cus * step_per_cu));
+        h->step_grid = balanced_grid(want, std::min<int64_t>((int64_t)kMaxStepGrid, (int64_t)cus * kStepGridPerCU));
         const int64_t wantb = (h->nvec + kBlock - 1) / kBlock;
-        h->block_grid = balanced_grid(wantb, (int64_t)cus * block_per_cu);
+        h->block_grid = balanced_grid(wantb, (int64_t)cus * kBlockGridPerCU);
         h->cus = cus;
-        h->gram32_per_cu = std::max(1, env_int("CDH_GRAM32_GRID_PER_CU", 3));
-        const int64_t wantg = (h->nvec + 64 * kGramWaves - 1) / (64 * kGramWaves);
-        h->gram_per_cu = std::max(1, std::min(4, env_int("CDH_GRAM_GRID_PER_CU", 2)));
-        h->lt_per_cu = std::max(0, std::min(4, env_int("CDH_LT_PER_CU", 0)));
-        h->gram_units = wantg;
+        h->gram_units = (h->nvec + 64 * kGramWaves - 1) / (64 * kGramWaves);
         const size_t colbytes = (size_t)h->ld * h->esz;
         HIPCHK(h, h->X.alloc(colbytes * (size_t)p));
         HIPCHK(h, h->y.alloc(colbytes));
@@ -1283,12 +1299,12 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
         HIPCHK(h, h->d_hs.alloc(sizeof(double) * h->cap));
         HIPCHK(h, h->d_newval.alloc(sizeof(double) * h->cap));
         HIPCHK(h, h->d_touched.alloc(sizeof(int32_t) * h->cap));
+        // (k_gramstep: the larger of its two paths' grids, gram_blocks_per_cu)
+        auto gram = [&](int NG, int N) { return (size_t)cus * std::max(gram_blocks_per_cu(NG, false), gram_blocks_per_cu(NG, true)) * N; };
         h->partials_doubles = std::max<size_t>({(size_t)kMaxStepGrid * kNSum,
                                                 (size_t)cus * kBlockGridPerCU * BlockRec<kMaxBlockB>::N,
                                                 (size_t)4096 * kColChunks * 2,
-                                                (size_t)cus * 2 * GramRec<4>::N,
-                                                (size_t)cus * std::max(h->gram32_per_cu, 4) * GramRec<2>::N,
-                                                (size_t)cus * 4 * GramRec<1>::N});
+                                                gram(4, GramRec<4>::N), gram(2, GramRec<2>::N), gram(1, GramRec<1>::N)});
         HIPCHK(h, h->d_partials.alloc(sizeof(double) * h->partials_doubles));
         HIPCHK(h, h->d_red.alloc(sizeof(double) * 4096));
         HIPCHK(h, h->d_colout.alloc(sizeof(double) * 2 * p));
@@ -1766,7 +1782,7 @@ static int32_t gram_launch(cdh_handle h, int m, std::vector<double>& rec) {
     if ((size_t)G * R::N > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partial buffer too small for this grid");
     CHK(dispatch(h, [&](auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
-        hipLaunchKernelGGL((k_gramstep<T, 4, true>), dim3(G), dim3(64 * kGramWaves), 0, h->stream,
+        hipLaunchKernelGGL((k_gramstep<T, 4>), dim3(G), dim3(64 * kGramWaves), 0, h->stream,
                            (const T*)h->X, h->ld, h->nvec, (const T*)nullptr, (T*)h->r, h->d_idx, h->d_hs, 0, m, 0,
                            h->d_partials);
         return CDH_OK;
@@ -2009,7 +2025,6 @@ int32_t cdh_device_loop_stats(cdh_handle h, int64_t* out12) {
     NEED_P(h, out12);
     out12[0] = h->gc.n_cs_launches; out12[1] = h->gc.n_cs_passes; out12[2] = h->gc.n_cs_folds; out12[3] = h->gc.n_cs_exact;
     for (int i = 0; i < 8; ++i) out12[4 + i] = h->gc.cs_ticks[i];
-    if (getenv("CDH_COV_SOLVE_CLOCK")) fprintf(stderr, "k_cov_solve: %lld cycles in %lld ticks of 10 ns: %.3f GHz\n", (long long)h->gc.cs_cycles, (long long)h->gc.cs_ticks_total, h->gc.cs_ticks_total ? (double)h->gc.cs_cycles / (double)h->gc.cs_ticks_total * 0.1 : 0.0);
     return CDH_OK;
 }
 
@@ -2045,7 +2060,7 @@ int32_t cdh_comm_init(cdh_handle h, const void* id_128_bytes, int32_t rank, int3
     if (h->host_fn) return fail(h, CDH_BAD_ARG, "the handle already exchanges through a host transport");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, CDH_BAD_ARG, "bad rank / nranks");
     // a 1-rank communicator is only built when asked for (exercises the RCCL path on one GPU)
-    if (nranks == 1 && !getenv("CDH_FORCE_RCCL")) { h->rank = 0; h->nranks = 1; return CDH_OK; }
+    if (nranks == 1 && !h->knobs.force_rccl) { h->rank = 0; h->nranks = 1; return CDH_OK; }
     std::string err;
     if (!load_rccl(err)) { h->err = err; return CDH_RCCL_ERROR; }
     HIPCHK(h, hipSetDevice(h->device));
@@ -2120,7 +2135,6 @@ int32_t cdh_p2p_connect(cdh_handle h, const void* handles_64_bytes_each, int32_t
         h->p2p_peers.inbox[q] = (unsigned long long*)mapped;
     }
     h->rank = rank; h->nranks = nranks; h->p2p_ranks = nranks;
-    if (const char* e = getenv("CDH_P2P_SPIN_LIMIT")) h->p2p_spin_limit = (unsigned)std::max<long long>(1, atoll(e));
     return CDH_OK;
 }
 

@@ -1239,7 +1239,6 @@ __global__ __launch_bounds__(256) void k_cov_colmax(double* __restrict__ colmax,
 enum { kCsNotNow = 0, kCsFinished = 1, kCsAgain = 2 };
 
 inline size_t cs_align(size_t v) { return (v + 255) / 256 * 256; }
-inline int cs_env_int(const char* nm, int dflt) { const char* v = getenv(nm); return v ? atoi(v) : dflt; }
 
 // scratch of the kernel (122 p bytes of device memory) and the pinned block it reads the support from and writes its
 // results into (zero-copy, as the one-launch solve's: nothing is copied around the launch)
@@ -1342,7 +1341,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     } else {
         if (!c.valid || !c.d_G) return CDH_OK;
         if (gc_support_outgrown(h)) { gc_invalidate(h, false); return CDH_OK; }
-        if (c.cov_since_ref > c.refresh_after) CHK(gc_rereference(h));
+        if (c.cov_since_ref > h->knobs.gc_refresh) CHK(gc_rereference(h));
         for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) return CDH_OK;
         gc_q_guard(h);
         if (h->loss == CDH_SQRT) CHK(gc_ensure_q(h));
@@ -1361,9 +1360,8 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
         const size_t budget = c.cs_lds_budget ? c.cs_lds_budget : kCsLdsBudget;
         while (ucap > 8 && 8 * cs_tri_doubles((size_t)ucap) + (kCsTrackedBytes + 8) * (size_t)ucap + shuffle_bytes > budget) ucap -= 4;
     }
-    // (visit lists beyond that run in the kernel's table mode, up to the table's rows; CDH_CS_TABLE=0: they stay with the host)
-    static const bool table_on = cs_env_int("CDH_CS_TABLE", 1) != 0;
-    const int64_t support_cap = table_on ? kCsTableCap - kCsTableMargin : ucap - kCsTrackedMargin;
+    // (visit lists beyond that run in the kernel's table mode, up to the table's rows)
+    const int64_t support_cap = kCsTableCap - kCsTableMargin;
     if (h->x.nnz() > support_cap) return not_now();
     CHK(cs_alloc(h));
     if (!c.cs_enabled) return not_now();
@@ -1371,20 +1369,18 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     // for all p after every block of moves -- p x moves gathers per pass, which twenty workgroups do in microseconds and one does not
     // (the bound of the loop's certificates is useless there: M_k TV exceeds the thresholds themselves once hundreds of coordinates move)
     // ... unless the launch brings helpers (the crew, above): then they do that work beside the visits, inside the loop
-    static const int full_env = cs_env_int("CDH_CS_FULL_CAP", 0);
-    const int crew_env = c.cs_helpers;
-    const int ucap_lists = c.cs_ucap_limit > 0 ? std::min(ucap, c.cs_ucap_limit) : ucap;
+    const int ucap_limit = h->knobs.cs_ucap;
+    const int ucap_lists = ucap_limit > 0 ? std::min(ucap, ucap_limit) : ucap;
     const int lds_margin = std::min(kCsTrackedMargin, ucap_lists / 4);
-    const int nhelp = (crew_env > 0 && table_on && h->x.nnz() + lds_margin / 2 > ucap_lists - lds_margin) ? std::min(crew_env, kCsCrewMax) : 0;
-    const int32_t full_cap = full_env > 0 ? full_env : (nhelp > 0 ? 0x7fffffff : ucap_lists - lds_margin);
+    const int nhelp = (c.cs_helpers > 0 && h->x.nnz() + lds_margin / 2 > ucap_lists - lds_margin) ? std::min(c.cs_helpers, kCsCrewMax) : 0;
+    const int32_t full_cap = nhelp > 0 ? 0x7fffffff : ucap_lists - lds_margin;
     if (full && h->x.nnz() > full_cap) return not_now();
     if (c.cs_table_reset) {          // a new X: the table's entries are void
         HIPCHK(h, hipMemsetAsync(c.cs_bufs.cidof, 0xff, sizeof(int32_t) * (size_t)h->p, h->stream));
         c.cs_ncid = 0; c.cs_table_reset = false;
     }
     // a fold is p x (pending moves) gathers: beyond a few moves the chip does it (gc_fold's kernel), not the one workgroup of the loop
-    static const int fold_env = cs_env_int("CDH_CS_FOLD_LIMIT", 0);
-    const int32_t fold_limit = fold_env > 0 ? fold_env : (int32_t)std::max<int64_t>(16, 120000 / h->p);
+    const int32_t fold_limit = (int32_t)std::max<int64_t>(16, 120000 / h->p);
     if ((int64_t)c.moved.size() > fold_limit) gc_fold(h);
     if (!c.slot_dev_ok) {             // the columns were dropped since the map last went down (a new X): the kernel asks d_slot who has one
         HIPCHK(h, hipMemcpyAsync(c.d_slot, c.slot.data(), sizeof(int32_t) * (size_t)h->p, hipMemcpyHostToDevice, h->stream));
@@ -1398,15 +1394,15 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     CovSolveCtl& ctl = *c.cs_ctl;
     ctl.lambda0 = h->ctrl.lambda0; ctl.n_total = (double)h->n_total; ctl.optTol = o->optTol; ctl.cert_abs = cert_abs;
     ctl.max_passes = o->maxIter - *iter;
-    ctl.cov_budget = std::max<int64_t>(0, c.refresh_after - c.cov_since_ref);
+    ctl.cov_budget = std::max<int64_t>(0, h->knobs.gc_refresh - c.cov_since_ref);
     ctl.loss = h->loss; ctl.has_omega = h->has_omega ? 1 : 0; ctl.randomize = o->randomize ? 1 : 0;
     {
         int64_t lim = gc_max_support(h);
         if (!(c.mode == 3 || gc_short_columns(h))) lim = std::min<int64_t>(lim, h->n_total / gc_rows_per_nnz(h));
         ctl.nnz_limit = (int32_t)std::min<int64_t>({lim, support_cap, (int64_t)0x7fffffff});
     }
-    ctl.busy_limit = kGcBusy; ctl.inject_every = c.inject_rollback; ctl.fold_limit = fold_limit;
-    ctl.tcap = table_on ? kCsTableCap : 0; ctl.ncid = c.cs_ncid; ctl.tepoch = c.cs_tepoch; ctl.full_cap = full_cap; ctl.ucap_limit = c.cs_ucap_limit;
+    ctl.busy_limit = kGcBusy; ctl.inject_every = h->knobs.gc_inject_rollback; ctl.fold_limit = fold_limit;
+    ctl.tcap = kCsTableCap; ctl.ncid = c.cs_ncid; ctl.tepoch = c.cs_tepoch; ctl.full_cap = full_cap; ctl.ucap_limit = ucap_limit;
     ctl.rng = sched.state(); ctl.q = c.q; ctl.q_floor = h->loss == CDH_SQRT ? kGcQGuard * c.q_exact : 0.0;
     ctl.nnz = (int32_t)h->x.nnz(); ctl.prev_conv = *prev_conv ? 1 : 0; ctl.conv = *conv ? 1 : 0; ctl.inject_count = c.inject_count;
     ctl.status = -1; ctl.n_list = 0;
@@ -1474,7 +1470,6 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     c.n_passes += ctl.full_passes; c.n_dev_passes += ctl.full_passes; c.n_certified += ctl.settled;
     c.n_cov += ctl.cov_visits; c.cov_since_ref += ctl.cov_visits; c.n_cs_passes += ctl.passes; c.n_cs_folds += ctl.folds; c.n_cs_exact += ctl.exact_rechecks;
     for (int i = 0; i < 8; ++i) c.cs_ticks[i] += ctl.ticks[i];
-    c.cs_cycles += ctl.cycles; c.cs_ticks_total += ctl.ticks_total;
     c.n_exact += ctl.cov_visits_full;
     if (ctl.domain_error) h->domain_error = true;
     sched.set_state(ctl.rng);

@@ -33,17 +33,16 @@ int32_t gc_size(cdh_handle h) {   // first use on this handle
     // one k_cross launch per batch: a block per (group of 64 columns, j of J), about two resident blocks per CU
     const int64_t launches = (h->p + kCrossA - 1) / kCrossA;      // column groups
     const int64_t nslabs = (h->nvec + kCrossSlab - 1) / kCrossSlab;
-    // gridDim.x = column groups in flight (super-groups of 4 x 64 columns; env CDH_CROSS_GX, default 4), gridDim.y = row lanes; never more blocks
+    // gridDim.x = column super-groups (4 x 64 columns each) in flight, 4 of them, gridDim.y = row lanes; never more blocks
     // than stay resident, kCrossOcc per CU (a partly filled second round would double the time)
-    const char* gxe = getenv("CDH_CROSS_GX");
     const int64_t nsuper = (launches + kGramWaves - 1) / kGramWaves;   // a block's four waves take four column groups
-    c.cross_GX = (int)std::max<int64_t>(1, std::min<int64_t>(nsuper, gxe ? atoi(gxe) : 4));
+    c.cross_GX = (int)std::max<int64_t>(1, std::min<int64_t>(nsuper, 4));
     const int64_t occ = h->dtype == CDH_F32 ? cross_occ<float>() : cross_occ<double>();
     c.cross_J = (int)std::max<int64_t>(1, std::min<int64_t>(nslabs, (occ * h->cus) / c.cross_GX));
     // short columns have few row slabs to hand out (n = 3000: two): the resident blocks they leave unused take further
     // column super-groups instead (benchmark/cd_bench.jl's shape: 8 blocks walked 79 column groups, 0.78 ms per batch of a
     // 120 MB X; 40 blocks: one group per wave)
-    if (!gxe) c.cross_GX = (int)std::min<int64_t>(nsuper, std::max<int64_t>(c.cross_GX, (occ * h->cus) / c.cross_J));
+    c.cross_GX = (int)std::min<int64_t>(nsuper, std::max<int64_t>(c.cross_GX, (occ * h->cus) / c.cross_J));
     // (a handle whose first sizing failed may be asked again: a failed attempt leaves nothing behind)
     DevBuf<double> cross, cross_part; DevBuf<int64_t> cols;
     bool fits = cross.alloc(sizeof(double) * (size_t)launches * kCrossRec) == hipSuccess &&
@@ -253,7 +252,7 @@ bool gc_ready_for_cov(cdh_handle h, const int64_t* idx0, int64_t m) {
     // the same bounds the full passes keep (gc_full_pass): the cache only pays on tall problems, and g is carried
     // through a bounded number of covariance-form updates before it is taken afresh from X
     if (gc_support_outgrown(h)) { gc_invalidate(h, false); return false; }
-    if (c.cov_since_ref > c.refresh_after && gc_rereference(h) != CDH_OK) return false;
+    if (c.cov_since_ref > h->knobs.gc_refresh && gc_rereference(h) != CDH_OK) return false;
     if (!c.moved.empty()) {
         for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) return false;
         gc_fold(h);
@@ -487,8 +486,7 @@ int32_t gc_fetch(cdh_handle h, const std::vector<int64_t>& cols) {
         return CDH_OK;
     }
     const int64_t launches = (h->p + kCrossA - 1) / kCrossA;      // column groups
-    const char* bmax = getenv("CDH_CROSS_BATCH");      // experiments: fewer B columns per launch (16: one tile column)
-    const size_t batch = (size_t)std::max(1, std::min(kCrossB, bmax ? atoi(bmax) : kCrossB));
+    const size_t batch = kCrossB;
     for (size_t b0 = 0; b0 < todo.size(); b0 += batch) {
         const int nbc = (int)std::min<size_t>(batch, todo.size() - b0);
         HIPCHK(h, hipMemcpyAsync(c.d_cols, todo.data() + b0, sizeof(int64_t) * (size_t)nbc, hipMemcpyHostToDevice, h->stream));
@@ -687,7 +685,8 @@ int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* max
         CHK(cov_fetch_results(h, cnt, true));
         // (tests: CDH_GC_INJECT_ROLLBACK=N declares every N-th device pass failed after the fact, so that the undo and the
         // windowed walk that takes over are exercised on every problem of the suite, not only where a certificate breaks)
-        const bool injected = c.inject_rollback > 0 && (++c.inject_count % c.inject_rollback) == 0;
+        const int every = h->knobs.gc_inject_rollback;
+        const bool injected = every > 0 && (++c.inject_count % every) == 0;
         if ((int64_t)c.h_scan->bad_pos < m) c.forced_dirty = true;     // (marks were set: wiped when this function returns)
         if ((int64_t)c.h_scan->bad_pos < m || injected) {       // a skipped certificate did not survive the pass's own moves: undo
             hipLaunchKernelGGL(k_cov_restore, dim3((unsigned)((h->p + 255) / 256)), dim3(256), 0, h->stream, c.d_g, h->beta, c.d_g_snap,
@@ -753,7 +752,7 @@ int32_t gc_prepare_full(cdh_handle h, bool* go, double* cert_abs_out, bool fold 
     // g has been carried through this many covariance-form updates without looking at X: it is taken afresh
     // below (rounding only ever accumulates in g; one dots-only pass resets it), or dropped if this pass turns
     // out to run the plain way -- the active passes that follow must not keep carrying it either
-    const bool refresh_due = c.valid && c.cov_since_ref > c.refresh_after;
+    const bool refresh_due = c.valid && c.cov_since_ref > h->knobs.gc_refresh;
     if (h->x.nnz() > gc_max_support(h)) { if (refresh_due) gc_invalidate(h, false); return CDH_OK; }
     if (c.cooldown > 0) { c.cooldown -= 1; if (c.valid) gc_invalidate(h, false); return CDH_OK; }
     CHK(gc_size(h));

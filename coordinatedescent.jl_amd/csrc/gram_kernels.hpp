@@ -78,7 +78,7 @@ template <int NG> struct LtTile {
 // 4.2 .. 5.0 rounds all take the time of 5).  Phase A then runs on a 2-D lane layout: NG/KS
 // column groups x chunk vectors, one load instruction covering NG/KS previous columns, the column
 // groups summed by a butterfly.
-template <typename T, int NG, bool NT_, bool LT = false, int KS = NG>
+template <typename T, int NG, bool LT = false, int KS = NG>
 __global__ __launch_bounds__(64 * kGramWaves, (NG >= 2 || LT) ? 2 : 3) void k_gramstep(
     const T* __restrict__ X, int64_t ld, int64_t nvec, const T* __restrict__ w, T* __restrict__ r,
     const int64_t* __restrict__ idx, const double* __restrict__ hs, int pos0, int nb, int nprev,
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(64 * kGramWaves, (NG >= 2 || LT) ? 2 : 3) void k_gr
                 for (int t = 0; t < PG; ++t) {
                     const int at = i0 + t * CGN + pa_cg;
                     const int ii = (at < nzp) ? at : nzp - 1;
-                    xp[t] = inb ? ld_stream<NT_>(reinterpret_cast<const V*>(X + s_kp[ii] * ld) + jv)
+                    xp[t] = inb ? ld_stream<true>(reinterpret_cast<const V*>(X + s_kp[ii] * ld) + jv)
                                 : vzero((V*)nullptr);
                 }
 #pragma unroll
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(64 * kGramWaves, (NG >= 2 || LT) ? 2 : 3) void k_gr
                 for (int t = 0; t < NL; ++t) {
                     const V* colp;
                     if constexpr (LDSCOL) colp = s_col[t * NG + lt_cl]; else colp = lt_col[t];
-                    xc[t] = (((lt_act >> t) & 1) && vsub < nvec) ? ld_stream<NT_>(colp + vsub) : vzero((V*)nullptr);
+                    xc[t] = (((lt_act >> t) & 1) && vsub < nvec) ? ld_stream<true>(colp + vsub) : vzero((V*)nullptr);
                 }
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(64 * kGramWaves, (NG >= 2 || LT) ? 2 : 3) void k_gr
                     const int64_t v = v0 + 4 * (u0 + u) + g;
 #pragma unroll
                     for (int grp = 0; grp < NG; ++grp)
-                        xf[u][grp] = (act[grp] && v < nvec) ? ld_stream<NT_>(cv[grp] + v) : vzero((V*)nullptr);
+                        xf[u][grp] = (act[grp] && v < nvec) ? ld_stream<true>(cv[grp] + v) : vzero((V*)nullptr);
                 }
             }
 #pragma unroll

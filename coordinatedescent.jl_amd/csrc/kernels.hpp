@@ -159,7 +159,7 @@ __device__ __forceinline__ double wave_sum_run(const double* __restrict__ run, i
 //   a = sum w x^2, b = sum w x r, q = sum r^2     (w = 1 unless HASW)
 // One partial record per block.  Streams: X_k (+X_prev) read, r read (+written).
 // ---------------------------------------------------------------------------------
-template <typename T, bool HASW, bool NT>
+template <typename T, bool HASW>
 __global__ __launch_bounds__(kBlock) void k_step(const T* __restrict__ X, int64_t ld, int64_t nvec,
                                                  const T* __restrict__ w, T* __restrict__ r,
                                                  const int64_t* __restrict__ idx,
@@ -187,9 +187,9 @@ __global__ __launch_bounds__(kBlock) void k_step(const T* __restrict__ X, int64_
             const int64_t j = base + (int64_t)u * kBlock;
             xc[u] = vzero((V*)nullptr); rr[u] = xc[u]; xp[u] = xc[u]; ww[u] = xc[u];
             if (j < nvec) {
-                xc[u] = ld_stream<NT>(cv + j);
+                xc[u] = ld_stream<true>(cv + j);
                 rr[u] = rv[j];
-                if (apply) xp[u] = ld_stream<NT>(pv + j);
+                if (apply) xp[u] = ld_stream<true>(pv + j);
                 if (HASW) ww[u] = wv[j];
             }
         }
@@ -385,7 +385,7 @@ template <int B> struct BlockRec {
     static constexpr int N = NG + B + 1;  // G (upper, row-major), c, q
 };
 
-template <typename T, int B, bool NT>
+template <typename T, int B>
 __global__ __launch_bounds__(kBlock) void k_blockstep(const T* __restrict__ X, int64_t ld,
                                                       int64_t nvec, T* __restrict__ r,
                                                       const int64_t* __restrict__ idx,
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(kBlock) void k_blockstep(const T* __restrict__ X, i
         V rr = rv[j];
         V xc[B];
 #pragma unroll
-        for (int i = 0; i < B; ++i) xc[i] = (i < nb) ? ld_stream<NT>(cv[i] + j) : vzero((V*)nullptr);
+        for (int i = 0; i < B; ++i) xc[i] = (i < nb) ? ld_stream<true>(cv[i] + j) : vzero((V*)nullptr);
         double re[NV];
 #pragma unroll
         for (int e = 0; e < NV; ++e) re[e] = (double)rr[e];
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(kBlock) void k_blockstep(const T* __restrict__ X, i
 #pragma unroll
             for (int i = 0; i < B; ++i) {
                 if (hp[i] != 0.0) {
-                    const V xp = ld_stream<NT>(pv[i] + j);
+                    const V xp = ld_stream<true>(pv[i] + j);
 #pragma unroll
                     for (int e = 0; e < NV; ++e) re[e] = fma(-hp[i], (double)xp[e], re[e]);
                 }

@@ -471,8 +471,8 @@ inline bool small_candidate(const cdh_handle_s* h, const cdh_options* o) {      
 inline bool small_applicable(const cdh_handle_s* h, const cdh_options* o, bool many_solves = false) {
     if (!small_candidate(h, o)) return false;
     const double bytes = (double)h->ld * (double)h->p * (double)h->esz;
-    if (h->small.max_bytes >= 0) return bytes <= (double)h->small.max_bytes;
-    if (h->small.G_valid || bytes <= (double)h->small.always_bytes) return true;
+    if (h->knobs.small_max_bytes >= 0) return bytes <= (double)h->knobs.small_max_bytes;
+    if (h->small.G_valid || bytes <= (double)h->knobs.small_always_bytes) return true;
     const double price = small_build_estimate(h);
     // (a cold start on the streamed kernels takes ~10 ms at any of these sizes -- the gradient cache serves most of its
     // passes -- so it buys outright only a build well under that)
@@ -609,9 +609,10 @@ int32_t small_solve(cdh_handle h, const cdh_options* o, const double* lambdas, i
     ctl.nnz_in = (int32_t)h->x.nnz();
     for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) sp.h_sup[s_] = (int32_t)h->x.coord(s_);
     // What crosses the bus per solve is one block each way -- [control][support] down, [control][support][beta] back.
-    // Zero-copy (default): the kernel reads and writes that block in the pinned host buffer itself, a few hundred bytes
-    // each way over the bus inside the launch, instead of two copies queued around it (~10 us of a 90 us solve at cfg1).
-    const bool zc = sp.zero_copy && sp.hd_io != nullptr;
+    // Zero-copy: the kernel reads and writes that block in the pinned host buffer itself, a few hundred bytes each way over
+    // the bus inside the launch, instead of two copies queued around it (~10 us of a 90 us solve at cfg1).  The copies remain
+    // for a runtime that gives the pinned block no device address.
+    const bool zc = sp.hd_io != nullptr;
     if (!zc)
         HIPCHK(h, hipMemcpyAsync(sp.d_io, sp.h_io, small_sup_off() + sizeof(int32_t) * (size_t)h->x.nnz(), hipMemcpyHostToDevice, h->stream));
     SmallCtl* k_ctl = zc ? reinterpret_cast<SmallCtl*>(sp.hd_io) : sp.d_ctl;

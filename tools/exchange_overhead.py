@@ -17,10 +17,11 @@ C = _lib.C
 
 def sweep_ms(kind, reps=8):
     os.environ.pop("CDH_FORCE_RCCL", None)
+    if kind == "rccl":
+        os.environ["CDH_FORCE_RCCL"] = "1"      # read when the handle is created
     f, _ = cd.CDLeastSquaresLoss.generate(n, p, seed=123, s=100, noise=6.0, dtype=np.float64, device=0,
                                           n_total=n, row_offset=0)
     if kind == "rccl":
-        os.environ["CDH_FORCE_RCCL"] = "1"
         buf = C.create_string_buffer(128)
         _lib.check(f._L.cdh_comm_unique_id(buf), None)
         f.comm_init(buf.raw, 0, 1)
