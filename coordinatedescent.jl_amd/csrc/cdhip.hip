@@ -1075,8 +1075,7 @@ int32_t screened_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double*
         if (handled) return CDH_OK;
     }
     const int B = (h->mode == CDH_SWEEP_BLOCK) ? h->blockB : 1;
-    const double lam = h->ctrl.lambda0, nt = (double)h->n_total;
-    const std::vector<double>& om = h->h_omega;
+    GcThresholds T(h, 0.0);           // (no certificate: the dots are fresh)
     std::vector<double> cd((size_t)(2 * kScreenMax));
     const int64_t scr_max = std::min<int64_t>({(int64_t)kScreenMax, h->p, h->cap});   // d_colout holds 2p values
     int64_t pos = 0, cool = 0, cool_len = kScreen, scr = std::min<int64_t>(kScreen, scr_max);
@@ -1092,29 +1091,19 @@ int32_t screened_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double*
         HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)S, hipMemcpyHostToDevice, h->stream));
         CHK(col_dots(h, 0, S, h->r, h->has_w, h->d_idx));   // X_k'W r, X_k'W X_k with observation weights
         HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, h->stream));
-        double rnorm = 0.0;
         if (h->loss == CDH_SQRT) {
             CHK(resid_moments_dev(h));
             HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->loss == CDH_SQRT) rnorm = std::sqrt(h->h_red[1]);
+        if (h->loss == CDH_SQRT) T.rnorm = std::sqrt(h->h_red[1]);
         int hit = S;
         for (int i = 0; i < S; ++i) {
             const int64_t k = idx0[pos + i];
-            const double b = cd[(size_t)(2 * i)];
-            const double w = h->has_omega ? om[(size_t)k] : 1.0;
-            const double thr = (h->loss == CDH_SQRT ? lam * w * rnorm : lam * nt * w) * (1.0 - 1e-9);
             // a zero column (a == 0) goes to the exact path too: the reference turns it into NaN
-            if (h->x.get(k) != 0.0 || !(std::fabs(b) <= thr) || !(cd[(size_t)(2 * i + 1)] > 0.0)) { hit = i; break; }
+            if (h->x.get(k) != 0.0 || !(std::fabs(cd[(size_t)(2 * i)]) <= T.thr_of(k)) || !(cd[(size_t)(2 * i + 1)] > 0.0)) { hit = i; break; }
         }
-        // visits [pos, pos + hit) are settled: h = 0; replay what the reference's SparseIterate
-        // would have seen (LS: x[k] += b/a stores a slot when b != 0, cdprox! zeroes it)
-        for (int i = 0; i < hit; ++i) {
-            const int64_t k = idx0[pos + i];
-            if (h->loss != CDH_SQRT && cd[(size_t)(2 * i)] != 0.0) h->x.set(k, 1.0);
-            h->x.set(k, 0.0);
-        }
+        for (int i = 0; i < hit; ++i) replay_settled(h, idx0[pos + i], cd[(size_t)(2 * i)] != 0.0);   // visits [pos, pos + hit) are settled
         pos += hit;
         if (hit < S) {
             const int mm = (int)std::min<int64_t>(std::max(B, 1), m - pos);

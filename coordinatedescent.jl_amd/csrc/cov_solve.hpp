@@ -42,7 +42,7 @@
 //     those passes to the host's device pass: kCsHostFull).
 // Both share one pipeline with two blocks of 64 visits in flight (see "Visit lists beyond the LDS block" in the kernel).
 // A full pass in which coordinates crossed their threshold through the pass's own moves runs again with those coordinates
-// visited (forced[], kCsForcedRounds) before anything is handed to the host.
+// visited (forced[], kMaxForcedRounds) before anything is handed to the host.
 // Why it looks the way it does (measured, LAB_NOTES.md round 4): on one CU every dependent global access is 0.2-0.5 us, so
 // the p-sized loops issue all their loads unconditionally (clamped indices, no short-circuit conditions: a conditional load
 // is compiled into a load that is waited for on its own) and rank several flags per pair of barriers.
@@ -59,7 +59,6 @@ constexpr int kCsTrackedMargin = 24;     // room in the tracked list for enterin
 constexpr int kCsTableCap = 1536;        // coordinates the Gram table of large visit lists holds (1536^2 doubles = 18.9 MB of device memory)
 constexpr int kCsTableMargin = 160;      // ... of which this many are left to entering and near-threshold coordinates next to the support
 constexpr size_t kCsTableLds = 2688 + 64 * 64 + 640;    // doubles of dynamic LDS table mode and crew passes use (a GramRec<4> record rounded up, a tile, a block's moves)
-constexpr int kCsForcedRounds = 4;       // a full pass whose re-check found coordinates crossing their threshold is run again this often with those visited
 constexpr int kCsUcapMax = 176;          // tracked coordinates whose Gram block is kept in LDS: symmetric, upper triangle packed (176 x 177 / 2 doubles = 122 KB)
 __host__ __device__ constexpr size_t cs_tri_doubles(size_t u) { return u * (u + 1) / 2; }
 // index of G_UU[i][j], i <= j, in the packed upper triangle of a cnt x cnt block (row i starts after rows 0 .. i - 1)
@@ -210,7 +209,7 @@ __device__ __forceinline__ void cs_crew_helper(const CovSolveCtl* ctl, const CsC
                 if (nmove == 0 && !need) continue;
                 double acc = b.g[k], q_run = q_start;
                 double cert_scale = 0.0, cert_off = 0.0;
-                if (need) { cert_scale = lambda0 * (has_omega ? b.omega[k] : 1.0) * (1.0 - 1e-9); cert_off = cert_abs * sqrt(b.a[k]); }
+                if (need) { cert_scale = lambda0 * (has_omega ? b.omega[k] : 1.0) * kThrMargin; cert_off = cert_abs * sqrt(b.a[k]); }
                 auto holds = [&](double gv, double qv) { return fabs(gv) <= cert_scale * (loss == 1 ? sqrt(qv) : n_total) - cert_off; };
                 for (int i0 = 0; i0 < nmove; i0 += 32) {
                     double gv[32];
@@ -515,7 +514,7 @@ __global__ __launch_bounds__(kCsThreads) void k_cov_solve(CovSolveCtl* ctl, CovS
                     // (a coordinate that has itself moved since the fold -- it left the support -- is never settled by the bound:
                     // M_k leaves out G_kk = a_k, by far the largest entry of its column)
                     st[e] = valid[e] & full & (bk[e] == 0.0) & (ak[e] > 0.0) & (inm[e] == 0) & (frc[e] == 0) &
-                            (fabs(gk[e]) + mk[e] * TV0 <= thr_base * om[e] * (1.0 - 1e-9) - cert_abs * sqrt(ak[e]));
+                            (fabs(gk[e]) + mk[e] * TV0 <= thr_base * om[e] * kThrMargin - cert_abs * sqrt(ak[e]));
                     uns[e] = valid[e] & !st[e];
                     nc[e] = uns[e] & (sl[e] < 0);
                     nz_mine += (st[e] & (gk[e] == 0.0)) ? 1 : 0;
@@ -911,7 +910,7 @@ __global__ __launch_bounds__(kCsThreads) void k_cov_solve(CovSolveCtl* ctl, CovS
                 for (int e = 0; e < E; ++e) {
                     const double tvk = TV0 + (vbk[e] > 0 ? tvb[e] : 0.0);
                     const double qk = vbk[e] > 0 ? qsb[e] : q_start;
-                    const double cert = lambda0 * (sqrt_loss ? sqrt(qk) : n_total) * om[e] * (1.0 - 1e-9) - cert_abs * sqrt(ak[e]);
+                    const double cert = lambda0 * (sqrt_loss ? sqrt(qk) : n_total) * om[e] * kThrMargin - cert_abs * sqrt(ak[e]);
                     const bool fails = chk[e] & (sf[e] != 0) & !(fabs(gk[e]) + mk[e] * tvk <= cert);
                     if (fails) {                                  // listed: the exact gradient when its turn came is a gather the block shares
                         const int at = atomicAdd(&s_nfail, 1);
@@ -988,7 +987,7 @@ __global__ __launch_bounds__(kCsThreads) void k_cov_solve(CovSolveCtl* ctl, CovS
             }
             // coordinates that crossed their threshold through the pass's own moves: the same pass again with those on the visit list
             // (visiting more than necessary is always right); after a few such rounds, or for anything else, the host walks it the careful way
-            if (crossed && !injected && s_nan == 0 && !(nzero > 0 && (TV0 > 0.0 || tv_pass > 0.0)) && forced_rounds_here < kCsForcedRounds) {
+            if (crossed && !injected && s_nan == 0 && !(nzero > 0 && (TV0 > 0.0 || tv_pass > 0.0)) && forced_rounds_here < kMaxForcedRounds) {
                 forced_rounds_here += 1; count(kForcedRounds, 1); forced_dirty = true;
                 tepoch += 1;              // (the table's gradients have seen the undone moves)
                 __syncthreads();
@@ -1240,6 +1239,15 @@ enum { kCsNotNow = 0, kCsFinished = 1, kCsAgain = 2 };
 
 inline size_t cs_align(size_t v) { return (v + 255) / 256 * 256; }
 
+// dynamic LDS of k_cov_solve for `ucap` tracked coordinates: their Gram block (upper triangle, packed) and arrays (a shuffle's
+// scratch overlays them), and the most tracked coordinates a budget of that many bytes holds
+inline size_t cs_lds_bytes(int ucap) { return 8 * cs_tri_doubles((size_t)ucap) + (kCsTrackedBytes + 8) * (size_t)ucap; }
+inline int cs_ucap(size_t budget) {
+    int ucap = kCsUcapMax;
+    while (ucap > 8 && cs_lds_bytes(ucap) > budget) ucap -= 4;
+    return ucap;
+}
+
 // scratch of the kernel (122 p bytes of device memory) and the pinned block it reads the support from and writes its
 // results into (zero-copy, as the one-launch solve's: nothing is copied around the launch)
 int32_t cs_alloc(cdh_handle h) {
@@ -1354,12 +1362,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     if (h->x.nnz() > gc_max_support(h)) return not_now();
     // The LDS of workgroup 0 holds the Gram block of ~170 tracked coordinates (ucap); longer visit lists run from the Gram table
     // and with the helpers (see the header).
-    const size_t shuffle_bytes = 0;              // (a shuffle's scratch overlays the tracked Gram block)
-    int ucap = kCsUcapMax;
-    {
-        const size_t budget = c.cs_lds_budget ? c.cs_lds_budget : kCsLdsBudget;
-        while (ucap > 8 && 8 * cs_tri_doubles((size_t)ucap) + (kCsTrackedBytes + 8) * (size_t)ucap + shuffle_bytes > budget) ucap -= 4;
-    }
+    int ucap = cs_ucap(c.cs_lds_budget ? c.cs_lds_budget : kCsLdsBudget);      // (cs_alloc, below, sets the budget)
     // (visit lists beyond that run in the kernel's table mode, up to the table's rows)
     const int64_t support_cap = kCsTableCap - kCsTableMargin;
     if (h->x.nnz() > support_cap) return not_now();
@@ -1411,13 +1414,11 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) c.cs_in_sup[s_] = (int32_t)h->x.coord(s_);
     CovSolveBufs b = c.cs_bufs;
     b.g = c.d_g; b.Gcols = c.d_G; b.slot = c.d_slot; b.a = c.d_a; b.omega = h->omega; b.beta = h->beta;
-    // the tracked coordinates' Gram block (8 u^2 bytes) and arrays (kCsTrackedBytes u, rounded up) next to the shuffle's
-    ucap = kCsUcapMax;
-    while (ucap > 8 && 8 * cs_tri_doubles((size_t)ucap) + (kCsTrackedBytes + 8) * (size_t)ucap + shuffle_bytes > c.cs_lds_budget) ucap -= 4;
+    ucap = cs_ucap(c.cs_lds_budget);                // (the budget cs_alloc has settled on)
     // (table mode keeps a second block record and a 64 x 64 tile where the LDS Gram block of small lists would be: kCsTableLds doubles)
     if (cs_tri_doubles((size_t)ucap) < kCsTableLds) ctl.tcap = 0;
     if (ctl.tcap == 0 && h->x.nnz() > ucap - kCsTrackedMargin) return not_now();     // (the budget the runtime really granted is smaller)
-    const unsigned lds = (unsigned)(8 * cs_tri_doubles((size_t)ucap) + (kCsTrackedBytes + 8) * (size_t)ucap + shuffle_bytes);
+    const unsigned lds = (unsigned)cs_lds_bytes(ucap);
     if (o->randomize && 24 * ((size_t)h->p + 1) > (size_t)lds) return not_now();   // the shuffle's scratch overlays the dynamic LDS
     const int nh = ctl.tcap > 0 ? nhelp : 0;
     // the instantiation with the large-list paths once a list has outgrown the LDS block on this handle (or is about to: helpers are coming)
@@ -1490,9 +1491,8 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
         if (ctl.tcap == 0) return CDH_OK;                           // (no room for its scratch in LDS: the host's passes)
         c.cs_big = true; *outcome = kCsAgain; return CDH_OK;
     case kCsHostFull: return CDH_OK;                                // the next (full) pass runs the pass-by-pass way
-    case kCsBusy:     // many inactive coordinates about to move: back off (1, 2, 4 ... 16 plain passes), as gc_pass_device does
-        c.cooldown = c.backoff; c.backoff = std::min(16, 2 * c.backoff);
-        gc_invalidate(h, false);
+    case kCsBusy:     // many inactive coordinates about to move: back off, as gc_pass_device does
+        gc_back_off(h);
         c.prep_state = 2;
         return CDH_OK;
     case kCsNeedColumns: {
@@ -1500,13 +1500,13 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
         c.cs_stalled = ctl.passes == 0;
         c.backoff = 1;
         std::vector<int64_t> enter(c.cs_out_list, c.cs_out_list + ctl.n_list);
-        for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) return fail(h, CDH_BAD_ARG, "gradient cache: a moved coordinate has no Gram column");
+        CHK(gc_check_moved_columns(h));
         gc_fold(h);
         if (!c.valid) return CDH_OK;
         CHK(gc_need_host_g(h));
-        GcThresholds T{h, h->ctrl.lambda0, (double)h->n_total, 0.0, cert_abs};
-        if (h->loss == CDH_SQRT) { CHK(gc_ensure_q(h)); T.rnorm = std::sqrt(c.q); }
-        CHK(gc_fetch_entering(h, enter, [&](int64_t k) { return T.cert(k); }, [&](int64_t k) { return T.ratio(k); }));
+        GcThresholds T(h, cert_abs);
+        CHK(T.sync_rnorm());
+        CHK(gc_fetch_entering(h, enter, T));
         if (c.mode == 0) return CDH_OK;
         *outcome = kCsAgain;
         return CDH_OK;

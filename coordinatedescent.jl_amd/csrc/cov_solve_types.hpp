@@ -3,6 +3,10 @@
 #pragma once
 #include <stdint.h>
 
+// a full pass whose re-check found coordinates crossing their threshold through the pass's own moves is run again this
+// often with those coordinates visited (the host's device pass and the device-resident loop alike)
+constexpr int kMaxForcedRounds = 4;
+
 enum { kCsConverged = 0, kCsMaxIter = 1, kCsNeedColumns = 2, kCsRollback = 3, kCsBusy = 4, kCsRefresh = 5, kCsOutgrown = 6, kCsNeedQ = 7, kCsNeedFold = 8, kCsHostFull = 9, kCsCrewLost = 10, kCsNeedBig = 11 };
 
 struct CovSolveCtl {

@@ -183,7 +183,7 @@ int32_t gc_need_dev_g(cdh_handle h) {
     return CDH_OK;
 }
 
-// What the certificates must allow for besides the 1e-9 relative margin: with fp32 storage the residual is rounded to
+// What the certificates must allow for besides the relative margin kThrMargin: with fp32 storage the residual is rounded to
 // fp32 by every launch that rewrites it, and the streamed kernels' own dots carry fp32 chunk sums -- the cache's g,
 // carried in fp64 from Gram entries summed in fp64, describes a slightly DIFFERENT residual than the one the exact
 // visit would read.  A rounding of relative size 2^-24 per element and rewrite, U rewrites since the residual was last
@@ -465,13 +465,35 @@ int32_t gc_rereference(cdh_handle h) {
     return CDH_OK;
 }
 
-// G[(b0 + b) p + k] <- the cross products of one k_cross batch (records of 64 x 32, tile-major): the batch's columns, slot-major
+// G[(b0 + b) p + k] <- the cross products of one k_cross batch: the batch's columns, slot-major (the gradient cache's
+// device store, and the one-launch solve's full Gram matrix)
 __global__ __launch_bounds__(256) void k_cross_unpack(const double* __restrict__ cross, int64_t p, int b0, int nbc, double* __restrict__ Gcols) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= p) return;
     const int64_t L = k / kCrossA, i = k % kCrossA;
-    for (int b = 0; b < nbc; ++b)
-        Gcols[(int64_t)(b0 + b) * p + k] = cross[L * kCrossRec + ((i >> 4) * kCrossTB + (b >> 4)) * 256 + (i & 15) * 16 + (b & 15)];
+    for (int b = 0; b < nbc; ++b) Gcols[(int64_t)(b0 + b) * p + k] = cross[cross_rec_index(L, i, b)];
+}
+
+// c.d_cross <- the cross products X'X_j (X'WX_j) of the nbc <= 32 columns listed at d_cols (device memory): k_cross for the
+// handle's dtype and weights, then k_cross_reduce.  This rank's rows only (gc_fetch all-reduces them).
+int32_t cross_batch(cdh_handle h, const int64_t* d_cols, int nbc) {
+    GradCache& c = h->gc;
+    const int64_t launches = (h->p + kCrossA - 1) / kCrossA;      // column groups
+    CHK(dispatch(h, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        const dim3 grid((unsigned)c.cross_GX, (unsigned)c.cross_J), block(64 * kGramWaves);
+        if (h->has_w)   // G = X'WX (CDWeightedLSLoss: cd_differentiable_function.jl:177-182)
+            hipLaunchKernelGGL((k_cross<T, true, 2, 2, cross_occ<T>()>), grid, block, 0, h->stream, (const T*)h->X, h->ld, h->nvec, h->p, d_cols, nbc,
+                               (const T*)h->w, c.d_cross_part);
+        else
+            hipLaunchKernelGGL((k_cross<T, false, 2, 2, cross_occ<T>()>), grid, block, 0, h->stream, (const T*)h->X, h->ld, h->nvec, h->p, d_cols, nbc,
+                               (const T*)nullptr, c.d_cross_part);
+        return CDH_OK;
+    }));
+    hipLaunchKernelGGL(k_cross_reduce, dim3(kCrossRec / 256, (unsigned)launches), dim3(256), 0, h->stream, c.d_cross_part,
+                       c.cross_J, c.d_cross);
+    HIPCHK(h, hipGetLastError());
+    return CDH_OK;
 }
 
 // Gram columns G_j = X'X_j for the coordinates in `cols` (those not cached yet), up to 32 per pass over X
@@ -490,20 +512,7 @@ int32_t gc_fetch(cdh_handle h, const std::vector<int64_t>& cols) {
     for (size_t b0 = 0; b0 < todo.size(); b0 += batch) {
         const int nbc = (int)std::min<size_t>(batch, todo.size() - b0);
         HIPCHK(h, hipMemcpyAsync(c.d_cols, todo.data() + b0, sizeof(int64_t) * (size_t)nbc, hipMemcpyHostToDevice, h->stream));
-        CHK(dispatch(h, [&](auto* t) {
-            using T = std::remove_pointer_t<decltype(t)>;
-            const dim3 grid((unsigned)c.cross_GX, (unsigned)c.cross_J), block(64 * kGramWaves);
-            if (h->has_w)   // G = X'WX (CDWeightedLSLoss: cd_differentiable_function.jl:177-182)
-                hipLaunchKernelGGL((k_cross<T, true, 2, 2, cross_occ<T>()>), grid, block, 0, h->stream, (const T*)h->X, h->ld, h->nvec, h->p, c.d_cols, nbc,
-                                   (const T*)h->w, c.d_cross_part);
-            else
-                hipLaunchKernelGGL((k_cross<T, false, 2, 2, cross_occ<T>()>), grid, block, 0, h->stream, (const T*)h->X, h->ld, h->nvec, h->p, c.d_cols, nbc,
-                                   (const T*)nullptr, c.d_cross_part);
-            return CDH_OK;
-        }));
-        hipLaunchKernelGGL(k_cross_reduce, dim3(kCrossRec / 256, (unsigned)launches), dim3(256), 0, h->stream, c.d_cross_part,
-                           c.cross_J, c.d_cross);
-        HIPCHK(h, hipGetLastError());
+        CHK(cross_batch(h, c.d_cols, nbc));
         CHK(allreduce(h, c.d_cross, (size_t)launches * kCrossRec));
         c.n_batches += 1; c.n_columns += nbc;
         // Where the device store has room, the batch's columns go into it straight from the cross-product records (round 4):
@@ -529,10 +538,7 @@ int32_t gc_fetch(cdh_handle h, const std::vector<int64_t>& cols) {
             for (int b = 0; b < nbc; ++b) {
                 c.G.emplace_back((size_t)h->p, 0.0);
                 std::vector<double>& col = c.G.back();
-                for (int64_t k = 0; k < h->p; ++k) {
-                    const int64_t L = k / kCrossA, i = k % kCrossA;
-                    col[(size_t)k] = c.h_cross[(size_t)(L * kCrossRec + ((i >> 4) * kCrossTB + (b >> 4)) * 256 + (i & 15) * 16 + (b & 15))];
-                }
+                for (int64_t k = 0; k < h->p; ++k) col[(size_t)k] = c.h_cross[(size_t)cross_rec_index(k / kCrossA, k % kCrossA, b)];
                 c.slot[(size_t)todo[b0 + (size_t)b]] = (int32_t)(c.G.size() - 1);
             }
         }
@@ -592,20 +598,71 @@ void gc_fold(cdh_handle h) {
 
 int32_t run_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH);
 
-// The inactive coordinates of `enter` are about to move and have no Gram column: fetch their columns now, the batch
-// filled with the inactive coordinates nearest their certificate (on a lambda path: the next entrants).  Needs the
-// host copy of g.  `cert(k)`: the bound |g_k| is compared with; `ratio(k)`: |g_k| relative to its threshold.
-template <typename Cert, typename Ratio>
-int32_t gc_fetch_entering(cdh_handle h, std::vector<int64_t>& enter, Cert&& cert, Ratio&& ratio) {
+// The thresholds a visit is settled against, as the host evaluates them (k_cov_scan's, on the host).  rnorm: ||r|| for the
+// sqrt-lasso, read by sync_rnorm(); a walk that moves r visit by visit sets it itself.
+struct GcThresholds {
+    cdh_handle h; double lam, nt, cert_abs, rnorm = 0.0;
+    GcThresholds(cdh_handle h_, double cert_abs_) : h(h_), lam(h_->ctrl.lambda0), nt((double)h_->n_total), cert_abs(cert_abs_) {}
+    int32_t sync_rnorm() {
+        if (h->loss != CDH_SQRT) return CDH_OK;
+        CHK(gc_ensure_q(h));
+        rnorm = std::sqrt(h->gc.q);
+        return CDH_OK;
+    }
+    double thr_of(int64_t k) const {
+        const double w = h->has_omega ? h->h_omega[(size_t)k] : 1.0;
+        return (h->loss == CDH_SQRT ? lam * w * rnorm : lam * nt * w) * kThrMargin;
+    }
+    // the bound a certificate compares |g_k| with
+    double cert(int64_t k) const { return thr_of(k) - cert_abs * std::sqrt(h->gc.a[(size_t)k]); }
+    double ratio(int64_t k) const { return std::fabs(h->gc.g[(size_t)k]) / thr_of(k); }
+    // settled = the exact visit would leave beta_k at zero and r untouched (zero columns take the exact path)
+    bool settled(int64_t k, const std::vector<double>& g) const {
+        return h->x.get(k) == 0.0 && h->gc.a[(size_t)k] > 0.0 && std::fabs(g[(size_t)k]) <= cert(k);
+    }
+    bool settled(int64_t k) const { return settled(k, h->gc.g); }
+};
+
+// A settled visit (h = 0): what the reference's SparseIterate would have seen.  LS stores x[k] += b/a first, which makes a
+// slot when b != 0; cdprox! zeroes it.
+void replay_settled(cdh_handle h, int64_t k, bool made_slot) {
+    if (h->loss != CDH_SQRT && made_slot) h->x.set(k, 1.0);
+    h->x.set(k, 0.0);
+}
+
+// Busy (many inactive coordinates about to move): back off (1, 2, 4 ... 16 plain passes) so that dense problems pay next to nothing
+void gc_back_off(cdh_handle h) {
     GradCache& c = h->gc;
-    const size_t room = (kCrossB - enter.size() % kCrossB) % kCrossB;
+    c.cooldown = c.backoff; c.backoff = std::min(16, 2 * c.backoff);
+    gc_invalidate(h, false);
+}
+
+int32_t gc_check_moved_columns(cdh_handle h) {
+    for (int64_t j : h->gc.moved)
+        if (h->gc.slot[(size_t)j] < 0) return fail(h, CDH_BAD_ARG, "gradient cache: a moved coordinate has no Gram column");
+    return CDH_OK;
+}
+
+// Fill the last batch of 32 in `cols` with the inactive coordinates without a Gram column nearest their threshold: the
+// likeliest to enter the support next (on a lambda path: at one of the next lambdas).  within_cert: only those whose |g_k|
+// is within its certificate.  Needs the host copy of g.
+void gc_fill_batch(cdh_handle h, const GcThresholds& T, bool within_cert, std::vector<int64_t>& cols) {
+    GradCache& c = h->gc;
+    const size_t room = (kCrossB - cols.size() % kCrossB) % kCrossB;
+    if (room == 0) return;
     std::vector<std::pair<double, int64_t>> near;
-    for (int64_t k = 0; k < h->p && room > 0; ++k)
-        if (c.slot[(size_t)k] < 0 && h->x.get(k) == 0.0 && c.a[(size_t)k] > 0.0 && std::fabs(c.g[(size_t)k]) <= cert(k))
-            near.emplace_back(ratio(k), k);
+    for (int64_t k = 0; k < h->p; ++k)
+        if (c.slot[(size_t)k] < 0 && h->x.get(k) == 0.0 && c.a[(size_t)k] > 0.0 && (!within_cert || std::fabs(c.g[(size_t)k]) <= T.cert(k)))
+            near.emplace_back(T.ratio(k), k);
     const size_t take = std::min(room, near.size());
     std::partial_sort(near.begin(), near.begin() + (std::ptrdiff_t)take, near.end(), std::greater<std::pair<double, int64_t>>());
-    for (size_t i = 0; i < take; ++i) enter.push_back(near[i].second);
+    for (size_t i = 0; i < take; ++i) cols.push_back(near[i].second);
+}
+
+// The inactive coordinates of `enter` are about to move and have no Gram column: fetch their columns now, the batch
+// filled with the candidates whose certificate holds.  Needs the host copy of g.
+int32_t gc_fetch_entering(cdh_handle h, std::vector<int64_t>& enter, const GcThresholds& T) {
+    gc_fill_batch(h, T, true, enter);
     return gc_fetch(h, enter);
 }
 
@@ -620,10 +677,7 @@ int32_t gc_fetch_entering(cdh_handle h, std::vector<int64_t>& enter, Cert&& cert
 // test_covariance_chunks_roll_back...) restores g and beta from the scan's snapshot and leaves the pass to the
 // windowed walk below, which knows how to stop at the offending position.
 enum { kDevDone = 0, kDevPlain = 1, kDevWalk = 2 };
-constexpr int kGcForcedRounds = 4;     // a device pass whose re-check failed is run again this often with the failing coordinates visited
-template <typename Cert, typename Ratio>
-int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH, double cert_abs, Cert&& cert, Ratio&& ratio,
-                       int* outcome) {
+int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH, const GcThresholds& T, int* outcome) {
     GradCache& c = h->gc;
     *outcome = kDevWalk;
     if (!c.cov || !c.d_G || !c.d_scan || !c.moved.empty() || c.dev_slots != (int64_t)c.G.size() || m > h->cap) return CDH_OK;
@@ -651,7 +705,7 @@ int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* max
         h->ctrl.maxH = 0.0;
         h->ctrl.domain_error = 0;
         h->ctrl.q_carry = c.q;
-        h->ctrl.cert_abs = cert_abs;
+        h->ctrl.cert_abs = T.cert_abs;
         CHK(upload_ctrl(h));
         hipLaunchKernelGGL(k_cov_scan, dim3(1), dim3(1024), 0, h->stream, c.d_g, c.d_a, h->beta, h->omega, h->d_ctrl, c.d_pass_idx, (int)m,
                            h->p, c.d_pos_of, c.d_setflag, c.d_upos, h->d_idx, c.d_g_snap, c.d_beta_snap, c.d_scan, c.d_forced);
@@ -667,14 +721,13 @@ int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* max
         }
         if (enter.empty()) break;
         if (attempt > 0) return CDH_OK;             // cannot happen (the fetch below gave every one of them a column)
-        if ((int)enter.size() > kGcBusy) {          // busy: back off (1, 2, 4 ... 16 plain passes) so that dense problems pay next to nothing
-            c.cooldown = c.backoff; c.backoff = std::min(16, 2 * c.backoff);
-            gc_invalidate(h, false);
+        if ((int)enter.size() > kGcBusy) {
+            gc_back_off(h);
             *outcome = kDevPlain;
             return CDH_OK;
         }
         CHK(gc_need_host_g(h));
-        CHK(gc_fetch_entering(h, enter, cert, ratio));
+        CHK(gc_fetch_entering(h, enter, T));
         if (c.mode == 0) { *outcome = kDevPlain; return CDH_OK; }
     }
     c.backoff = 1;
@@ -697,7 +750,7 @@ int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* max
             // coordinates that crossed their threshold through the pass's own moves (the first full pass after lambda has changed,
             // on large supports: benchmark/cd_bench.jl's shape has them in most full passes beyond ~200 non-zeros): the same pass
             // again with those on the visit list -- a device pass, not the windowed walk
-            if (!injected && round < kGcForcedRounds) { c.forced_dirty = true; c.n_forced_rounds += 1; continue; }
+            if (!injected && round < kMaxForcedRounds) { c.forced_dirty = true; c.n_forced_rounds += 1; continue; }
             c.n_rollbacks += 1;
             return CDH_OK;                          // -> the windowed walk
         }
@@ -712,10 +765,7 @@ int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* max
     for (int64_t q = 0; q < m; ++q) {
         const int64_t k = idx0[q];
         if (j < cnt && c.h_upos[j] == (int32_t)q) { cov_apply_visit(h, k, j); ++j; }
-        else {                                       // settled, g_k != 0: LS stores x[k] += b/a first, cdprox! zeroes it
-            if (h->loss != CDH_SQRT) h->x.set(k, 1.0);
-            h->x.set(k, 0.0);
-        }
+        else replay_settled(h, k, true);             // settled, g_k != 0 (the scan stopped the pass on nzero > 0)
     }
     c.n_exact += cnt; c.n_certified += m - cnt; c.n_dev_passes += 1;
     cov_accept_tail(h, cnt, maxH, false);
@@ -727,15 +777,6 @@ int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* max
 // (re-reference when there is none or the carried one is due; the Gram columns of the support and of what has moved,
 // the last batch filled with the inactive coordinates nearest their threshold; the fold) and ||r|| for the sqrt-lasso.
 // *go = false: the pass runs the plain way.  Shared by gc_full_pass and the device-resident solve (cov_solve.hpp).
-struct GcThresholds {             // the certificates' bounds as the host evaluates them (k_cov_scan's, on the host)
-    cdh_handle h; double lam, nt, rnorm, cert_abs;
-    double thr_of(int64_t k) const {
-        const double w = h->has_omega ? h->h_omega[(size_t)k] : 1.0;
-        return (h->loss == CDH_SQRT ? lam * w * rnorm : lam * nt * w) * (1.0 - 1e-9);
-    }
-    double cert(int64_t k) const { return thr_of(k) - cert_abs * std::sqrt(h->gc.a[(size_t)k]); }
-    double ratio(int64_t k) const { return std::fabs(h->gc.g[(size_t)k]) / thr_of(k); }
-};
 int32_t gc_prepare_full(cdh_handle h, bool* go, double* cert_abs_out, bool fold = true /* false: the caller carries the pending moves itself (cov_solve) */) {
     GradCache& c = h->gc;
     *go = false;
@@ -772,25 +813,17 @@ int32_t gc_prepare_full(cdh_handle h, bool* go, double* cert_abs_out, bool fold 
     for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_)       // the support moves in every pass: its columns first
         if (c.slot[(size_t)h->x.coord(s_)] < 0) want.push_back(h->x.coord(s_));
     if (!want.empty()) {
-        // fill the last batch of 32 with the inactive coordinates nearest their threshold: the likeliest to
-        // enter the support next (on a lambda path: at one of the next lambdas)
-        const size_t room = (kCrossB - want.size() % kCrossB) % kCrossB;
-        if (room > 0 && c.moved.empty()) {
+        // the last batch of 32 filled with whatever has no column yet, certificate or not
+        if (want.size() % kCrossB != 0 && c.moved.empty()) {
             CHK(gc_need_host_g(h));
-            GcThresholds T{h, h->ctrl.lambda0, (double)h->n_total, 0.0, cert_abs};
-            if (h->loss == CDH_SQRT) { CHK(gc_ensure_q(h)); T.rnorm = std::sqrt(c.q); }
-            std::vector<std::pair<double, int64_t>> near;
-            for (int64_t k = 0; k < h->p; ++k)
-                if (c.slot[(size_t)k] < 0 && h->x.get(k) == 0.0 && c.a[(size_t)k] > 0.0)
-                    near.emplace_back(std::fabs(c.g[(size_t)k]) / T.thr_of(k), k);
-            const size_t take = std::min(room, near.size());
-            std::partial_sort(near.begin(), near.begin() + (std::ptrdiff_t)take, near.end(), std::greater<std::pair<double, int64_t>>());
-            for (size_t i = 0; i < take; ++i) want.push_back(near[i].second);
+            GcThresholds T(h, cert_abs);
+            CHK(T.sync_rnorm());
+            gc_fill_batch(h, T, false, want);
         }
         CHK(gc_fetch(h, want));
         if (c.mode == 0) return CDH_OK;
     }
-    for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) return fail(h, CDH_BAD_ARG, "gradient cache: a moved coordinate has no Gram column");
+    CHK(gc_check_moved_columns(h));
     if (fold) gc_fold(h);
     if (!c.valid) return CDH_OK;      // (a device fold that failed hard leaves no gradient: the pass runs the plain way)
     gc_q_guard(h);
@@ -810,32 +843,13 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
         else CHK(gc_prepare_full(h, &go, &cert_abs));
         if (!go) return CDH_OK;
     }
-    const double lam = h->ctrl.lambda0, nt = (double)h->n_total;
-    const std::vector<double>& om = h->h_omega;
-    double rnorm = 0.0;
-    auto refresh_rnorm = [&]() -> int32_t {
-        if (h->loss != CDH_SQRT) return CDH_OK;
-        CHK(gc_ensure_q(h));
-        rnorm = std::sqrt(c.q);
-        return CDH_OK;
-    };
-    auto thr_of = [&](int64_t k) {
-        const double w = h->has_omega ? om[(size_t)k] : 1.0;
-        return (h->loss == CDH_SQRT ? lam * w * rnorm : lam * nt * w) * (1.0 - 1e-9);
-    };
-    // the bound a certificate compares |g_k| with (k_cov_scan's, on the host)
-    auto cert = [&](int64_t k) { return thr_of(k) - cert_abs * std::sqrt(c.a[(size_t)k]); };
-    auto ratio = [&](int64_t k) { return std::fabs(c.g[(size_t)k]) / thr_of(k); };
-    // settled = the exact visit would leave beta_k at zero and r untouched (zero columns take the exact path)
-    auto settled = [&](int64_t k) {
-        return h->x.get(k) == 0.0 && c.a[(size_t)k] > 0.0 && std::fabs(c.g[(size_t)k]) <= cert(k);
-    };
-    CHK(refresh_rnorm());
+    GcThresholds T(h, cert_abs);
+    CHK(T.sync_rnorm());
     // 2. the whole pass on the device where it can be (g stays there); else -- and after a failed re-check -- the
     //    windowed walk below, with g on the host
     {
         int outcome = kDevWalk;
-        CHK(gc_pass_device(h, idx0, m, maxH, cert_abs, cert, ratio, &outcome));
+        CHK(gc_pass_device(h, idx0, m, maxH, T, &outcome));
         if (outcome == kDevDone) { *handled = true; c.n_passes += 1; return CDH_OK; }
         if (outcome == kDevPlain) return CDH_OK;
         if (!c.valid) return CDH_OK;
@@ -845,19 +859,15 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
     std::vector<int64_t> enter;
     for (int64_t i = 0; i < m; ++i) {
         const int64_t k = idx0[i];
-        if (h->x.get(k) == 0.0 && !settled(k) && c.slot[(size_t)k] < 0) enter.push_back(k);
+        if (h->x.get(k) == 0.0 && !T.settled(k) && c.slot[(size_t)k] < 0) enter.push_back(k);
     }
     std::sort(enter.begin(), enter.end());
     enter.erase(std::unique(enter.begin(), enter.end()), enter.end());
-    if ((int)enter.size() > kGcBusy) {   // busy: back off (1, 2, 4 ... 16 plain passes) so that dense problems pay next to nothing
-        c.cooldown = c.backoff; c.backoff = std::min(16, 2 * c.backoff);
-        gc_invalidate(h, false);
-        return CDH_OK;
-    }
+    if ((int)enter.size() > kGcBusy) { gc_back_off(h); return CDH_OK; }
     c.backoff = 1;
     if (!enter.empty()) {
         // their columns now, with the nearest other candidates filling the batch
-        CHK(gc_fetch_entering(h, enter, cert, ratio));
+        CHK(gc_fetch_entering(h, enter, T));
         if (c.mode == 0) return CDH_OK;
     }
     *handled = true;
@@ -870,9 +880,8 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
     while (pos < m) {
         CHK(gc_need_host_g(h));       // (a covariance-form chunk or a device fold below leaves g on the device)
         const int64_t k = idx0[pos];
-        if (settled(k)) {
-            if (h->loss != CDH_SQRT && c.g[(size_t)k] != 0.0) h->x.set(k, 1.0);   // x[k] += b/a stores a slot ...
-            h->x.set(k, 0.0);                                                          // ... cdprox! zeroes it
+        if (T.settled(k)) {
+            replay_settled(h, k, c.g[(size_t)k] != 0.0);
             c.n_certified += 1;
             ++pos;
             continue;
@@ -887,7 +896,7 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
             int64_t wend = pos;
             bool have_all = true;
             for (; wend < m && (int64_t)upos.size() < maxlen && wend - pos < kGcCovWindow; ++wend)
-                if (!settled(idx0[wend])) {
+                if (!T.settled(idx0[wend])) {
                     if (c.slot[(size_t)idx0[wend]] < 0) { have_all = false; break; }
                     upos.push_back(wend);
                 }
@@ -901,12 +910,9 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
                     // re-check the skipped positions in visit order, carrying g through the chunk's moves
                     std::vector<double> gv(c.g);
                     double q_run = c.q;                  // sqrt-lasso: ||r|| moves with every visit, and the thresholds with it
-                    const double rnorm_before = rnorm;
+                    const double rnorm_before = T.rnorm;
                     int64_t bad = -1;
                     size_t iu = 0;
-                    auto settled_at = [&](int64_t kq) {
-                        return h->x.get(kq) == 0.0 && c.a[(size_t)kq] > 0.0 && std::fabs(gv[(size_t)kq]) <= cert(kq);
-                    };
                     for (int64_t q = pos; q < wend; ++q) {
                         if (iu < upos.size() && upos[iu] == q) {
                             const double hv = h->h_hs[iu];
@@ -915,29 +921,25 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
                                 if (h->loss == CDH_SQRT) {
                                     q_run = q_run - 2.0 * hv * gv[(size_t)kv] + hv * hv * c.a[(size_t)kv];
                                     if (q_run < 0.0) q_run = 0.0;
-                                    rnorm = std::sqrt(q_run);
+                                    T.rnorm = std::sqrt(q_run);
                                 }
                                 CHK(gc_host_column(h, c.slot[(size_t)kv]));
                                 const std::vector<double>& col = c.G[(size_t)c.slot[(size_t)kv]];
                                 for (int64_t kk = 0; kk < h->p; ++kk) gv[(size_t)kk] -= hv * col[(size_t)kk];
                             }
                             ++iu;
-                        } else if (!settled_at(idx0[q])) { bad = q; break; }
+                        } else if (!T.settled(idx0[q], gv)) { bad = q; break; }
                     }
-                    rnorm = rnorm_before;
+                    T.rnorm = rnorm_before;
                     if (bad < 0) {
                         iu = 0;
                         for (int64_t q = pos; q < wend; ++q) {      // bookkeeping in visit order
                             const int64_t kq = idx0[q];
                             if (iu < upos.size() && upos[iu] == q) { cov_apply_visit(h, kq, (int)iu); ++iu; c.n_exact += 1; }
-                            else {   // settled: what the reference's SparseIterate would have seen (LS stores x[k] += b/a first)
-                                if (h->loss != CDH_SQRT && c.g[(size_t)kq] != 0.0) h->x.set(kq, 1.0);
-                                h->x.set(kq, 0.0);
-                                c.n_certified += 1;
-                            }
+                            else { replay_settled(h, kq, c.g[(size_t)kq] != 0.0); c.n_certified += 1; }
                         }
                         cov_accept_tail(h, mv, maxH, true);
-                        if (h->loss == CDH_SQRT) rnorm = std::sqrt(c.q);
+                        if (h->loss == CDH_SQRT) T.rnorm = std::sqrt(c.q);
                         break;
                     }
                     CHK(cov_reject(h, vis.data(), mv));
@@ -953,7 +955,7 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
         // streamed visits [pos, end): up to the last unsettled position that is no more than 4 past the previous one
         int64_t end = pos + 1;
         for (int64_t q = pos + 1; q < m && q - end < 4 && end - pos < maxlen; ++q)
-            if (!settled(idx0[q])) end = q + 1;
+            if (!T.settled(idx0[q])) end = q + 1;
         if (cov_ok(h, idx0 + pos, end - pos)) CHK(cov_chunk(h, idx0 + pos, (int)(end - pos), maxH));
         else CHK(run_chunk(h, idx0 + pos, (int)(end - pos), maxH));
         c.n_exact += end - pos;
@@ -964,7 +966,7 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
             for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) miss.push_back(j);
             if (!miss.empty()) { CHK(gc_fetch(h, miss)); if (c.mode == 0) break; }
             gc_fold(h);
-            CHK(refresh_rnorm());
+            CHK(T.sync_rnorm());
         }
     }
     if (pos < m) {   // the cache went away mid-pass: the rest of the list the plain way, chunk by chunk

@@ -606,6 +606,10 @@ __global__ __launch_bounds__(64) void k_gram_scalar(const double* __restrict__ r
 // piece of w per sub-chunk, fetched by every wave to the same place so that all waves count the same loads).
 constexpr int kCrossTA = 4, kCrossTB = 2, kCrossA = 16 * kCrossTA, kCrossB = 16 * kCrossTB,
               kCrossRec = kCrossTA * kCrossTB * 256;
+// where G[k][b] (row k = L kCrossA + i, the batch's column b) sits in k_cross_reduce's output: records of 64 x 32, tile-major
+__host__ __device__ inline int64_t cross_rec_index(int64_t L, int64_t i, int b) {
+    return L * kCrossRec + ((i >> 4) * kCrossTB + (b >> 4)) * 256 + (i & 15) * 16 + (b & 15);
+}
 constexpr int kCrossSlab = 1024;         // vectors per row slab (fp64: 2048 rows)
 constexpr int kCrossOcc = 3;             // blocks per CU of k_cross (its 44 KB of LDS and 151 registers allow three)
 // ... of the fp64 kernel.  The fp32 one keeps fp32 tiles next to the fp64 running tiles (32 more registers): two blocks per CU
@@ -876,9 +880,9 @@ __global__ __launch_bounds__(256) void k_cov_block(const double* __restrict__ g,
 // ---- a whole full pass from the cache, on the device (grad_cache.hpp: gc_pass_device) ------------------------------
 // A visit of coordinate k is SETTLED when the exact visit would leave beta_k at zero and r untouched:
 //   beta_k == 0, a_k > 0 (a zero column goes to the exact path: the reference turns it into NaN) and
-//   |g_k| <= thr_k (1 - 1e-9) - cert_abs sqrt(a_k),   thr_k = lambda0 omega_k n   (sqrt-lasso: lambda0 omega_k ||r||).
+//   |g_k| <= thr_k kThrMargin - cert_abs sqrt(a_k),   thr_k = lambda0 omega_k n   (sqrt-lasso: lambda0 omega_k ||r||).
 __device__ __forceinline__ bool cov_settled(double g, double a, double beta, double thr_base, double om, double cert_abs) {
-    return beta == 0.0 && a > 0.0 && fabs(g) <= thr_base * om * (1.0 - 1e-9) - cert_abs * sqrt(a);
+    return beta == 0.0 && a > 0.0 && fabs(g) <= thr_base * om * kThrMargin - cert_abs * sqrt(a);
 }
 struct CovScanOut { int32_t count, nzero, bad_pos, pad; };
 // One block: classifies the m positions of the pass against the gradient as it stands, compacts the UNSETTLED ones in
@@ -979,7 +983,7 @@ __global__ __launch_bounds__(256) void k_cov_gupdate_chk(double* __restrict__ g,
     double acc = g[k], q_run = *q_start;
     double cert_scale = 0.0, cert_off = 0.0;
     if (need) {
-        cert_scale = ctrl->lambda0 * (ctrl->has_omega ? omega[k] : 1.0) * (1.0 - 1e-9);
+        cert_scale = ctrl->lambda0 * (ctrl->has_omega ? omega[k] : 1.0) * kThrMargin;
         cert_off = ctrl->cert_abs * sqrt(a[k]);
     }
     const double n_total = ctrl->n_total;

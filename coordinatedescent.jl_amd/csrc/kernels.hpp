@@ -37,9 +37,13 @@ struct Ctrl {
     int32_t domain_error;
     int32_t pad;
     double q_carry;      // r'r carried from block to block by the covariance-form visits (sqrt-lasso)
-    double cert_abs;     // gradient-cache certificates: |g_k| <= thr_k (1 - 1e-9) - cert_abs sqrt(a_k); 0 for fp64 storage,
+    double cert_abs;     // gradient-cache certificates: |g_k| <= thr_k kThrMargin - cert_abs sqrt(a_k); 0 for fp64 storage,
                          // the rounding of an fp32 residual otherwise (cdhip.hip, gc_cert_abs)
 };
+
+// The relative margin of every "settled without a visit" threshold (screens, gradient-cache certificates, the device
+// loop's bounds): borderline coordinates take the exact path.
+constexpr double kThrMargin = 1.0 - 1e-9;
 
 // 16-byte native vectors (clang ext_vector_type: element access v[e] stays in registers and
 // __builtin_nontemporal_load accepts them).

@@ -435,17 +435,6 @@ __global__ __launch_bounds__(64) void k_solve_small(SmallCtl* ctl, int p, int nc
     }
 }
 
-// G[k][b0 + b] <- the cross products of one k_cross batch (records of 64 x 32, tile-major): the batch's columns of the
-// full Gram matrix, without a trip through the host
-__global__ __launch_bounds__(256) void k_small_unpack(const double* __restrict__ cross, int64_t p, int b0, int nbc,
-                                                      double* __restrict__ Gfull) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= p) return;
-    const int64_t L = k / kCrossA, i = k % kCrossA;
-    for (int b = 0; b < nbc; ++b)
-        Gfull[(int64_t)(b0 + b) * p + k] = cross[L * kCrossRec + ((i >> 4) * kCrossTB + (b >> 4)) * 256 + (i & 15) * 16 + (b & 15)];
-}
-
 // ---- host side ---------------------------------------------------------------------------------------------------
 inline size_t small_sup_off() { return (sizeof(SmallCtl) + 15) / 16 * 16; }
 inline size_t small_beta_off(int64_t p) { return small_sup_off() + ((size_t)p * sizeof(int32_t) + 15) / 16 * 16; }
@@ -553,7 +542,6 @@ int32_t small_prepare(cdh_handle h) {     // buffers, X'y and diag(G) of the cur
         sp.c_valid = true;
     }
     if (sp.G_valid) return CDH_OK;
-    const int64_t launches = (h->p + kCrossA - 1) / kCrossA;
     if (!sp.d_iota) {                 // the column lists of all batches, uploaded once: the batches then run back to back
         std::vector<int64_t> iota((size_t)h->p);
         for (int64_t k = 0; k < h->p; ++k) iota[(size_t)k] = k;
@@ -565,22 +553,8 @@ int32_t small_prepare(cdh_handle h) {     // buffers, X'y and diag(G) of the cur
     }
     for (int64_t b0 = 0; b0 < h->p; b0 += kCrossB) {
         const int nbc = (int)std::min<int64_t>(kCrossB, h->p - b0);
-        const int64_t* cols = sp.d_iota + b0;
-        CHK(dispatch(h, [&](auto* t) {
-            using T = std::remove_pointer_t<decltype(t)>;
-            const dim3 grid((unsigned)c.cross_GX, (unsigned)c.cross_J), block(64 * kGramWaves);
-            if (h->has_w)
-                hipLaunchKernelGGL((k_cross<T, true, 2, 2, cross_occ<T>()>), grid, block, 0, h->stream, (const T*)h->X, h->ld, h->nvec, h->p, cols, nbc,
-                                   (const T*)h->w, c.d_cross_part);
-            else
-                hipLaunchKernelGGL((k_cross<T, false, 2, 2, cross_occ<T>()>), grid, block, 0, h->stream, (const T*)h->X, h->ld, h->nvec, h->p, cols, nbc,
-                                   (const T*)nullptr, c.d_cross_part);
-            return CDH_OK;
-        }));
-        hipLaunchKernelGGL(k_cross_reduce, dim3(kCrossRec / 256, (unsigned)launches), dim3(256), 0, h->stream, c.d_cross_part,
-                           c.cross_J, c.d_cross);
-        hipLaunchKernelGGL(k_small_unpack, dim3((unsigned)((h->p + 255) / 256)), dim3(256), 0, h->stream, c.d_cross, h->p, (int)b0, nbc,
-                           sp.d_G);
+        CHK(cross_batch(h, sp.d_iota + b0, nbc));
+        hipLaunchKernelGGL(k_cross_unpack, dim3((unsigned)((h->p + 255) / 256)), dim3(256), 0, h->stream, c.d_cross, h->p, (int)b0, nbc, sp.d_G);
         HIPCHK(h, hipGetLastError());
     }
     sp.G_valid = true;
