@@ -17,4 +17,6 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   OrderedIterator, RandomIterator, reset_, numCoordinates, initialize_, gradient,
                   descendCoordinate_, coordinateDescent_, cdPass_, findLambdaMax, stdX, objective,
                   lasso, sqrtLasso, scaledLasso_, LassoPath, LassoSolution, LassoPathResult,
+                  SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
+                  get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1,
                   DimensionMismatch, ArgumentError, DomainError, HipError)

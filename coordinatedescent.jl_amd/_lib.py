@@ -27,6 +27,7 @@ CDH_OK, CDH_DIM_MISMATCH, CDH_BAD_ARG, CDH_DOMAIN, CDH_HIP_ERROR, CDH_RCCL_ERROR
 CDH_F64, CDH_F32 = 0, 1
 CDH_LS, CDH_SQRT, CDH_WLS = 0, 1, 2
 CDH_SWEEP_COORD, CDH_SWEEP_BLOCK = 0, 1
+CDH_VC_GAUSSIAN, CDH_VC_EPANECHNIKOV = 0, 1
 
 
 class DimensionMismatch(Exception):
@@ -110,6 +111,7 @@ def lib():
         "cdh_set_y": [vp, vp],
         "cdh_get_y": [vp, vp],
         "cdh_set_obs_weights": [vp, vp],
+        "cdh_get_obs_weights": [vp, vp],
         "cdh_set_loss": [vp, i32],
         "cdh_generate": [vp, C.c_uint64, i64, f64, vp],
         "cdh_set_penalty": [vp, f64, vp, i64],
@@ -129,6 +131,10 @@ def lib():
         "cdh_xt_r": [vp, vp],
         "cdh_gram": [vp, i64, vp, vp, vp, P(f64)],
         "cdh_xt_r_cols": [vp, i64, vp, vp],
+        "cdh_gram_weighted": [vp, i64, vp, vp, vp, P(f64)],
+        "cdh_col_wrms": [vp, vp],
+        "cdh_vc_set_data": [vp, i64, i32, vp, i64, vp],
+        "cdh_vc_set_point": [vp, i32, f64, f64, vp],
         "cdh_resid_std": [vp, P(f64), P(f64)],
         "cdh_set_reuse_residual": [vp, i32],
         "cdh_resid_moments": [vp, P(f64), P(f64)],

@@ -15,6 +15,7 @@ Reference files mirrored (relative to the reference's src/):
   coordinate_descent.jl              coordinateDescent!, _findLambdaMax
   atom_iterator.jl                   OrderedIterator, RandomIterator
   lasso.jl                           lasso, sqrtLasso, scaledLasso!, LassoPath
+  varying_coefficient_lasso.jl       the smoothing kernels, locpolyl1, get_nonzero_coordinates
   ProximalBase 0.3.0 (not vendored)  ProxL1, SparseIterate (contract: SURVEY.md App. B)
 """
 from __future__ import annotations
@@ -27,6 +28,7 @@ import numpy as np
 from . import _lib
 from ._lib import (ArgumentError, DimensionMismatch, DomainError, HipError,  # noqa: F401
                    CDH_F32, CDH_F64, CDH_LS, CDH_SQRT, CDH_WLS, CDH_SWEEP_BLOCK, CDH_SWEEP_COORD,
+                   CDH_VC_EPANECHNIKOV, CDH_VC_GAUSSIAN,
                    cdh_options, cdh_stats, check)
 
 
@@ -272,6 +274,13 @@ class _HipLoss(CoordinateDifferentiableFunction):
         check(self._L.cdh_get_y(self._h, _vp(out)), self._h)
         return out
 
+    @property
+    def w(self):
+        """f.w: the observation weights of a weighted loss (copied from HBM)."""
+        out = np.zeros(self.n, dtype=self.dtype)
+        check(self._L.cdh_get_obs_weights(self._h, _vp(out)), self._h)
+        return out
+
     def X_cols(self, j0, ncols):
         """Columns [j0, j0+ncols) (0-based bulk helper) copied back from HBM."""
         out = np.zeros((self.n, ncols), dtype=self.dtype, order="F")
@@ -469,6 +478,96 @@ class CDWeightedLSLoss(_HipLoss):
         super().__init__(y, X, w, **kw)
 
 
+# --------------------------------------------------------------------------------------
+# Smoothing kernels (src/varying_coefficient_lasso.jl:3-21)
+# --------------------------------------------------------------------------------------
+class SmoothingKernel:
+    """abstract type SmoothingKernel{T} (src/varying_coefficient_lasso.jl:3); field h, the bandwidth."""
+    _kind = None
+
+    def __init__(self, h):
+        self.h = float(h)
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.h!r})"
+
+
+class GaussianKernel(SmoothingKernel):
+    """GaussianKernel(h) (:6-8)."""
+    _kind = CDH_VC_GAUSSIAN
+
+
+class EpanechnikovKernel(SmoothingKernel):
+    """EpanechnikovKernel(h) (:10-12)."""
+    _kind = CDH_VC_EPANECHNIKOV
+
+
+def createKernel(kernelType, h):
+    """createKernel(::Type{K}, h) (:14-15)."""
+    if not (isinstance(kernelType, type) and issubclass(kernelType, SmoothingKernel) and kernelType._kind is not None):
+        raise TypeError("MethodError: createKernel(::Type{<:SmoothingKernel}, h)")
+    return kernelType(h)
+
+
+def evaluate(k, x, y):
+    """evaluate(k, x, y) (:17-21), on the host and as the reference writes it -- not the textbook forms: the Gaussian is
+    exp(-(x-y)^2 / h) / h, the Epanechnikov 0.75 (1 - u^2) / h with u = (x-y) / h, zero from |u| = 1 on.  Broadcasts."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if isinstance(k, GaussianKernel):
+        out = np.exp(-(x - y) ** 2 / k.h) / k.h
+    elif isinstance(k, EpanechnikovKernel):
+        u = (x - y) / k.h
+        out = np.where(np.abs(u) >= 1.0, 0.0, 0.75 * (1.0 - u * u) / k.h)
+    else:
+        raise TypeError("MethodError: evaluate(k::SmoothingKernel, x, y)")
+    return float(out) if out.ndim == 0 else out
+
+
+def get_nonzero_coordinates(beta, p, degree, expanded):
+    """get_nonzero_coordinates(β, p, degree, expanded) (:479-512): which of the p groups of degree + 1 consecutive
+    coefficients hold a non-zero -- as a mask over the p (degree + 1) coefficients (expanded) or over the p groups."""
+    b = beta.dense() if isinstance(beta, SparseIterate) else np.asarray(beta, dtype=np.float64)
+    if b.shape[0] != p * (degree + 1):
+        raise DimensionMismatch("length(β) != p * (degree + 1)")
+    groups = (b.reshape(p, degree + 1) != 0.0).any(axis=1)
+    return np.repeat(groups, degree + 1) if expanded else groups
+
+
+class CDVaryingCoefficientLoss(CDWeightedLSLoss):
+    """The CDWeightedLSLoss(y, expandX, w) that locpolyl1 keeps rewriting (src/varying_coefficient_lasso.jl:50-65), with the
+    base design X (n x p) and z resident in HBM: `set_point` regenerates the kernel weights, the expanded design
+    X[i,:] ⊗ [1, (z_i - z0), ..., (z_i - z0)^degree] and its weighted column scales on the device for a new z0
+    (cdh_vc_set_data / cdh_vc_set_point).  numCoordinates is p (degree + 1); base column j is expanded column j (degree + 1)."""
+
+    def __init__(self, y, X, z, degree, *, device=0):
+        X, y, z = np.asarray(X), np.asarray(y), np.asarray(z)
+        if X.dtype not in (np.float64, np.float32) or y.dtype != X.dtype or z.dtype != X.dtype or X.ndim != 2:
+            raise TypeError("MethodError: X::Matrix{T}, z::Vector{T}, y::Vector{T}, T<:AbstractFloat")
+        if y.shape[0] != X.shape[0]:
+            raise DimensionMismatch("length(y) != size(X, 1)")
+        if z.shape[0] != X.shape[0]:
+            raise DimensionMismatch("length(z) != size(X, 1)")
+        degree = int(degree)
+        if not 0 <= degree <= 3:
+            raise ArgumentError("the polynomial degree must be 0 .. 3")
+        n, pb = X.shape
+        self.p_base, self.degree = int(pb), degree
+        self._create(X.dtype, n, pb * (degree + 1), device, None, 0)
+        Xf, zz = np.asfortranarray(X), np.ascontiguousarray(z)
+        check(self._L.cdh_vc_set_data(self._h, pb, degree, _vp(Xf), n, _vp(zz)), self._h)
+        check(self._L.cdh_set_y(self._h, _vp(np.ascontiguousarray(y))), self._h)
+        self.point_stats = []
+
+    def set_point(self, kernel, z0):
+        """w .= evaluate.(kernel, z, z0); _expand_X!(expandX, X, z, z0, degree); _stdX!(stdX, w, expandX) (:63-65) on the
+        device; returns stdX.  The iterate the handle holds is kept (the next solve warm-starts from it)."""
+        if not isinstance(kernel, SmoothingKernel) or kernel._kind is None:
+            raise TypeError("MethodError: kernel::SmoothingKernel")
+        out = np.zeros(self.p)
+        check(self._L.cdh_vc_set_point(self._h, kernel._kind, kernel.h, float(z0), _vp(out)), self._h)
+        return out
+
+
 def initialize_(f, x):
     """initialize!(f, x): r = y - Xβ (src/cd_differentiable_function.jl:59-72)."""
     f._push(x, rebuild=True)
@@ -606,10 +705,11 @@ def findLambdaMax(x, f, g):
     return out.value
 
 
-def stdX(f):
-    """_stdX!(out, X) (src/utils.jl:127-138) for the X resident behind loss f."""
+def stdX(f, weighted=False):
+    """_stdX!(out, X) (src/utils.jl:127-138) for the X resident behind loss f; weighted: _stdX!(out, w, X) (:140-151)
+    with the observation weights of a CDWeightedLSLoss."""
     out = np.zeros(f.p)
-    check(f._L.cdh_col_rms(f._h, _vp(out)), f._h)
+    check((f._L.cdh_col_wrms if weighted else f._L.cdh_col_rms)(f._h, _vp(out)), f._h)
     return out
 
 
@@ -779,3 +879,54 @@ def LassoPath(X, Y, lambdapath, options=None, max_hat_s=np.inf, standardizeX=Tru
         if mode_before == 1:
             check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
     return LassoPathResult(lambdapath, betapath)
+
+
+# --------------------------------------------------------------------------------------
+# Varying-coefficient lasso (src/varying_coefficient_lasso.jl:30-79)
+# --------------------------------------------------------------------------------------
+def _vc_refit(f, beta, S):
+    """(Xs'W Xs) \\ (Xs'W y) (:73-75) without a second copy of y or anything n-sized on the host: with β supported inside S,
+    Xs'Wy = Xs'Wr + (Xs'WXs) β_S, so the solution is β_S + (Xs'WXs)⁻¹ Xs'Wr -- one weighted Gram block at the solve's own
+    residual, solved on the host after scaling it to unit diagonal."""
+    idx1 = np.ascontiguousarray(np.nonzero(S)[0] + 1, dtype=np.int64)
+    m = idx1.shape[0]
+    if m > 4096:
+        raise ArgumentError("refit support larger than 4096 columns")
+    G, c = np.zeros((m, m)), np.zeros(m)
+    check(f._L.cdh_gram_weighted(f._h, m, _vp(idx1), _vp(G), _vp(c), None), f._h)
+    d = np.sqrt(np.diag(G))
+    return beta[idx1 - 1] + np.linalg.solve(G / np.outer(d, d), c / d) / d
+
+
+def locpolyl1(X, z, y, zgrid, degree, kernel, lambda0, refit, options=None):
+    """locpolyl1(X, z, y, zgrid, degree, kernel, λ0, refit, options) (src/varying_coefficient_lasso.jl:30-79) ->
+    (out, outR), two dense p (degree + 1) x length(zgrid) arrays (the reference returns them sparse).  β is carried from one
+    grid point to the next (the inner options force warmStart, :39-42).  X may also be an existing
+    CDVaryingCoefficientLoss (data already resident in HBM); z, y and degree are then the loss's own.  The statistics of
+    every solve and the support in SparseIterate order are appended to f.point_stats."""
+    o = options or CDOptions()
+    opt = CDOptions(o.maxIter, o.optTol, o.randomize, True, o.numSteps, o.seed)
+    if isinstance(X, CDVaryingCoefficientLoss):
+        f = X
+    else:
+        X = np.asarray(X)
+        if np.asarray(z).shape[0] != X.shape[0]:
+            raise DimensionMismatch("length(z) != size(X, 1)")
+        if np.asarray(y).shape[0] != X.shape[0]:
+            raise DimensionMismatch("length(y) != size(X, 1)")
+        f = CDVaryingCoefficientLoss(y, X, z, degree)
+    zgrid = np.atleast_1d(np.asarray(zgrid, dtype=np.float64))
+    ep = f.p
+    out, outR = np.zeros((ep, zgrid.shape[0])), np.zeros((ep, zgrid.shape[0]))
+    beta = SparseIterate(ep)
+    for ind, z0 in enumerate(zgrid):
+        sx = f.set_point(kernel, z0)                                   # :63-65
+        coordinateDescent_(beta, f, ProxL1(lambda0, sx), opt)          # :68
+        f.point_stats.append(dict(f.last_stats, support=beta.nzval2ind.copy()))
+        b = beta.dense()
+        out[:, ind] = b
+        if refit:                                                      # :71-76
+            S = get_nonzero_coordinates(b, f.p_base, f.degree, True)
+            if S.any():
+                outR[S, ind] = _vc_refit(f, b, S)
+    return out, outR

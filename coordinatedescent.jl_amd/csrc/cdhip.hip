@@ -17,6 +17,7 @@
 
 #include "kernels.hpp"
 #include "gram_kernels.hpp"
+#include "vc_kernels.hpp"
 #include "p2p_exchange.hpp"
 #include "sparse_iterate.hpp"
 
@@ -289,6 +290,10 @@ struct cdh_handle_s {
     hipStream_t stream = nullptr;
     // device
     DevBuf<void> X, y, r, w;
+    // varying-coefficient mode (cdh_vc_set_data): z, typed as X; base column j of the design sits at column j (vc_degree + 1)
+    DevBuf<void> vc_z;
+    int64_t vc_pbase = 0;
+    int vc_degree = -1;           // -1: not in varying-coefficient mode
     DevBuf<double> beta, omega;
     DevBuf<Ctrl> d_ctrl;
     DevBuf<int64_t> d_idx;
@@ -567,17 +572,21 @@ inline void drop_r_pending(cdh_handle h) {
 }
 
 // ---- column dots over columns [j0, j0+nc): d_colout[2*j + {0,1}] = (x.r (w), x.x (w)) ----
+constexpr int64_t kColBatch = 4096;   // columns per launch of k_col_dots: keeps the partial buffer small
+// row chunks of a k_col_dots launch over bc columns (k_vc_expand splits its rows the same way: its sums are these sums)
+inline int col_dots_chunks(const cdh_handle_s* h, int64_t bc) {
+    const int64_t groups = (bc + kColGroup - 1) / kColGroup;
+    // enough row chunks to fill the chip (~8 blocks per CU) but no more than kColChunks
+    const int64_t want_chunks = std::max<int64_t>(1, ((int64_t)h->cus * 8 + groups - 1) / groups);
+    return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)kColChunks, want_chunks, (h->nvec + kBlock - 1) / kBlock}));
+}
 int32_t col_dots(cdh_handle h, int64_t j0, int64_t nc, const void* rvec, bool use_w,
                  const int64_t* d_cols = nullptr) {
     if (rvec == h->r) CHK(sync_r(h));
-    // batches of at most 4096 columns keep the partial buffer small
-    for (int64_t b0 = 0; b0 < nc; b0 += 4096) {
-        const int64_t bc = std::min<int64_t>(4096, nc - b0);
+    for (int64_t b0 = 0; b0 < nc; b0 += kColBatch) {
+        const int64_t bc = std::min<int64_t>(kColBatch, nc - b0);
         const int64_t groups = (bc + kColGroup - 1) / kColGroup;
-        // enough row chunks to fill the chip (~8 blocks per CU) but no more than kColChunks
-        const int64_t want_chunks = std::max<int64_t>(1, ((int64_t)h->cus * 8 + groups - 1) / groups);
-        const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)kColChunks, want_chunks,
-                                                                          (h->nvec + kBlock - 1) / kBlock}));
+        const int chunks = col_dots_chunks(h, bc);
         if ((size_t)groups * chunks * 2 * kColGroup > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partials too small");
         dim3 grid(chunks, (unsigned)groups);
         CHK(dispatch(h, [&](auto* t) {
@@ -1332,10 +1341,11 @@ int32_t cdh_synchronize(cdh_handle h) {
     return CDH_OK;
 }
 
-int32_t cdh_set_X_cols(cdh_handle h, int64_t j0, int64_t ncols, const void* host, int64_t ld) {
-    NEED_H(h);
-    if (ncols > 0) NEED_P(h, host);
-    if (!h->r_pending_list.empty() || h->r_lazy) {   // r still owes updates (or its rebuild) in terms of the OLD columns
+// X or W is about to change (cdh_set_X_cols, cdh_set_obs_weights, cdh_vc_set_data, cdh_vc_set_point): nothing derived from
+// them survives -- the carried residual's consistency, the stashed dots, the gradient cache with its Gram columns, the
+// one-launch solve's Gram matrix.  With `columns`, r first catches up with what it owes in terms of the OLD columns.
+static int32_t design_changes(cdh_handle h, bool columns) {
+    if (columns && (!h->r_pending_list.empty() || h->r_lazy)) {
         HIPCHK(h, hipSetDevice(h->device));
         CHK(sync_r(h));
     }
@@ -1343,6 +1353,13 @@ int32_t cdh_set_X_cols(cdh_handle h, int64_t j0, int64_t ncols, const void* host
     touch_r(h);
     gc_invalidate(h, true);
     h->small.G_valid = false; h->small.c_valid = false; h->small.rent_paid = 0.0;
+    return CDH_OK;
+}
+
+int32_t cdh_set_X_cols(cdh_handle h, int64_t j0, int64_t ncols, const void* host, int64_t ld) {
+    NEED_H(h);
+    if (ncols > 0) NEED_P(h, host);
+    CHK(design_changes(h, true));
     if (j0 < 0 || ncols < 0 || j0 + ncols > h->p || ld < h->n) return fail(h, CDH_DIM_MISMATCH, "column block outside X");
     if (ncols == 0) return CDH_OK;
     HIPCHK(h, hipSetDevice(h->device));
@@ -1406,16 +1423,23 @@ static int32_t ensure_weights_buffer(cdh_handle h) {
 int32_t cdh_set_obs_weights(cdh_handle h, const void* host_w) {
     NEED_H(h);
     NEED_P(h, host_w);
-    h->r_consistent = false;
-    touch_r(h);
-    gc_invalidate(h, true);
-    h->small.G_valid = false; h->small.c_valid = false; h->small.rent_paid = 0.0;
+    CHK(design_changes(h, false));
     if (h->loss != CDH_WLS) return fail(h, CDH_BAD_ARG, "observation weights need the CDH_WLS loss");
     HIPCHK(h, hipSetDevice(h->device));
     CHK(ensure_weights_buffer(h));
     HIPCHK(h, hipMemcpyAsync(h->w, host_w, (size_t)h->n * h->esz, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->has_w = true;
+    return CDH_OK;
+}
+
+int32_t cdh_get_obs_weights(cdh_handle h, void* host_w) {
+    NEED_H(h);
+    NEED_P(h, host_w);
+    if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "no observation weights are set");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(host_w, h->w, (size_t)h->n * h->esz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
 }
 
@@ -1762,8 +1786,9 @@ static int32_t cdh_xt_r_impl(cdh_handle h, double* out_p) {
     return CDH_OK;
 }
 
-// one launch of the wide-block Gram kernel over up to 64 columns (0-based, in h->h_idx[0 .. m)): rec <- (G, c = X_S'r, q = r'r)
-static int32_t gram_launch(cdh_handle h, int m, std::vector<double>& rec) {
+// one launch of the wide-block Gram kernel over up to 64 columns (0-based, in h->h_idx[0 .. m)): rec <- (G, c = X_S'r, q = r'r);
+// with `weighted`, G = X_S'WX_S and c = X_S'Wr (q stays r'r: the kernel weights its A operands only)
+static int32_t gram_launch(cdh_handle h, int m, std::vector<double>& rec, bool weighted) {
     using R = GramRec<4>;
     HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, h->stream));
     // one k_gramstep launch with no pending update: r is only read
@@ -1772,8 +1797,8 @@ static int32_t gram_launch(cdh_handle h, int m, std::vector<double>& rec) {
     CHK(dispatch(h, [&](auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         hipLaunchKernelGGL((k_gramstep<T, 4>), dim3(G), dim3(64 * kGramWaves), 0, h->stream,
-                           (const T*)h->X, h->ld, h->nvec, (const T*)nullptr, (T*)h->r, h->d_idx, h->d_hs, 0, m, 0,
-                           h->d_partials);
+                           (const T*)h->X, h->ld, h->nvec, weighted ? (const T*)h->w : (const T*)nullptr, (T*)h->r, h->d_idx,
+                           h->d_hs, 0, m, 0, h->d_partials);
         return CDH_OK;
     }));
     hipLaunchKernelGGL(k_gram_reduce, dim3((R::N + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream, h->d_partials, G, R::N, h->d_red);
@@ -1785,7 +1810,8 @@ static int32_t gram_launch(cdh_handle h, int m, std::vector<double>& rec) {
     return CDH_OK;
 }
 constexpr int64_t kGramMaxCols = 4096;
-static int32_t cdh_gram_impl(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) {
+static int32_t cdh_gram_impl(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q,
+                             bool weighted = false) {
     if (m < 1 || m > kGramMaxCols) return fail(h, CDH_BAD_ARG, "need 1 <= m <= 4096 columns");
     NEED_P(h, idx1);
     NEED_P(h, out_G);
@@ -1797,7 +1823,7 @@ static int32_t cdh_gram_impl(cdh_handle h, int64_t m, const int64_t* idx1, doubl
     std::vector<double> rec;
     if (m <= 64) {
         for (int64_t i = 0; i < m; ++i) h->h_idx[i] = idx1[i] - 1;
-        CHK(gram_launch(h, (int)m, rec));
+        CHK(gram_launch(h, (int)m, rec, weighted));
         for (int64_t i = 0; i < m; ++i) {
             for (int64_t j = 0; j < m; ++j) {
                 const int s = (int)std::min(i, j), l = (int)std::max(i, j);
@@ -1817,7 +1843,7 @@ static int32_t cdh_gram_impl(cdh_handle h, int64_t m, const int64_t* idx1, doubl
             const int na = (int)(a1 - a0), nb = (int)(b1 - b0);
             for (int i = 0; i < na; ++i) h->h_idx[i] = idx1[a0 + i] - 1;
             for (int i = 0; i < nb; ++i) h->h_idx[na + i] = idx1[b0 + i] - 1;
-            CHK(gram_launch(h, na + nb, rec));
+            CHK(gram_launch(h, na + nb, rec, weighted));
             // column -> position inside the launch; every block and dot the launch holds is written (a diagonal block comes out
             // of every pair its group is in, each time from the same sums over the same rows)
             auto col_of = [&](int pos) { return pos < na ? a0 + pos : b0 + (pos - na); };
@@ -1851,6 +1877,135 @@ static int32_t cdh_xt_r_cols_impl(cdh_handle h, int64_t m, const int64_t* idx1, 
         HIPCHK(h, hipStreamSynchronize(h->stream));
         for (int64_t i = 0; i < mm; ++i) out_m[o + i] = cd[(size_t)(2 * i)];
     }
+    return CDH_OK;
+}
+
+// X_S'WX_S, X_S'Wr, r'Wr: the weighted normal equations of the refit of locpolyl1 (varying_coefficient_lasso.jl:71-76) at the
+// current residual.  The Gram kernel weights G and c; r'Wr is the weighted moment of r.
+static int32_t cdh_gram_weighted_impl(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) {
+    if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "a weighted Gram block needs the CDH_WLS loss with its weights set");
+    CHK(cdh_gram_impl(h, m, idx1, out_G, out_c, nullptr, true));
+    if (out_q) {
+        CHK(resid_moments_dev(h));
+        HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *out_q = h->h_red[2];
+    }
+    return CDH_OK;
+}
+
+// _stdX!(out, w, X) (utils.jl:140-151): out_j = sqrt(sum_i w_i X_ij^2 / n_total)
+static int32_t cdh_col_wrms_impl(cdh_handle h, double* out_p) {
+    NEED_P(h, out_p);
+    if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "weighted column scales need the CDH_WLS loss with its weights set");
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(col_dots(h, 0, h->p, h->y, true));      // (the dots with y are not used; r may owe updates nobody needs here)
+    std::vector<double> cd((size_t)(2 * h->p));
+    HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(cd[(size_t)(2 * j + 1)] / (double)h->n_total);
+    return CDH_OK;
+}
+
+// ---- varying-coefficient mode (varying_coefficient_lasso.jl:30-79) -------------------------------------------------
+static int32_t vc_refuse_shards(cdh_handle h) {
+    if (h->n != h->n_total || sharded(h))
+        return fail(h, CDH_BAD_ARG, "varying-coefficient mode does not run on row-sharded handles");
+    return CDH_OK;
+}
+
+static int32_t cdh_vc_set_data_impl(cdh_handle h, int64_t p_base, int32_t degree, const void* host_X, int64_t ld,
+                                    const void* host_z) {
+    NEED_P(h, host_X);
+    NEED_P(h, host_z);
+    if (degree < 0 || degree > 3) return fail(h, CDH_BAD_ARG, "the polynomial degree must be 0 .. 3");
+    CHK(vc_refuse_shards(h));
+    if (h->loss != CDH_WLS || p_base < 1 || h->p != p_base * (degree + 1) || ld < h->n)
+        return fail(h, CDH_DIM_MISMATCH, "need a CDH_WLS handle with p == p_base * (degree + 1) and ld >= n");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t colbytes = (size_t)h->ld * h->esz;
+    DevBuf<void> z;                      // complete before the handle changes: a failed allocation leaves it as it was
+    if (!h->vc_z) {
+        HIPCHK(h, z.alloc(colbytes));
+        HIPCHK(h, hipMemsetAsync(z, 0, colbytes, h->stream));
+    }
+    CHK(design_changes(h, true));
+    if (!h->vc_z) h->vc_z = std::move(z);
+    h->vc_pbase = p_base; h->vc_degree = degree;
+    // base column j -> column j (degree + 1): one strided copy
+    HIPCHK(h, hipMemcpy2DAsync(h->X, colbytes * (size_t)(degree + 1), host_X, (size_t)ld * h->esz, (size_t)h->n * h->esz,
+                               (size_t)p_base, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->vc_z, host_z, (size_t)h->n * h->esz, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CDH_OK;
+}
+
+static int32_t cdh_vc_set_point_impl(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double* out_std) {
+    if (h->vc_degree < 0) return fail(h, CDH_BAD_ARG, "cdh_vc_set_point needs cdh_vc_set_data first");
+    if (kernel_kind != kVcGaussian && kernel_kind != kVcEpanechnikov) return fail(h, CDH_BAD_ARG, "unknown smoothing kernel");
+    if (!(bandwidth > 0.0) || !std::isfinite(bandwidth)) return fail(h, CDH_BAD_ARG, "the bandwidth must be positive");
+    if (!std::isfinite(z0)) return fail(h, CDH_BAD_ARG, "z0 must be finite");
+    CHK(vc_refuse_shards(h));
+    if (h->loss != CDH_WLS) return fail(h, CDH_BAD_ARG, "varying-coefficient mode needs the CDH_WLS loss");
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(design_changes(h, true));
+    CHK(ensure_weights_buffer(h));
+    const int Q = h->vc_degree, Q1 = Q + 1;
+    if (h->prof) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    const int wgrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (h->nvec + kBlock - 1) / kBlock));
+    CHK(dispatch(h, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        hipLaunchKernelGGL(k_vc_weights<T>, dim3(wgrid), dim3(kBlock), 0, h->stream, (const T*)h->vc_z, (T*)h->w, h->n,
+                           h->nvec, (int)kernel_kind, bandwidth, z0);
+        return CDH_OK;
+    }));
+    HIPCHK(h, hipGetLastError());
+    h->has_w = true;
+    int64_t launches = 1;
+    std::vector<double> cd;
+    if (Q == 0) {                        // nothing to expand: the weighted scales of the base columns
+        CHK(col_dots(h, 0, h->p, h->y, true));
+        cd.resize((size_t)(2 * h->p));
+        HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
+        if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int64_t j = 0; j < h->p; ++j) cd[(size_t)j] = cd[(size_t)(2 * j + 1)];
+    } else {
+        // One launch per k_col_dots batch of expanded columns, split into that batch's row chunks: the sums then are the
+        // ones cdh_col_wrms takes.  A base column whose group straddles two batches is expanded by both launches (the
+        // same values twice); each keeps the sums of its own columns.
+        for (int64_t b0 = 0; b0 < h->p; b0 += kColBatch) {
+            const int64_t b1 = std::min<int64_t>(b0 + kColBatch, h->p);
+            const int chunks = col_dots_chunks(h, b1 - b0);
+            const int64_t jb0 = b0 / Q1, jb1 = (b1 + Q1 - 1) / Q1;
+            if ((size_t)(jb1 - jb0) * Q1 * chunks > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partials too small");
+            CHK(dispatch(h, [&](auto* t) {
+                using T = std::remove_pointer_t<decltype(t)>;
+                auto go = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3((unsigned)chunks, (unsigned)(jb1 - jb0)), dim3(kBlock), 0, h->stream,
+                                       (T*)h->X, h->ld, h->nvec, (const T*)h->vc_z, (const T*)h->w, (T)z0, jb0, h->d_partials);
+                };
+                if (Q == 1) go(k_vc_expand<T, 1>); else if (Q == 2) go(k_vc_expand<T, 2>); else go(k_vc_expand<T, 3>);
+                return CDH_OK;
+            }));
+            hipLaunchKernelGGL(k_vc_reduce, dim3((unsigned)((jb1 - jb0) * Q1)), dim3(64), 0, h->stream, h->d_partials, chunks,
+                               jb0 * Q1, b0, b1, h->d_colout);
+            HIPCHK(h, hipGetLastError());
+            launches += 1;
+        }
+        if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        cd.resize((size_t)h->p);
+        HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * h->p, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (h->prof) {
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        h->prof_ms += ms;
+        h->prof_launches += launches;
+        h->prof_bytes += (double)h->n * (double)h->esz * ((double)h->p + 2.0);   // read p_base columns, write p_base Q, z, w
+    }
+    if (out_std) for (int64_t j = 0; j < h->p; ++j) out_std[j] = std::sqrt(cd[(size_t)j] / (double)h->n_total);
     return CDH_OK;
 }
 
@@ -2282,6 +2437,30 @@ int32_t cdh_xt_r(cdh_handle h, double* out_p) {
 int32_t cdh_gram(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) {
     NEED_H(h);
     try { return cdh_gram_impl(h, m, idx1, out_G, out_c, out_q); }
+    CDH_CATCH(h)
+}
+
+int32_t cdh_gram_weighted(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) {
+    NEED_H(h);
+    try { return cdh_gram_weighted_impl(h, m, idx1, out_G, out_c, out_q); }
+    CDH_CATCH(h)
+}
+
+int32_t cdh_col_wrms(cdh_handle h, double* out_p) {
+    NEED_H(h);
+    try { return cdh_col_wrms_impl(h, out_p); }
+    CDH_CATCH(h)
+}
+
+int32_t cdh_vc_set_data(cdh_handle h, int64_t p_base, int32_t degree, const void* host_X, int64_t ld, const void* host_z) {
+    NEED_H(h);
+    try { return cdh_vc_set_data_impl(h, p_base, degree, host_X, ld, host_z); }
+    CDH_CATCH(h)
+}
+
+int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double* out_std) {
+    NEED_H(h);
+    try { return cdh_vc_set_point_impl(h, kernel_kind, bandwidth, z0, out_std); }
     CDH_CATCH(h)
 }
 

@@ -54,6 +54,10 @@ typedef enum cdh_dtype { CDH_F64 = 0, CDH_F32 = 1 } cdh_dtype;
  * (:202-291), CDWeightedLSLoss (:118-194). */
 typedef enum cdh_loss { CDH_LS = 0, CDH_SQRT = 1, CDH_WLS = 2 } cdh_loss;
 
+/* SmoothingKernel subtypes (varying_coefficient_lasso.jl:3-21), evaluated as the reference writes them -- not the textbook
+ * forms: Gaussian K(x, y) = exp(-(x - y)^2 / h) / h; Epanechnikov u = (x - y) / h, K = |u| >= 1 ? 0 : 0.75 (1 - u^2) / h. */
+typedef enum cdh_vc_kernel { CDH_VC_GAUSSIAN = 0, CDH_VC_EPANECHNIKOV = 1 } cdh_vc_kernel;
+
 /* How a pass is executed on the device (no reference counterpart).
  *  CDH_SWEEP_COORD : one fused kernel per coordinate visit (apply the previous
  *                    visit's residual update, then the dots of this column),
@@ -113,6 +117,31 @@ int32_t cdh_set_y(cdh_handle h, const void *host_y);
 int32_t cdh_get_y(cdh_handle h, void *host_y);
 /* Observation weights of CDWeightedLSLoss. */
 int32_t cdh_set_obs_weights(cdh_handle h, const void *host_w);
+/* f.w (cd_differentiable_function.jl:118-126) as the handle holds it -- uploaded, or evaluated by cdh_vc_set_point;
+ * CDH_BAD_ARG while none are set. */
+int32_t cdh_get_obs_weights(cdh_handle h, void *host_w);
+/* ---- varying-coefficient mode: locpolyl1 (varying_coefficient_lasso.jl:30-79) ------------------------------------
+ * The reference rebuilds, on the host and for every grid point z0, the kernel weights (:63), the expanded design
+ * X[i,:] (x) [1, (z_i - z0), ..., (z_i - z0)^degree] (_expand_X!, :550-569) and its weighted column scales (_stdX!,
+ * utils.jl:140-151).  Here the base design and z stay in HBM and all three are regenerated on the device.
+ *
+ * cdh_vc_set_data replaces the allocation of expandX around X and z (:50-54): the handle must be CDH_WLS with
+ * p == p_base * (degree + 1) (else CDH_DIM_MISMATCH); degree outside 0 .. 3 is CDH_BAD_ARG.  Base column j (host_X, column-major
+ * n x p_base with leading dimension ld, dtype T) goes to column j (degree + 1) of the handle's X, host_z (n values of T) to a
+ * buffer the handle owns.  The other columns hold nothing meaningful until the first cdh_vc_set_point.
+ *
+ * cdh_vc_set_point replaces :63-65 for one z0: w_i = K(z_i, z0) (evaluated in double, rounded once to T), the higher-order
+ * columns by the reference's recurrence v = x; v *= (z_i - z0) in T, and out_std[j] = sqrt(sum_i w_i X_ij^2 / n_total) for
+ * the p expanded columns (out_std may be NULL).  It leaves the handle as cdh_set_X_cols + cdh_set_obs_weights would:
+ * residual, gradient cache and the one-launch solve's Gram matrix are void; the iterate is kept (the reference warm-starts
+ * from the previous grid point on purpose, :39-42).  bandwidth <= 0, an unknown kernel, or a call before cdh_vc_set_data:
+ * CDH_BAD_ARG.  Sums are taken in a fixed order (bit-identical run to run, and to cdh_col_wrms of the same state).
+ *
+ * Row-sharded handles (n_local != n_total, or any exchange installed) are refused with CDH_BAD_ARG by both calls: the
+ * column sums would have to go through the all-reduce, and nothing tests that yet. */
+int32_t cdh_vc_set_data(cdh_handle h, int64_t p_base, int32_t degree, const void *host_X, int64_t ld,
+                        const void *host_z);
+int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double *out_std);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects
@@ -168,6 +197,8 @@ int32_t cdh_get_support(cdh_handle h, int64_t *out_idx1, int64_t *out_nnz); /* n
 int32_t cdh_get_residual(cdh_handle h, void *out_n_local);               /* f.r (dtype) */
 /* _stdX!(out, X) (utils.jl:127-138): out_j = sqrt(sum_i X_ij^2 / n_total). */
 int32_t cdh_col_rms(cdh_handle h, double *out_p);
+/* _stdX!(out, w, X) (utils.jl:140-151): out_j = sqrt(sum_i w_i X_ij^2 / n_total); CDH_WLS with weights set, else CDH_BAD_ARG. */
+int32_t cdh_col_wrms(cdh_handle h, double *out_p);
 /* out_j = X_j' r for every column at the current r (At_mul_B_row for all j: the
  * screening scores of _findLargestCorrelations, utils.jl:96-106; KKT checks). */
 int32_t cdh_xt_r(cdh_handle h, double *out_p);
@@ -178,6 +209,12 @@ int32_t cdh_xt_r(cdh_handle h, double *out_p);
  * reference takes any s) in groups of 32, one launch per pair of groups. */
 int32_t cdh_gram(cdh_handle h, int64_t m, const int64_t *idx1, double *out_G, double *out_c,
                  double *out_q);
+/* The same block with the observation weights of a CDH_WLS handle: out_G[i*m+j] = X_i'WX_j, out_c[i] = X_i'Wr,
+ * *out_q = r'Wr; same limits and grouping as cdh_gram, whose result does not depend on the weights.  The refit of locpolyl1
+ * (varying_coefficient_lasso.jl:71-76: (Xs'W Xs) \ (Xs'W y)) reads its normal equations off this at the solve's own
+ * residual: Xs'Wy = Xs'Wr + (Xs'WXs) beta_S when beta is supported inside S.  Without weights set: CDH_BAD_ARG. */
+int32_t cdh_gram_weighted(cdh_handle h, int64_t m, const int64_t *idx1, double *out_G, double *out_c,
+                          double *out_q);
 /* out_m[i] = X_idx1[i]' r (X'Wr for the weighted loss) for a LIST of columns at the current r: one pass over those
  * columns only.  The refinement step of the screening init: Xs \ y (utils.jl:70, a QR in the reference) is solved from the
  * Gram block, and the normal equations' residual Xs'(y - Xs b) read off here corrects b -- so near-collinear screening
@@ -328,7 +365,7 @@ int32_t cdh_exchange_stats(cdh_handle h, int64_t *out_rccl_calls, int64_t *out_p
  * Collective: every rank calls it with the same arguments. */
 int32_t cdh_exchange_latency(cdh_handle h, int64_t count, int32_t iters, double *out_us);
 /* HIP-event timing of the sweep kernels on the handle's stream: everything
- * launched by cdh_pass / cdh_solve between begin and end.  out_launches counts
+ * launched by cdh_pass / cdh_solve (and the kernels of cdh_vc_set_point) between begin and end.  out_launches counts
  * the dominant (column-streaming) kernel launches, out_ms the event time they
  * span in total. */
 int32_t cdh_profile_begin(cdh_handle h);

@@ -425,6 +425,91 @@ function LassoPath(X::HipMatrix{T}, Y::StridedVector{T}, λpath::Vector{T}, opti
   LassoPath{T}(copy(λpath), βpath)
 end
 
+# ---- locpolyl1 with the design expanded on the device (src/varying_coefficient_lasso.jl:30-79) ----------------
+# The reference rebuilds w, expandX and stdX on the host for every z0 (:63-65).  A HipVaryingDesign keeps the base
+# design and z in HBM; cdh_vc_set_point regenerates all three there, and the refit (:71-76) reads its weighted normal
+# equations off one Gram block at the solve's own residual.  Nothing n-sized crosses the bus per grid point.
+kernel_code(::CoordinateDescent.GaussianKernel) = Int32(0)
+kernel_code(::CoordinateDescent.EpanechnikovKernel) = Int32(1)
+
+mutable struct HipVaryingDesign{T<:Union{Float32,Float64}}
+  handle::Ptr{Cvoid}
+  n::Int
+  p::Int          # base columns
+  degree::Int
+end
+
+"Upload X (n x p) and z once: base column j becomes column (j-1)(degree+1)+1 of the expanded design in HBM."
+function HipVaryingDesign(X::StridedMatrix{T}, z::Vector{T}, degree::Int; device::Integer=0) where {T}
+  n, p = size(X)
+  length(z) == n || throw(DimensionMismatch())
+  0 <= degree <= 3 || throw(ArgumentError("the polynomial degree must be 0 .. 3"))
+  ref = Ref{Ptr{Cvoid}}(C_NULL)
+  check(C_NULL, ccall((:cdh_create, libcdhip), Int32,
+                      (Ref{Ptr{Cvoid}}, Int32, Int32, Int64, Int64, Int64, Int64, Int32),
+                      ref, dtype_code(T), CDH_WLS, n, n, 0, p * (degree + 1), device))
+  h = ref[]
+  GC.@preserve X z check(h, ccall((:cdh_vc_set_data, libcdhip), Int32,
+                                  (Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+                                  h, p, degree, X, stride(X, 2), z))
+  D = HipVaryingDesign{T}(h, n, p, degree)
+  finalizer(d -> ccall((:cdh_destroy, libcdhip), Int32, (Ptr{Cvoid},), d.handle), D)
+  D
+end
+
+"w, expandX and stdX of one grid point (:63-65), on the device; returns stdX"
+function set_point!(D::HipVaryingDesign{T}, kernel::CoordinateDescent.SmoothingKernel{T}, z0::T) where {T}
+  out = Vector{Float64}(undef, D.p * (D.degree + 1))
+  check(D.handle, ccall((:cdh_vc_set_point, libcdhip), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Ptr{Float64}),
+                        D.handle, kernel_code(kernel), Float64(kernel.h), Float64(z0), out))
+  out
+end
+
+"_stdX!(out, w, X) (utils.jl:140-151) of whatever weights and columns the handle holds"
+function weighted_stdX(D::HipVaryingDesign)
+  out = Vector{Float64}(undef, D.p * (D.degree + 1))
+  check(D.handle, ccall((:cdh_col_wrms, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Float64}), D.handle, out))
+  out
+end
+
+function CoordinateDescent.locpolyl1(D::HipVaryingDesign{T}, y::Vector{T}, zgrid::Vector{T},
+                                     kernel::CoordinateDescent.SmoothingKernel{T}, λ0::T, refit::Bool,
+                                     options::CDOptions=CDOptions()) where {T}
+  length(y) == D.n || throw(DimensionMismatch())
+  opt = CDOptions(options.maxIter, options.optTol, options.randomize, true, options.numSteps)   # :39-42
+  h, ep = D.handle, D.p * (D.degree + 1)
+  out = zeros(T, ep, length(zgrid)); outR = zeros(T, ep, length(zgrid))
+  GC.@preserve y check(h, ccall((:cdh_set_y, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), h, y))
+  check(h, ccall((:cdh_set_iterate, libcdhip), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                 h, ep, 0, C_NULL, C_NULL))                       # β = SparseIterate(ep), kept on the handle from here on
+  beta = Vector{Float64}(undef, ep)
+  for (ind, z0) in enumerate(zgrid)
+    stdX = set_point!(D, kernel, z0)                              # :63-65
+    check(h, ccall((:cdh_set_penalty, libcdhip), Int32, (Ptr{Cvoid}, Float64, Ptr{Float64}, Int64),
+                   h, Float64(λ0), stdX, ep))
+    o = Ref(CdhOptions(opt)); st = CdhStats()
+    check(h, ccall((:cdh_coordinate_descent, libcdhip), Int32, (Ptr{Cvoid}, Ref{CdhOptions}, Ref{CdhStats}), h, o, st))   # :68
+    check(h, ccall((:cdh_get_beta, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Float64}), h, beta))
+    out[:, ind] .= T.(beta)
+    refit || continue
+    S = Int64[]                                                   # get_nonzero_coordinates!(S, β, p, degree, true)
+    for j in 1:D.p
+      ks = ((j - 1) * (D.degree + 1) + 1):(j * (D.degree + 1))
+      any(!iszero, view(beta, ks)) && append!(S, ks)
+    end
+    isempty(S) && continue
+    m = length(S)
+    m <= 4096 || throw(ArgumentError("refit support larger than 4096 columns"))
+    G = Matrix{Float64}(undef, m, m); c = Vector{Float64}(undef, m)
+    check(h, ccall((:cdh_gram_weighted, libcdhip), Int32,
+                   (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, m, S, G, c, C_NULL))
+    # Xs'Wy = Xs'Wr + (Xs'WXs) β_S: (Xs'WXs) \ (Xs'Wy) = β_S + (Xs'WXs) \ (Xs'Wr), solved at unit diagonal (:73-75)
+    d = sqrt.([G[i, i] for i in 1:m])
+    outR[S, ind] .= T.(beta[S] .+ ((G ./ (d * d')) \ (c ./ d)) ./ d)
+  end
+  out, outR
+end
+
 # Optional knobs (no reference counterpart): blocked sweep width, screened full passes, the gradient
 # cache of repeated solves, hipGraph replay, reuse of the carried residual by warm starts (what LassoPath
 # wants: src/lasso.jl:250-252).
