@@ -20,6 +20,7 @@
 #include "vc_kernels.hpp"
 #include "p2p_exchange.hpp"
 #include "sparse_iterate.hpp"
+#include "resid_state.hpp"
 
 using namespace cdk;
 
@@ -119,13 +120,12 @@ template <class T> using PinBuf = HipBuf<T, true>;
 struct GradCache {
     int mode = 1;                   // 0 off, 1 rent-or-buy, 2 from the first full pass (both only where the host-side
                                     // fold is cheaper than reading X), 3 from the first full pass, unconditionally
-    bool valid = false;             // g (with the pending dbeta) describes X'r of the device's current r
+    bool valid = false;             // g (with the pending `moved`) describes X'r of the device's current r
     bool beta_ok = false;           // r == y - X beta_ref up to rounding
     int64_t full_seen = 0;          // screened full passes since the data last changed
     int cooldown = 0, backoff = 1;  // after a busy pass: this many full passes run the plain way
-    std::vector<double> g, a, dbeta, beta_ref;
-    std::vector<int64_t> moved;     // coordinates with dbeta != 0, each once
-    std::vector<uint8_t> in_moved;
+    std::vector<double> g, a, beta_ref;
+    cdh::MoveLedger moved;          // what the coordinates have moved by since g was last folded
     std::vector<int32_t> slot;      // coordinate -> Gram column, -1 = not cached
     std::vector<std::vector<double>> G;
     DevBuf<double> d_cross;         // device: ceil(p / 64) records of 64 x 32 cross products
@@ -324,24 +324,7 @@ struct cdh_handle_s {
     bool use_graph = false;
     int screening = 1;            // 0 never, 1 the solves' full passes over sparse iterates, 2 cdh_pass too
     bool reuse_residual = false;  // warm starts skip initialize! when r is known to match beta
-    bool r_consistent = false;    // r == y - X beta (up to rounding) for the handle's current iterate
-    // The one-launch solve never touches r: afterwards the residual on the device is STALE and stands for
-    // y - X * x_lazy, rebuilt (one k_init_resid launch) by sync_r when something asks for r -- a residual nobody reads
-    // is never formed.  x_lazy is the iterate that residual belongs to: the solve's result, and still that after the
-    // caller loads another iterate without initialize! (cdh_set_iterate leaves r alone, as the reference's x[k] = ... does).
-    bool r_lazy = false;
-    cdh::SupportList x_lazy;
-    // What is known about the residual BUFFER: `r_pristine` -- it is bit for bit what initialize! makes of the iterate
-    // x_pristine (k_init_resid is deterministic) and nothing has written it since: another initialize! of that very iterate
-    // changes nothing and is skipped (lasso.jl:250-252 calls initialize! at every lambda; utils.jl / lasso.jl front-ends call
-    // it right after _findLambdaMax).  `dots_valid` -- dots_stash holds (X_k'W r, X_k'W X_k) for all k of the residual the
-    // handle stands for as of now (taken by _findLambdaMax / cdh_xt_r): the gradient cache's reference pass adopts them
-    // instead of reading X again.  Everything that writes r, queues updates for it, or changes X, y, W clears both.
-    bool r_pristine = false, dots_valid = false, dots_w = false;
-    cdh::SupportList x_pristine;
-    std::vector<double> dots_stash;
-    int64_t n_rebuild_skipped = 0, n_dots_adopted = 0;
-    int64_t r_roundings = 0;      // launches that have rewritten r (each rounds it to the storage type once) since it was last rebuilt
+    cdh::ResidState rs;           // what r holds and stands for, the moves it owes, the stashed dots (resid_state.hpp)
     bool chunk_dup = false;       // the current chunk's visit list repeats a coordinate
     std::vector<int32_t> stamp;   // duplicate detection scratch, size p
     struct GraphEntry { uint64_t key; hipGraphExec_t exec; unsigned exchanges; unsigned rccl; };
@@ -375,10 +358,6 @@ struct cdh_handle_s {
     // profile
     GradCache gc;
     SmallPath small;
-    // beta changes the covariance-form visits have made that r has not seen yet: r_actual = r_virtual + X * pending
-    std::vector<double> r_pending;
-    std::vector<int64_t> r_pending_list;
-    std::vector<uint8_t> r_in_pending;
     bool prof = false;
     double prof_ms = 0.0, prof_bytes = 0.0;
     int64_t prof_launches = 0;
@@ -411,11 +390,7 @@ int32_t fail(cdh_handle h, int32_t code, const char* msg) {
     return code;
 }
 
-// every export checks what it dereferences: a NULL handle or out-pointer is CDH_BAD_ARG, never a crash
-#define NEED_H(h)                                                              \
-    do {                                                                       \
-        if (!(h)) return fail(nullptr, CDH_BAD_ARG, "handle is NULL");         \
-    } while (0)
+// every export checks what it dereferences: a NULL handle (guarded, below) or out-pointer is CDH_BAD_ARG, never a crash
 #define NEED_P(h, ptr)                                                         \
     do {                                                                       \
         if (!(ptr)) return fail((h), CDH_BAD_ARG, #ptr " is NULL");            \
@@ -446,9 +421,6 @@ int32_t upload_ctrl(cdh_handle h) {
 inline bool sharded(const cdh_handle_s* h) {
     return h->comm != nullptr || h->p2p_on || h->p2p_dead || h->lost_exchange || h->host_fn != nullptr;
 }
-
-// r (the buffer, or the residual it stands for) is about to change, or X / y / W are: what was known about it is void
-inline void touch_r(cdh_handle_s* h) { h->r_pristine = false; h->dots_valid = false; }
 
 // A shard that has lost its exchange refuses to sweep at all -- also where a pass could be served from sums exchanged
 // earlier (the gradient cache): the ranks of one problem must fail together, not one by one as they come to need an exchange.
@@ -536,18 +508,18 @@ int32_t allreduce(cdh_handle h, double* dbuf, size_t count) {
 // download (cdh_get_residual) -- and before X itself changes; nothing else needs r, so a warm-started path
 // whose solves all run from the cache pays for one catch-up when its caller finally asks for the residual
 // (moves of the same coordinate merge in the meantime).
-int32_t rebuild_residual_from(cdh_handle h, const cdh::SupportList& x, bool upload_beta);
+// (declared ahead, not moved above: where sync_r stands decides the order in which the kernel templates are first used, and
+// with it the order of the kernels in the code object -- kept as it was, so that the device code is unchanged)
+int32_t rebuild_residual_from(cdh_handle h, const cdh::SupportList& x, bool with_beta);
 int32_t sync_r(cdh_handle h) {
-    if (h->r_lazy) {                  // r = y - X * x_lazy, now that somebody wants it (beta on the device mirrors h->x: left alone)
-        h->r_lazy = false;
-        return rebuild_residual_from(h, h->x_lazy, false);
-    }
-    if (h->r_pending_list.empty()) return CDH_OK;
-    h->r_pristine = false;            // (the residual the handle stands for does not change: dots taken of it stay good)
-    std::vector<int64_t>& L = h->r_pending_list;
+    cdh::ResidState& rs = h->rs;
+    if (rs.lazy()) return rebuild_residual_from(h, rs.take_lazy(), false);   // (beta on the device mirrors h->x: left alone)
+    if (rs.pending().empty()) return CDH_OK;
+    rs.catchup_begins();
+    const cdh::MoveLedger& L = rs.pending();
     for (size_t o = 0; o < L.size(); o += 64) {
         const int cnt = (int)std::min<size_t>(64, L.size() - o);
-        for (int i = 0; i < cnt; ++i) { h->h_idx[i] = L[o + (size_t)i]; h->h_hs[i] = h->r_pending[(size_t)L[o + (size_t)i]]; }
+        for (int i = 0; i < cnt; ++i) { h->h_idx[i] = L[o + (size_t)i]; h->h_hs[i] = L.value(L[o + (size_t)i]); }
         HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)cnt, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->d_hs, h->h_hs, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, h->stream));
         CHK(dispatch(h, [&](auto* t) {
@@ -558,17 +530,11 @@ int32_t sync_r(cdh_handle h) {
         }));
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipStreamSynchronize(h->stream));   // the pinned staging arrays are reused
-        h->r_roundings += 1;
+        rs.catchup_batch_applied();
     }
-    for (int64_t k : L) { h->r_pending[(size_t)k] = 0.0; h->r_in_pending[(size_t)k] = 0; }
-    L.clear();
+    rs.catchup_done();
     h->gc.n_reconcile += 1;
     return CDH_OK;
-}
-// r is about to be overwritten from scratch (initialize!, a new y): nothing to catch up with
-inline void drop_r_pending(cdh_handle h) {
-    for (int64_t k : h->r_pending_list) { h->r_pending[(size_t)k] = 0.0; h->r_in_pending[(size_t)k] = 0; }
-    h->r_pending_list.clear();
 }
 
 // ---- column dots over columns [j0, j0+nc): d_colout[2*j + {0,1}] = (x.r (w), x.x (w)) ----
@@ -662,7 +628,6 @@ void gc_invalidate(cdh_handle h, bool columns) {
     GradCache& c = h->gc;
     c.valid = false; c.beta_ok = false; c.q_valid = false;
     c.g_host_ok = true; c.g_dev_ok = false;      // whatever g held is void; the next reference pass fills the host copy
-    for (int64_t j : c.moved) { c.dbeta[(size_t)j] = 0.0; c.in_moved[(size_t)j] = 0; }
     c.moved.clear();
     if (columns) {
         c.a_dev_ok = false;
@@ -686,10 +651,7 @@ void gc_after_rebuild(cdh_handle h, const cdh::SupportList& x) {
     if (c.valid) {
         for (int64_t k = 0; k < h->p; ++k) {
             const double d = nb[(size_t)k] - c.beta_ref[(size_t)k];
-            if (d != 0.0) {
-                c.dbeta[(size_t)k] += d;
-                if (!c.in_moved[(size_t)k]) { c.in_moved[(size_t)k] = 1; c.moved.push_back(k); }
-            }
+            if (d != 0.0) c.moved.add(k, d);
         }
     }
     c.beta_ref.swap(nb);
@@ -707,72 +669,52 @@ void gc_note_moves(cdh_handle h, const int64_t* idx0, int m) {
         const int64_t k = idx0[i];
         if (c.beta_ok) c.beta_ref[(size_t)k] += hv;
         c.q_valid = false;            // a streamed visit has changed r
-        if (c.valid) {
-            c.dbeta[(size_t)k] += hv;
-            if (!c.in_moved[(size_t)k]) { c.in_moved[(size_t)k] = 1; c.moved.push_back(k); }
-        }
+        if (c.valid) c.moved.add(k, hv);
     }
 }
 
 // ---- initialize!: upload support, r = y - X beta ------------------------------------
-inline bool same_iterate(const cdh::SupportList& a, const cdh::SupportList& b) {
-    if (a.size() != b.size() || a.nnz() != b.nnz()) return false;
-    for (int64_t s = 0; s < a.nnz(); ++s) if (a.coord(s) != b.coord(s) || !(a.slot_value(s) == b.slot_value(s))) return false;
-    return true;
+// the dense beta of x goes to the device (nothing host-side stays in flight)
+int32_t upload_beta(cdh_handle h, const cdh::SupportList& x) {
+    if (x.nnz() == 0) {
+        HIPCHK(h, hipMemsetAsync(h->beta, 0, sizeof(double) * h->p, h->stream));
+        return CDH_OK;
+    }
+    std::vector<double> dense((size_t)h->p, 0.0);
+    for (int64_t s = 0; s < x.nnz(); ++s) dense[(size_t)x.coord(s)] = x.slot_value(s);
+    HIPCHK(h, hipMemcpyAsync(h->beta, dense.data(), sizeof(double) * h->p, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // `dense` goes out of scope
+    return CDH_OK;
 }
-int32_t rebuild_residual_from(cdh_handle h, const cdh::SupportList& x, bool upload_beta) {
-    if (h->r_pristine && !h->r_lazy && h->r_pending_list.empty() && same_iterate(x, h->x_pristine)) {
-        // the buffer already holds exactly what this rebuild would write
-        if (upload_beta) {
-            if (x.nnz() == 0) HIPCHK(h, hipMemsetAsync(h->beta, 0, sizeof(double) * h->p, h->stream));
-            else {
-                std::vector<double> dense((size_t)h->p, 0.0);
-                for (int64_t s = 0; s < x.nnz(); ++s) dense[(size_t)x.coord(s)] = x.slot_value(s);
-                HIPCHK(h, hipMemcpyAsync(h->beta, dense.data(), sizeof(double) * h->p, hipMemcpyHostToDevice, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-            }
-        }
-        h->r_roundings = 1;
-        h->r_consistent = true;
-        h->n_rebuild_skipped += 1;
+int32_t rebuild_residual_from(cdh_handle h, const cdh::SupportList& x, bool with_beta) {
+    if (h->rs.rebuild_is_noop(x)) {   // the buffer already holds exactly what this rebuild would write
+        if (with_beta) CHK(upload_beta(h, x));
+        h->rs.rebuild_skipped();
         gc_after_rebuild(h, x);
         return CDH_OK;
     }
-    touch_r(h);
-    drop_r_pending(h);
-    h->r_lazy = false;
-    h->r_roundings = 1;               // r = y - X beta, summed in fp64 and rounded once
+    h->rs.rebuild_begins();           // r = y - X beta, summed in fp64 and rounded once
+    if (with_beta) CHK(upload_beta(h, x));
     const int64_t nnz = x.nnz();
     if (nnz == 0) {   // the cold start: beta = 0, r = y; nothing host-side is in flight, so no wait either
-        if (upload_beta) HIPCHK(h, hipMemsetAsync(h->beta, 0, sizeof(double) * h->p, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->r, h->y, (size_t)h->ld * h->esz, hipMemcpyDeviceToDevice, h->stream));
-        h->r_consistent = true;
-        h->r_pristine = true; h->x_pristine = x;
-        gc_after_rebuild(h, x);
-        return CDH_OK;
+    } else {
+        std::vector<int64_t> si((size_t)nnz);
+        std::vector<double> sv((size_t)nnz);
+        for (int64_t s = 0; s < nnz; ++s) { si[(size_t)s] = x.coord(s); sv[(size_t)s] = x.slot_value(s); }
+        HIPCHK(h, hipMemcpyAsync(h->d_sup_idx, si.data(), sizeof(int64_t) * nnz, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_sup_val, sv.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, h->stream));
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (h->nvec + kBlock - 1) / kBlock));
+        CHK(dispatch(h, [&](auto* t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            hipLaunchKernelGGL(k_init_resid<T>, dim3(grid), dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
+                               h->nvec, (const T*)h->y, (T*)h->r, h->d_sup_idx, h->d_sup_val, (int)nnz);
+            return CDH_OK;
+        }));
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipStreamSynchronize(h->stream));  // host vectors above go out of scope
     }
-    if (upload_beta) {
-        std::vector<double> dense((size_t)h->p, 0.0);
-        for (int64_t s = 0; s < nnz; ++s) dense[(size_t)x.coord(s)] = x.slot_value(s);
-        HIPCHK(h, hipMemcpyAsync(h->beta, dense.data(), sizeof(double) * h->p, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));   // `dense` goes out of scope
-    }
-    std::vector<int64_t> si((size_t)nnz);
-    std::vector<double> sv((size_t)nnz);
-    for (int64_t s = 0; s < nnz; ++s) { si[(size_t)s] = x.coord(s); sv[(size_t)s] = x.slot_value(s); }
-    HIPCHK(h, hipMemcpyAsync(h->d_sup_idx, si.data(), sizeof(int64_t) * nnz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_sup_val, sv.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, h->stream));
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (h->nvec + kBlock - 1) / kBlock));
-    CHK(dispatch(h, [&](auto* t) {
-        using T = std::remove_pointer_t<decltype(t)>;
-        hipLaunchKernelGGL(k_init_resid<T>, dim3(grid), dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
-                           h->nvec, (const T*)h->y, (T*)h->r, h->d_sup_idx, h->d_sup_val, (int)nnz);
-        return CDH_OK;
-    }));
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // host vectors above go out of scope
-    h->r_consistent = true;
-    h->r_pristine = true; h->x_pristine = x;
+    h->rs.rebuilt_from(x);
     gc_after_rebuild(h, x);
     return CDH_OK;
 }
@@ -952,7 +894,7 @@ int32_t agree_default_width(cdh_handle h) {
 int32_t run_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH) {
     CHK(agree_default_width(h));
     CHK(sync_r(h));   // the streaming kernels read and write r
-    touch_r(h);
+    h->rs.stream_begins();
     if (h->p2p_epoch >= kEpochSoftWrap) h->p2p_epoch = (h->p2p_epoch & 1u) ? 1u : 2u;   // slot parity keeps alternating
     std::memcpy(h->h_idx, idx0, sizeof(int64_t) * (size_t)m);
     note_duplicates(h, idx0, m);
@@ -1025,7 +967,7 @@ int32_t run_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH) {
         }
     }
     if (!launched) CHK(enqueue());
-    h->r_roundings += blocked ? (m + h->blockB - 1) / h->blockB + 1 : m + 1;   // one rewrite of r per launch that applies updates
+    h->rs.stream_enqueued(blocked ? (m + h->blockB - 1) / h->blockB + 1 : m + 1);   // one rewrite of r per launch that applies updates
     HIPCHK(h, hipGetLastError());
     if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     CHK(finish_chunk(h, idx0, m, maxH));
@@ -1188,7 +1130,7 @@ int32_t lambda_max(cdh_handle h, double* out, std::vector<double>* dots = nullpt
         HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->dots_stash = cd; h->dots_valid = true; h->dots_w = h->loss == CDH_WLS;   // (col_dots has brought r up to date first)
+    h->rs.dots_taken(cd, h->loss == CDH_WLS);   // (col_dots has brought r up to date first)
     if (h->loss == CDH_SQRT) denom = std::sqrt(h->h_red[1]);
     const std::vector<double>& om = h->h_omega;
     double lmax = 0.0;
@@ -1214,24 +1156,41 @@ void free_all(cdh_handle h) {
     if (stream) (void)hipStreamDestroy(stream);
 }
 
+// ---- exception firewall: nothing may unwind across the C ABI -------------------------------------
+// Every export that returns a status runs its body through here.  Without a handle (cdh_create, cdh_destroy, cdh_device_count,
+// cdh_comm_unique_id) the message goes where cdh_last_error(NULL) finds it.
+template <typename F> int32_t guarded_as(cdh_handle h, F&& body) {
+    try { return body(); }
+    catch (const std::bad_alloc&) { return fail(h, CDH_OOM, "host allocation failed"); }
+    catch (const std::exception& e) { return fail(h, CDH_BAD_ARG, e.what()); }
+    catch (...) { return fail(h, CDH_BAD_ARG, "unknown C++ exception"); }
+}
+template <typename F> int32_t guarded(F&& body) { return guarded_as(nullptr, body); }
+template <typename F> int32_t guarded(cdh_handle h, F&& body) {
+    if (!h) return fail(nullptr, CDH_BAD_ARG, "handle is NULL");
+    return guarded_as(h, body);
+}
+
 }  // namespace
 
 // ====================================================================================
 extern "C" {
 
-int32_t cdh_device_count(int32_t* out) {
+int32_t cdh_device_count(int32_t* out) { return guarded([&]() -> int32_t {
     NEED_P(nullptr, out);
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess) { g_create_error = hipGetErrorString(e); *out = 0; return CDH_HIP_ERROR; }
     *out = n;
     return CDH_OK;
-}
+}); }
 
 const char* cdh_last_error(cdh_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local, int64_t n_total,
                    int64_t row_offset, int64_t p, int32_t device) {
+    cdh_handle h = nullptr;           // while it is being built: freed below unless it was handed over
+    const int32_t status = guarded([&]() -> int32_t {
     if (!out) return fail(nullptr, CDH_BAD_ARG, "out is NULL");
     *out = nullptr;
     if (dtype != CDH_F64 && dtype != CDH_F32) return fail(nullptr, CDH_BAD_ARG, "dtype must be CDH_F64 or CDH_F32");
@@ -1243,7 +1202,7 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
     if (e != hipSuccess || ndev <= 0)
         return fail(nullptr, CDH_HIP_ERROR, "no HIP device: this library has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(nullptr, CDH_BAD_ARG, "device index out of range");
-    cdh_handle h = new cdh_handle_s();
+    h = new cdh_handle_s();
     h->dtype = dtype; h->loss = loss; h->device = device;
     h->n = n_local; h->n_total = n_total; h->row0 = row_offset; h->p = p;
     h->esz = dtype == CDH_F64 ? 8 : 4;
@@ -1257,8 +1216,7 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
     // no LDS-transposed B = 64 kernel and keeps 32.
     if (dtype == CDH_F64 && n_local < (int64_t)512 * kGramWaves * 64 * 2) h->blockB = 64;
     h->x.resize(p);
-    h->r_pending.assign((size_t)p, 0.0);
-    h->r_in_pending.assign((size_t)p, 0);
+    h->rs.resize(p);
     int32_t rc = [&]() -> int32_t {
         HIPCHK(h, hipSetDevice(device));
         HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -1322,42 +1280,43 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
         HIPCHK(h, hipStreamSynchronize(h->stream));
         return CDH_OK;
     }();
-    if (rc != CDH_OK) { g_create_error = h->err; free_all(h); return rc; }
+    if (rc != CDH_OK) { g_create_error = h->err; return rc; }
     *out = h;
     return CDH_OK;
+    });
+    if (status != CDH_OK) free_all(h);   // (after a throw as well; nothing to free if it never came to be)
+    return status;
 }
 
-int32_t cdh_destroy(cdh_handle h) {
+int32_t cdh_destroy(cdh_handle h) { return guarded([&]() -> int32_t {
     if (!h) return CDH_OK;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     free_all(h);
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_synchronize(cdh_handle h) {
-    NEED_H(h);
+int32_t cdh_synchronize(cdh_handle h) { return guarded(h, [&]() -> int32_t {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
-}
+}); }
 
 // X or W is about to change (cdh_set_X_cols, cdh_set_obs_weights, cdh_vc_set_data, cdh_vc_set_point): nothing derived from
 // them survives -- the carried residual's consistency, the stashed dots, the gradient cache with its Gram columns, the
 // one-launch solve's Gram matrix.  With `columns`, r first catches up with what it owes in terms of the OLD columns.
+static void small_invalidate(cdh_handle h) { h->small.G_valid = false; h->small.c_valid = false; h->small.rent_paid = 0.0; }
 static int32_t design_changes(cdh_handle h, bool columns) {
-    if (columns && (!h->r_pending_list.empty() || h->r_lazy)) {
+    if (columns && h->rs.owes_catchup()) {
         HIPCHK(h, hipSetDevice(h->device));
         CHK(sync_r(h));
     }
-    h->r_consistent = false;
-    touch_r(h);
+    h->rs.design_or_loss_changed();
     gc_invalidate(h, true);
-    h->small.G_valid = false; h->small.c_valid = false; h->small.rent_paid = 0.0;
+    small_invalidate(h);
     return CDH_OK;
 }
 
-int32_t cdh_set_X_cols(cdh_handle h, int64_t j0, int64_t ncols, const void* host, int64_t ld) {
-    NEED_H(h);
+int32_t cdh_set_X_cols(cdh_handle h, int64_t j0, int64_t ncols, const void* host, int64_t ld) { return guarded(h, [&]() -> int32_t {
     if (ncols > 0) NEED_P(h, host);
     CHK(design_changes(h, true));
     if (j0 < 0 || ncols < 0 || j0 + ncols > h->p || ld < h->n) return fail(h, CDH_DIM_MISMATCH, "column block outside X");
@@ -1368,10 +1327,9 @@ int32_t cdh_set_X_cols(cdh_handle h, int64_t j0, int64_t ncols, const void* host
                                hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_get_X_cols(cdh_handle h, int64_t j0, int64_t ncols, void* host, int64_t ld) {
-    NEED_H(h);
+int32_t cdh_get_X_cols(cdh_handle h, int64_t j0, int64_t ncols, void* host, int64_t ld) { return guarded(h, [&]() -> int32_t {
     if (ncols > 0) NEED_P(h, host);
     if (j0 < 0 || ncols < 0 || j0 + ncols > h->p || ld < h->n) return fail(h, CDH_DIM_MISMATCH, "column block outside X");
     if (ncols == 0) return CDH_OK;
@@ -1381,34 +1339,29 @@ int32_t cdh_get_X_cols(cdh_handle h, int64_t j0, int64_t ncols, void* host, int6
                                hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_y(cdh_handle h, const void* host_y) {
-    NEED_H(h);
+int32_t cdh_set_y(cdh_handle h, const void* host_y) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, host_y);
-    h->r_consistent = false;
-    touch_r(h);
+    h->rs.overwritten_with_y();        // r = copy(y) below
     gc_invalidate(h, false);
     h->gc.yy_ok = false;
     h->small.c_valid = false;
-    drop_r_pending(h);                 // r = copy(y) below
-    h->r_lazy = false;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(h->y, host_y, (size_t)h->n * h->esz, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->r, h->y, (size_t)h->n * h->esz, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->y_set = true;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_get_y(cdh_handle h, void* host_y) {
-    NEED_H(h);
+int32_t cdh_get_y(cdh_handle h, void* host_y) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, host_y);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(host_y, h->y, (size_t)h->n * h->esz, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
-}
+}); }
 
 static int32_t ensure_weights_buffer(cdh_handle h) {
     if (h->w) return CDH_OK;
@@ -1420,8 +1373,7 @@ static int32_t ensure_weights_buffer(cdh_handle h) {
     return CDH_OK;
 }
 
-int32_t cdh_set_obs_weights(cdh_handle h, const void* host_w) {
-    NEED_H(h);
+int32_t cdh_set_obs_weights(cdh_handle h, const void* host_w) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, host_w);
     CHK(design_changes(h, false));
     if (h->loss != CDH_WLS) return fail(h, CDH_BAD_ARG, "observation weights need the CDH_WLS loss");
@@ -1431,43 +1383,38 @@ int32_t cdh_set_obs_weights(cdh_handle h, const void* host_w) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->has_w = true;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_get_obs_weights(cdh_handle h, void* host_w) {
-    NEED_H(h);
+int32_t cdh_get_obs_weights(cdh_handle h, void* host_w) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, host_w);
     if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "no observation weights are set");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(host_w, h->w, (size_t)h->n * h->esz, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_loss(cdh_handle h, int32_t loss) {
-    NEED_H(h);
+int32_t cdh_set_loss(cdh_handle h, int32_t loss) { return guarded(h, [&]() -> int32_t {
     if (loss != CDH_LS && loss != CDH_SQRT && loss != CDH_WLS) return fail(h, CDH_BAD_ARG, "unknown loss");
     if (loss == h->loss) return CDH_OK;
     HIPCHK(h, hipSetDevice(h->device));
     if (loss == CDH_WLS) CHK(ensure_weights_buffer(h));
     h->loss = loss;
     h->ctrl.loss = loss;          // goes to the device with the next chunk's control block
-    if (h->has_w) { h->small.G_valid = false; h->small.c_valid = false; h->small.rent_paid = 0.0; gc_invalidate(h, true); }   // X'WX is not X'X
+    if (h->has_w) { small_invalidate(h); gc_invalidate(h, true); }   // X'WX is not X'X
     h->has_w = false;             // a weighted loss gets its weights from cdh_set_obs_weights
-    h->r_consistent = false;
-    touch_r(h);
+    h->rs.design_or_loss_changed();
     gc_invalidate(h, false);
     h->domain_error = false;
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_generate_impl(cdh_handle h, uint64_t seed, int64_t s, double noise, double* out_beta_star) {
+int32_t cdh_generate(cdh_handle h, uint64_t seed, int64_t s, double noise, double* out_beta_star) { return guarded(h, [&]() -> int32_t {
     if (s < 0 || s > h->p) return fail(h, CDH_BAD_ARG, "need 0 <= s <= p");
-    touch_r(h);
+    h->rs.regenerated();
     gc_invalidate(h, true);
     h->gc.yy_ok = false;
-    h->small.G_valid = false; h->small.c_valid = false; h->small.rent_paid = 0.0;
-    drop_r_pending(h);
-    h->r_lazy = false;
+    small_invalidate(h);
     HIPCHK(h, hipSetDevice(h->device));
     // planted coefficients: beta*_j = z_j (1 + u_j) (benchmark/cd_bench.jl:14), stream 2
     std::vector<double> bstar((size_t)std::max<int64_t>(s, 1), 0.0);
@@ -1504,9 +1451,9 @@ static int32_t cdh_generate_impl(cdh_handle h, uint64_t seed, int64_t s, double 
     HIPCHK(h, hipMemsetAsync(h->beta, 0, sizeof(double) * h->p, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_set_penalty_impl(cdh_handle h, double lambda0, const double* omega, int64_t n_omega) {
+int32_t cdh_set_penalty(cdh_handle h, double lambda0, const double* omega, int64_t n_omega) { return guarded(h, [&]() -> int32_t {
     HIPCHK(h, hipSetDevice(h->device));
     bool uploaded = false;
     if (omega) {
@@ -1528,46 +1475,41 @@ static int32_t cdh_set_penalty_impl(cdh_handle h, double lambda0, const double* 
     // weight buffer, borrowed for this call, has to be consumed before returning
     if (uploaded) HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_num_coordinates(cdh_handle h, int64_t* out) {
-    NEED_H(h);
+int32_t cdh_num_coordinates(cdh_handle h, int64_t* out) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out);
     *out = h->p;
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_set_iterate_impl(cdh_handle h, int64_t x_length, int64_t nnz, const int64_t* idx1, const double* val) {
+static int32_t load_iterate(cdh_handle h, int64_t x_length, int64_t nnz, const int64_t* idx1, const double* val) {
     if (x_length != h->p) return fail(h, CDH_DIM_MISMATCH, "numCoordinates(x) != numCoordinates(f)");
     if (nnz < 0 || nnz > h->p) return fail(h, CDH_BAD_ARG, "nnz out of range");
     if (nnz > 0) { NEED_P(h, idx1); NEED_P(h, val); }
     for (int64_t i = 0; i < nnz; ++i)
         if (idx1[i] < 1 || idx1[i] > h->p) return fail(h, CDH_BAD_ARG, "support index out of range");
     HIPCHK(h, hipSetDevice(h->device));
-    h->r_consistent = false;
+    h->rs.iterate_loaded();
     h->x.clear();
     for (int64_t i = 0; i < nnz; ++i) {
         // a stored zero keeps its slot in the reference's SparseIterate; mirror that
         if (val[i] == 0.0) { h->x.set(idx1[i] - 1, 1.0); h->x.set(idx1[i] - 1, 0.0); }
         else h->x.set(idx1[i] - 1, val[i]);
     }
-    if (h->x.nnz() == 0) {   // beta = 0: nothing to upload, nothing to wait for
-        HIPCHK(h, hipMemsetAsync(h->beta, 0, sizeof(double) * h->p, h->stream));
-        return CDH_OK;
-    }
-    std::vector<double> dense((size_t)h->p, 0.0);
-    for (int64_t s = 0; s < h->x.nnz(); ++s) dense[(size_t)h->x.coord(s)] = h->x.slot_value(s);
-    HIPCHK(h, hipMemcpyAsync(h->beta, dense.data(), sizeof(double) * h->p, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return CDH_OK;
+    return upload_beta(h, h->x);     // (beta = 0: nothing to upload, nothing to wait for)
 }
 
-static int32_t cdh_initialize_impl(cdh_handle h, int64_t x_length, int64_t nnz, const int64_t* idx1, const double* val) {
-    CHK(cdh_set_iterate_impl(h, x_length, nnz, idx1, val));
+int32_t cdh_set_iterate(cdh_handle h, int64_t x_length, int64_t nnz, const int64_t* idx1, const double* val) { return guarded(h, [&]() -> int32_t {
+    return load_iterate(h, x_length, nnz, idx1, val);
+}); }
+
+int32_t cdh_initialize(cdh_handle h, int64_t x_length, int64_t nnz, const int64_t* idx1, const double* val) { return guarded(h, [&]() -> int32_t {
+    CHK(load_iterate(h, x_length, nnz, idx1, val));
     return rebuild_residual(h);
-}
+}); }
 
-static int32_t cdh_gradient_impl(cdh_handle h, int64_t k1, double* out) {
+int32_t cdh_gradient(cdh_handle h, int64_t k1, double* out) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out);
     if (k1 < 1 || k1 > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1588,9 +1530,9 @@ static int32_t cdh_gradient_impl(cdh_handle h, int64_t k1, double* out) {
     }
     *out = -xr / denom;
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_descend_impl(cdh_handle h, int64_t k1, double* out_h) {
+int32_t cdh_descend(cdh_handle h, int64_t k1, double* out_h) { return guarded(h, [&]() -> int32_t {
     if (k1 < 1 || k1 > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
     HIPCHK(h, hipSetDevice(h->device));
     const int64_t k0 = k1 - 1;
@@ -1602,15 +1544,15 @@ static int32_t cdh_descend_impl(cdh_handle h, int64_t k1, double* out_h) {
     if (rc != CDH_OK) return rc;
     if (out_h) *out_h = h->h_hs[0];
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_lambda_max_impl(cdh_handle h, double* out) {
+int32_t cdh_lambda_max(cdh_handle h, double* out) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out);
     HIPCHK(h, hipSetDevice(h->device));
     return lambda_max(h, out);
-}
+}); }
 
-static int32_t cdh_pass_impl(cdh_handle h, int64_t m, const int64_t* idx1, double* out_maxH) {
+int32_t cdh_pass(cdh_handle h, int64_t m, const int64_t* idx1, double* out_maxH) { return guarded(h, [&]() -> int32_t {
     if (m < 0) return fail(h, CDH_BAD_ARG, "m < 0");
     CHK(exchange_alive(h));
     if (m > 0) NEED_P(h, idx1);
@@ -1626,9 +1568,9 @@ static int32_t cdh_pass_impl(cdh_handle h, int64_t m, const int64_t* idx1, doubl
     else h->x.dropzeros();
     if (out_maxH) *out_maxH = maxH;
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_solve_impl(cdh_handle h, const cdh_options* opt, cdh_stats* out) {
+int32_t cdh_solve(cdh_handle h, const cdh_options* opt, cdh_stats* out) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, opt);
     CHK(exchange_alive(h));
     HIPCHK(h, hipSetDevice(h->device));
@@ -1652,9 +1594,9 @@ static int32_t cdh_solve_impl(cdh_handle h, const cdh_options* opt, cdh_stats* o
     rent.pay(st);
     if (out) *out = st;
     return rc;
-}
+}); }
 
-static int32_t cdh_coordinate_descent_impl(cdh_handle h, const cdh_options* opt, cdh_stats* out) {
+int32_t cdh_coordinate_descent(cdh_handle h, const cdh_options* opt, cdh_stats* out) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, opt);
     CHK(exchange_alive(h));
     HIPCHK(h, hipSetDevice(h->device));
@@ -1700,7 +1642,7 @@ static int32_t cdh_coordinate_descent_impl(cdh_handle h, const cdh_options* opt,
     } else if (opt->warmStart) {
         // initialize!(f, x) (:21).  Optional shortcut for warm-started paths (LassoPath): the
         // carried residual already equals y - X beta, so the rebuild only re-rounds it.
-        if (!(h->reuse_residual && h->r_consistent)) CHK(rebuild_residual(h));
+        if (!(h->reuse_residual && h->rs.consistent())) CHK(rebuild_residual(h));
         rc = solve(h, opt, sched, &st);
     } else {
         const double target = h->ctrl.lambda0;          // g itself is never mutated by the reference:
@@ -1734,36 +1676,33 @@ static int32_t cdh_coordinate_descent_impl(cdh_handle h, const cdh_options* opt,
     if (!small) rent.pay(st);
     if (out) *out = st;
     return rc;
-}
+}); }
 
-int32_t cdh_get_beta(cdh_handle h, double* out_p) {
-    NEED_H(h);
+int32_t cdh_get_beta(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_p);
     std::memset(out_p, 0, sizeof(double) * (size_t)h->p);
     for (int64_t s = 0; s < h->x.nnz(); ++s) out_p[h->x.coord(s)] = h->x.slot_value(s);
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_get_support(cdh_handle h, int64_t* out_idx1, int64_t* out_nnz) {
-    NEED_H(h);
+int32_t cdh_get_support(cdh_handle h, int64_t* out_idx1, int64_t* out_nnz) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_idx1);
     NEED_P(h, out_nnz);
     for (int64_t s = 0; s < h->x.nnz(); ++s) out_idx1[s] = h->x.coord(s) + 1;
     *out_nnz = h->x.nnz();
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_get_residual(cdh_handle h, void* out_n_local) {
-    NEED_H(h);
+int32_t cdh_get_residual(cdh_handle h, void* out_n_local) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_n_local);
     HIPCHK(h, hipSetDevice(h->device));
     CHK(sync_r(h));
     HIPCHK(h, hipMemcpyAsync(out_n_local, h->r, (size_t)h->n * h->esz, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_col_rms_impl(cdh_handle h, double* out_p) {
+int32_t cdh_col_rms(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_p);
     HIPCHK(h, hipSetDevice(h->device));
     CHK(col_dots(h, 0, h->p, h->r, false));
@@ -1772,9 +1711,9 @@ static int32_t cdh_col_rms_impl(cdh_handle h, double* out_p) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(cd[(size_t)(2 * j + 1)] / (double)h->n_total);
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_xt_r_impl(cdh_handle h, double* out_p) {
+int32_t cdh_xt_r(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_p);
     HIPCHK(h, hipSetDevice(h->device));
     CHK(col_dots(h, 0, h->p, h->r, false));
@@ -1782,9 +1721,9 @@ static int32_t cdh_xt_r_impl(cdh_handle h, double* out_p) {
     HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t j = 0; j < h->p; ++j) out_p[j] = cd[(size_t)(2 * j)];
-    h->dots_stash.swap(cd); h->dots_valid = true; h->dots_w = false;
+    h->rs.dots_taken(std::move(cd), false);
     return CDH_OK;
-}
+}); }
 
 // one launch of the wide-block Gram kernel over up to 64 columns (0-based, in h->h_idx[0 .. m)): rec <- (G, c = X_S'r, q = r'r);
 // with `weighted`, G = X_S'WX_S and c = X_S'Wr (q stays r'r: the kernel weights its A operands only)
@@ -1810,8 +1749,7 @@ static int32_t gram_launch(cdh_handle h, int m, std::vector<double>& rec, bool w
     return CDH_OK;
 }
 constexpr int64_t kGramMaxCols = 4096;
-static int32_t cdh_gram_impl(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q,
-                             bool weighted = false) {
+static int32_t gram_block(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q, bool weighted) {
     if (m < 1 || m > kGramMaxCols) return fail(h, CDH_BAD_ARG, "need 1 <= m <= 4096 columns");
     NEED_P(h, idx1);
     NEED_P(h, out_G);
@@ -1858,9 +1796,13 @@ static int32_t cdh_gram_impl(cdh_handle h, int64_t m, const int64_t* idx1, doubl
     return CDH_OK;
 }
 
+int32_t cdh_gram(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) { return guarded(h, [&]() -> int32_t {
+    return gram_block(h, m, idx1, out_G, out_c, out_q, false);
+}); }
+
 // X_S'r (X_S'Wr for the weighted loss) for a list of columns: the refinement step of the screening init reads the normal
 // equations' residual off it (src/utils.jl:65-77 solves Xs \ y by QR; here: the Gram block plus refinement)
-static int32_t cdh_xt_r_cols_impl(cdh_handle h, int64_t m, const int64_t* idx1, double* out_m) {
+int32_t cdh_xt_r_cols(cdh_handle h, int64_t m, const int64_t* idx1, double* out_m) { return guarded(h, [&]() -> int32_t {
     if (m < 1 || m > h->cap) return fail(h, CDH_BAD_ARG, "need 1 <= m <= max(p, 4096) columns");
     NEED_P(h, idx1);
     NEED_P(h, out_m);
@@ -1878,13 +1820,13 @@ static int32_t cdh_xt_r_cols_impl(cdh_handle h, int64_t m, const int64_t* idx1, 
         for (int64_t i = 0; i < mm; ++i) out_m[o + i] = cd[(size_t)(2 * i)];
     }
     return CDH_OK;
-}
+}); }
 
 // X_S'WX_S, X_S'Wr, r'Wr: the weighted normal equations of the refit of locpolyl1 (varying_coefficient_lasso.jl:71-76) at the
 // current residual.  The Gram kernel weights G and c; r'Wr is the weighted moment of r.
-static int32_t cdh_gram_weighted_impl(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) {
+int32_t cdh_gram_weighted(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) { return guarded(h, [&]() -> int32_t {
     if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "a weighted Gram block needs the CDH_WLS loss with its weights set");
-    CHK(cdh_gram_impl(h, m, idx1, out_G, out_c, nullptr, true));
+    CHK(gram_block(h, m, idx1, out_G, out_c, nullptr, true));
     if (out_q) {
         CHK(resid_moments_dev(h));
         HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1892,10 +1834,10 @@ static int32_t cdh_gram_weighted_impl(cdh_handle h, int64_t m, const int64_t* id
         *out_q = h->h_red[2];
     }
     return CDH_OK;
-}
+}); }
 
 // _stdX!(out, w, X) (utils.jl:140-151): out_j = sqrt(sum_i w_i X_ij^2 / n_total)
-static int32_t cdh_col_wrms_impl(cdh_handle h, double* out_p) {
+int32_t cdh_col_wrms(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_p);
     if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "weighted column scales need the CDH_WLS loss with its weights set");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1905,7 +1847,7 @@ static int32_t cdh_col_wrms_impl(cdh_handle h, double* out_p) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(cd[(size_t)(2 * j + 1)] / (double)h->n_total);
     return CDH_OK;
-}
+}); }
 
 // ---- varying-coefficient mode (varying_coefficient_lasso.jl:30-79) -------------------------------------------------
 static int32_t vc_refuse_shards(cdh_handle h) {
@@ -1914,8 +1856,8 @@ static int32_t vc_refuse_shards(cdh_handle h) {
     return CDH_OK;
 }
 
-static int32_t cdh_vc_set_data_impl(cdh_handle h, int64_t p_base, int32_t degree, const void* host_X, int64_t ld,
-                                    const void* host_z) {
+int32_t cdh_vc_set_data(cdh_handle h, int64_t p_base, int32_t degree, const void* host_X, int64_t ld,
+                                    const void* host_z) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, host_X);
     NEED_P(h, host_z);
     if (degree < 0 || degree > 3) return fail(h, CDH_BAD_ARG, "the polynomial degree must be 0 .. 3");
@@ -1938,9 +1880,9 @@ static int32_t cdh_vc_set_data_impl(cdh_handle h, int64_t p_base, int32_t degree
     HIPCHK(h, hipMemcpyAsync(h->vc_z, host_z, (size_t)h->n * h->esz, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_vc_set_point_impl(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double* out_std) {
+int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double* out_std) { return guarded(h, [&]() -> int32_t {
     if (h->vc_degree < 0) return fail(h, CDH_BAD_ARG, "cdh_vc_set_point needs cdh_vc_set_data first");
     if (kernel_kind != kVcGaussian && kernel_kind != kVcEpanechnikov) return fail(h, CDH_BAD_ARG, "unknown smoothing kernel");
     if (!(bandwidth > 0.0) || !std::isfinite(bandwidth)) return fail(h, CDH_BAD_ARG, "the bandwidth must be positive");
@@ -2007,11 +1949,11 @@ static int32_t cdh_vc_set_point_impl(cdh_handle h, int32_t kernel_kind, double b
     }
     if (out_std) for (int64_t j = 0; j < h->p; ++j) out_std[j] = std::sqrt(cd[(size_t)j] / (double)h->n_total);
     return CDH_OK;
-}
+}); }
 
 // std(f.r) as Statistics.std computes it (two passes: the mean, then the centred sum of squares; Bessel-corrected) --
 // lasso.jl:37,52,81,97,143 -- without the cancellation of the one-pass form when the mean is large against the spread
-static int32_t cdh_resid_std_impl(cdh_handle h, double* out_std, double* out_mean) {
+int32_t cdh_resid_std(cdh_handle h, double* out_std, double* out_mean) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_std);
     HIPCHK(h, hipSetDevice(h->device));
     CHK(resid_moments_dev(h));
@@ -2030,16 +1972,14 @@ static int32_t cdh_resid_std_impl(cdh_handle h, double* out_std, double* out_mea
     *out_std = std::sqrt(std::max(ss - s1 * s1 / n, 0.0) / (n - 1.0));
     if (out_mean) *out_mean = mean;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_reuse_residual(cdh_handle h, int32_t on) {
-    NEED_H(h);
+int32_t cdh_set_reuse_residual(cdh_handle h, int32_t on) { return guarded(h, [&]() -> int32_t {
     h->reuse_residual = on != 0;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_resid_moments(cdh_handle h, double* out_sum, double* out_sumsq) {
-    NEED_H(h);
+int32_t cdh_resid_moments(cdh_handle h, double* out_sum, double* out_sumsq) { return guarded(h, [&]() -> int32_t {
     HIPCHK(h, hipSetDevice(h->device));
     CHK(resid_moments_dev(h));
     HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
@@ -2047,9 +1987,9 @@ int32_t cdh_resid_moments(cdh_handle h, double* out_sum, double* out_sumsq) {
     if (out_sum) *out_sum = h->h_red[0];
     if (out_sumsq) *out_sumsq = h->h_red[1];
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_objective_impl(cdh_handle h, double* out) {
+int32_t cdh_objective(cdh_handle h, double* out) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out);
     HIPCHK(h, hipSetDevice(h->device));
     CHK(resid_moments_dev(h));
@@ -2063,63 +2003,56 @@ static int32_t cdh_objective_impl(cdh_handle h, double* out) {
     const double ss = h->loss == CDH_WLS ? h->h_red[2] : h->h_red[1];
     *out = (h->loss == CDH_SQRT ? std::sqrt(ss) : ss / (2.0 * (double)h->n_total)) + pen;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_sweep_mode(cdh_handle h, int32_t mode, int32_t block) {
-    NEED_H(h);
+int32_t cdh_set_sweep_mode(cdh_handle h, int32_t mode, int32_t block) { return guarded(h, [&]() -> int32_t {
     if (mode != CDH_SWEEP_COORD && mode != CDH_SWEEP_BLOCK) return fail(h, CDH_BAD_ARG, "unknown sweep mode");
     if (mode == CDH_SWEEP_BLOCK && block != 2 && block != 4 && block != 8 && block != 16 && block != 32 && block != 64)
         return fail(h, CDH_BAD_ARG, "block size must be 2, 4, 8, 16, 32 or 64");
     h->mode = mode;
     if (mode == CDH_SWEEP_BLOCK) { h->blockB = block; h->width_default = false; }   // the caller's choice: the caller keeps the ranks alike
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_screening(cdh_handle h, int32_t on) {
-    NEED_H(h);
+int32_t cdh_set_screening(cdh_handle h, int32_t on) { return guarded(h, [&]() -> int32_t {
     if (on < 0 || on > 2) return fail(h, CDH_BAD_ARG, "screening: 0 = never, 1 = solves, 2 = cdh_pass as well");
     h->screening = on;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_gradient_cache(cdh_handle h, int32_t mode) {
-    NEED_H(h);
+int32_t cdh_set_gradient_cache(cdh_handle h, int32_t mode) { return guarded(h, [&]() -> int32_t {
     if (mode < 0 || mode > 3) return fail(h, CDH_BAD_ARG, "gradient cache: 0 = off, 1 = rent-or-buy, 2 = from the first full pass, 3 = 2 without the size guard");
     if (mode == 0) gc_invalidate(h, true);
     h->gc.mode = mode;
     h->gc.cooldown = 0; h->gc.backoff = 1;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_onchip_solve(cdh_handle h, int32_t on) {
-    NEED_H(h);
+int32_t cdh_set_onchip_solve(cdh_handle h, int32_t on) { return guarded(h, [&]() -> int32_t {
     h->small.enabled = on != 0;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_onchip_stats(cdh_handle h, int64_t* out2) {
-    NEED_H(h);
+int32_t cdh_onchip_stats(cdh_handle h, int64_t* out2) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out2);
     out2[0] = h->small.n_solves; out2[1] = h->small.n_gram;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_onchip_last(cdh_handle h, int64_t* out3) {
-    NEED_H(h);
+int32_t cdh_onchip_last(cdh_handle h, int64_t* out3) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out3);
     out3[0] = out3[1] = out3[2] = 0;
     if (h->small.h_ctl) { out3[0] = h->small.h_ctl->steps; out3[1] = (int64_t)h->small.h_ctl->cycles; out3[2] = (int64_t)h->small.h_ctl->ticks; }
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_get_gradient_cache(cdh_handle h, int32_t* out_mode) {
-    NEED_H(h);
+int32_t cdh_get_gradient_cache(cdh_handle h, int32_t* out_mode) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_mode);
     *out_mode = h->gc.mode;
     return CDH_OK;
-}
+}); }
 
-static int32_t cdh_cache_drift_impl(cdh_handle h, int32_t rereference_now, double* out3) {
+int32_t cdh_cache_drift(cdh_handle h, int32_t rereference_now, double* out3) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out3);
     GradCache& c = h->gc;
     if (rereference_now && c.valid && gc_applicable(h)) {
@@ -2128,10 +2061,9 @@ static int32_t cdh_cache_drift_impl(cdh_handle h, int32_t rereference_now, doubl
     }
     out3[0] = c.drift_last; out3[1] = c.drift_max; out3[2] = (double)c.n_drift;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_cache_stats(cdh_handle h, int64_t* out10) {
-    NEED_H(h);
+int32_t cdh_cache_stats(cdh_handle h, int64_t* out10) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out10);
     const GradCache& c = h->gc;
     out10[0] = c.n_passes; out10[1] = c.n_certified; out10[2] = c.n_exact;
@@ -2139,10 +2071,9 @@ int32_t cdh_cache_stats(cdh_handle h, int64_t* out10) {
     out10[6] = c.n_cov; out10[7] = c.n_reconcile; out10[8] = c.n_rollbacks;
     out10[9] = c.n_dev_passes;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_cache_gram_column(cdh_handle h, int64_t k1, double* out_p, double* out_eps) {
-    NEED_H(h);
+int32_t cdh_cache_gram_column(cdh_handle h, int64_t k1, double* out_p, double* out_eps) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_p);
     if (k1 < 1 || k1 > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
     GradCache& c = h->gc;
@@ -2154,40 +2085,36 @@ int32_t cdh_cache_gram_column(cdh_handle h, int64_t k1, double* out_p, double* o
     std::memcpy(out_p, col.data(), sizeof(double) * (size_t)h->p);
     if (out_eps) *out_eps = h->dtype == CDH_F32 ? 5.9604644775390625e-8 * kCrossF32EpsFactor / std::sqrt((double)h->n_total) : 0.0;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_device_loop(cdh_handle h, int32_t on) {
-    NEED_H(h);
+int32_t cdh_set_device_loop(cdh_handle h, int32_t on) { return guarded(h, [&]() -> int32_t {
     h->gc.cs_enabled = on != 0;
     if (on == 2) h->gc.cs_helpers = 0;                 // the loop without its helper workgroups
     else if (on > 2) h->gc.cs_helpers = std::min(kCsCrewMax, on);
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_device_loop_stats(cdh_handle h, int64_t* out12) {
-    NEED_H(h);
+int32_t cdh_device_loop_stats(cdh_handle h, int64_t* out12) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out12);
     out12[0] = h->gc.n_cs_launches; out12[1] = h->gc.n_cs_passes; out12[2] = h->gc.n_cs_folds; out12[3] = h->gc.n_cs_exact;
     for (int i = 0; i < 8; ++i) out12[4 + i] = h->gc.cs_ticks[i];
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_device_loop_table(cdh_handle h, int64_t* out6 /* eight values by now */) {
-    NEED_H(h);
+int32_t cdh_device_loop_table(cdh_handle h, int64_t* out6 /* eight values by now */) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out6);
     out6[0] = h->gc.n_cs_table_passes; out6[1] = h->gc.n_cs_table_rows; out6[2] = h->gc.cs_table_reset ? 0 : h->gc.cs_ncid; out6[3] = kCsTableCap;
     out6[4] = h->gc.n_forced_rounds; out6[5] = h->gc.n_cs_forced_rounds; out6[6] = h->gc.n_cs_crew_passes; out6[7] = h->gc.n_cs_crew_jobs;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_use_graph(cdh_handle h, int32_t on) {
-    NEED_H(h);
+int32_t cdh_set_use_graph(cdh_handle h, int32_t on) { return guarded(h, [&]() -> int32_t {
     h->use_graph = on != 0;
     if (on) h->graph_broken = false;   // asking again retries a capture that failed earlier
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_comm_unique_id(void* out_128_bytes) {
+int32_t cdh_comm_unique_id(void* out_128_bytes) { return guarded([&]() -> int32_t {
     NEED_P(nullptr, out_128_bytes);
     std::string err;
     if (!load_rccl(err)) { g_create_error = err; return CDH_RCCL_ERROR; }
@@ -2196,10 +2123,9 @@ int32_t cdh_comm_unique_id(void* out_128_bytes) {
     if (g_rccl.GetUniqueId(&id) != 0) { g_create_error = "ncclGetUniqueId failed"; return CDH_RCCL_ERROR; }
     std::memcpy(out_128_bytes, &id, sizeof id);
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_comm_init(cdh_handle h, const void* id_128_bytes, int32_t rank, int32_t nranks) {
-    NEED_H(h);
+int32_t cdh_comm_init(cdh_handle h, const void* id_128_bytes, int32_t rank, int32_t nranks) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, id_128_bytes);
     if (h->host_fn) return fail(h, CDH_BAD_ARG, "the handle already exchanges through a host transport");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, CDH_BAD_ARG, "bad rank / nranks");
@@ -2218,10 +2144,9 @@ int32_t cdh_comm_init(cdh_handle h, const void* id_128_bytes, int32_t rank, int3
     h->rank = rank; h->nranks = nranks;
     h->lost_exchange = false;          // an exchange is installed again (after a drop: cdh_comm_drop)
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_comm_drop(cdh_handle h) {
-    NEED_H(h);
+int32_t cdh_comm_drop(cdh_handle h) { return guarded(h, [&]() -> int32_t {
     if (!h->comm) return CDH_OK;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2231,11 +2156,10 @@ int32_t cdh_comm_drop(cdh_handle h) {
     h->comm = nullptr;
     if (h->nranks > 1 && !h->p2p_on && !h->host_fn) h->lost_exchange = true;
     return CDH_OK;
-}
+}); }
 
 // ---- optional direct exchange (p2p_exchange.hpp) -------------------------------------------------
-int32_t cdh_p2p_local_handle(cdh_handle h, void* out_64_bytes) {
-    NEED_H(h);
+int32_t cdh_p2p_local_handle(cdh_handle h, void* out_64_bytes) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_64_bytes);
     static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size is part of the ABI");
     HIPCHK(h, hipSetDevice(h->device));
@@ -2256,10 +2180,9 @@ int32_t cdh_p2p_local_handle(cdh_handle h, void* out_64_bytes) {
     HIPCHK(h, hipIpcGetMemHandle(&ipc, h->p2p_inbox));
     std::memcpy(out_64_bytes, &ipc, sizeof ipc);
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_p2p_connect(cdh_handle h, const void* handles_64_bytes_each, int32_t rank, int32_t nranks) {
-    NEED_H(h);
+int32_t cdh_p2p_connect(cdh_handle h, const void* handles_64_bytes_each, int32_t rank, int32_t nranks) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, handles_64_bytes_each);
     if (h->host_fn) return fail(h, CDH_BAD_ARG, "the handle already exchanges through a host transport");
     if (nranks < 1 || nranks > kP2PMaxRanks || rank < 0 || rank >= nranks)
@@ -2280,20 +2203,18 @@ int32_t cdh_p2p_connect(cdh_handle h, const void* handles_64_bytes_each, int32_t
     }
     h->rank = rank; h->nranks = nranks; h->p2p_ranks = nranks;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_p2p_enable(cdh_handle h, int32_t on) {
-    NEED_H(h);
+int32_t cdh_p2p_enable(cdh_handle h, int32_t on) { return guarded(h, [&]() -> int32_t {
     if (on && !h->p2p_ranks) return fail(h, CDH_BAD_ARG, "p2p exchange is not connected");
     if (on && *(volatile int*)h->p2p_timeout)
         return fail(h, CDH_RCCL_ERROR, "p2p exchange timed out earlier on this handle; it stays off");
     h->p2p_on = on != 0;
     if (h->p2p_on) h->lost_exchange = false;   // the direct exchange serves the shard again
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_set_host_exchange(cdh_handle h, cdh_host_allreduce_fn fn, void* user, int32_t rank, int32_t nranks) {
-    NEED_H(h);
+int32_t cdh_set_host_exchange(cdh_handle h, cdh_host_allreduce_fn fn, void* user, int32_t rank, int32_t nranks) { return guarded(h, [&]() -> int32_t {
     if (!fn) {
         // a shard of a multi-rank problem must not quietly fall into the single-process kernels on its local rows
         if (h->host_fn && h->nranks > 1 && !h->comm && !h->p2p_ranks) h->lost_exchange = true;
@@ -2311,11 +2232,10 @@ int32_t cdh_set_host_exchange(cdh_handle h, cdh_host_allreduce_fn fn, void* user
     h->host_fn = fn; h->host_user = user; h->rank = rank; h->nranks = nranks;
     h->lost_exchange = false;
     return CDH_OK;
-}
+}); }
 
 int32_t cdh_exchange_stats(cdh_handle h, int64_t* out_rccl_calls, int64_t* out_p2p_calls, int64_t* out_host_calls,
-                           int32_t* out_nranks) {
-    NEED_H(h);
+                           int32_t* out_nranks) { return guarded(h, [&]() -> int32_t {
     if (out_rccl_calls) *out_rccl_calls = h->n_rccl_calls;
     if (out_p2p_calls) *out_p2p_calls = h->n_p2p_calls;
     if (out_host_calls) *out_host_calls = h->n_host_calls;
@@ -2332,10 +2252,9 @@ int32_t cdh_exchange_stats(cdh_handle h, int64_t* out_rccl_calls, int64_t* out_p
         *out_nranks = n;
     }
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_exchange_probe(cdh_handle h, double* inout, int64_t count) {
-    NEED_H(h);
+int32_t cdh_exchange_probe(cdh_handle h, double* inout, int64_t count) { return guarded(h, [&]() -> int32_t {
     if (count < 0 || count > 4096 || (count > 0 && !inout)) return fail(h, CDH_BAD_ARG, "probe: 0 <= count <= 4096");
     if (!h->d_red) return fail(h, CDH_BAD_ARG, "probe: handle has no data yet");
     HIPCHK(h, hipSetDevice(h->device));
@@ -2344,10 +2263,9 @@ int32_t cdh_exchange_probe(cdh_handle h, double* inout, int64_t count) {
     HIPCHK(h, hipMemcpyAsync(inout, h->d_red, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return p2p_check(h);
-}
+}); }
 
-int32_t cdh_exchange_latency(cdh_handle h, int64_t count, int32_t iters, double* out_us) {
-    NEED_H(h);
+int32_t cdh_exchange_latency(cdh_handle h, int64_t count, int32_t iters, double* out_us) { return guarded(h, [&]() -> int32_t {
     if (count < 1 || count > 4096 || iters < 1 || iters > 100000 || !out_us) return fail(h, CDH_BAD_ARG, "latency probe: 1 <= count <= 4096, 1 <= iters <= 100000");
     if (!h->d_red) return fail(h, CDH_BAD_ARG, "probe: handle has no data yet");
     HIPCHK(h, hipSetDevice(h->device));
@@ -2363,153 +2281,19 @@ int32_t cdh_exchange_latency(cdh_handle h, int64_t count, int32_t iters, double*
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
     *out_us = (double)ms * 1e3 / iters;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_profile_begin(cdh_handle h) {
-    NEED_H(h);
+int32_t cdh_profile_begin(cdh_handle h) { return guarded(h, [&]() -> int32_t {
     h->prof = true; h->prof_ms = 0.0; h->prof_bytes = 0.0; h->prof_launches = 0;
     return CDH_OK;
-}
+}); }
 
-int32_t cdh_profile_end(cdh_handle h, double* out_ms, int64_t* out_launches, double* out_algorithmic_bytes) {
-    NEED_H(h);
+int32_t cdh_profile_end(cdh_handle h, double* out_ms, int64_t* out_launches, double* out_algorithmic_bytes) { return guarded(h, [&]() -> int32_t {
     h->prof = false;
     if (out_ms) *out_ms = h->prof_ms;
     if (out_launches) *out_launches = h->prof_launches;
     if (out_algorithmic_bytes) *out_algorithmic_bytes = h->prof_bytes;
     return CDH_OK;
-}
-
-// ---- exception firewall: nothing may unwind across the C ABI ----------------------------------
-#define CDH_CATCH(h)                                                              \
-    catch (const std::bad_alloc&) { return fail((h), CDH_OOM, "host allocation failed"); } \
-    catch (const std::exception& e) { return fail((h), CDH_BAD_ARG, e.what()); }  \
-    catch (...) { return fail((h), CDH_BAD_ARG, "unknown C++ exception"); }
-
-int32_t cdh_pass(cdh_handle h, int64_t m, const int64_t* idx1, double* out_maxH) {
-    NEED_H(h);
-    try { return cdh_pass_impl(h, m, idx1, out_maxH); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_solve(cdh_handle h, const cdh_options* opt, cdh_stats* out) {
-    NEED_H(h);
-    try { return cdh_solve_impl(h, opt, out); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_coordinate_descent(cdh_handle h, const cdh_options* opt, cdh_stats* out) {
-    NEED_H(h);
-    try { return cdh_coordinate_descent_impl(h, opt, out); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_initialize(cdh_handle h, int64_t x_length, int64_t nnz, const int64_t* idx1, const double* val) {
-    NEED_H(h);
-    try { return cdh_initialize_impl(h, x_length, nnz, idx1, val); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_set_iterate(cdh_handle h, int64_t x_length, int64_t nnz, const int64_t* idx1, const double* val) {
-    NEED_H(h);
-    try { return cdh_set_iterate_impl(h, x_length, nnz, idx1, val); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_lambda_max(cdh_handle h, double* out) {
-    NEED_H(h);
-    try { return cdh_lambda_max_impl(h, out); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_col_rms(cdh_handle h, double* out_p) {
-    NEED_H(h);
-    try { return cdh_col_rms_impl(h, out_p); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_xt_r(cdh_handle h, double* out_p) {
-    NEED_H(h);
-    try { return cdh_xt_r_impl(h, out_p); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_gram(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) {
-    NEED_H(h);
-    try { return cdh_gram_impl(h, m, idx1, out_G, out_c, out_q); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_gram_weighted(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) {
-    NEED_H(h);
-    try { return cdh_gram_weighted_impl(h, m, idx1, out_G, out_c, out_q); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_col_wrms(cdh_handle h, double* out_p) {
-    NEED_H(h);
-    try { return cdh_col_wrms_impl(h, out_p); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_vc_set_data(cdh_handle h, int64_t p_base, int32_t degree, const void* host_X, int64_t ld, const void* host_z) {
-    NEED_H(h);
-    try { return cdh_vc_set_data_impl(h, p_base, degree, host_X, ld, host_z); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double* out_std) {
-    NEED_H(h);
-    try { return cdh_vc_set_point_impl(h, kernel_kind, bandwidth, z0, out_std); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_xt_r_cols(cdh_handle h, int64_t m, const int64_t* idx1, double* out_m) {
-    NEED_H(h);
-    try { return cdh_xt_r_cols_impl(h, m, idx1, out_m); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_resid_std(cdh_handle h, double* out_std, double* out_mean) {
-    NEED_H(h);
-    try { return cdh_resid_std_impl(h, out_std, out_mean); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_generate(cdh_handle h, uint64_t seed, int64_t s, double noise, double* out_beta_star) {
-    NEED_H(h);
-    try { return cdh_generate_impl(h, seed, s, noise, out_beta_star); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_objective(cdh_handle h, double* out) {
-    NEED_H(h);
-    try { return cdh_objective_impl(h, out); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_gradient(cdh_handle h, int64_t k1, double* out) {
-    NEED_H(h);
-    try { return cdh_gradient_impl(h, k1, out); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_descend(cdh_handle h, int64_t k1, double* out_h) {
-    NEED_H(h);
-    try { return cdh_descend_impl(h, k1, out_h); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_cache_drift(cdh_handle h, int32_t rereference_now, double* out3) {
-    NEED_H(h);
-    try { return cdh_cache_drift_impl(h, rereference_now, out3); }
-    CDH_CATCH(h)
-}
-
-int32_t cdh_set_penalty(cdh_handle h, double lambda0, const double* omega, int64_t n_omega) {
-    NEED_H(h);
-    try { return cdh_set_penalty_impl(h, lambda0, omega, n_omega); }
-    CDH_CATCH(h)
-}
+}); }
 
 }  // extern "C"

@@ -1410,7 +1410,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     ctl.nnz = (int32_t)h->x.nnz(); ctl.prev_conv = *prev_conv ? 1 : 0; ctl.conv = *conv ? 1 : 0; ctl.inject_count = c.inject_count;
     ctl.status = -1; ctl.n_list = 0;
     ctl.n_moved = (int32_t)c.moved.size();      // in: the moves still pending on g (out: those pending when the kernel stops)
-    for (size_t m = 0; m < c.moved.size(); ++m) { c.cs_out_moved_idx[m] = (int32_t)c.moved[m]; c.cs_out_moved_val[m] = c.dbeta[(size_t)c.moved[m]]; }
+    for (size_t m = 0; m < c.moved.size(); ++m) { c.cs_out_moved_idx[m] = (int32_t)c.moved[m]; c.cs_out_moved_val[m] = c.moved.value(c.moved[m]); }
     for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) c.cs_in_sup[s_] = (int32_t)h->x.coord(s_);
     CovSolveBufs b = c.cs_bufs;
     b.g = c.d_g; b.Gcols = c.d_G; b.slot = c.d_slot; b.a = c.d_a; b.omega = h->omega; b.beta = h->beta;
@@ -1435,13 +1435,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     const int64_t nnz_old = h->x.nnz();
     std::vector<int64_t> old_idx((size_t)nnz_old);
     for (int64_t s_ = 0; s_ < nnz_old; ++s_) { old_idx[(size_t)s_] = h->x.coord(s_); c.cs_old[(size_t)h->x.coord(s_)] = h->x.slot_value(s_); }
-    auto note_move = [&](int64_t k, double d) {
-        if (d == 0.0) return;
-        h->dots_valid = false;        // the residual the handle stands for moves
-        if (!h->r_in_pending[(size_t)k]) { h->r_in_pending[(size_t)k] = 1; h->r_pending_list.push_back(k); }
-        h->r_pending[(size_t)k] += d;
-        if (c.beta_ok) c.beta_ref[(size_t)k] += d;
-    };
+    auto note_move = [&](int64_t k, double d) { if (d != 0.0) note_move_off_stream(h, k, d, true); };
     h->x.clear();
     for (int32_t s_ = 0; s_ < ctl.nnz; ++s_) {
         const int64_t k = c.cs_out_sup_idx[s_];
@@ -1453,14 +1447,11 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     }
     for (int64_t k : old_idx) { if (c.cs_old[(size_t)k] != 0.0) note_move(k, -c.cs_old[(size_t)k]); c.cs_old[(size_t)k] = 0.0; }
     // ---- the cache: moves still pending on g, r'r, the counters ----
-    for (int64_t j : c.moved) { c.dbeta[(size_t)j] = 0.0; c.in_moved[(size_t)j] = 0; }      // what went in is in the kernel's list (or folded)
-    c.moved.clear();
+    c.moved.clear();                 // what went in is in the kernel's list (or folded)
     for (int32_t m = 0; m < ctl.n_moved; ++m) {
         const int64_t k = c.cs_out_moved_idx[m];
         const double v = c.cs_out_moved_val[m];
-        if (v == 0.0) continue;
-        c.dbeta[(size_t)k] = v;
-        if (!c.in_moved[(size_t)k]) { c.in_moved[(size_t)k] = 1; c.moved.push_back(k); }
+        if (v != 0.0) c.moved.set(k, v);
     }
     c.cs_ncid = ctl.ncid; c.cs_tepoch = ctl.tepoch; c.n_cs_table_passes += ctl.table_passes; c.n_cs_table_rows += ctl.table_rows;
     c.n_cs_forced_rounds += ctl.forced_rounds; c.n_cs_crew_passes += ctl.crew_passes; c.n_cs_crew_jobs += ctl.crew_jobs;

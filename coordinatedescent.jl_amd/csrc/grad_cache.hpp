@@ -53,9 +53,9 @@ int32_t gc_size(cdh_handle h) {   // first use on this handle
     c.d_cross = std::move(cross); c.d_cross_part = std::move(cross_part); c.d_cols = std::move(cols);
     c.h_cross.assign((size_t)launches * kCrossRec, 0.0);
     const size_t p = (size_t)h->p;
-    c.g.assign(p, 0.0); c.a.assign(p, 0.0); c.dbeta.assign(p, 0.0);
-    c.in_moved.assign(p, 0); c.slot.assign(p, -1); c.beta_ref.assign(p, 0.0);
-    c.beta_ok = h->r_consistent;          // r == y - X * (the handle's iterate) right now?
+    c.g.assign(p, 0.0); c.a.assign(p, 0.0); c.moved.resize(h->p);
+    c.slot.assign(p, -1); c.beta_ref.assign(p, 0.0);
+    c.beta_ok = h->rs.consistent();         // r == y - X * (the handle's iterate) right now?
     if (c.beta_ok)
         for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) c.beta_ref[(size_t)h->x.coord(s_)] = h->x.slot_value(s_);
     return CDH_OK;
@@ -206,7 +206,7 @@ int32_t gc_cert_abs(cdh_handle h, double* out) {
     // for fully correlated columns (measured: tests/test_gpu_parity.py::test_fp32_gram_columns_carry_the_declared_error); a
     // carried gradient updated with them is off by at most eps_G sqrt(a_k) sum_j |dbeta_j| sqrt(a_j) <~ eps_G sqrt(a_k y'y).
     // Declared with a factor 4: 2^-24 * 512 / sqrt(n) -- eight times the residual's own term at U = 0.
-    *out = 5.9604644775390625e-8 * std::sqrt(c.yy / (double)h->n_total) * (64.0 * std::sqrt((double)(h->r_roundings + 1)) + kCrossF32EpsFactor);
+    *out = 5.9604644775390625e-8 * std::sqrt(c.yy / (double)h->n_total) * (64.0 * std::sqrt((double)(h->rs.roundings() + 1)) + kCrossF32EpsFactor);
     return CDH_OK;
 }
 
@@ -336,16 +336,20 @@ int32_t cov_run(cdh_handle h, const int64_t* idx0, int m, bool want_g) {
     c.g_host_ok = false;              // d_g has moved on; c.g is the gradient BEFORE the chunk until it is accepted
     return CDH_OK;
 }
+// Coordinate k of the iterate moved by d in a kernel that leaves r alone: r owes the move, and a cache whose reference
+// follows the iterate (beta_ok) learns of it.  ref_takes_nan: the reference takes a NaN move as well (the device loop's
+// moves, as they always have); otherwise it skips it.
+inline void note_move_off_stream(cdh_handle h, int64_t k, double d, bool ref_takes_nan) {
+    h->rs.moved(k, d);
+    if (h->gc.beta_ok && (ref_takes_nan || d == d)) h->gc.beta_ref[(size_t)k] += d;
+}
 // the staged results of visit i become real: SparseIterate writes, the move noted for r, maxH
 void cov_apply_visit(cdh_handle h, int64_t k, int i) {
     if (h->h_touched[i] && h->x.get(k) == 0.0) h->x.set(k, 1.0);  // pre-prox non-zero: slot appended
     h->x.set(k, h->h_newval[i]);
     const double hv = h->h_hs[i];
     if (hv == 0.0) return;
-    h->dots_valid = false;            // the residual the handle stands for moves
-    if (!h->r_in_pending[(size_t)k]) { h->r_in_pending[(size_t)k] = 1; h->r_pending_list.push_back(k); }
-    h->r_pending[(size_t)k] += hv;
-    if (hv == hv && h->gc.beta_ok) h->gc.beta_ref[(size_t)k] += hv;
+    note_move_off_stream(h, k, hv, false);
 }
 // the chunk is accepted: maxH, r'r, the counters; `have_g_new`: c.g_new is the gradient after the chunk
 void cov_accept_tail(cdh_handle h, int m, double* maxH, bool have_g_new) {
@@ -387,20 +391,18 @@ int32_t cov_reject(cdh_handle h, const int64_t* idx0, int m) {
 int32_t gc_validate(cdh_handle h) {
     GradCache& c = h->gc;
     std::vector<double> cd;
-    if (h->dots_valid && h->dots_w == h->has_w && (int64_t)h->dots_stash.size() == 2 * h->p) {
+    if (h->rs.can_adopt_dots(h->has_w, h->p)) {
         // the dots of all p columns with this very residual were taken a moment ago (_findLambdaMax, coordinate_descent.jl:118-149,
         // or cdh_xt_r, before the first solve of a path): that pass over X is the reference pass
-        cd = h->dots_stash;
-        h->n_dots_adopted += 1;
+        cd = h->rs.adopt_dots();
     } else {
         CHK(col_dots(h, 0, h->p, h->r, h->has_w));
         cd.resize((size_t)(2 * h->p));
         HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->dots_stash = cd; h->dots_valid = true; h->dots_w = h->has_w;
+        h->rs.dots_taken(cd, h->has_w);
     }
     for (int64_t k = 0; k < h->p; ++k) { c.g[(size_t)k] = cd[(size_t)(2 * k)]; c.a[(size_t)k] = cd[(size_t)(2 * k + 1)]; }
-    for (int64_t j : c.moved) { c.dbeta[(size_t)j] = 0.0; c.in_moved[(size_t)j] = 0; }
     c.moved.clear();
     c.valid = true;
     c.g_host_ok = true; c.g_dev_ok = false; c.a_dev_ok = false;
@@ -557,7 +559,7 @@ bool gc_fold_device(cdh_handle h) {
     const int64_t M = (int64_t)c.moved.size();
     if (M > h->cap) return false;
     if (gc_need_dev_g(h) != CDH_OK) { (void)hipGetLastError(); return false; }
-    for (int64_t i = 0; i < M; ++i) { h->h_idx[i] = c.moved[(size_t)i]; h->h_hs[i] = c.dbeta[(size_t)c.moved[(size_t)i]]; }
+    for (int64_t i = 0; i < M; ++i) { h->h_idx[i] = c.moved[(size_t)i]; h->h_hs[i] = c.moved.value(c.moved[(size_t)i]); }
     bool ok = hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)M, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
               hipMemcpyAsync(h->d_hs, h->h_hs, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, h->stream) == hipSuccess;
     for (int64_t pos0 = 0; ok && pos0 < M; pos0 += 64)
@@ -585,13 +587,12 @@ void gc_fold(cdh_handle h) {
         c.g_dev_ok = false;
     }
     for (int64_t j : c.moved) {
-        const double d = c.dbeta[(size_t)j];
+        const double d = c.moved.value(j);
         if (!on_device && d != 0.0) {
             (void)gc_host_column(h, c.slot[(size_t)j]);
             const std::vector<double>& col = c.G[(size_t)c.slot[(size_t)j]];
             for (int64_t k = 0; k < h->p; ++k) c.g[(size_t)k] -= d * col[(size_t)k];
         }
-        c.dbeta[(size_t)j] = 0.0; c.in_moved[(size_t)j] = 0;
     }
     c.moved.clear();
 }

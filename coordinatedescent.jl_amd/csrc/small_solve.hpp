@@ -18,7 +18,7 @@
 // dropzeros!'s swap-with-last) replayed on the device, because the ORDER of the support is the visit order of
 // the next active pass.  The 51 solves of a cold start (coordinate_descent.jl:24-37) run inside the same launch.
 // One host round trip per solve: beta, the support and the statistics come back (written by the kernel into pinned host
-// memory); the residual is left to be rebuilt when something reads it (r_lazy), or learns of the moves through the same
+// memory); the residual is left to be rebuilt when something reads it (ResidState::left_lazy), or learns of the moves through the same
 // deferred catch-up as the gradient cache's covariance-form visits (sync_r).
 // A visit step evaluates 64 consecutive positions of the visit list at once against the current g: every position
 // before the first one that moves is settled exactly (g does not change until something moves), so a full pass over a
@@ -565,7 +565,7 @@ int32_t small_prepare(cdh_handle h) {     // buffers, X'y and diag(G) of the cur
 // the solves lambdas[0 .. nlam) of one coordinateDescent! call, back to back in one launch; r must describe the handle's
 // iterate on entry (initialize! has run, or the carried residual is being reused)
 // from_c: the residual of the handle's iterate is y - X beta by definition (initialize! semantics), so nothing is read
-// from r: g = X'y - G beta inside the kernel, and r is left to be rebuilt lazily (r_lazy).  Otherwise (cdh_solve: "assumes
+// from r: g = X'y - G beta inside the kernel, and r is left to be rebuilt lazily (ResidState::left_lazy).  Otherwise (cdh_solve: "assumes
 // r is initialised", whatever it holds) g = X'r is taken from the device's r and the moves become pending updates of it.
 int32_t small_solve(cdh_handle h, const cdh_options* o, const double* lambdas, int nlam, uint64_t* rng, cdh_stats* st, bool from_c) {
     SmallPath& sp = h->small;
@@ -604,37 +604,29 @@ int32_t small_solve(cdh_handle h, const cdh_options* o, const double* lambdas, i
     if (!zc) HIPCHK(h, hipMemcpyAsync(sp.h_io, sp.d_io, small_io_bytes(h->p), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (ctl.precision_lost) {          // r'r ran out of digits (k_solve_small): nothing of the launch is used
-        std::vector<double> dense((size_t)h->p, 0.0);
-        for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) dense[(size_t)h->x.coord(s_)] = h->x.slot_value(s_);
-        HIPCHK(h, hipMemcpyAsync(h->beta, dense.data(), sizeof(double) * (size_t)h->p, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        CHK(upload_beta(h, h->x));
         sp.n_precision += 1;
         return kSmallPrecisionLost;
     }
     // what moved becomes pending residual updates (r_actual = r_virtual + X * pending: sync_r applies them before anything
     // reads r) and, for a gradient cache that holds a reference, pending moves like those of any other visit
     GradCache& c = h->gc;
-    h->dots_valid = false;             // the residual the handle stands for moves with the iterate
     if (from_c) {                      // r was never read and is not touched: it stands for the new iterate, to be formed on demand
         if (c.valid || c.beta_ok) gc_invalidate(h, false);
-        drop_r_pending(h);
+    } else {
+        h->rs.iterate_moved();         // (also where no coordinate did: the stash is not kept across a solve)
     }
     for (int64_t k = 0; k < h->p && !from_c; ++k) {
         const double d = sp.h_beta[k] - h->x.get(k);
         if (d == 0.0) continue;
-        if (!h->r_in_pending[(size_t)k]) { h->r_in_pending[(size_t)k] = 1; h->r_pending_list.push_back(k); }
-        h->r_pending[(size_t)k] += d;
-        if (d != d) { if (c.valid || c.beta_ok) gc_invalidate(h, false); continue; }
-        if (c.beta_ok) c.beta_ref[(size_t)k] += d;
-        if (c.valid) {
-            c.dbeta[(size_t)k] += d;
-            if (!c.in_moved[(size_t)k]) { c.in_moved[(size_t)k] = 1; c.moved.push_back(k); }
-        }
+        note_move_off_stream(h, k, d, false);
+        if (d != d) { if (c.valid || c.beta_ok) gc_invalidate(h, false); continue; }   // a NaN move: the cache knows nothing any more
+        if (c.valid) c.moved.add(k, d);
     }
     c.q_valid = false;
     h->x.clear();
     for (int32_t s_ = 0; s_ < ctl.nnz; ++s_) h->x.set(sp.h_sup[s_], sp.h_beta[sp.h_sup[s_]]);
-    if (from_c) { h->r_lazy = true; h->x_lazy = h->x; h->r_consistent = true; }
+    if (from_c) h->rs.left_lazy(h->x);
     *rng = ctl.rng;
     st->passes += ctl.passes; st->full_passes += ctl.full_passes; st->visits += ctl.visits;
     st->converged = ctl.converged; st->maxH = ctl.maxH;

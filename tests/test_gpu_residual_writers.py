@@ -348,7 +348,7 @@ def test_init_resid_is_exact_on_integer_data(cus, dtype):
 @gpu
 @pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
 def test_lazy_rebuild_after_a_one_launch_solve(monkeypatch, cus, dtype):
-    """The one-launch solve leaves r stale; reading f.r rebuilds it (sync_r -> rebuild_residual_from(x_lazy): one
+    """The one-launch solve leaves r stale; reading f.r rebuilds it (sync_r -> rebuild_residual_from(the lazy iterate): one
     k_init_resid launch with a non-integer iterate): M = nnz + 1 operations, one store, TV = |beta|."""
     monkeypatch.setenv("CDH_SMALL_PATH", "1")
     n, p, s = 1003, 50, 12
@@ -657,7 +657,7 @@ def test_catch_up_after_cache_served_solves(cus, dtype, P):
     reading f.r applies them with k_multi_axpy, 64 columns per launch: two batches with 36 = 4 * 8 + 4 in the second
     (P = 100), exactly one (64), one and a batch of a single column (65).  r was rebuilt by the solve's own initialize!
     (nnz + 1 operations, one store); the catch-up adds P moves and ceil(P / 64) stores.  Then once more after another
-    solve on the same handle: what the first catch-up left in r_pending must be gone."""
+    solve on the same handle: what the first catch-up left in the pending ledger must be gone."""
     n, p = 6007, 4 * P + 40
     rng0 = np.random.default_rng(P)
     sup = np.sort(rng0.choice(p, size=P, replace=False)).tolist()
@@ -693,7 +693,7 @@ def test_catch_up_after_cache_served_solves(cus, dtype, P):
 def test_catch_up_of_moves_merged_over_several_solves(cus, dtype, P):
     """With the residual reused between warm starts (cdh_set_reuse_residual: what LassoPath runs by default) a solve does not
     rebuild r, so the moves of three cache-served solves in a row stay pending and merge, coordinate by coordinate, in
-    r_pending; the list keeps the order the first of them gave it.  r is read once, at the end: it was last rebuilt by the
+    the pending ledger; the list keeps the order the first of them gave it.  r is read once, at the end: it was last rebuilt by the
     first solve's initialize! (nnz + 1 operations, one store), and the catch-up applies one merged move per coordinate in
     ceil(P / 64) launches.  TV is summed solve by solve; the move applied is the net one, and every one of them -- so the
     second batch's too -- is detectable."""
