@@ -18,5 +18,6 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   descendCoordinate_, coordinateDescent_, cdPass_, findLambdaMax, stdX, objective,
                   lasso, sqrtLasso, scaledLasso_, LassoPath, LassoSolution, LassoPathResult,
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
-                  get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1,
+                  get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
+                  getSigma, findInitResiduals_,
                   DimensionMismatch, ArgumentError, DomainError, HipError)

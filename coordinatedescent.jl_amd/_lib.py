@@ -135,6 +135,9 @@ def lib():
         "cdh_col_wrms": [vp, vp],
         "cdh_vc_set_data": [vp, i64, i32, vp, i64, vp],
         "cdh_vc_set_point": [vp, i32, f64, f64, vp],
+        "cdh_vc_set_point_loo": [vp, i32, f64, i64, vp, vp],
+        "cdh_resid_wmoments": [vp, P(f64), P(f64)],
+        "cdh_get_X_row": [vp, i64, i64, vp, vp],
         "cdh_resid_std": [vp, P(f64), P(f64)],
         "cdh_set_reuse_residual": [vp, i32],
         "cdh_resid_moments": [vp, P(f64), P(f64)],

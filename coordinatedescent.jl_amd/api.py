@@ -15,7 +15,7 @@ Reference files mirrored (relative to the reference's src/):
   coordinate_descent.jl              coordinateDescent!, _findLambdaMax
   atom_iterator.jl                   OrderedIterator, RandomIterator
   lasso.jl                           lasso, sqrtLasso, scaledLasso!, LassoPath
-  varying_coefficient_lasso.jl       the smoothing kernels, locpolyl1, get_nonzero_coordinates
+  varying_coefficient_lasso.jl       the smoothing kernels, locpolyl1, lvocv_locpolyl1, get_nonzero_coordinates
   ProximalBase 0.3.0 (not vendored)  ProxL1, SparseIterate (contract: SURVEY.md App. B)
 """
 from __future__ import annotations
@@ -567,6 +567,17 @@ class CDVaryingCoefficientLoss(CDWeightedLSLoss):
         check(self._L.cdh_vc_set_point(self._h, kernel._kind, kernel.h, float(z0), _vp(out)), self._h)
         return out
 
+    def set_point_leave_out(self, kernel, row):
+        """The point of lvocv_locpolyl1 for observation `row` (0-based, as X_cols counts columns): z0 = z[row] as stored,
+        w .= evaluate.(kernel, z, z0); w[row] = 0; _expand_X!; _stdX! (:109-113), and the screening scores |Σ_i X_ij w_i y_i| of
+        _findLargestCorrelations(w, X, y, s) (src/utils.jl:108-124) from the same pass over the design; returns
+        (stdX, scores).  The iterate the handle holds is kept."""
+        if not isinstance(kernel, SmoothingKernel) or kernel._kind is None:
+            raise TypeError("MethodError: kernel::SmoothingKernel")
+        std, scores = np.zeros(self.p), np.zeros(self.p)
+        check(self._L.cdh_vc_set_point_loo(self._h, kernel._kind, kernel.h, int(row), _vp(std), _vp(scores)), self._h)
+        return std, scores
+
 
 def initialize_(f, x):
     """initialize!(f, x): r = y - Xβ (src/cd_differentiable_function.jl:59-72)."""
@@ -930,3 +941,116 @@ def locpolyl1(X, z, y, zgrid, degree, kernel, lambda0, refit, options=None):
             if S.any():
                 outR[S, ind] = _vc_refit(f, b, S)
     return out, outR
+
+
+def getSigma(f):
+    """_getSigma(w, f.r) (src/utils.jl:167-175): sqrt(Σ w r² / Σ w) at the residual the handle stands for; both sums are
+    taken on the device (cdh_resid_wmoments)."""
+    sw, swr2 = C.c_double(), C.c_double()
+    check(f._L.cdh_resid_wmoments(f._h, C.byref(sw), C.byref(swr2)), f._h)
+    return float(np.sqrt(swr2.value / sw.value))
+
+
+def findInitResiduals_(f, scores, s):
+    """_findInitResiduals!(w, X, y, s, f.r) (src/utils.jl:79-92) given the scores |X_j'Wy| of _findLargestCorrelations
+    (:108-124): S = the columns whose score is at least the s-th largest (ties kept), and f.r = y - X_S (X_S'WX_S) \\ (X_S'Wy),
+    formed on the device -- the weighted normal equations from one Gram block at r = y, solved on the host as
+    solve_screening_ols solves them, the residual by initialize!.  The handle's iterate is the fit afterwards (nobody's x).
+    Returns the 1-based columns of S."""
+    L = f._L
+    scores = np.asarray(scores, dtype=np.float64)
+    S = np.nonzero(scores >= np.sort(scores)[::-1][s - 1])[0]
+    if len(S) > 4096:
+        raise ArgumentError("screening set larger than 4096 columns")
+    idx1 = np.ascontiguousarray(S + 1, dtype=np.int64)
+    m = len(S)
+    check(L.cdh_initialize(f._h, f.p, 0, None, None), f._h)            # beta = 0, r = y: X_S'Wr == X_S'Wy
+    f._synced = None
+    G, c = np.zeros((m, m)), np.zeros(m)
+    check(L.cdh_gram_weighted(f._h, m, _vp(idx1), _vp(G), _vp(c), None), f._h)
+
+    def normal_residual(b):                  # Xs'W(y - Xs b)
+        check(L.cdh_initialize(f._h, f.p, m, _vp(idx1), _vp(np.ascontiguousarray(b))), f._h)
+        out = np.zeros(m)
+        check(L.cdh_xt_r_cols(f._h, m, _vp(idx1), _vp(out)), f._h)
+        return out
+
+    coef = solve_screening_ols(G, c, normal_residual)
+    check(L.cdh_initialize(f._h, f.p, m, _vp(idx1), _vp(np.ascontiguousarray(coef))), f._h)
+    return idx1
+
+
+def _lvocv_point(f, beta, row, sx, scores, lambda0, opt, y_row, p_base, degree):
+    """One point of lvocv_locpolyl1 (:114-133) on a loss whose weights, design and y are those of the point that left `row`
+    out, given its stdX and screening scores: the screening σ, the σ loop, the refit and the prediction -> the point's record
+    (lvocv_locpolyl1 lists its fields)."""
+    Q1 = degree + 1
+    findInitResiduals_(f, scores, min(10, f.p))                                      # :114
+    sigma = getSigma(f)                                                              # :117
+    sigmas, solves = [sigma], []
+    for _ in range(10):                                                              # :119-127
+        coordinateDescent_(beta, f, ProxL1(lambda0 * sigma, sx), opt)
+        solves.append(f.last_stats)
+        sigmanew = getSigma(f)
+        sigmas.append(sigmanew)
+        if abs(sigmanew - sigma) / sigma < 1e-2:
+            break
+        sigma = sigmanew
+    b = beta.dense()
+    S = get_nonzero_coordinates(b, p_base, degree, True)                             # :130
+    coef, yhat = None, 0.0
+    if S.any():                                                                      # :131-132
+        coef = _vc_refit(f, b, S)
+        base = np.ascontiguousarray(np.nonzero(S)[0][::Q1] + 1, dtype=np.int64)      # the power-0 column of every group in S
+        xrow = np.zeros(base.shape[0])
+        check(f._L.cdh_get_X_row(f._h, int(row), base.shape[0], _vp(base), _vp(xrow)), f._h)
+        yhat = float(xrow @ coef[::Q1])
+    return {"row": int(row), "sigma_iters": len(solves), "sigmas": sigmas, "sigma": sigma, "solves": solves,
+            "support": beta.nzval2ind.copy(), "beta": b, "refit": coef, "yhat": yhat, "sq_err": (yhat - y_row) ** 2}
+
+
+def lvocv_locpolyl1(X, z, y, degree, hArr, kernelType, lambda0, options=None):
+    """lvocv_locpolyl1(X, z, y, degree, hArr, kernelType, λ0, options) (src/varying_coefficient_lasso.jl:82-137) -> MSE, a
+    float64 array of length(hArr): for every bandwidth the sum over the observations i of (Yh_i - y_i)², Yh_i the refitted
+    prediction at z0 = z[i] of the scaled lasso that left observation i out.  Per point: the leave-one-out setup and the
+    screening scores in one pass on the device (set_point_leave_out), the weighted screening init for the first σ
+    (findInitResiduals_, getSigma), at most ten warm-started solves with σ re-estimated after each (:119-127; the warm start
+    rebuilds r = y - Xβ, so the screening residual feeds the first σ only), the refit on the support's groups (_vc_refit)
+    and the prediction from the base row: at z0 = z[i] the expanded row i is X[i, j] at power 0 and exactly 0 above it.
+    β is one iterate carried over all points and all bandwidths, as in the reference.
+
+    An empty support -- which the reference never handles: its `\\` of a 0 x 0 system gives an empty vector and `dot` over
+    an empty selection 0 -- predicts Yh = 0 here as well.
+
+    X may also be an existing CDVaryingCoefficientLoss (z, y and degree are then the loss's own); a loss built here from
+    arrays is closed before returning.  One record per point is appended to the caller's f.point_stats: h, row, sigma_iters (solves run), sigmas (the screening σ, then σnew after every solve), sigma
+    (the σ of the last penalty), solves (the statistics of every solve), support (SparseIterate order), beta (dense), refit
+    (the coefficients on the support's groups, None when it is empty), yhat, sq_err ((Yh - y[row])²)."""
+    o = options or CDOptions()
+    opt = CDOptions(o.maxIter, o.optTol, o.randomize, True, o.numSteps, o.seed)          # :94
+    hArr = np.atleast_1d(np.asarray(hArr, dtype=np.float64))
+    kernels = [createKernel(kernelType, h) for h in hArr]                                # :106
+    if isinstance(X, CDVaryingCoefficientLoss):
+        f = X
+    else:
+        X = np.asarray(X)
+        if np.asarray(z).shape[0] != X.shape[0]:
+            raise DimensionMismatch("length(z) != size(X, 1)")
+        if np.asarray(y).shape[0] != X.shape[0]:
+            raise DimensionMismatch("length(y) != size(X, 1)")
+        f = CDVaryingCoefficientLoss(y, X, z, degree)
+    try:
+        yv = f.y.astype(np.float64)
+        MSE = np.zeros(hArr.shape[0])
+        beta = SparseIterate(f.p)
+        for indH, kernel in enumerate(kernels):
+            for i in range(f.n):
+                sx, scores = f.set_point_leave_out(kernel, i)                            # :109-113
+                rec = _lvocv_point(f, beta, i, sx, scores, lambda0, opt, yv[i], f.p_base, f.degree)
+                MSE[indH] += rec["sq_err"]                                               # :133
+                if f is X:                 # a caller's loss keeps the records; one built here is gone when this returns
+                    f.point_stats.append(dict(rec, h=kernel.h))
+    finally:
+        if f is not X:
+            f.close()
+    return MSE

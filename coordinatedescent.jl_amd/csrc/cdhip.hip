@@ -570,13 +570,16 @@ int32_t col_dots(cdh_handle h, int64_t j0, int64_t nc, const void* rvec, bool us
     return CDH_OK;
 }
 
-int32_t resid_moments_dev(cdh_handle h, const void* vec = nullptr, double shift = 0.0) {  // -> d_red[0..2] = sum v, sum v^2, sum w v^2 (v = r unless given; minus shift)
+int32_t resid_moments_dev(cdh_handle h, const void* vec = nullptr, double shift = 0.0, bool sum_w = false) {  // -> d_red[0..2] = sum v (sum_w: sum w; needs weights), sum v^2, sum w v^2 (v = r unless given; minus shift)
     if (!vec) { CHK(sync_r(h)); vec = h->r; }
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (h->nvec + kBlock - 1) / kBlock));
     CHK(dispatch(h, [&](auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
-        hipLaunchKernelGGL(k_resid_moments<T>, dim3(grid), dim3(kBlock), 0, h->stream, h->nvec,
-                           (const T*)vec, h->has_w ? (const T*)h->w : (const T*)nullptr, h->d_partials, shift, h->n);
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, h->stream, h->nvec,
+                               (const T*)vec, h->has_w ? (const T*)h->w : (const T*)nullptr, h->d_partials, shift, h->n);
+        };
+        if (sum_w) go(k_resid_moments<T, true>); else go(k_resid_moments<T>);
         return CDH_OK;
     }));
     hipLaunchKernelGGL(k_sum_records, dim3(1), dim3(kBlock), 0, h->stream, h->d_partials, grid, h->d_red);
@@ -1882,8 +1885,12 @@ int32_t cdh_vc_set_data(cdh_handle h, int64_t p_base, int32_t degree, const void
     return CDH_OK;
 }); }
 
-int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double* out_std) { return guarded(h, [&]() -> int32_t {
-    if (h->vc_degree < 0) return fail(h, CDH_BAD_ARG, "cdh_vc_set_point needs cdh_vc_set_data first");
+// One point of the varying-coefficient design: weights, expansion, weighted column scales -- around z0 (row0 < 0), or around
+// the stored z[row0] with that row's weight zero and the screening scores |X_j'Wy| on top (the leave-one-out point).
+static int32_t vc_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, int64_t row0, double* out_std,
+                        double* out_scores) {
+    const bool loo = row0 >= 0;
+    if (h->vc_degree < 0) return fail(h, CDH_BAD_ARG, "a varying-coefficient point needs cdh_vc_set_data first");
     if (kernel_kind != kVcGaussian && kernel_kind != kVcEpanechnikov) return fail(h, CDH_BAD_ARG, "unknown smoothing kernel");
     if (!(bandwidth > 0.0) || !std::isfinite(bandwidth)) return fail(h, CDH_BAD_ARG, "the bandwidth must be positive");
     if (!std::isfinite(z0)) return fail(h, CDH_BAD_ARG, "z0 must be finite");
@@ -1898,20 +1905,21 @@ int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, do
     CHK(dispatch(h, [&](auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         hipLaunchKernelGGL(k_vc_weights<T>, dim3(wgrid), dim3(kBlock), 0, h->stream, (const T*)h->vc_z, (T*)h->w, h->n,
-                           h->nvec, (int)kernel_kind, bandwidth, z0);
+                           h->nvec, (int)kernel_kind, bandwidth, z0, row0);
         return CDH_OK;
     }));
     HIPCHK(h, hipGetLastError());
     h->has_w = true;
     int64_t launches = 1;
     std::vector<double> cd;
-    if (Q == 0) {                        // nothing to expand: the weighted scales of the base columns
+    if (Q == 0) {                        // nothing to expand: the weighted scales of the base columns (and their dots with y)
         CHK(col_dots(h, 0, h->p, h->y, true));
         cd.resize((size_t)(2 * h->p));
         HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
         if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int64_t j = 0; j < h->p; ++j) cd[(size_t)j] = cd[(size_t)(2 * j + 1)];
+        std::vector<double> ab(cd);      // -> the layout of the other branch: p scales, then p scores
+        for (int64_t j = 0; j < h->p; ++j) { cd[(size_t)j] = ab[(size_t)(2 * j + 1)]; cd[(size_t)(h->p + j)] = ab[(size_t)(2 * j)]; }
     } else {
         // One launch per k_col_dots batch of expanded columns, split into that batch's row chunks: the sums then are the
         // ones cdh_col_wrms takes.  A base column whose group straddles two batches is expanded by both launches (the
@@ -1920,24 +1928,30 @@ int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, do
             const int64_t b1 = std::min<int64_t>(b0 + kColBatch, h->p);
             const int chunks = col_dots_chunks(h, b1 - b0);
             const int64_t jb0 = b0 / Q1, jb1 = (b1 + Q1 - 1) / Q1;
-            if ((size_t)(jb1 - jb0) * Q1 * chunks > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partials too small");
+            const size_t table = (size_t)(jb1 - jb0) * Q1 * chunks;      // the sums of w v^2; with a left-out row, those of w v y behind it
+            if (table * (loo ? 2 : 1) > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partials too small");
             CHK(dispatch(h, [&](auto* t) {
                 using T = std::remove_pointer_t<decltype(t)>;
                 auto go = [&](auto kernel) {
                     hipLaunchKernelGGL(kernel, dim3((unsigned)chunks, (unsigned)(jb1 - jb0)), dim3(kBlock), 0, h->stream,
-                                       (T*)h->X, h->ld, h->nvec, (const T*)h->vc_z, (const T*)h->w, (T)z0, jb0, h->d_partials);
+                                       (T*)h->X, h->ld, h->nvec, (const T*)h->vc_z, (const T*)h->w, (T)z0, jb0, h->d_partials,
+                                       (const T*)h->y, row0);
                 };
-                if (Q == 1) go(k_vc_expand<T, 1>); else if (Q == 2) go(k_vc_expand<T, 2>); else go(k_vc_expand<T, 3>);
+                if (loo) { if (Q == 1) go(k_vc_expand<T, 1, true>); else if (Q == 2) go(k_vc_expand<T, 2, true>); else go(k_vc_expand<T, 3, true>); }
+                else if (Q == 1) go(k_vc_expand<T, 1>); else if (Q == 2) go(k_vc_expand<T, 2>); else go(k_vc_expand<T, 3>);
                 return CDH_OK;
             }));
             hipLaunchKernelGGL(k_vc_reduce, dim3((unsigned)((jb1 - jb0) * Q1)), dim3(64), 0, h->stream, h->d_partials, chunks,
                                jb0 * Q1, b0, b1, h->d_colout);
+            if (loo)
+                hipLaunchKernelGGL(k_vc_reduce, dim3((unsigned)((jb1 - jb0) * Q1)), dim3(64), 0, h->stream, h->d_partials + table,
+                                   chunks, jb0 * Q1, b0, b1, h->d_colout + h->p);
             HIPCHK(h, hipGetLastError());
             launches += 1;
         }
         if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-        cd.resize((size_t)h->p);
-        HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * h->p, hipMemcpyDeviceToHost, h->stream));
+        cd.resize((size_t)(loo ? 2 * h->p : h->p));
+        HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * cd.size(), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     if (h->prof) {
@@ -1948,6 +1962,57 @@ int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, do
         h->prof_bytes += (double)h->n * (double)h->esz * ((double)h->p + 2.0);   // read p_base columns, write p_base Q, z, w
     }
     if (out_std) for (int64_t j = 0; j < h->p; ++j) out_std[j] = std::sqrt(cd[(size_t)j] / (double)h->n_total);
+    if (out_scores) for (int64_t j = 0; j < h->p; ++j) out_scores[j] = std::fabs(cd[(size_t)(h->p + j)]);
+    return CDH_OK;
+}
+
+int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double* out_std) { return guarded(h, [&]() -> int32_t {
+    return vc_point(h, kernel_kind, bandwidth, z0, -1, out_std, nullptr);
+}); }
+
+// :109-113 and the scores of _findLargestCorrelations(w, X, y, s) (utils.jl:108-124) for the point z0 = z[row0], row0 left out
+int32_t cdh_vc_set_point_loo(cdh_handle h, int32_t kernel_kind, double bandwidth, int64_t row0, double* out_std,
+                             double* out_scores) { return guarded(h, [&]() -> int32_t {
+    if (row0 < 0 || row0 >= h->n) return fail(h, CDH_BAD_ARG, "the left-out row is outside 0 .. n - 1");
+    if (!h->y_set) return fail(h, CDH_BAD_ARG, "the screening scores need y: cdh_set_y first");
+    return vc_point(h, kernel_kind, bandwidth, 0.0, row0, out_std, out_scores);
+}); }
+
+// _getSigma(w, r) (utils.jl:167-175): sum w, sum w r^2 at the current residual
+int32_t cdh_resid_wmoments(cdh_handle h, double* out_sum_w, double* out_sum_wr2) { return guarded(h, [&]() -> int32_t {
+    if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "weighted moments need the CDH_WLS loss with its weights set");
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(resid_moments_dev(h, nullptr, 0.0, true));
+    HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (out_sum_w) *out_sum_w = h->h_red[0];
+    if (out_sum_wr2) *out_sum_wr2 = h->h_red[2];
+    return CDH_OK;
+}); }
+
+// wX[i, S] (:132): out_m[k] = X[row0, idx1[k]] of the resident design, as doubles
+int32_t cdh_get_X_row(cdh_handle h, int64_t row0, int64_t m, const int64_t* idx1, double* out_m) { return guarded(h, [&]() -> int32_t {
+    if (m < 1 || m > kGramMaxCols) return fail(h, CDH_BAD_ARG, "need 1 <= m <= 4096 columns");
+    NEED_P(h, idx1);
+    NEED_P(h, out_m);
+    if (row0 < 0 || row0 >= h->n) return fail(h, CDH_BAD_ARG, "row outside 0 .. n_local - 1");
+    for (int64_t i = 0; i < m; ++i)
+        if (idx1[i] < 1 || idx1[i] > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
+    HIPCHK(h, hipSetDevice(h->device));
+    for (int64_t o = 0; o < m; o += 2 * h->p) {          // d_colout holds 2p values
+        const int64_t mm = std::min<int64_t>(2 * h->p, m - o);
+        for (int64_t i = 0; i < mm; ++i) h->h_idx[i] = idx1[o + i] - 1;
+        HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)mm, hipMemcpyHostToDevice, h->stream));
+        CHK(dispatch(h, [&](auto* t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            hipLaunchKernelGGL(k_gather_row<T>, dim3((unsigned)((mm + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
+                               (const T*)h->X, h->ld, row0, h->d_idx, (int)mm, h->d_colout);
+            return CDH_OK;
+        }));
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(out_m + o, h->d_colout, sizeof(double) * (size_t)mm, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
     return CDH_OK;
 }); }
 

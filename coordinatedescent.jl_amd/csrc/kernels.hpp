@@ -725,8 +725,9 @@ __global__ __launch_bounds__(64) void k_col_dots_reduce(const double* __restrict
 }
 
 // sum (r - shift), sum (r - shift)^2 (+ sum w (r - shift)^2 when w) -> partials[(block, 4)]; rows beyond n (the zero pad of
-// the last vectors) are left out when a shift is given (shift == 0: they contribute nothing anyway)
-template <typename T>
+// the last vectors) are left out when a shift is given (shift == 0: they contribute nothing anyway).  SUMW: the first sum is
+// sum w instead -- with the third, the two sums of _getSigma(w, r) (utils.jl:167-175); w must be given.
+template <typename T, bool SUMW = false>
 __global__ __launch_bounds__(kBlock) void k_resid_moments(int64_t nvec, const T* __restrict__ r,
                                                           const T* __restrict__ w,
                                                           double* __restrict__ partials, double shift = 0.0, int64_t n = 0) {
@@ -747,7 +748,7 @@ __global__ __launch_bounds__(kBlock) void k_resid_moments(int64_t nvec, const T*
         for (int e = 0; e < NV; ++e) {
             double re = (double)rp[e] - shift;
             if (shift != 0.0 && j * NV + e >= n) re = 0.0;
-            acc[0] += re;
+            if constexpr (SUMW) acc[0] += (double)wp[e]; else acc[0] += re;
             acc[1] = fma(re, re, acc[1]);
             acc[2] = fma(w ? (double)wp[e] * re : re, re, acc[2]);
         }

@@ -112,6 +112,10 @@ int32_t cdh_synchronize(cdh_handle h);
  * coordinate) of the local row shard from a host column-major block. */
 int32_t cdh_set_X_cols(cdh_handle h, int64_t j0, int64_t ncols, const void *host, int64_t ld);
 int32_t cdh_get_X_cols(cdh_handle h, int64_t j0, int64_t ncols, void *host, int64_t ld);
+/* out_m[k] = X[row0, idx1[k]] of the resident design as doubles, 1 <= m <= 4096 (row0 0-based and local, idx1 1-based as
+ * coordinates are): the row wX[i, S] that the prediction of lvocv_locpolyl1 dots with the refit
+ * (varying_coefficient_lasso.jl:132).  A row or a coordinate out of range: CDH_BAD_ARG. */
+int32_t cdh_get_X_row(cdh_handle h, int64_t row0, int64_t m, const int64_t *idx1, double *out_m);
 /* y (and r = copy(y), as the loss constructors do). */
 int32_t cdh_set_y(cdh_handle h, const void *host_y);
 int32_t cdh_get_y(cdh_handle h, void *host_y);
@@ -142,6 +146,16 @@ int32_t cdh_get_obs_weights(cdh_handle h, void *host_w);
 int32_t cdh_vc_set_data(cdh_handle h, int64_t p_base, int32_t degree, const void *host_X, int64_t ld,
                         const void *host_z);
 int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double *out_std);
+/* The leave-one-out point of lvocv_locpolyl1 (varying_coefficient_lasso.jl:82-137), replacing :109-113 and the scores of
+ * _findLargestCorrelations(w, X, y, s) (utils.jl:108-124) for observation row0 (0-based: a bulk helper, like j0 above): z0 is
+ * the stored z[row0], read on the device; weights, expansion and out_std exactly as cdh_vc_set_point(z0 = z[row0]) gives them,
+ * except that w[row0] = 0 (:111) -- so out_std is _stdX! with the left-out weight already zero (:113) -- and
+ * out_scores[j] = |sum_i X_ij w_i y_i| for the p expanded columns, accumulated in double in the pass that writes the
+ * expansion (degree 0: in the pass that takes the scales).  Either output may be NULL.  Invalidates what cdh_vc_set_point
+ * invalidates, keeps the iterate, and refuses the same things with CDH_BAD_ARG; so is row0 outside 0 .. n - 1, and a call
+ * before cdh_set_y. */
+int32_t cdh_vc_set_point_loo(cdh_handle h, int32_t kernel_kind, double bandwidth, int64_t row0, double *out_std,
+                             double *out_scores);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects
@@ -225,6 +239,9 @@ int32_t cdh_xt_r_cols(cdh_handle h, int64_t m, const int64_t *idx1, double *out_
 int32_t cdh_resid_std(cdh_handle h, double *out_std, double *out_mean);
 /* sum r, sum r^2 over all shards (sigma of scaledLasso!, lasso.jl:134; std(f.r)). */
 int32_t cdh_resid_moments(cdh_handle h, double *out_sum, double *out_sumsq);
+/* The two sums of _getSigma(w, r) (utils.jl:167-175: sigma = sqrt(sum_i w_i r_i^2 / sum_i w_i)) at the current residual, in
+ * double and in a fixed order; either out pointer may be NULL.  CDH_WLS with weights set, else CDH_BAD_ARG. */
+int32_t cdh_resid_wmoments(cdh_handle h, double *out_sum_w, double *out_sum_wr2);
 /* f(beta) + lambda0 sum omega|beta| at the current state (coordinate_descent.jl:1-3). */
 int32_t cdh_objective(cdh_handle h, double *out);
 

@@ -26,7 +26,7 @@
 module CoordinateDescentHIP
 
 using CoordinateDescent, ProximalBase
-using LinearAlgebra: Symmetric, eigen
+using LinearAlgebra: Symmetric, eigen, dot
 using SparseArrays: nnz
 using DataStructures: nlargest
 import CoordinateDescent: coordinateDescent!, initialize!, gradient, descendCoordinate!,
@@ -508,6 +508,118 @@ function CoordinateDescent.locpolyl1(D::HipVaryingDesign{T}, y::Vector{T}, zgrid
     outR[S, ind] .= T.(beta[S] .+ ((G ./ (d * d')) \ (c ./ d)) ./ d)
   end
   out, outR
+end
+
+# ---- lvocv_locpolyl1 on the same resident design (src/varying_coefficient_lasso.jl:82-137) --------------------------
+# Per bandwidth and observation i the reference rebuilds w (with w[i] = 0), wX and stdX around z0 = z[i] on the host
+# (:109-113).  cdh_vc_set_point_loo regenerates them on the device and returns the screening scores of
+# _findLargestCorrelations(w, X, y, s) (utils.jl:108-124) from the same pass; the weighted OLS of _findInitResiduals!
+# (utils.jl:79-92), _getSigma (utils.jl:167-175), the refit and the prediction read s x s blocks, two sums and one row.
+"w (w[row] = 0), wX, stdX of the point z0 = z[row] (:109-113) and the scores |X_j'Wy|; `row` is 1-based; returns (stdX, scores)"
+function set_point_leave_out!(D::HipVaryingDesign{T}, kernel::CoordinateDescent.SmoothingKernel{T}, row::Int) where {T}
+  ep = D.p * (D.degree + 1)
+  stdX = Vector{Float64}(undef, ep); scores = Vector{Float64}(undef, ep)
+  check(D.handle, ccall((:cdh_vc_set_point_loo, libcdhip), Int32,
+                        (Ptr{Cvoid}, Int32, Float64, Int64, Ptr{Float64}, Ptr{Float64}),
+                        D.handle, kernel_code(kernel), Float64(kernel.h), row - 1, stdX, scores))
+  stdX, scores
+end
+
+"_getSigma(w, f.r) (utils.jl:167-175) at the device-side residual"
+function getSigma(D::HipVaryingDesign)
+  sw = Ref{Float64}(0); swr2 = Ref{Float64}(0)
+  check(D.handle, ccall((:cdh_resid_wmoments, libcdhip), Int32, (Ptr{Cvoid}, Ref{Float64}, Ref{Float64}), D.handle, sw, swr2))
+  sqrt(swr2[] / sw[])
+end
+
+"_findInitResiduals!(w, wX, y, s, f.r) (utils.jl:79-92) from the scores: leaves r = y - X_S (X_S'WX_S) \\ (X_S'Wy) on the device"
+function weighted_screening_init!(D::HipVaryingDesign, scores::Vector{Float64}, s::Int)
+  h, ep = D.handle, D.p * (D.degree + 1)
+  idx = Int64.(findall(scores .>= nlargest(s, scores)[end]))
+  m = length(idx)
+  m <= 4096 || throw(ArgumentError("screening set larger than 4096 columns"))
+  check(h, ccall((:cdh_initialize, libcdhip), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                 h, ep, 0, C_NULL, C_NULL))                       # r = y: X_S'Wr == X_S'Wy
+  G = Matrix{Float64}(undef, m, m); c = Vector{Float64}(undef, m)
+  check(h, ccall((:cdh_gram_weighted, libcdhip), Int32,
+                 (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, m, idx, G, c, C_NULL))
+  E = eigen(Symmetric(G))
+  keep = E.values .> 1e-13 * max(E.values[end], 0.0)
+  V = E.vectors[:, keep]
+  pinvG = (V ./ E.values[keep]') * V'
+  coef = pinvG * c
+  res = Vector{Float64}(undef, m)
+  for _ in 1:2                                                    # refined against X_S'W(y - X_S b), as screening_ols! refines
+    check(h, ccall((:cdh_initialize, libcdhip), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                   h, ep, m, idx, coef))
+    check(h, ccall((:cdh_xt_r_cols, libcdhip), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}), h, m, idx, res))
+    coef .+= pinvG * res
+  end
+  check(h, ccall((:cdh_initialize, libcdhip), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                 h, ep, m, idx, coef))
+  idx
+end
+
+"lvocv_locpolyl1 (:82-137) for a design in HBM; an empty support, which the reference never handles, predicts Yh = 0"
+function CoordinateDescent.lvocv_locpolyl1(D::HipVaryingDesign{T}, y::Vector{T}, hArr::Vector{T},
+                                           kernelType::Type{<:CoordinateDescent.SmoothingKernel}, λ0::T,
+                                           options::CDOptions=CDOptions()) where {T}
+  length(y) == D.n || throw(DimensionMismatch())
+  opt = CDOptions(options.maxIter, options.optTol, options.randomize, true, options.numSteps)   # :94
+  h, ep, Q1 = D.handle, D.p * (D.degree + 1), D.degree + 1
+  MSE = zeros(length(hArr))
+  GC.@preserve y check(h, ccall((:cdh_set_y, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), h, y))
+  nsup = 0; sup = Vector{Int64}(undef, ep); val = Vector{Float64}(undef, ep)   # β = SparseIterate(ep), carried over all points
+  beta = Vector{Float64}(undef, ep)
+  for (indH, bw) in enumerate(hArr)
+    kernel = CoordinateDescent.createKernel(kernelType, bw)                   # :106
+    for i in 1:D.n
+      stdX, scores = set_point_leave_out!(D, kernel, i)                       # :109-113
+      weighted_screening_init!(D, scores, min(10, ep))                        # :114
+      σ = getSigma(D)                                                         # :117
+      # the screening fit is the handle's iterate now: put β back (the warm start below rebuilds r = y - Xβ from it)
+      check(h, ccall((:cdh_set_iterate, libcdhip), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                     h, ep, nsup, sup, val))
+      for iter = 1:10                                                         # :119-127
+        check(h, ccall((:cdh_set_penalty, libcdhip), Int32, (Ptr{Cvoid}, Float64, Ptr{Float64}, Int64),
+                       h, Float64(λ0) * σ, stdX, ep))
+        o = Ref(CdhOptions(opt)); st = CdhStats()
+        check(h, ccall((:cdh_coordinate_descent, libcdhip), Int32, (Ptr{Cvoid}, Ref{CdhOptions}, Ref{CdhStats}), h, o, st))
+        σnew = getSigma(D)
+        abs(σnew - σ) / σ < 1e-2 && break
+        σ = σnew
+      end
+      n_ref = Ref{Int64}(0)
+      check(h, ccall((:cdh_get_support, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ref{Int64}), h, sup, n_ref))
+      check(h, ccall((:cdh_get_beta, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Float64}), h, beta))
+      nsup = n_ref[]
+      for s in 1:nsup
+        val[s] = beta[sup[s]]
+      end
+      S = Int64[]                                                             # get_nonzero_coordinates!(S, β, p, degree, true), :130
+      for j in 1:D.p
+        ks = ((j - 1) * Q1 + 1):(j * Q1)
+        any(!iszero, view(beta, ks)) && append!(S, ks)
+      end
+      Yh = 0.0
+      if !isempty(S)                                                          # :131-132
+        m = length(S)
+        m <= 4096 || throw(ArgumentError("refit support larger than 4096 columns"))
+        G = Matrix{Float64}(undef, m, m); c = Vector{Float64}(undef, m)
+        check(h, ccall((:cdh_gram_weighted, libcdhip), Int32,
+                       (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, m, S, G, c, C_NULL))
+        d = sqrt.([G[k, k] for k in 1:m])
+        coef = beta[S] .+ ((G ./ (d * d')) \ (c ./ d)) ./ d
+        base = S[1:Q1:end]                 # at z0 = z[i] row i of wX is X[i, j] at power 0 and exactly 0 above it
+        row = Vector{Float64}(undef, length(base))
+        check(h, ccall((:cdh_get_X_row, libcdhip), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                       h, i - 1, length(base), base, row))
+        Yh = dot(row, coef[1:Q1:end])
+      end
+      MSE[indH] += (Yh - y[i])^2                                              # :133
+    end
+  end
+  MSE
 end
 
 # Optional knobs (no reference counterpart): blocked sweep width, screened full passes, the gradient
