@@ -21,6 +21,7 @@
 #include "p2p_exchange.hpp"
 #include "sparse_iterate.hpp"
 #include "resid_state.hpp"
+#include "exchange_state.hpp"
 
 using namespace cdk;
 
@@ -103,6 +104,32 @@ class HipBuf {
 };
 template <class T> using DevBuf = HipBuf<T, false>;
 template <class T> using PinBuf = HipBuf<T, true>;
+
+// The captured launch sequences of the chunks (run_chunk), by key: owns their executables.  At most 32: an insert into
+// a full cache destroys the oldest.  Entries are found again by key, never kept by pointer across an insert.
+struct GraphEntry { uint64_t key; hipGraphExec_t exec; cdh::Captured holds; };
+class GraphCache {
+  public:
+    GraphCache() = default;
+    GraphCache(const GraphCache&) = delete;
+    GraphCache& operator=(const GraphCache&) = delete;
+    ~GraphCache() { clear(); }
+    const GraphEntry* find(uint64_t key) const {
+        for (const GraphEntry& e : v_) if (e.key == key) return &e;
+        return nullptr;
+    }
+    const GraphEntry* insert(const GraphEntry& e) {
+        if (v_.size() >= 32) { (void)hipGraphExecDestroy(v_.front().exec); v_.erase(v_.begin()); }
+        v_.push_back(e);
+        return &v_.back();
+    }
+    void clear() {
+        for (const GraphEntry& e : v_) (void)hipGraphExecDestroy(e.exec);
+        v_.clear();
+    }
+  private:
+    std::vector<GraphEntry> v_;
+};
 
 }  // namespace
 
@@ -327,34 +354,23 @@ struct cdh_handle_s {
     cdh::ResidState rs;           // what r holds and stands for, the moves it owes, the stashed dots (resid_state.hpp)
     bool chunk_dup = false;       // the current chunk's visit list repeats a coordinate
     std::vector<int32_t> stamp;   // duplicate detection scratch, size p
-    struct GraphEntry { uint64_t key; hipGraphExec_t exec; unsigned exchanges; unsigned rccl; };
-    std::vector<GraphEntry> graphs;  // captured chunk launch sequences
+    GraphCache graphs;               // captured chunk launch sequences
     bool graph_broken = false;       // a capture failed on this handle: launch node by node from now on
     bool domain_error = false;
     int step_grid = 1, block_grid = 1, cus = 1;
     int64_t gram_units = 1;
     Knobs knobs;     // the environment as cdh_create found it
-    // comm
-    void* comm = nullptr;
-    int rank = 0, nranks = 1;
-    // optional direct exchange of the short records (p2p_exchange.hpp); off unless connected and enabled
+    // the row-shard exchange: who serves it, where an all-reduce goes, epochs, capture bookkeeping (exchange_state.hpp) ...
+    cdh::ExchangeState xs;
+    // ... and the HIP resources behind it.  The optional direct exchange of the short records (p2p_exchange.hpp):
     DevBuf<unsigned long long> p2p_inbox;
     cdk::P2PPeers p2p_peers{};
     std::vector<void*> p2p_mapped;
     PinBuf<int> p2p_timeout;     // pinned host flag written by a kernel whose bounded spin ran out
-    unsigned p2p_epoch = 0;
-    int p2p_ranks = 0;
-    bool p2p_on = false, p2p_dead = false;
-    bool lost_exchange = false;       // a multi-rank shard whose host transport was taken away: allreduce() refuses
     DevBuf<unsigned> d_p2p_base;      // epoch base of a replayed graph's exchanges (device memory)
-    bool capturing = false;           // run_chunk is recording a graph: exchanges take base + offset epochs
-    unsigned cap_exchanges = 0, cap_rccl = 0;   // exchanges recorded in the graph being captured
     // bring-your-own transport (cdh_set_host_exchange): staged through pinned host memory
-    cdh_host_allreduce_fn host_fn = nullptr;
-    void* host_user = nullptr;
     PinBuf<double> h_xchg;
     size_t h_xchg_doubles = 0;
-    int64_t n_rccl_calls = 0, n_p2p_calls = 0, n_host_calls = 0;
     // profile
     GradCache gc;
     SmallPath small;
@@ -416,90 +432,65 @@ int32_t upload_ctrl(cdh_handle h) {
     return CDH_OK;
 }
 
-// p2p_dead counts: a shard that lost its exchange must never fall into the single-process (fused)
-// finalize kernels on its local rows -- every path then reaches allreduce(), which refuses
-inline bool sharded(const cdh_handle_s* h) {
-    return h->comm != nullptr || h->p2p_on || h->p2p_dead || h->lost_exchange || h->host_fn != nullptr;
-}
-
-// A shard that has lost its exchange refuses to sweep at all -- also where a pass could be served from sums exchanged
-// earlier (the gradient cache): the ranks of one problem must fail together, not one by one as they come to need an exchange.
-int32_t exchange_alive(cdh_handle h) {
-    if (h->p2p_dead) return fail(h, CDH_RCCL_ERROR, "the shard lost its exchange (p2p timed out earlier); rebuild the handle");
-    if (h->lost_exchange) return fail(h, CDH_RCCL_ERROR, "the shard's host exchange was removed and nothing replaced it: its sums would cover local rows only");
-    return CDH_OK;
-}
-
+// what the exchange's state refuses is the export's error (exchange_state.hpp)
+inline int32_t refused(cdh_handle h, const cdh::Refusal& r) { return r.status == CDH_OK ? (int32_t)CDH_OK : fail(h, r.status, r.msg); }
+int32_t exchange_alive(cdh_handle h) { return refused(h, h->xs.alive()); }
+// has a kernel of the direct exchange run out of its bounded spin?
 int32_t p2p_check(cdh_handle h) {
-    // after a timeout the ranks no longer agree on what has been exchanged: the handle refuses every
-    // later exchange (falling back to RCCL here could pair mismatched all-reduces and hang)
-    if (h->p2p_on && *(volatile int*)h->p2p_timeout) {
-        h->p2p_on = false;
-        h->p2p_dead = true;
-        h->err = "p2p exchange timed out waiting for a peer (rank died, or ranks ran different sweeps)";
-        return CDH_RCCL_ERROR;
-    }
+    if (h->xs.direct_on() && *(volatile int*)h->p2p_timeout) return refused(h, h->xs.p2p_timed_out());
     return CDH_OK;
 }
 
 static_assert(GramRec<4>::N <= cdk::kP2PMaxCount, "the widest block record must fit one inbox slot");
-// Epochs count direct exchanges; 0 means "never written".  Consecutive epochs must alternate the
-// inbox slot (parity), also across the 32-bit wrap.
-constexpr unsigned kEpochWrap = 0xfffffff0u;
-// Chunks start below this: every rank passes a chunk boundary with the same epoch count whether it replays a
-// graph or launches node by node, so wrapping THERE keeps ranks on different paths in step (a chunk issues far
-// fewer than 2^28 exchanges, so the hard wrap above is never reached inside one)
-constexpr unsigned kEpochSoftWrap = 0xf0000000u;
-inline unsigned epoch_after(unsigned e) { return e >= kEpochWrap ? ((e & 1u) ? 2u : 3u) : e + 1u; }
 // the arguments of the next direct exchange.  While a graph is being recorded the epoch is
 // (device-resident base) + (position of the exchange in the graph), so one graph serves every replay.
 cdk::P2PCall next_p2p_call(cdh_handle h) {
-    if (h->capturing) {
-        h->cap_exchanges += 1;
-        return cdk::P2PCall{h->p2p_peers, h->rank, h->p2p_ranks, h->cap_exchanges, h->knobs.p2p_spin_limit, h->p2p_timeout, h->d_p2p_base};
-    }
-    h->p2p_epoch = epoch_after(h->p2p_epoch);
-    return cdk::P2PCall{h->p2p_peers, h->rank, h->p2p_ranks, h->p2p_epoch, h->knobs.p2p_spin_limit, h->p2p_timeout, nullptr};
+    cdh::ExchangeState& xs = h->xs;
+    return cdk::P2PCall{h->p2p_peers, xs.rank(), xs.direct_ranks(), xs.next_epoch(), h->knobs.p2p_spin_limit, h->p2p_timeout,
+                        xs.in_capture() ? (const unsigned*)h->d_p2p_base : nullptr};
 }
 
 // The one exchange seam of the row-sharded path: sum `count` doubles at dbuf (device) over all ranks,
 // in stream order.  Behind it: the direct exchange (short records), RCCL, or a caller-supplied host
 // transport.  Not sharded: nothing to do.
 int32_t allreduce(cdh_handle h, double* dbuf, size_t count) {
-    if (h->host_fn) {
-        if (h->capturing) return fail(h, CDH_BAD_ARG, "the host-staged exchange cannot be recorded in a graph");
+    cdh::ExchangeState& xs = h->xs;
+    const cdh::Routing to = xs.route(count);
+    switch (to.route) {
+    case cdh::Route::Refuse: return refused(h, to.why);
+    case cdh::Route::Nothing: return CDH_OK;
+    case cdh::Route::Host:
         for (size_t o = 0; o < count; o += h->h_xchg_doubles) {   // long records go through the staging buffer in pieces
             const size_t cnt = std::min(h->h_xchg_doubles, count - o);
             HIPCHK(h, hipMemcpyAsync(h->h_xchg, dbuf + o, sizeof(double) * cnt, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
-            const int32_t rc = h->host_fn(h->host_user, h->h_xchg, (int64_t)cnt);
+            const int32_t rc = xs.host_callback()(xs.host_context(), h->h_xchg, (int64_t)cnt);
             if (rc != 0) return fail(h, CDH_RCCL_ERROR, "the host exchange callback reported a failure");
             HIPCHK(h, hipMemcpyAsync(dbuf + o, h->h_xchg, sizeof(double) * cnt, hipMemcpyHostToDevice, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));   // the staging buffer is reused by the next exchange
         }
-        h->n_host_calls += 1;
-        return CDH_OK;
-    }
-    if (h->p2p_on && (count <= (size_t)cdk::kP2PMaxCount || !h->comm)) {
+        break;
+    case cdh::Route::Direct:
         CHK(p2p_check(h));
         for (size_t o = 0; o < count; o += cdk::kP2PMaxCount) {
             const int c = (int)std::min<size_t>(cdk::kP2PMaxCount, count - o);
             hipLaunchKernelGGL(cdk::k_p2p_allreduce, dim3((c + 255) / 256), dim3(256), 0, h->stream, dbuf + o, c,
                                next_p2p_call(h));
-            if (!h->capturing) h->n_p2p_calls += 1;
+            xs.issued(to.route);
         }
         HIPCHK(h, hipGetLastError());
         return CDH_OK;
+    case cdh::Route::Rccl: {
+        const int rc = g_rccl.AllReduce(dbuf, dbuf, count, kNcclDouble, kNcclSum, xs.communicator(), h->stream);
+        if (rc != 0) {
+            h->err = std::string("ncclAllReduce failed: ") +
+                     (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "?");
+            return CDH_RCCL_ERROR;
+        }
+        break;
     }
-    CHK(exchange_alive(h));
-    if (!h->comm) return CDH_OK;
-    int rc = g_rccl.AllReduce(dbuf, dbuf, count, kNcclDouble, kNcclSum, h->comm, h->stream);
-    if (rc != 0) {
-        h->err = std::string("ncclAllReduce failed: ") +
-                 (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "?");
-        return CDH_RCCL_ERROR;
     }
-    if (h->capturing) h->cap_rccl += 1; else h->n_rccl_calls += 1;
+    xs.issued(to.route);   // host, RCCL: once per all-reduce that went through
     return CDH_OK;
 }
 
@@ -765,7 +756,7 @@ template <typename T, int B> int32_t launch_block_chunk(cdh_handle h, int m) {
         const int nb = std::min(B, m - pos0);
         hipLaunchKernelGGL((k_blockstep<T, B>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
                            h->ld, h->nvec, (T*)h->r, h->d_idx, h->d_hs, pos0, nb, nprev, h->d_partials);
-        if (!sharded(h)) {
+        if (!h->xs.sharded()) {
             hipLaunchKernelGGL((k_block_finalize<B, true>), dim3(1), dim3(1024), 0, h->stream,
                                h->d_partials, G, nb, h->d_ctrl, h->beta, h->omega, h->d_idx, h->d_hs,
                                h->d_newval, h->d_touched, pos0, h->d_red);
@@ -866,7 +857,7 @@ template <typename T> int32_t launch_coord_chunk(cdh_handle h, int m) {
         else
             hipLaunchKernelGGL((k_step<T, false>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
                                h->ld, h->nvec, (const T*)nullptr, (T*)h->r, h->d_idx, h->d_hs, pos, h->d_partials);
-        if (!sharded(h)) {
+        if (!h->xs.sharded()) {
             hipLaunchKernelGGL(k_finalize<true>, dim3(1), dim3(kBlock), 0, h->stream, h->d_partials, G,
                                h->d_ctrl, h->beta, h->omega, h->d_idx, h->d_hs, h->d_newval, h->d_touched,
                                pos, h->d_red);
@@ -886,7 +877,7 @@ template <typename T> int32_t launch_coord_chunk(cdh_handle h, int m) {
 
 int32_t all_ranks_agree(cdh_handle h, bool mine, bool* all);   // grad_cache.hpp
 int32_t agree_default_width(cdh_handle h) {
-    if (h->width_agreed || !h->width_default || !sharded(h) || h->nranks <= 1) return CDH_OK;
+    if (h->width_agreed || !h->width_default || !h->xs.sharded() || h->xs.nranks() <= 1) return CDH_OK;
     bool all64 = false;
     CHK(all_ranks_agree(h, h->blockB == 64, &all64));
     if (!all64) h->blockB = 32;      // some shard is on the long side of the cut: every rank takes the long-column width
@@ -898,7 +889,7 @@ int32_t run_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH) {
     CHK(agree_default_width(h));
     CHK(sync_r(h));   // the streaming kernels read and write r
     h->rs.stream_begins();
-    if (h->p2p_epoch >= kEpochSoftWrap) h->p2p_epoch = (h->p2p_epoch & 1u) ? 1u : 2u;   // slot parity keeps alternating
+    h->xs.chunk_begins();
     std::memcpy(h->h_idx, idx0, sizeof(int64_t) * (size_t)m);
     note_duplicates(h, idx0, m);
     HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, h->stream));
@@ -928,43 +919,31 @@ int32_t run_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH) {
     // be recorded.  A failed capture switches the handle back to node-by-node launches for good.
     bool launched = false;
     // (a graph of one or two launches saves nothing and costs a capture: short chunks go node by node)
-    if (h->use_graph && !h->graph_broken && !h->host_fn && !h->p2p_dead && m >= (blocked ? 2 * h->blockB : 8)) {
-        const uint64_t key = ((uint64_t)m << 20) | ((uint64_t)(blocked ? h->blockB : 0) << 8) |
-                             (h->comm ? 32u : 0u) | (h->p2p_on ? 16u : 0u) |
+    if (h->use_graph && !h->graph_broken && h->xs.may_capture() && m >= (blocked ? 2 * h->blockB : 8)) {
+        const uint64_t key = ((uint64_t)m << 20) | ((uint64_t)(blocked ? h->blockB : 0) << 8) | h->xs.graph_key_bits() |
                              (h->chunk_dup ? 4u : 0u) | (h->has_w ? 2u : 0u);
-        cdh_handle_s::GraphEntry* entry = nullptr;
-        for (auto& e : h->graphs) if (e.key == key) entry = &e;
+        const GraphEntry* entry = h->graphs.find(key);
         if (!entry) {
             hipGraph_t graph = nullptr;
             hipGraphExec_t exec = nullptr;
-            h->capturing = true; h->cap_exchanges = 0; h->cap_rccl = 0;
+            h->xs.capture_begins();
             hipError_t e0 = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
             const int32_t erc = e0 == hipSuccess ? enqueue() : (int32_t)CDH_HIP_ERROR;
             hipError_t e1 = e0 == hipSuccess ? hipStreamEndCapture(h->stream, &graph) : e0;
-            h->capturing = false;
+            const cdh::Captured holds = h->xs.capture_ends();
             if (erc == CDH_OK && e1 == hipSuccess && graph) e1 = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
             if (graph) (void)hipGraphDestroy(graph);
             if (erc != CDH_OK || e1 != hipSuccess || !exec) {
                 (void)hipGetLastError();
                 h->graph_broken = true;
             } else {
-                if (h->graphs.size() >= 32) {  // bounded cache: drop the oldest
-                    (void)hipGraphExecDestroy(h->graphs.front().exec);
-                    h->graphs.erase(h->graphs.begin());
-                }
-                h->graphs.push_back({key, exec, h->cap_exchanges, h->cap_rccl});
-                entry = &h->graphs.back();
+                entry = h->graphs.insert({key, exec, holds});
             }
         }
         if (entry) {
-            if (entry->exchanges) {
-                // epochs base+1 .. base+exchanges; across the 32-bit wrap the slot parity keeps alternating
-                if ((uint64_t)h->p2p_epoch + entry->exchanges >= (uint64_t)kEpochWrap) h->p2p_epoch = (h->p2p_epoch & 1u) ? 1u : 2u;
-                hipLaunchKernelGGL(cdk::k_set_u32, dim3(1), dim3(1), 0, h->stream, h->d_p2p_base, h->p2p_epoch);
-                h->p2p_epoch += entry->exchanges;
-                h->n_p2p_calls += entry->exchanges;
-            }
-            h->n_rccl_calls += entry->rccl;
+            if (entry->holds.exchanges)   // they run under the epochs base + 1 .. base + exchanges
+                hipLaunchKernelGGL(cdk::k_set_u32, dim3(1), dim3(1), 0, h->stream, h->d_p2p_base, h->xs.reserve_epochs(entry->holds.exchanges));
+            h->xs.replay_counted(entry->holds);
             HIPCHK(h, hipGraphLaunch(entry->exec, h->stream));
             launched = true;
         }
@@ -1149,12 +1128,11 @@ int32_t lambda_max(cdh_handle h, double* out, std::vector<double>* dots = nullpt
 void free_all(cdh_handle h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
+    if (h->xs.communicator() && g_rccl.CommDestroy) g_rccl.CommDestroy(h->xs.communicator());
     for (void* m : h->p2p_mapped) (void)hipIpcCloseMemHandle(m);
-    for (auto& e : h->graphs) (void)hipGraphExecDestroy(e.exec);
     const hipEvent_t ev[] = {h->ev0, h->ev1};
     const hipStream_t stream = h->stream;
-    delete h;   // the owners free the device and pinned memory, before the stream goes
+    delete h;   // the owners free the device and pinned memory and the captured graphs, before the stream goes
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
 }
@@ -1854,7 +1832,7 @@ int32_t cdh_col_wrms(cdh_handle h, double* out_p) { return guarded(h, [&]() -> i
 
 // ---- varying-coefficient mode (varying_coefficient_lasso.jl:30-79) -------------------------------------------------
 static int32_t vc_refuse_shards(cdh_handle h) {
-    if (h->n != h->n_total || sharded(h))
+    if (h->n != h->n_total || h->xs.sharded())
         return fail(h, CDH_BAD_ARG, "varying-coefficient mode does not run on row-sharded handles");
     return CDH_OK;
 }
@@ -2192,34 +2170,32 @@ int32_t cdh_comm_unique_id(void* out_128_bytes) { return guarded([&]() -> int32_
 
 int32_t cdh_comm_init(cdh_handle h, const void* id_128_bytes, int32_t rank, int32_t nranks) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, id_128_bytes);
-    if (h->host_fn) return fail(h, CDH_BAD_ARG, "the handle already exchanges through a host transport");
-    if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, CDH_BAD_ARG, "bad rank / nranks");
+    CHK(refused(h, h->xs.comm_refused(rank, nranks)));
     // a 1-rank communicator is only built when asked for (exercises the RCCL path on one GPU)
-    if (nranks == 1 && !h->knobs.force_rccl) { h->rank = 0; h->nranks = 1; return CDH_OK; }
+    if (nranks == 1 && !h->knobs.force_rccl) { h->xs.comm_not_needed(); return CDH_OK; }
     std::string err;
     if (!load_rccl(err)) { h->err = err; return CDH_RCCL_ERROR; }
     HIPCHK(h, hipSetDevice(h->device));
     UniqueId id;
     std::memcpy(&id, id_128_bytes, sizeof id);
-    int rc = ((comm_init_rank_fn)g_rccl.CommInitRank)(&h->comm, nranks, id, rank);
+    void* comm = nullptr;
+    int rc = ((comm_init_rank_fn)g_rccl.CommInitRank)(&comm, nranks, id, rank);
     if (rc != 0) {
         h->err = std::string("ncclCommInitRank failed: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "?");
         return CDH_RCCL_ERROR;
     }
-    h->rank = rank; h->nranks = nranks;
-    h->lost_exchange = false;          // an exchange is installed again (after a drop: cdh_comm_drop)
+    h->xs.comm_installed(comm, rank, nranks);   // an exchange is installed (again, after a cdh_comm_drop)
     return CDH_OK;
 }); }
 
 int32_t cdh_comm_drop(cdh_handle h) { return guarded(h, [&]() -> int32_t {
-    if (!h->comm) return CDH_OK;
+    void* comm = h->xs.communicator();
+    if (!comm) return CDH_OK;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (auto& e : h->graphs) (void)hipGraphExecDestroy(e.exec);   // captured passes hold the communicator's all-reduces
-    h->graphs.clear();
-    if (g_rccl.CommAbort) g_rccl.CommAbort(h->comm); else if (g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
-    h->comm = nullptr;
-    if (h->nranks > 1 && !h->p2p_on && !h->host_fn) h->lost_exchange = true;
+    h->graphs.clear();   // captured passes hold the communicator's all-reduces
+    if (g_rccl.CommAbort) g_rccl.CommAbort(comm); else if (g_rccl.CommDestroy) g_rccl.CommDestroy(comm);
+    h->xs.comm_dropped();
     return CDH_OK;
 }); }
 
@@ -2249,13 +2225,7 @@ int32_t cdh_p2p_local_handle(cdh_handle h, void* out_64_bytes) { return guarded(
 
 int32_t cdh_p2p_connect(cdh_handle h, const void* handles_64_bytes_each, int32_t rank, int32_t nranks) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, handles_64_bytes_each);
-    if (h->host_fn) return fail(h, CDH_BAD_ARG, "the handle already exchanges through a host transport");
-    if (nranks < 1 || nranks > kP2PMaxRanks || rank < 0 || rank >= nranks)
-        return fail(h, CDH_BAD_ARG, "p2p exchange: bad rank / nranks (at most 8 ranks)");
-    if (!h->p2p_inbox) return fail(h, CDH_BAD_ARG, "cdh_p2p_local_handle must be called first");
-    if (h->comm && (rank != h->rank || nranks != h->nranks))
-        return fail(h, CDH_BAD_ARG, "p2p exchange: rank / nranks differ from the RCCL communicator's");
-    if (h->p2p_ranks) return fail(h, CDH_BAD_ARG, "p2p exchange is already connected");
+    CHK(refused(h, h->xs.p2p_connect_refused(rank, nranks, h->p2p_inbox != nullptr)));
     HIPCHK(h, hipSetDevice(h->device));
     for (int q = 0; q < nranks; ++q) {
         if (q == rank) { h->p2p_peers.inbox[q] = h->p2p_inbox; continue; }
@@ -2266,54 +2236,38 @@ int32_t cdh_p2p_connect(cdh_handle h, const void* handles_64_bytes_each, int32_t
         h->p2p_mapped.push_back(mapped);
         h->p2p_peers.inbox[q] = (unsigned long long*)mapped;
     }
-    h->rank = rank; h->nranks = nranks; h->p2p_ranks = nranks;
+    h->xs.p2p_connected(rank, nranks);
     return CDH_OK;
 }); }
 
 int32_t cdh_p2p_enable(cdh_handle h, int32_t on) { return guarded(h, [&]() -> int32_t {
-    if (on && !h->p2p_ranks) return fail(h, CDH_BAD_ARG, "p2p exchange is not connected");
-    if (on && *(volatile int*)h->p2p_timeout)
-        return fail(h, CDH_RCCL_ERROR, "p2p exchange timed out earlier on this handle; it stays off");
-    h->p2p_on = on != 0;
-    if (h->p2p_on) h->lost_exchange = false;   // the direct exchange serves the shard again
-    return CDH_OK;
+    if (!on) { h->xs.p2p_disabled(); return CDH_OK; }
+    return refused(h, h->xs.p2p_enabled(h->xs.direct_ranks() && *(volatile int*)h->p2p_timeout));   // (connected: the flag is there)
 }); }
 
 int32_t cdh_set_host_exchange(cdh_handle h, cdh_host_allreduce_fn fn, void* user, int32_t rank, int32_t nranks) { return guarded(h, [&]() -> int32_t {
-    if (!fn) {
-        // a shard of a multi-rank problem must not quietly fall into the single-process kernels on its local rows
-        if (h->host_fn && h->nranks > 1 && !h->comm && !h->p2p_ranks) h->lost_exchange = true;
-        h->host_fn = nullptr; h->host_user = nullptr;
-        return CDH_OK;
-    }
-    if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, CDH_BAD_ARG, "bad rank / nranks");
-    if (h->comm || h->p2p_ranks) return fail(h, CDH_BAD_ARG, "the handle already has an exchange (RCCL / direct)");
+    if (!fn) { h->xs.host_removed(); return CDH_OK; }
+    CHK(refused(h, h->xs.host_refused(rank, nranks)));
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->h_xchg) {   // the longest record is the 2p column dots of _findLambdaMax / _stdX!
         const size_t doubles = (size_t)std::max<int64_t>(4096, 2 * h->p);
         HIPCHK(h, h->h_xchg.alloc(sizeof(double) * doubles));
         h->h_xchg_doubles = doubles;
     }
-    h->host_fn = fn; h->host_user = user; h->rank = rank; h->nranks = nranks;
-    h->lost_exchange = false;
+    h->xs.host_installed(fn, user, rank, nranks);
     return CDH_OK;
 }); }
 
 int32_t cdh_exchange_stats(cdh_handle h, int64_t* out_rccl_calls, int64_t* out_p2p_calls, int64_t* out_host_calls,
                            int32_t* out_nranks) { return guarded(h, [&]() -> int32_t {
-    if (out_rccl_calls) *out_rccl_calls = h->n_rccl_calls;
-    if (out_p2p_calls) *out_p2p_calls = h->n_p2p_calls;
-    if (out_host_calls) *out_host_calls = h->n_host_calls;
+    const cdh::ExchangeState& xs = h->xs;
+    if (out_rccl_calls) *out_rccl_calls = xs.rccl_calls();
+    if (out_p2p_calls) *out_p2p_calls = xs.direct_calls();
+    if (out_host_calls) *out_host_calls = xs.host_calls();
     if (out_nranks) {
-        int n = 1;
-        if (h->comm) {   // what the communicator itself says, not what we asked for
-            n = h->nranks;
-            if (g_rccl.CommCount && g_rccl.CommCount(h->comm, &n) != 0) n = -1;
-        } else if (h->p2p_on) {
-            n = h->p2p_ranks;
-        } else if (h->host_fn) {
-            n = h->nranks;
-        }
+        int n = xs.reported_ranks();
+        // with a communicator: what the communicator itself says, not what we asked for
+        if (xs.communicator() && g_rccl.CommCount && g_rccl.CommCount(xs.communicator(), &n) != 0) n = -1;
         *out_nranks = n;
     }
     return CDH_OK;

@@ -16,13 +16,13 @@ int32_t finish_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH);
 // buffers fit on THIS device -- is agreed on through the exchange itself.  One rank: the local answer.
 int32_t all_ranks_agree(cdh_handle h, bool mine, bool* all) {
     *all = mine;
-    if (!sharded(h) || h->nranks <= 1) return CDH_OK;
+    if (!h->xs.sharded() || h->xs.nranks() <= 1) return CDH_OK;
     h->h_red[0] = mine ? 1.0 : 0.0;
     HIPCHK(h, hipMemcpyAsync(h->d_red, h->h_red, sizeof(double), hipMemcpyHostToDevice, h->stream));
     CHK(allreduce(h, h->d_red, 1));
     HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    *all = h->h_red[0] == (double)h->nranks;
+    *all = h->h_red[0] == (double)h->xs.nranks();
     return CDH_OK;
 }
 

@@ -453,7 +453,7 @@ inline double small_build_estimate(const cdh_handle_s* h) {
     return (double)((h->p + 31) / 32 + 1) * std::max(bytes / 4.0e12, 40e-6);
 }
 inline bool small_candidate(const cdh_handle_s* h, const cdh_options* o) {      // everything but the rent-or-buy decision
-    return h->small.enabled && !sharded(h) && h->p <= kSmallMaxP &&
+    return h->small.enabled && !h->xs.sharded() && h->p <= kSmallMaxP &&
            h->gc.mode != 3 /* tests force the gradient cache's own path with mode 3 */ && (h->loss != CDH_WLS || h->has_w) &&
            o->numSteps + 1 <= kSmallMaxLam && o->numSteps >= 1;
 }
