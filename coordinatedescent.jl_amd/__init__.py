@@ -10,10 +10,10 @@ The directory name contains a dot, so import it through the root-level shim:
   sharded.py   row-sharded multi-process driver (torch.distributed + RCCL)
 """
 from . import _lib
-from ._lib import build, declared_symbols, needs_build, SO_PATH  # noqa: F401
+from ._lib import build, declared_symbols, needs_build, SO_PATH, CDH_QUAD_MAX_P  # noqa: F401
 from .api import *  # noqa: F401,F403
 from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSquaresLoss,  # noqa: F401
-                  CDSqrtLassoLoss, CDWeightedLSLoss, CoordinateDifferentiableFunction,
+                  CDSqrtLassoLoss, CDWeightedLSLoss, CDQuadraticLoss, CoordinateDifferentiableFunction,
                   OrderedIterator, RandomIterator, reset_, numCoordinates, initialize_, gradient,
                   descendCoordinate_, coordinateDescent_, cdPass_, findLambdaMax, stdX, objective,
                   lasso, sqrtLasso, scaledLasso_, LassoPath, LassoSolution, LassoPathResult,

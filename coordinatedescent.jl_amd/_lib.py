@@ -28,6 +28,7 @@ CDH_F64, CDH_F32 = 0, 1
 CDH_LS, CDH_SQRT, CDH_WLS = 0, 1, 2
 CDH_SWEEP_COORD, CDH_SWEEP_BLOCK = 0, 1
 CDH_VC_GAUSSIAN, CDH_VC_EPANECHNIKOV = 0, 1
+CDH_QUAD_MAX_P = 2559    # include/cdhip.h; derived in csrc/quad_solve_types.hpp (tests/test_quad_host.py holds the three together)
 
 
 class DimensionMismatch(Exception):
@@ -168,6 +169,18 @@ def lib():
         "cdh_exchange_latency": [vp, i64, i32, P(f64)],
         "cdh_profile_begin": [vp],
         "cdh_profile_end": [vp, P(f64), P(i64), P(f64)],
+        "cdh_quad_create": [P(vp), i64, i64, i32],
+        "cdh_quad_destroy": [vp],
+        "cdh_quad_set_A": [vp, vp, i64],
+        "cdh_quad_set_b": [vp, i64, vp, i64],
+        "cdh_quad_set_penalty": [vp, vp, vp, i64],
+        "cdh_quad_set_iterate": [vp, i64, i64, vp, vp],
+        "cdh_quad_get_iterate": [vp, i64, P(i64), vp, vp],
+        "cdh_quad_initialize": [vp],
+        "cdh_quad_get_gradient": [vp, i64, vp],
+        "cdh_quad_descend": [vp, i64, i64, P(f64)],
+        "cdh_quad_pass": [vp, i64, i64, vp, P(f64)],
+        "cdh_quad_coordinate_descent": [vp, P(cdh_options), vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

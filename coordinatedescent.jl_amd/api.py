@@ -579,21 +579,215 @@ class CDVaryingCoefficientLoss(CDWeightedLSLoss):
         return std, scores
 
 
-def initialize_(f, x):
-    """initialize!(f, x): r = y - Xβ (src/cd_differentiable_function.jl:59-72)."""
+class CDQuadraticLoss(CoordinateDifferentiableFunction):
+    """CDQuadraticLoss(A, b): x'Ax/2 + x'b (src/cd_differentiable_function.jl:299-348), behind one cdh_quad handle.
+
+    A p-vector `b` is the reference's single problem; a p x m `b` is a batch of m problems that share A (problem j has
+    b[:, j]) and are solved by coordinateDescent_ in one launch.  fp64 only (the reference's Ax is Float64 whatever T is).
+    The generic functions take `problem=j` (0-based) to address one problem of a batch."""
+
+    def __init__(self, A, b, *, device=0, max_batch=None):
+        A, b = np.asarray(A), np.asarray(b)
+        if A.dtype != np.float64 or b.dtype != np.float64:
+            raise TypeError("MethodError: CDQuadraticLoss is Float64 only (A::Matrix{Float64}, b::Vector{Float64})")
+        if A.ndim != 2 or A.shape[0] != A.shape[1]:          # :306 issymmetric(A)
+            raise ArgumentError("A must be square")
+        if b.ndim not in (1, 2) or b.shape[0] != A.shape[0] or (b.ndim == 2 and b.shape[1] < 1):
+            raise ArgumentError("length(b) != size(A, 1)")
+        if not np.array_equal(A, A.T):
+            raise ArgumentError("A must be symmetric")
+        self.p = int(A.shape[0])
+        self.batched = b.ndim == 2
+        self.m = int(b.shape[1]) if self.batched else 1
+        self.max_batch = self.m if max_batch is None else int(max_batch)
+        if self.m > self.max_batch:
+            raise ArgumentError(f"m = {self.m} problems exceed the handle's max_batch = {self.max_batch}")
+        if self.p > _lib.CDH_QUAD_MAX_P:
+            raise ArgumentError(f"p = {self.p} exceeds CDH_QUAD_MAX_P = {_lib.CDH_QUAD_MAX_P}, the largest problem whose state fits "
+                                "160 KiB of LDS")
+        self._L = _lib.lib()
+        self._h = None
+        h = C.c_void_p()
+        check(self._L.cdh_quad_create(C.byref(h), self.p, self.max_batch, int(device)), None)
+        self._h = h
+        Af = np.asfortranarray(A)
+        self._q(self._L.cdh_quad_set_A(self._h, _vp(Af), self.p))
+        self.last_stats = None
+        self._load_b(b)
+
+    def _load_b(self, b):
+        self.b = np.array(b.reshape(self.p, self.m), dtype=np.float64, order="F", copy=True)   # column j = problem j, ldb = p
+        self._q(self._L.cdh_quad_set_b(self._h, self.m, _vp(self.b), self.p))
+        self._synced = [None] * self.m       # (id(x), version) of the iterate the handle mirrors, per problem
+        self._zero = [True] * self.m         # the handle's iterate is still the zero a new b leaves: an empty x needs no upload
+        self._lam0 = np.zeros(self.m)
+        self._omega = None                   # None, a p-vector shared by all problems, or p x m (column-major)
+        self._pen_sent = False
+
+    def set_b(self, b):
+        """Another b (p-vector, or p x m with m <= max_batch) on the same A: as a new loss, every iterate zero and Ax = 0."""
+        b = np.asarray(b)
+        if b.dtype != np.float64:
+            raise TypeError("MethodError: CDQuadraticLoss is Float64 only")
+        if b.ndim not in (1, 2) or b.shape[0] != self.p or (b.ndim == 2 and b.shape[1] < 1):
+            raise ArgumentError("length(b) != size(A, 1)")
+        m = int(b.shape[1]) if b.ndim == 2 else 1
+        if m > self.max_batch:
+            raise ArgumentError(f"m = {m} problems exceed the handle's max_batch = {self.max_batch}")
+        self.batched, self.m = b.ndim == 2, m
+        self._load_b(b)
+
+    def _q(self, status):
+        check(status, None)                  # (a quad handle reports through cdh_last_error(NULL))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._L.cdh_quad_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    close = __del__
+
+    # -- penalty -----------------------------------------------------------------------------
+    def _send_penalty(self):
+        om = self._omega
+        ldo = 0 if om is None or om.ndim == 1 else self.p
+        self._q(self._L.cdh_quad_set_penalty(self._h, _vp(self._lam0), _vp(om), ldo))
+        self._pen_sent = True
+
+    def _set_penalty(self, g, problem=0):
+        """ProxL1 of ONE problem; the others keep theirs."""
+        if not isinstance(g, ProxL1):
+            raise TypeError("MethodError: descendCoordinate! is defined for g::ProxL1 only")
+        j, om = int(problem), self._omega
+        col = None if om is None else (om if om.ndim == 1 else om[:, j])
+        same = self._pen_sent and self._lam0[j] == g.lambda0 and \
+            ((g.lam is None and col is None) or (g.lam is not None and col is not None and np.array_equal(g.lam, col)))
+        if same:
+            return
+        self._lam0[j] = g.lambda0
+        if self.m == 1:
+            self._omega = None if g.lam is None else g.lam.copy()
+        elif not (g.lam is None and om is None):
+            if om is None or om.ndim == 1:
+                self._omega = np.asfortranarray(np.tile((np.ones(self.p) if om is None else om)[:, None], (1, self.m)))
+            self._omega[:, j] = 1.0 if g.lam is None else g.lam
+        self._send_penalty()
+
+    def _set_penalties(self, gs):
+        """One ProxL1 per problem, or one for all."""
+        shared = isinstance(gs, ProxL1)
+        glist = [gs] * self.m if shared else list(gs)
+        if len(glist) != self.m or not all(isinstance(g, ProxL1) for g in glist):
+            raise ArgumentError("need one ProxL1, or one per problem")
+        self._lam0 = np.array([g.lambda0 for g in glist], dtype=np.float64)
+        if all(g.lam is None for g in glist):
+            self._omega = None
+        elif shared or self.m == 1:
+            self._omega = glist[0].lam.copy()
+        else:
+            self._omega = np.asfortranarray(np.stack([np.ones(self.p) if g.lam is None else g.lam for g in glist], axis=1))
+        self._send_penalty()
+
+    # -- iterates ------------------------------------------------------------------------------
+    def _problem(self, problem):
+        j = int(problem)
+        if not 0 <= j < self.m:
+            raise ArgumentError(f"problem {j} outside 0 .. {self.m - 1}")
+        return j
+
+    def _push(self, x, j):
+        idx = np.ascontiguousarray(x.nzval2ind, dtype=np.int64)
+        val = np.ascontiguousarray(x._val[: x.nnz], dtype=np.float64)
+        self._q(self._L.cdh_quad_set_iterate(self._h, j, x.nnz, _vp(idx), _vp(val)))
+        self._synced[j] = (id(x), x._version)
+        self._zero[j] = x.nnz == 0
+
+    def _ensure_synced(self, x, j):
+        if numCoordinates(x) != self.p:
+            raise DimensionMismatch("numCoordinates(x) != numCoordinates(f)")
+        if self._synced[j] != (id(x), x._version):
+            if x.nnz == 0 and self._zero[j]:
+                self._synced[j] = (id(x), x._version)
+            else:
+                self._push(x, j)
+
+    def _pull(self, x, j):
+        if getattr(self, "_pull_idx", None) is None:
+            self._pull_idx, self._pull_val = np.zeros(self.p, dtype=np.int64), np.zeros(self.p)
+        nnz = C.c_int64()
+        self._q(self._L.cdh_quad_get_iterate(self._h, j, C.byref(nnz), _vp(self._pull_idx), _vp(self._pull_val)))
+        x._load(self._pull_idx[: nnz.value], self._pull_val[: nnz.value])
+        self._synced[j] = (id(x), x._version)
+        self._zero[j] = nnz.value == 0
+
+    def _gradient_vector(self, j):
+        """Ax + b of problem j as the handle holds it (p doubles)."""
+        out = np.zeros(self.p)
+        self._q(self._L.cdh_quad_get_gradient(self._h, j, _vp(out)))
+        return out
+
+    def _omega_of(self, j):
+        om = self._omega
+        return None if om is None else (om if om.ndim == 1 else om[:, j])
+
+    # -- the driver ----------------------------------------------------------------------------
+    def _coordinate_descent(self, x, g, options):
+        xs = list(x) if self.batched else [x]
+        if self.batched and (isinstance(x, SparseIterate) or len(xs) != self.m):
+            raise ArgumentError("a batch takes a list of one SparseIterate per problem")
+        gl = [g] * self.m if isinstance(g, ProxL1) else list(g)
+        if len(gl) != self.m:
+            raise ArgumentError("need one ProxL1, or one per problem")
+        for xj, gj in zip(xs, gl):
+            _check_dims(xj, self, gj)
+        self._set_penalties(g if isinstance(g, ProxL1) else gl)
+        if options.warmStart:
+            for j, xj in enumerate(xs):
+                self._ensure_synced(xj, j)
+        o, st = options._c(), (cdh_stats * self.m)()
+        self._q(self._L.cdh_quad_coordinate_descent(self._h, C.byref(o), st))
+        stats = [_stats(s) for s in st]
+        self.last_stats = stats if self.batched else stats[0]
+        for j, xj in enumerate(xs):
+            self._pull(xj, j)
+        return x
+
+
+def initialize_(f, x, problem=0):
+    """initialize!(f, x): r = y - Xβ (src/cd_differentiable_function.jl:59-72); CDQuadraticLoss: Ax (:311-320)."""
+    if isinstance(f, CDQuadraticLoss):
+        j = f._problem(problem)
+        f._ensure_synced(x, j)
+        f._q(f._L.cdh_quad_initialize(f._h))
+        return
     f._push(x, rebuild=True)
 
 
-def gradient(f, x, k):
-    """gradient(f, x, k) (src/cd_differentiable_function.jl:75-76, 234-235)."""
+def gradient(f, x, k, problem=0):
+    """gradient(f, x, k) (src/cd_differentiable_function.jl:75-76, 234-235; CDQuadraticLoss: Ax[k] + b[k], :321-322)."""
+    if isinstance(f, CDQuadraticLoss):
+        j = f._problem(problem)
+        f._ensure_synced(x, j)
+        return float(f._gradient_vector(j)[int(k) - 1])
     f._ensure_synced(x)
     out = C.c_double()
     check(f._L.cdh_gradient(f._h, int(k), C.byref(out)), f._h)
     return out.value
 
 
-def descendCoordinate_(f, g, x, k):
-    """descendCoordinate!(f, g, x, k) -> h (src/cd_differentiable_function.jl:83-111, 242-291)."""
+def descendCoordinate_(f, g, x, k, problem=0):
+    """descendCoordinate!(f, g, x, k) -> h (src/cd_differentiable_function.jl:83-111, 242-291; CDQuadraticLoss: :324-348)."""
+    if isinstance(f, CDQuadraticLoss):
+        j = f._problem(problem)
+        f._set_penalty(g, j)
+        f._ensure_synced(x, j)
+        out = C.c_double()
+        f._q(f._L.cdh_quad_descend(f._h, j, int(k), C.byref(out)))
+        f._pull(x, j)
+        return out.value
     f._set_penalty(g)
     f._ensure_synced(x)
     out = C.c_double()
@@ -679,6 +873,8 @@ def coordinateDescent_(x, f, g, options=None):
     """coordinateDescent!(x, f, g::ProxL1, options=CDOptions()) (src/coordinate_descent.jl:7-39).
     Returns x; pass/convergence statistics are left in f.last_stats."""
     options = options or CDOptions()
+    if isinstance(f, CDQuadraticLoss):       # a single problem, or a batch: lists of iterates and penalties, one launch
+        return f._coordinate_descent(x, g, options)
     _check_dims(x, f, g)
     f._set_penalty(g)
     f._ensure_synced(x)
@@ -692,23 +888,37 @@ def coordinateDescent_(x, f, g, options=None):
     return x
 
 
-def cdPass_(x, f, g, visit):
+def cdPass_(x, f, g, visit, problem=0):
     """_cdPass!(x, f, g, it) (src/coordinate_descent.jl:94-110) over an explicit 1-based
     visit list; returns maxH."""
-    f._set_penalty(g)
-    f._ensure_synced(x)
     if isinstance(visit, np.ndarray) and visit.dtype == np.int64 and visit.flags.c_contiguous:
         idx = visit                      # a prepared list crosses as is (sweep loops reuse one)
     else:
         idx = np.ascontiguousarray(list(visit), dtype=np.int64)
     out = C.c_double()
+    if isinstance(f, CDQuadraticLoss):
+        j = f._problem(problem)
+        f._set_penalty(g, j)
+        f._ensure_synced(x, j)
+        f._q(f._L.cdh_quad_pass(f._h, j, idx.shape[0], _vp(idx), C.byref(out)))
+        f._pull(x, j)
+        return out.value
+    f._set_penalty(g)
+    f._ensure_synced(x)
     check(f._L.cdh_pass(f._h, idx.shape[0], _vp(idx), C.byref(out)), f._h)
     f._pull(x)
     return out.value
 
 
-def findLambdaMax(x, f, g):
+def findLambdaMax(x, f, g, problem=0):
     """_findLambdaMax(x, f, g) (src/coordinate_descent.jl:118-149)."""
+    if isinstance(f, CDQuadraticLoss):       # max_k |gradient(f, x, k)| / omega_k, on the host from the handle's Ax + b
+        j = f._problem(problem)
+        f._ensure_synced(x, j)
+        t = np.abs(f._gradient_vector(j))
+        if g.lam is not None:
+            t = t / g.lam
+        return float(t.max())
     f._set_penalty(g)
     f._ensure_synced(x)
     out = C.c_double()
@@ -724,8 +934,19 @@ def stdX(f, weighted=False):
     return out
 
 
-def objective(f, g=None):
+def objective(f, g=None, problem=0):
     """f(β) + λ0 Σ ω|β| at the handle's current state (src/coordinate_descent.jl:1-3)."""
+    if isinstance(f, CDQuadraticLoss):       # x'Ax/2 + x'b = sum_k x_k (g_k + b_k) / 2 with g = Ax + b as the handle holds it
+        j = f._problem(problem)
+        x = SparseIterate(f.p)
+        f._pull(x, j)
+        f._synced[j] = None
+        k, grad = x._slot2ind[: x.nnz], f._gradient_vector(j)
+        val = float(np.sum(x._val[: x.nnz] * (grad[k] + f.b[k, j]) * 0.5))
+        if g is not None:
+            om = np.ones(x.nnz) if g.lam is None else g.lam[k]
+            val += g.lambda0 * float(np.sum(np.abs(x._val[: x.nnz]) * om))
+        return val
     if g is not None:
         f._set_penalty(g)
     out = C.c_double()

@@ -381,6 +381,29 @@ struct cdh_handle_s {
     std::string err;
 };
 
+// ---- the second handle: a batch of CDQuadraticLoss problems on one A (quad_solve.hpp) ----------------------------------------
+#include "quad_solve_types.hpp"   // the LDS layout, CDH_QUAD_MAX_P's formula, the argument checks: host-only arithmetic
+static_assert(kQuadMaxP == CDH_QUAD_MAX_P, "cdhip.h names the limit quad_solve_types.hpp derives");
+struct cdh_quad_s {
+    int64_t p = 0, max_batch = 0, m = 0;   // m: the problems loaded by the last cdh_quad_set_b
+    int32_t device = 0;
+    hipStream_t stream = nullptr;
+    unsigned lds_bytes = 0;
+    bool A_set = false, penalty_set = false, has_omega = false, omega_shared = false;
+    // device: A (p x p), 1 / diag(A); per problem b, omega, lambda0 and a cold start's grid, beta (dense), g = A x + b, the
+    // support in slot order and its length, the statistics; the explicit list of cdh_quad_pass and a descent's h
+    DevBuf<double> A, inv_a, B, omega, lambda0, grid, beta, g, h_out;
+    DevBuf<int32_t> sup, nnz, list;
+    int64_t list_cap = 0;
+    DevBuf<QuadStat> stats;
+    PinBuf<QuadStat> h_stats;
+    PinBuf<double> h_h;
+    // host: what lambda_max of a cold start is taken from, and the iterates as last fetched (host_stale: the device has moved on)
+    std::vector<double> h_B, h_omega, h_lambda0, h_beta;
+    std::vector<int32_t> h_sup, h_nnz;
+    bool host_stale = true;
+};
+
 namespace {
 
 #define HIPCHK(h, call)                                                                     \
@@ -986,6 +1009,7 @@ constexpr int kScreenMinPass = 16;   // screens / the cache: passes over fewer c
 #include "grad_cache.hpp"   // gc_size, gc_validate, gc_fetch, gc_fold, gc_full_pass
 #include "small_solve.hpp"  // small_applicable, small_prepare, small_solve
 #include "cov_solve.hpp"    // k_cov_solve, cov_solve: the pass loop of a cache-served solve on the device
+#include "quad_solve.hpp"   // k_quad_solve, k_quad_init: a batch of CDQuadraticLoss problems, one workgroup each
 
 // _cdPass! (coordinate_descent.jl:94-110)
 // Screening of a FULL pass (exact, no reference counterpart).  A visit of a coordinate with
@@ -2313,6 +2337,168 @@ int32_t cdh_profile_end(cdh_handle h, double* out_ms, int64_t* out_launches, dou
     if (out_launches) *out_launches = h->prof_launches;
     if (out_algorithmic_bytes) *out_algorithmic_bytes = h->prof_bytes;
     return CDH_OK;
+}); }
+
+// ---- cdh_quad: CDQuadraticLoss, a batch of problems on one A (quad_solve.hpp) -------------------------------------------------
+int32_t cdh_quad_create(cdh_quad* out, int64_t p, int64_t max_batch, int32_t device) { return guarded([&]() -> int32_t {
+    QNEED(out, "out is NULL");
+    *out = nullptr;
+    QREFUSE(quad_check_create(p, max_batch));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return quad_fail(CDH_HIP_ERROR, "no HIP device: this library has no CPU fallback");
+    QNEED(device >= 0 && device < ndev, "device index out of range");
+    QuadOwner own{new cdh_quad_s()};       // freed on every early return below
+    cdh_quad q = own.q;
+    q->p = p; q->max_batch = max_batch; q->device = device;
+    q->lds_bytes = (unsigned)quad_lds_bytes(p);
+    QCHK(hipSetDevice(device));
+    QCHK(hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking));
+    CHK(quad_alloc(q));
+    // a problem's state may take more dynamic LDS than a kernel gets unasked (64 KiB): up to the CU's 160 KiB
+    if (q->lds_bytes > 48 * 1024) {
+        QCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quad_solve<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuadLdsBudget));
+        QCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_quad_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuadLdsBudget));
+    }
+    *out = own.release();
+    return CDH_OK;
+}); }
+
+int32_t cdh_quad_destroy(cdh_quad q) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    quad_free(q);
+    return CDH_OK;
+}); }
+
+int32_t cdh_quad_set_A(cdh_quad q, const double* A, int64_t lda) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    QNEED(A, "A is NULL");
+    QNEED(lda >= q->p, "lda must be at least p");
+    QCHK(hipSetDevice(q->device));
+    const size_t p = (size_t)q->p;
+    std::vector<double> inv(p);
+    for (size_t k = 0; k < p; ++k) {
+        const double d = A[k + (size_t)lda * k];
+        QNEED(d > 0.0, "diag(A) must be positive");
+        inv[k] = 1.0 / d;                  // a = 1 / A_kk (cd_differentiable_function.jl:326), once per A
+    }
+    QCHK(hipMemcpy2DAsync(q->A, sizeof(double) * p, A, sizeof(double) * (size_t)lda, sizeof(double) * p, p, hipMemcpyHostToDevice, q->stream));
+    QCHK(hipMemcpyAsync(q->inv_a, inv.data(), sizeof(double) * p, hipMemcpyHostToDevice, q->stream));
+    QCHK(hipStreamSynchronize(q->stream));
+    q->A_set = true;
+    return CDH_OK;
+}); }
+
+int32_t cdh_quad_set_b(cdh_quad q, int64_t m, const double* B, int64_t ldb) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    QNEED(B, "B is NULL");
+    QNEED(m >= 1, "m must be positive");
+    if (m > q->max_batch) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "m = %lld problems exceed the handle's max_batch = %lld", (long long)m, (long long)q->max_batch);
+        return quad_fail(CDH_BAD_ARG, buf);
+    }
+    QNEED(ldb >= q->p, "ldb must be at least p");
+    QCHK(hipSetDevice(q->device));
+    const size_t p = (size_t)q->p;
+    q->h_B.resize(p * (size_t)m);
+    for (int64_t j = 0; j < m; ++j) std::memcpy(q->h_B.data() + (size_t)j * p, B + (size_t)j * (size_t)ldb, sizeof(double) * p);
+    q->m = m; q->penalty_set = false; q->host_stale = true;
+    QCHK(hipMemcpyAsync(q->B, q->h_B.data(), sizeof(double) * p * (size_t)m, hipMemcpyHostToDevice, q->stream));
+    QCHK(hipMemcpyAsync(q->g, q->h_B.data(), sizeof(double) * p * (size_t)m, hipMemcpyHostToDevice, q->stream));   // Ax = 0 (:304-308)
+    QCHK(hipMemsetAsync(q->beta, 0, sizeof(double) * p * (size_t)m, q->stream));
+    QCHK(hipMemsetAsync(q->nnz, 0, sizeof(int32_t) * (size_t)m, q->stream));
+    QCHK(hipStreamSynchronize(q->stream));
+    return CDH_OK;
+}); }
+
+int32_t cdh_quad_set_penalty(cdh_quad q, const double* lambda0, const double* omega, int64_t ldo) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    QNEED(lambda0, "lambda0 is NULL");
+    QNEED(q->m > 0, "no problems are loaded: cdh_quad_set_b first");
+    QNEED(!omega || ldo == 0 || ldo >= q->p, "ldo must be 0 (one shared vector) or at least p");
+    QCHK(hipSetDevice(q->device));
+    const size_t p = (size_t)q->p, m = (size_t)q->m;
+    q->h_lambda0.assign(lambda0, lambda0 + m);
+    q->has_omega = omega != nullptr; q->omega_shared = omega && ldo == 0;
+    const size_t ncol = !omega ? 0 : (ldo == 0 ? 1 : m);
+    q->h_omega.resize(p * ncol);
+    for (size_t j = 0; j < ncol; ++j) std::memcpy(q->h_omega.data() + j * p, omega + j * (size_t)ldo, sizeof(double) * p);
+    QCHK(hipMemcpyAsync(q->lambda0, q->h_lambda0.data(), sizeof(double) * m, hipMemcpyHostToDevice, q->stream));
+    if (ncol) QCHK(hipMemcpyAsync(q->omega, q->h_omega.data(), sizeof(double) * p * ncol, hipMemcpyHostToDevice, q->stream));
+    QCHK(hipStreamSynchronize(q->stream));
+    q->penalty_set = true;
+    return CDH_OK;
+}); }
+
+int32_t cdh_quad_set_iterate(cdh_quad q, int64_t j, int64_t nnz, const int64_t* idx1, const double* val) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    QREFUSE(quad_check_problem(j, q->m));
+    QNEED(nnz == 0 || (idx1 && val), "idx1 or val is NULL");
+    std::vector<unsigned char> seen((size_t)q->p, 0);
+    QREFUSE(quad_check_support(q->p, nnz, idx1, seen.data()));
+    QCHK(hipSetDevice(q->device));
+    const size_t p = (size_t)q->p;
+    std::vector<double> dense(p, 0.0);
+    std::vector<int32_t> sup((size_t)nnz);
+    for (int64_t s = 0; s < nnz; ++s) { sup[(size_t)s] = (int32_t)(idx1[s] - 1); dense[(size_t)(idx1[s] - 1)] = val[s]; }
+    const int32_t n32 = (int32_t)nnz;
+    QCHK(hipMemcpyAsync(q->beta + (size_t)j * p, dense.data(), sizeof(double) * p, hipMemcpyHostToDevice, q->stream));
+    if (nnz) QCHK(hipMemcpyAsync(q->sup + (size_t)j * p, sup.data(), sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, q->stream));
+    QCHK(hipMemcpyAsync(q->nnz + j, &n32, sizeof(int32_t), hipMemcpyHostToDevice, q->stream));
+    QCHK(hipStreamSynchronize(q->stream));
+    q->host_stale = true;
+    return CDH_OK;
+}); }
+
+int32_t cdh_quad_get_iterate(cdh_quad q, int64_t j, int64_t* nnz, int64_t* idx1, double* val) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    QREFUSE(quad_check_problem(j, q->m));
+    QNEED(nnz && idx1 && val, "nnz, idx1 or val is NULL");
+    QCHK(hipSetDevice(q->device));
+    CHK(quad_pull(q));
+    const size_t p = (size_t)q->p, off = (size_t)j * p;
+    const int32_t n = q->h_nnz[(size_t)j];
+    for (int32_t s = 0; s < n; ++s) { const int32_t k = q->h_sup[off + (size_t)s]; idx1[s] = (int64_t)k + 1; val[s] = q->h_beta[off + (size_t)k]; }
+    *nnz = n;
+    return CDH_OK;
+}); }
+
+int32_t cdh_quad_initialize(cdh_quad q) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    CHK(quad_ready(q, false));
+    hipLaunchKernelGGL(k_quad_init, dim3((unsigned)q->m), dim3(256), 0, q->stream, (int)q->p, q->A, q->B, q->beta, q->sup, q->nnz, q->g);
+    QCHK(hipGetLastError());
+    QCHK(hipStreamSynchronize(q->stream));
+    return CDH_OK;
+}); }
+
+int32_t cdh_quad_get_gradient(cdh_quad q, int64_t j, double* out) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    QREFUSE(quad_check_problem(j, q->m));
+    QNEED(out, "out is NULL");
+    QCHK(hipSetDevice(q->device));
+    QCHK(hipMemcpyAsync(out, q->g + (size_t)j * (size_t)q->p, sizeof(double) * (size_t)q->p, hipMemcpyDeviceToHost, q->stream));
+    QCHK(hipStreamSynchronize(q->stream));
+    return CDH_OK;
+}); }
+
+int32_t cdh_quad_descend(cdh_quad q, int64_t j, int64_t k1, double* out_h) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    QNEED(out_h, "out_h is NULL");
+    return quad_explicit(q, j, 1, &k1, false, nullptr, out_h);
+}); }
+
+int32_t cdh_quad_pass(cdh_quad q, int64_t j, int64_t n, const int64_t* idx1, double* maxH) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    QNEED(maxH, "maxH is NULL");
+    return quad_explicit(q, j, n, idx1, true, maxH, nullptr);
+}); }
+
+int32_t cdh_quad_coordinate_descent(cdh_quad q, const cdh_options* opt, cdh_stats* stats) { return guarded([&]() -> int32_t {
+    QNEED(q, "quad handle is NULL");
+    QNEED(opt, "opt is NULL");
+    return quad_coordinate_descent(q, opt, stats);
 }); }
 
 }  // extern "C"

@@ -389,6 +389,54 @@ int32_t cdh_profile_begin(cdh_handle h);
 int32_t cdh_profile_end(cdh_handle h, double *out_ms, int64_t *out_launches,
                         double *out_algorithmic_bytes);
 
+/* ---- CDQuadraticLoss: f(x) = x'Ax/2 + x'b (cd_differentiable_function.jl:299-348) ------------------------------------
+ * A second handle in the same library, for a BATCH of up to max_batch problems that share one symmetric p x p matrix A and
+ * differ in b, lambda0 and omega (neighbourhood selection of a graph: b_j = -A_j, omega_jj = +inf; CLIME columns; grids of
+ * lambda; many right-hand sides).  cdh_quad_coordinate_descent solves all of them in ONE launch, one workgroup per problem
+ * running the reference's whole pass loop with the problem's state in LDS; A stays in device memory, shared.
+ *   - fp64 only: the reference's Ax is Float64 whatever T is (:301).
+ *   - p <= CDH_QUAD_MAX_P, the largest p whose per-problem state fits the 160 KiB of LDS of a CU; more is CDH_BAD_ARG.
+ *   - diag(A) must be positive (the reference's a = 1 / A_kk, :326, is not pinned for anything else): else CDH_BAD_ARG.
+ *   - Problems are numbered j = 0 .. m - 1 (a bulk index, like j0 above); coordinates are 1-based as everywhere.
+ *   - A quad handle keeps no error text of its own: whatever one of these calls refuses or fails on, NULL or live handle,
+ *     is described by cdh_last_error(NULL).
+ *   - Same iterates, support order and pass counts as visiting coordinate by coordinate; ordered and shuffled sweeps (the
+ *     splitmix64 substitute, seeded per call: every problem of a batch starts from opt->seed, as m separate calls would). */
+#define CDH_QUAD_MAX_P 2559
+typedef struct cdh_quad_s *cdh_quad;
+/* The CDQuadraticLoss constructor (cd_differentiable_function.jl:304-308) for problems of p coordinates. */
+int32_t cdh_quad_create(cdh_quad *out, int64_t p, int64_t max_batch, int32_t device);
+int32_t cdh_quad_destroy(cdh_quad q); /* NULL is CDH_BAD_ARG here */
+/* f.A (cd_differentiable_function.jl:300, 306): column-major p x p with leading dimension lda; only symmetry makes "row k = column k" true, and it is the
+ * caller's contract as it is the reference's. */
+int32_t cdh_quad_set_A(cdh_quad q, const double *A, int64_t lda);
+/* f.b (cd_differentiable_function.jl:300) of m <= max_batch problems, column j of B (leading dimension ldb); as the constructor leaves a new loss (:307):
+ * every iterate zero, Ax = 0, so g = b.  The penalty has to be set again afterwards. */
+int32_t cdh_quad_set_b(cdh_quad q, int64_t m, const double *B, int64_t ldb);
+/* ProxL1(lambda0[j]) / ProxL1(lambda0[j], omega) per problem (coordinate_descent.jl:7-16): omega NULL: unweighted; ldo == 0:
+ * one p-vector for all problems; else column j of a p x m matrix with leading dimension ldo >= p.  +inf entries are allowed
+ * (that coordinate stays zero). */
+int32_t cdh_quad_set_penalty(cdh_quad q, const double *lambda0, const double *omega, int64_t ldo);
+/* Load the iterate of problem j (support in SparseIterate order) without touching g: what the binding does when the caller's
+ * x changed (the reference reads x[k] directly, cd_differentiable_function.jl:328). */
+int32_t cdh_quad_set_iterate(cdh_quad q, int64_t j, int64_t nnz, const int64_t *idx1, const double *val);
+/* The iterate of problem j as coordinateDescent! leaves its x (coordinate_descent.jl:7-11): nzval2ind and nzval in slot order
+ * (idx1 and val hold up to p entries). */
+int32_t cdh_quad_get_iterate(cdh_quad q, int64_t j, int64_t *nnz, int64_t *idx1, double *val);
+/* initialize!(f, x) (cd_differentiable_function.jl:311-320) for all m problems: g_j = A x_j + b_j, summed in slot order. */
+int32_t cdh_quad_initialize(cdh_quad q);
+/* gradient(f, x, k) for every k (cd_differentiable_function.jl:321-322): out[k] = (Ax)_k + b_k of problem j, p doubles. */
+int32_t cdh_quad_get_gradient(cdh_quad q, int64_t j, double *out);
+/* descendCoordinate!(f, g, x, k) -> h (cd_differentiable_function.jl:324-348) on problem j; no dropzeros!. */
+int32_t cdh_quad_descend(cdh_quad q, int64_t j, int64_t k1, double *out_h);
+/* _cdPass! over an explicit visit list on problem j (coordinate_descent.jl:94-110): maxH = max |h|, then dropzeros!. */
+int32_t cdh_quad_pass(cdh_quad q, int64_t j, int64_t n, const int64_t *idx1, double *maxH);
+/* coordinateDescent!(x, f, g::ProxL1, options) (coordinate_descent.jl:7-39) for all m problems in one launch and one host
+ * round trip: warm start = initialize! from the iterates the handle holds + one solve each; cold start = zero iterates,
+ * lambda_max_j = max_k |b_jk| / omega_jk, numSteps + 1 <= 64 solves down each problem's own log grid.  stats: m entries
+ * (may be NULL). */
+int32_t cdh_quad_coordinate_descent(cdh_quad q, const cdh_options *opt, cdh_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
