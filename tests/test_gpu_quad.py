@@ -3,7 +3,7 @@ solved by k_quad_solve (csrc/quad_solve.hpp) with one workgroup per problem.
 
 Parity bar, against the oracle's per-coordinate sweep of the same problem: beta within 1e-10, the SAME
 passes, full passes, visits and convergence flag, and the same support ORDER (nzval2ind), ordered and shuffled.
-A = X'X / n of a Gaussian X with n = 2p + 2 rows: positive diagonal, well conditioned."""
+A = X'X / n of a Gaussian X with n = 2p + 2 rows: positive diagonal, well conditioned (tests/_quad_cases.py)."""
 import ctypes as C
 import functools
 
@@ -12,38 +12,12 @@ import pytest
 
 import coordinatedescent_jl_amd as cd
 import oracle as O
+from _quad_cases import BETA_TOL, _A, _b, _same
 
 pytestmark = pytest.mark.gpu
 
-BETA_TOL = 1e-10
 PMAX = cd.CDH_QUAD_MAX_P
 OPT = dict(maxIter=20000, optTol=1e-12)
-
-
-@functools.lru_cache(maxsize=None)
-def _A(p, seed=0):
-    rng = np.random.default_rng(1000 * seed + p)
-    X = rng.standard_normal((2 * p + 2, p))
-    A = X.T @ X / X.shape[0]
-    A = (A + A.T) / 2
-    A.setflags(write=False)
-    return A
-
-
-def _b(p, seed, s=None):
-    """b = -(A beta* + noise): the covariance form of a regression on s planted coordinates."""
-    rng = np.random.default_rng(7 + seed)
-    s = min(p, 8) if s is None else s
-    bstar = np.zeros(p)
-    bstar[rng.choice(p, size=s, replace=False)] = rng.standard_normal(s) * 2
-    return -(_A(p) @ bstar + 0.1 * rng.standard_normal(p))
-
-
-def _same(f_stats, x, st, xo, tag=""):
-    np.testing.assert_allclose(x.dense(), xo.dense(), rtol=0, atol=BETA_TOL, err_msg=str(tag))
-    for key in ("passes", "full_passes", "visits", "converged"):
-        assert f_stats[key] == st[key], (tag, key, f_stats, st)
-    assert x.nzval2ind.tolist() == xo.nzval2ind.tolist(), tag
 
 
 # ---- 1. the reference's known answer (test/coordinate_descent.jl:13-25) ------------------------------------------------------
