@@ -21,6 +21,7 @@
 #include "p2p_exchange.hpp"
 #include "sparse_iterate.hpp"
 #include "resid_state.hpp"
+#include "cache_state.hpp"
 #include "exchange_state.hpp"
 
 using namespace cdk;
@@ -147,12 +148,10 @@ class GraphCache {
 struct GradCache {
     int mode = 1;                   // 0 off, 1 rent-or-buy, 2 from the first full pass (both only where the host-side
                                     // fold is cheaper than reading X), 3 from the first full pass, unconditionally
-    bool valid = false;             // g (with the pending `moved`) describes X'r of the device's current r
-    bool beta_ok = false;           // r == y - X beta_ref up to rounding
+    cdh::CacheState st;             // what is known ABOUT the data below (which copy of g is current, whether g describes r, ...): cache_state.hpp
     int64_t full_seen = 0;          // screened full passes since the data last changed
     int cooldown = 0, backoff = 1;  // after a busy pass: this many full passes run the plain way
-    std::vector<double> g, a, beta_ref;
-    cdh::MoveLedger moved;          // what the coordinates have moved by since g was last folded
+    std::vector<double> g, a;
     std::vector<int32_t> slot;      // coordinate -> Gram column, -1 = not cached
     std::vector<std::vector<double>> G;
     DevBuf<double> d_cross;         // device: ceil(p / 64) records of 64 x 32 cross products
@@ -165,14 +164,12 @@ struct GradCache {
     DevBuf<double> d_g, d_G;
     PinBuf<double> h_g_pin; DevBuf<int32_t> d_slot;
     // whole full passes on the device (gc_pass_device): g lives in d_g between passes and comes back only when host
-    // code asks for it.  g_host_ok / g_dev_ok say which copies are current (at least one always is while `valid`).
-    bool g_host_ok = true, g_dev_ok = false;
+    // code asks for it (st.host_g_current() / st.dev_g_current() say which copies are current).
     DevBuf<double> d_a, d_g_snap, d_beta_snap, d_qs;
     DevBuf<int64_t> d_pass_idx;           // the pass's visit list (0-based), as uploaded last
     std::vector<int64_t> pass_idx_host;   // ... and what it holds
     DevBuf<int32_t> d_pos_of; int32_t* d_upos = nullptr;
     DevBuf<uint8_t> d_setflag; uint8_t* d_forced = nullptr;   // (d_forced: the second half of d_setflag's allocation)
-    bool forced_dirty = false;
     int64_t n_forced_rounds = 0, n_cs_forced_rounds = 0, n_cs_crew_passes = 0, n_cs_crew_jobs = 0;
     // the scan's counters sit at the head of the buffer of unsettled positions (one copy brings both back); the results of
     // a pass come back through k_cov_pack's block
@@ -181,18 +178,11 @@ struct GradCache {
     cdk::CovScanOut* h_scan = nullptr;    // = h_scanbuf
     int32_t* h_upos = nullptr;            // = h_scanbuf + 4
     DevBuf<double> d_pack; PinBuf<double> h_pack;           // kPackHead + 2.5 cap doubles
-    bool a_dev_ok = false;                // d_a mirrors c.a
-    double yy = 0.0;                      // y'y over all shards (fp32 certificate margin), valid while yy_ok
-    bool yy_ok = false;
     int64_t n_dev_passes = 0;
     int inject_count = 0;           // device passes so far, for Knobs::gc_inject_rollback (tests)
     int64_t dev_slots_cap = 0, dev_slots = 0;   // columns the device store can hold / holds
     std::vector<DevBuf<double>> d_G_retired;    // stores outgrown on the way (freed with the handle)
-    int64_t cov_since_ref = 0;      // covariance-form visits since g was last taken from X itself (re-read after Knobs::gc_refresh)
     std::vector<double> g_new;      // g as a covariance-form chunk left it, until the chunk is accepted
-    double q = 0.0;                 // r'r of the (virtual) residual g describes: sqrt-lasso thresholds and updates
-    double q_exact = 0.0;           // ... as last summed from r itself (the carried value is refreshed once it has fallen far below it)
-    bool q_valid = false;
     int64_t n_rollbacks = 0;
     double drift_last = 0.0, drift_max = 0.0;   // max_k |g_carried - X'r| / thr_k at the re-references so far
     int64_t n_drift = 0;
@@ -202,7 +192,7 @@ struct GradCache {
     bool cs_enabled = true;          // Knobs::cov_solve, cdh_set_device_loop
     bool cs_big = false;             // a visit list has outgrown the loop's LDS block on this handle: launches use the instantiation with the table and the helpers
     int cs_helpers = 31;             // helper workgroups a launch that expects large visit lists brings (Knobs::cs_crew, cdh_set_device_loop; 0: none)
-    bool cs_shuffle_ok = true, cs_stalled = false;
+    bool cs_shuffle_ok = true;
     size_t cs_lds_budget = 0;
     DevBuf<char> cs_dev; PinBuf<char> cs_pin; char* cs_pin_dev = nullptr;
     CovSolveBufs cs_bufs{};
@@ -210,13 +200,9 @@ struct GradCache {
     int32_t *cs_in_sup = nullptr, *cs_out_sup_idx = nullptr, *cs_out_moved_idx = nullptr, *cs_out_list = nullptr;
     double *cs_out_sup_val = nullptr, *cs_out_moved_val = nullptr, *d_colmax = nullptr;
     int64_t colmax_slots = 0;        // columns of the device store already folded into d_colmax
-    bool slot_dev_ok = false;        // d_slot mirrors `slot`
     std::vector<double> cs_old;      // scratch: the iterate's values before a launch, by coordinate (zero between launches)
-    int prep_state = 0;              // gc_prepare_full has run for the pass about to be walked: 1 go, 2 no-go (0: not yet)
-    double prep_cert_abs = 0.0;
     int64_t n_cs_launches = 0, n_cs_passes = 0, n_cs_folds = 0, n_cs_exact = 0, n_cs_table_passes = 0, n_cs_table_rows = 0;
-    int32_t cs_ncid = 0, cs_tepoch = 0;      // the kernel's Gram table: coordinates it holds, the epoch of its carried gradients
-    bool cs_table_reset = true;
+    int32_t cs_tepoch = 0;           // the kernel's Gram table: the epoch of its carried gradients
     int64_t cs_ticks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -643,51 +629,21 @@ inline bool gc_applicable(const cdh_handle_s* h) {
 // g no longer describes r (y or the loss changed); with `columns` the Gram columns are gone too (X changed)
 void gc_invalidate(cdh_handle h, bool columns) {
     GradCache& c = h->gc;
-    c.valid = false; c.beta_ok = false; c.q_valid = false;
-    c.g_host_ok = true; c.g_dev_ok = false;      // whatever g held is void; the next reference pass fills the host copy
-    c.moved.clear();
+    c.st.invalidated(columns);
     if (columns) {
-        c.a_dev_ok = false;
         c.G.clear(); c.G.shrink_to_fit();
-        std::fill(c.slot.begin(), c.slot.end(), -1);
-        c.slot_dev_ok = false;           // d_slot still names the old columns until the next upload (cov_solve.hpp reads it)
+        std::fill(c.slot.begin(), c.slot.end(), -1);     // (d_slot still names the old columns until the next upload)
         c.colmax_slots = 0;
-        c.cs_table_reset = true;         // ... and so does the device loop's Gram table
         c.dev_slots = 0;                 // the device store is refilled from slot 0 (its memory is kept)
         c.full_seen = 0;
     }
 }
-// r was just set to y - X * (the handle's iterate) by a kernel: beta_ref follows; what changed against the
-// previous reference becomes pending moves (a warm start from another x is a move like any other)
-void gc_after_rebuild(cdh_handle h, const cdh::SupportList& x) {
-    GradCache& c = h->gc;
-    if (c.beta_ref.empty()) return;   // cache never sized (not applicable so far)
-    if (c.valid && !c.beta_ok) gc_invalidate(h, false);
-    std::vector<double> nb((size_t)h->p, 0.0);
-    for (int64_t s_ = 0; s_ < x.nnz(); ++s_) nb[(size_t)x.coord(s_)] = x.slot_value(s_);
-    if (c.valid) {
-        for (int64_t k = 0; k < h->p; ++k) {
-            const double d = nb[(size_t)k] - c.beta_ref[(size_t)k];
-            if (d != 0.0) c.moved.add(k, d);
-        }
-    }
-    c.beta_ref.swap(nb);
-    c.beta_ok = true;
-    c.q_valid = false;
-}
+// r was just set to y - X * (the handle's iterate) by a kernel
+void gc_after_rebuild(cdh_handle h, const cdh::SupportList& x) { h->gc.st.rebuilt(x, h->p); }
 // the streamed visits of a chunk have updated r: g learns of them at the next fold
 void gc_note_moves(cdh_handle h, const int64_t* idx0, int m) {
-    GradCache& c = h->gc;
-    if (!c.valid && !c.beta_ok) return;
-    for (int i = 0; i < m; ++i) {
-        const double hv = h->h_hs[i];
-        if (hv == 0.0) continue;
-        if (hv != hv) { gc_invalidate(h, false); return; }   // a NaN step: nothing is known about r any more
-        const int64_t k = idx0[i];
-        if (c.beta_ok) c.beta_ref[(size_t)k] += hv;
-        c.q_valid = false;            // a streamed visit has changed r
-        if (c.valid) c.moved.add(k, hv);
-    }
+    for (int i = 0; i < m; ++i)
+        if (h->h_hs[i] != 0.0 && !h->gc.st.moved(idx0[i], h->h_hs[i], cdh::MoveKind::streamed)) return;
 }
 
 // ---- initialize!: upload support, r = y - X beta ------------------------------------
@@ -1112,7 +1068,7 @@ int32_t solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched, cd
         double maxH = 0.0;
         if (!visit.empty()) CHK(run_pass(h, visit.data(), (int64_t)visit.size(), &maxH, full));
         else h->x.dropzeros();
-        h->gc.prep_state = 0;
+        h->gc.st.unprepared();
         st->passes += 1; st->visits += (int64_t)visit.size(); st->maxH = maxH;
         if (full) st->full_passes += 1;
         prev_converged = converged;
@@ -1350,7 +1306,7 @@ int32_t cdh_set_y(cdh_handle h, const void* host_y) { return guarded(h, [&]() ->
     NEED_P(h, host_y);
     h->rs.overwritten_with_y();        // r = copy(y) below
     gc_invalidate(h, false);
-    h->gc.yy_ok = false;
+    h->gc.st.yy_void();
     h->small.c_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(h->y, host_y, (size_t)h->n * h->esz, hipMemcpyHostToDevice, h->stream));
@@ -1418,7 +1374,7 @@ int32_t cdh_generate(cdh_handle h, uint64_t seed, int64_t s, double noise, doubl
     if (s < 0 || s > h->p) return fail(h, CDH_BAD_ARG, "need 0 <= s <= p");
     h->rs.regenerated();
     gc_invalidate(h, true);
-    h->gc.yy_ok = false;
+    h->gc.st.yy_void();
     small_invalidate(h);
     HIPCHK(h, hipSetDevice(h->device));
     // planted coefficients: beta*_j = z_j (1 + u_j) (benchmark/cd_bench.jl:14), stream 2
@@ -1568,7 +1524,7 @@ int32_t cdh_pass(cdh_handle h, int64_t m, const int64_t* idx1, double* out_maxH)
         idx0[(size_t)i] = idx1[i] - 1;
     }
     double maxH = 0.0;
-    h->gc.prep_state = 0;
+    h->gc.st.unprepared();
     if (m > 0) CHK(run_pass(h, idx0.data(), m, &maxH, h->screening >= 2));
     else h->x.dropzeros();
     if (out_maxH) *out_maxH = maxH;
@@ -2122,7 +2078,7 @@ int32_t cdh_get_gradient_cache(cdh_handle h, int32_t* out_mode) { return guarded
 int32_t cdh_cache_drift(cdh_handle h, int32_t rereference_now, double* out3) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out3);
     GradCache& c = h->gc;
-    if (rereference_now && c.valid && gc_applicable(h)) {
+    if (rereference_now && c.st.valid() && gc_applicable(h)) {
         HIPCHK(h, hipSetDevice(h->device));
         CHK(gc_rereference(h));
     }
@@ -2170,7 +2126,7 @@ int32_t cdh_device_loop_stats(cdh_handle h, int64_t* out12) { return guarded(h, 
 
 int32_t cdh_device_loop_table(cdh_handle h, int64_t* out6 /* eight values by now */) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out6);
-    out6[0] = h->gc.n_cs_table_passes; out6[1] = h->gc.n_cs_table_rows; out6[2] = h->gc.cs_table_reset ? 0 : h->gc.cs_ncid; out6[3] = kCsTableCap;
+    out6[0] = h->gc.n_cs_table_passes; out6[1] = h->gc.n_cs_table_rows; out6[2] = h->gc.st.table_entries(); out6[3] = kCsTableCap;
     out6[4] = h->gc.n_forced_rounds; out6[5] = h->gc.n_cs_forced_rounds; out6[6] = h->gc.n_cs_crew_passes; out6[7] = h->gc.n_cs_crew_jobs;
     return CDH_OK;
 }); }

@@ -1294,7 +1294,7 @@ int32_t cs_alloc(cdh_handle h) {
     HIPCHK(h, hipMemsetAsync(b.forced, 0, p, h->stream));
     c.cs_dev = std::move(dev); c.cs_pin = std::move(pin); c.cs_pin_dev = pin_dev;   // all there: the handle takes the group
     c.cs_bufs = b; c.d_colmax = colmax;
-    c.cs_ncid = 0; c.cs_table_reset = true;
+    c.st.table_allocated();
     c.cs_ctl = (CovSolveCtl*)c.cs_pin;
     c.cs_in_sup = reinterpret_cast<int32_t*>(c.cs_pin + o_in);
     c.cs_out_sup_idx = reinterpret_cast<int32_t*>(c.cs_pin + o_si); c.cs_out_moved_idx = reinterpret_cast<int32_t*>(c.cs_pin + o_mi);
@@ -1334,7 +1334,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
                   int64_t* iter, int* outcome) {
     GradCache& c = h->gc;
     *outcome = kCsNotNow;
-    c.prep_state = 0;
+    c.st.unprepared();
     if (!c.cs_enabled || !c.cov || !gc_applicable(h) || c.mode == 0 || h->p < kScreenMinPass || h->p > ((int64_t)1 << 26)) return CDH_OK;
     if (o->randomize && h->p > kCsShuffleMaxP) return CDH_OK;
     const bool full = *conv;
@@ -1344,20 +1344,20 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
         if (!h->screening || h->x.nnz() * 4 > h->p) return CDH_OK;
         bool go = false;
         CHK(gc_prepare_full(h, &go, &cert_abs, false));             // the moves still pending on g go into the kernel with it
-        c.prep_state = go ? 1 : 2; c.prep_cert_abs = cert_abs;      // gc_full_pass, if it comes to that, does not prepare twice
+        c.st.prepared(go, cert_abs);                                // gc_full_pass, if it comes to that, does not prepare twice
         if (!go) { gc_fold(h); return CDH_OK; }
     } else {
-        if (!c.valid || !c.d_G) return CDH_OK;
+        if (!c.st.valid() || !c.d_G) return CDH_OK;
         if (gc_support_outgrown(h)) { gc_invalidate(h, false); return CDH_OK; }
-        if (c.cov_since_ref > h->knobs.gc_refresh) CHK(gc_rereference(h));
-        for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) return CDH_OK;
+        if (c.st.cov_since_ref() > h->knobs.gc_refresh) CHK(gc_rereference(h));
+        for (int64_t j : c.st.moved()) if (c.slot[(size_t)j] < 0) return CDH_OK;
         gc_q_guard(h);
         if (h->loss == CDH_SQRT) CHK(gc_ensure_q(h));
         CHK(gc_cert_abs(h, &cert_abs));
     }
     // (from here on a "not now" hands the pass to the round-3 code, which expects the pending moves folded into g)
     auto not_now = [&]() -> int32_t { gc_fold(h); return CDH_OK; };
-    if (!c.d_G || !c.d_scan || c.dev_slots != (int64_t)c.G.size() || (int64_t)c.moved.size() > h->p) return not_now();
+    if (!c.d_G || !c.d_scan || c.dev_slots != (int64_t)c.G.size() || (int64_t)c.st.moved().size() > h->p) return not_now();
     for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) if (c.slot[(size_t)h->x.coord(s_)] < 0) return not_now();
     if (h->x.nnz() > gc_max_support(h)) return not_now();
     // The LDS of workgroup 0 holds the Gram block of ~170 tracked coordinates (ucap); longer visit lists run from the Gram table
@@ -1378,26 +1378,26 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     const int nhelp = (c.cs_helpers > 0 && h->x.nnz() + lds_margin / 2 > ucap_lists - lds_margin) ? std::min(c.cs_helpers, kCsCrewMax) : 0;
     const int32_t full_cap = nhelp > 0 ? 0x7fffffff : ucap_lists - lds_margin;
     if (full && h->x.nnz() > full_cap) return not_now();
-    if (c.cs_table_reset) {          // a new X: the table's entries are void
+    if (c.st.table_void()) {         // a new X: the table's entries are void
         HIPCHK(h, hipMemsetAsync(c.cs_bufs.cidof, 0xff, sizeof(int32_t) * (size_t)h->p, h->stream));
-        c.cs_ncid = 0; c.cs_table_reset = false;
+        c.st.table_reset_done();
     }
     // a fold is p x (pending moves) gathers: beyond a few moves the chip does it (gc_fold's kernel), not the one workgroup of the loop
     const int32_t fold_limit = (int32_t)std::max<int64_t>(16, 120000 / h->p);
-    if ((int64_t)c.moved.size() > fold_limit) gc_fold(h);
-    if (!c.slot_dev_ok) {             // the columns were dropped since the map last went down (a new X): the kernel asks d_slot who has one
+    if ((int64_t)c.st.moved().size() > fold_limit) gc_fold(h);
+    if (!c.st.dev_slot_current()) {           // the columns were dropped since the map last went down (a new X): the kernel asks d_slot who has one
         HIPCHK(h, hipMemcpyAsync(c.d_slot, c.slot.data(), sizeof(int32_t) * (size_t)h->p, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        c.slot_dev_ok = true;
+        c.st.dev_slot_uploaded();
     }
     CHK(cs_update_colmax(h));
     CHK(gc_need_dev_g(h));
-    c.prep_state = 0;                                               // from here on the state moves: a later pass prepares afresh
+    c.st.unprepared();                                              // from here on the state moves: a later pass prepares afresh
 
     CovSolveCtl& ctl = *c.cs_ctl;
     ctl.lambda0 = h->ctrl.lambda0; ctl.n_total = (double)h->n_total; ctl.optTol = o->optTol; ctl.cert_abs = cert_abs;
     ctl.max_passes = o->maxIter - *iter;
-    ctl.cov_budget = std::max<int64_t>(0, h->knobs.gc_refresh - c.cov_since_ref);
+    ctl.cov_budget = std::max<int64_t>(0, h->knobs.gc_refresh - c.st.cov_since_ref());
     ctl.loss = h->loss; ctl.has_omega = h->has_omega ? 1 : 0; ctl.randomize = o->randomize ? 1 : 0;
     {
         int64_t lim = gc_max_support(h);
@@ -1405,12 +1405,13 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
         ctl.nnz_limit = (int32_t)std::min<int64_t>({lim, support_cap, (int64_t)0x7fffffff});
     }
     ctl.busy_limit = kGcBusy; ctl.inject_every = h->knobs.gc_inject_rollback; ctl.fold_limit = fold_limit;
-    ctl.tcap = kCsTableCap; ctl.ncid = c.cs_ncid; ctl.tepoch = c.cs_tepoch; ctl.full_cap = full_cap; ctl.ucap_limit = ucap_limit;
-    ctl.rng = sched.state(); ctl.q = c.q; ctl.q_floor = h->loss == CDH_SQRT ? kGcQGuard * c.q_exact : 0.0;
+    ctl.tcap = kCsTableCap; ctl.ncid = c.st.table_entries(); ctl.tepoch = c.cs_tepoch; ctl.full_cap = full_cap; ctl.ucap_limit = ucap_limit;
+    ctl.rng = sched.state(); ctl.q = c.st.q(); ctl.q_floor = h->loss == CDH_SQRT ? kGcQGuard * c.st.q_exact() : 0.0;
     ctl.nnz = (int32_t)h->x.nnz(); ctl.prev_conv = *prev_conv ? 1 : 0; ctl.conv = *conv ? 1 : 0; ctl.inject_count = c.inject_count;
     ctl.status = -1; ctl.n_list = 0;
-    ctl.n_moved = (int32_t)c.moved.size();      // in: the moves still pending on g (out: those pending when the kernel stops)
-    for (size_t m = 0; m < c.moved.size(); ++m) { c.cs_out_moved_idx[m] = (int32_t)c.moved[m]; c.cs_out_moved_val[m] = c.moved.value(c.moved[m]); }
+    const cdh::MoveLedger& moved = c.st.moved();
+    ctl.n_moved = (int32_t)moved.size();        // in: the moves still pending on g (out: those pending when the kernel stops)
+    for (size_t m = 0; m < moved.size(); ++m) { c.cs_out_moved_idx[m] = (int32_t)moved[m]; c.cs_out_moved_val[m] = moved.value(moved[m]); }
     for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) c.cs_in_sup[s_] = (int32_t)h->x.coord(s_);
     CovSolveBufs b = c.cs_bufs;
     b.g = c.d_g; b.Gcols = c.d_G; b.slot = c.d_slot; b.a = c.d_a; b.omega = h->omega; b.beta = h->beta;
@@ -1435,7 +1436,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     const int64_t nnz_old = h->x.nnz();
     std::vector<int64_t> old_idx((size_t)nnz_old);
     for (int64_t s_ = 0; s_ < nnz_old; ++s_) { old_idx[(size_t)s_] = h->x.coord(s_); c.cs_old[(size_t)h->x.coord(s_)] = h->x.slot_value(s_); }
-    auto note_move = [&](int64_t k, double d) { if (d != 0.0) note_move_off_stream(h, k, d, true); };
+    auto note_move = [&](int64_t k, double d) { if (d != 0.0) note_move_off_stream(h, k, d, cdh::MoveKind::carried, true); };
     h->x.clear();
     for (int32_t s_ = 0; s_ < ctl.nnz; ++s_) {
         const int64_t k = c.cs_out_sup_idx[s_];
@@ -1447,20 +1448,14 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     }
     for (int64_t k : old_idx) { if (c.cs_old[(size_t)k] != 0.0) note_move(k, -c.cs_old[(size_t)k]); c.cs_old[(size_t)k] = 0.0; }
     // ---- the cache: moves still pending on g, r'r, the counters ----
-    c.moved.clear();                 // what went in is in the kernel's list (or folded)
-    for (int32_t m = 0; m < ctl.n_moved; ++m) {
-        const int64_t k = c.cs_out_moved_idx[m];
-        const double v = c.cs_out_moved_val[m];
-        if (v != 0.0) c.moved.set(k, v);
-    }
-    c.cs_ncid = ctl.ncid; c.cs_tepoch = ctl.tepoch; c.n_cs_table_passes += ctl.table_passes; c.n_cs_table_rows += ctl.table_rows;
+    c.st.pending_replaced(c.cs_out_moved_idx, c.cs_out_moved_val, ctl.n_moved);   // what went in is in the kernel's list (or folded)
+    c.st.table_holds(ctl.ncid); c.cs_tepoch = ctl.tepoch; c.n_cs_table_passes += ctl.table_passes; c.n_cs_table_rows += ctl.table_rows;
     c.n_cs_forced_rounds += ctl.forced_rounds; c.n_cs_crew_passes += ctl.crew_passes; c.n_cs_crew_jobs += ctl.crew_jobs;
-    if (ctl.crew_passes > 0) c.g_host_ok = false;       // the helpers have moved d_g along
-    if (ctl.folds > 0) c.g_host_ok = false;
-    if (h->loss == CDH_SQRT) c.q = ctl.q;
+    if (ctl.crew_passes > 0 || ctl.folds > 0) c.st.dev_g_moved_on();   // the helpers, or a fold in the loop
+    if (h->loss == CDH_SQRT) c.st.q_carried(ctl.q);
     c.inject_count = ctl.inject_count;
     c.n_passes += ctl.full_passes; c.n_dev_passes += ctl.full_passes; c.n_certified += ctl.settled;
-    c.n_cov += ctl.cov_visits; c.cov_since_ref += ctl.cov_visits; c.n_cs_passes += ctl.passes; c.n_cs_folds += ctl.folds; c.n_cs_exact += ctl.exact_rechecks;
+    c.n_cov += ctl.cov_visits; c.st.cov_visited(ctl.cov_visits); c.n_cs_passes += ctl.passes; c.n_cs_folds += ctl.folds; c.n_cs_exact += ctl.exact_rechecks;
     for (int i = 0; i < 8; ++i) c.cs_ticks[i] += ctl.ticks[i];
     c.n_exact += ctl.cov_visits_full;
     if (ctl.domain_error) h->domain_error = true;
@@ -1475,7 +1470,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     case kCsRollback: c.n_rollbacks += 1; return CDH_OK;            // the host walks this pass the careful way
     case kCsOutgrown: return CDH_OK;                                // gc_prepare_full / gc_ready_for_cov draw the consequences
     case kCsRefresh: CHK(gc_rereference(h)); *outcome = kCsAgain; return CDH_OK;
-    case kCsNeedQ: c.q_valid = false; CHK(gc_ensure_q(h)); *outcome = kCsAgain; return CDH_OK;
+    case kCsNeedQ: c.st.q_void(); CHK(gc_ensure_q(h)); *outcome = kCsAgain; return CDH_OK;
     case kCsNeedFold: gc_fold(h); *outcome = kCsAgain; return CDH_OK;
     case kCsCrewLost: return fail(h, CDH_HIP_ERROR, "the device-resident solve lost its helper workgroups (a wait ran into its 20 s bound)");
     case kCsNeedBig:                                                // a visit list has outgrown the LDS block: the instantiation that knows what to do
@@ -1484,16 +1479,15 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     case kCsHostFull: return CDH_OK;                                // the next (full) pass runs the pass-by-pass way
     case kCsBusy:     // many inactive coordinates about to move: back off, as gc_pass_device does
         gc_back_off(h);
-        c.prep_state = 2;
+        c.st.prepared_no_go();
         return CDH_OK;
     case kCsNeedColumns: {
-        if (ctl.passes == 0 && c.cs_stalled) { c.cs_stalled = false; return CDH_OK; }   // (twice in a row without progress: the old way)
-        c.cs_stalled = ctl.passes == 0;
+        if (c.st.stalled_twice(ctl.passes == 0)) return CDH_OK;     // (twice in a row without progress: the old way)
         c.backoff = 1;
         std::vector<int64_t> enter(c.cs_out_list, c.cs_out_list + ctl.n_list);
         CHK(gc_check_moved_columns(h));
         gc_fold(h);
-        if (!c.valid) return CDH_OK;
+        if (!c.st.valid()) return CDH_OK;
         CHK(gc_need_host_g(h));
         GcThresholds T(h, cert_abs);
         CHK(T.sync_rnorm());

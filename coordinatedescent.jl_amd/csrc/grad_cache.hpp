@@ -53,11 +53,8 @@ int32_t gc_size(cdh_handle h) {   // first use on this handle
     c.d_cross = std::move(cross); c.d_cross_part = std::move(cross_part); c.d_cols = std::move(cols);
     c.h_cross.assign((size_t)launches * kCrossRec, 0.0);
     const size_t p = (size_t)h->p;
-    c.g.assign(p, 0.0); c.a.assign(p, 0.0); c.moved.resize(h->p);
-    c.slot.assign(p, -1); c.beta_ref.assign(p, 0.0);
-    c.beta_ok = h->rs.consistent();         // r == y - X * (the handle's iterate) right now?
-    if (c.beta_ok)
-        for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) c.beta_ref[(size_t)h->x.coord(s_)] = h->x.slot_value(s_);
+    c.g.assign(p, 0.0); c.a.assign(p, 0.0); c.slot.assign(p, -1);
+    c.st.size(h->p, h->rs.consistent(), h->x);         // r == y - X * (the handle's iterate) right now?
     return CDH_OK;
 }
 
@@ -102,8 +99,8 @@ int32_t gc_dev_reserve(cdh_handle h, int64_t have) {
         c.d_setflag = std::move(setflag); c.d_pack = std::move(pack); c.h_scanbuf = std::move(h_scanbuf); c.h_pack = std::move(h_pack);
         c.d_scan = (cdk::CovScanOut*)c.d_scanbuf; c.d_upos = c.d_scanbuf + 4;
         c.h_scan = (cdk::CovScanOut*)c.h_scanbuf; c.h_upos = c.h_scanbuf + 4;
-        c.d_forced = c.d_setflag + p; c.forced_dirty = false;
-        c.g_dev_ok = false; c.a_dev_ok = false;
+        c.d_forced = c.d_setflag + p;
+        c.st.mirrors_allocated();
     }
     if (have > c.dev_slots_cap) {   // grow the store (at least 64 columns more, doubling once it holds 128: a path that ends at 800 columns
                                     // reallocates 5 times, not 14 -- each is an allocation, a copy and a free, milliseconds apiece on a
@@ -137,7 +134,7 @@ int32_t gc_dev_upload(cdh_handle h) {
     c.dev_slots = have;
     HIPCHK(h, hipMemcpyAsync(c.d_slot, c.slot.data(), sizeof(int32_t) * (size_t)p, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    c.slot_dev_ok = true;
+    c.st.dev_slot_uploaded();
     return CDH_OK;
 }
 
@@ -159,27 +156,27 @@ int32_t gc_host_column(cdh_handle h, int64_t s_) {
 // fetch, a re-reference's drift measurement) asks for it first.  The other direction likewise.
 int32_t gc_need_host_g(cdh_handle h) {
     GradCache& c = h->gc;
-    if (c.g_host_ok) return CDH_OK;
+    if (c.st.host_g_current()) return CDH_OK;
     HIPCHK(h, hipMemcpyAsync(c.h_g_pin, c.d_g, sizeof(double) * (size_t)h->p, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::memcpy(c.g.data(), c.h_g_pin, sizeof(double) * (size_t)h->p);
-    c.g_host_ok = true;
+    c.st.host_g_fetched();
     return CDH_OK;
 }
 int32_t gc_need_dev_g(cdh_handle h) {
     GradCache& c = h->gc;
-    if (!c.a_dev_ok) {
+    if (!c.st.dev_a_current()) {
         HIPCHK(h, hipStreamSynchronize(h->stream));                 // h_g_pin's second half doubles as staging for a
         std::memcpy(c.h_g_pin + h->p, c.a.data(), sizeof(double) * (size_t)h->p);
         HIPCHK(h, hipMemcpyAsync(c.d_a, c.h_g_pin + h->p, sizeof(double) * (size_t)h->p, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        c.a_dev_ok = true;
+        c.st.dev_a_uploaded();
     }
-    if (c.g_dev_ok) return CDH_OK;
+    if (c.st.dev_g_current()) return CDH_OK;
     std::memcpy(c.h_g_pin, c.g.data(), sizeof(double) * (size_t)h->p);
     HIPCHK(h, hipMemcpyAsync(c.d_g, c.h_g_pin, sizeof(double) * (size_t)h->p, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));                     // the staging buffer is free again
-    c.g_dev_ok = true;
+    c.st.dev_g_uploaded();
     return CDH_OK;
 }
 
@@ -194,19 +191,18 @@ int32_t gc_cert_abs(cdh_handle h, double* out) {
     GradCache& c = h->gc;
     *out = 0.0;
     if (h->dtype != CDH_F32) return CDH_OK;
-    if (!c.yy_ok) {
+    if (!c.st.yy_current()) {
         CHK(resid_moments_dev(h, h->y));
         HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        c.yy = h->h_red[1];
-        c.yy_ok = true;
+        c.st.yy_summed(h->h_red[1]);
     }
     // ... plus (round 4) what the Gram entries themselves carry: k_cross takes fp32 storage on the fp32 matrix pipe, 256-row
     // partial sums in fp32 folded into fp64 tiles, so an entry is good to eps_G sqrt(a_i a_j) with eps_G ~ 2^-24 * 128 / sqrt(n)
     // for fully correlated columns (measured: tests/test_gpu_parity.py::test_fp32_gram_columns_carry_the_declared_error); a
     // carried gradient updated with them is off by at most eps_G sqrt(a_k) sum_j |dbeta_j| sqrt(a_j) <~ eps_G sqrt(a_k y'y).
     // Declared with a factor 4: 2^-24 * 512 / sqrt(n) -- eight times the residual's own term at U = 0.
-    *out = 5.9604644775390625e-8 * std::sqrt(c.yy / (double)h->n_total) * (64.0 * std::sqrt((double)(h->rs.roundings() + 1)) + kCrossF32EpsFactor);
+    *out = 5.9604644775390625e-8 * std::sqrt(c.st.yy() / (double)h->n_total) * (64.0 * std::sqrt((double)(h->rs.roundings() + 1)) + kCrossF32EpsFactor);
     return CDH_OK;
 }
 
@@ -214,8 +210,8 @@ int32_t gc_cert_abs(cdh_handle h, double* out) {
 // fold, and a Gram column on the device for every coordinate of the chunk.
 bool cov_ok(cdh_handle h, const int64_t* idx0, int64_t m) {
     const GradCache& c = h->gc;
-    if (!c.cov || !c.valid || !c.moved.empty() || !gc_applicable(h) || !c.d_G) return false;
-    if (h->loss == CDH_SQRT && !c.q_valid) return false;
+    if (!c.cov || !c.st.valid() || !c.st.moved().empty() || !gc_applicable(h) || !c.d_G) return false;
+    if (h->loss == CDH_SQRT && !c.st.q_usable()) return false;
     if (c.dev_slots != (int64_t)c.G.size()) return false;
     for (int64_t i = 0; i < m; ++i) if (c.slot[(size_t)idx0[i]] < 0) return false;
     return true;
@@ -226,13 +222,11 @@ bool cov_ok(cdh_handle h, const int64_t* idx0, int64_t m) {
 // a rebuild or a re-reference has changed r behind its back
 int32_t gc_ensure_q(cdh_handle h) {
     GradCache& c = h->gc;
-    if (c.q_valid) return CDH_OK;
+    if (c.st.q_usable()) return CDH_OK;
     CHK(resid_moments_dev(h));
     HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    c.q = h->h_red[1];
-    c.q_exact = c.q;
-    c.q_valid = true;
+    c.st.q_summed(h->h_red[1]);
     return CDH_OK;
 }
 // The carried r'r is only good to ~1e-16 of the value its recurrence started from (q <- q - 2 h b + h^2 a, block after block,
@@ -240,21 +234,20 @@ int32_t gc_ensure_q(cdh_handle h) {
 // next pass (one pass over r, after it has caught up with the moves) -- near-noiseless problems, ||r|| << ||y||.
 constexpr double kGcQGuard = 1e-4;
 inline void gc_q_guard(cdh_handle h) {
-    GradCache& c = h->gc;
-    if (h->loss == CDH_SQRT && c.q_valid && c.q < kGcQGuard * c.q_exact) c.q_valid = false;
+    if (h->loss == CDH_SQRT) h->gc.st.q_guard(kGcQGuard);
 }
 
 // fold what can be folded, then ask cov_ok (the active passes of a solve call this before every chunk)
 int32_t gc_rereference(cdh_handle h);
 bool gc_ready_for_cov(cdh_handle h, const int64_t* idx0, int64_t m) {
     GradCache& c = h->gc;
-    if (!c.cov || !c.valid || !gc_applicable(h) || !c.d_G) return false;
+    if (!c.cov || !c.st.valid() || !gc_applicable(h) || !c.d_G) return false;
     // the same bounds the full passes keep (gc_full_pass): the cache only pays on tall problems, and g is carried
     // through a bounded number of covariance-form updates before it is taken afresh from X
     if (gc_support_outgrown(h)) { gc_invalidate(h, false); return false; }
-    if (c.cov_since_ref > h->knobs.gc_refresh && gc_rereference(h) != CDH_OK) return false;
-    if (!c.moved.empty()) {
-        for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) return false;
+    if (c.st.cov_since_ref() > h->knobs.gc_refresh && gc_rereference(h) != CDH_OK) return false;
+    if (!c.st.moved().empty()) {
+        for (int64_t j : c.st.moved()) if (c.slot[(size_t)j] < 0) return false;
         gc_fold(h);
     }
     gc_q_guard(h);
@@ -323,7 +316,7 @@ int32_t cov_run(cdh_handle h, const int64_t* idx0, int m, bool want_g) {
     HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, h->stream));
     h->ctrl.maxH = 0.0;
     h->ctrl.domain_error = 0;
-    h->ctrl.q_carry = c.q;
+    h->ctrl.q_carry = c.st.q();
     CHK(upload_ctrl(h));
     CHK(launch_cov_blocks(h, m));
     HIPCHK(h, hipGetLastError());
@@ -333,15 +326,15 @@ int32_t cov_run(cdh_handle h, const int64_t* idx0, int m, bool want_g) {
     }
     CHK(cov_fetch_results(h, m, false));
     if (want_g) std::memcpy(c.g_new.data(), c.h_g_pin + h->p, sizeof(double) * (size_t)h->p);
-    c.g_host_ok = false;              // d_g has moved on; c.g is the gradient BEFORE the chunk until it is accepted
+    c.st.dev_g_moved_on();            // c.g is the gradient BEFORE the chunk until it is accepted
     return CDH_OK;
 }
-// Coordinate k of the iterate moved by d in a kernel that leaves r alone: r owes the move, and a cache whose reference
-// follows the iterate (beta_ok) learns of it.  ref_takes_nan: the reference takes a NaN move as well (the device loop's
-// moves, as they always have); otherwise it skips it.
-inline void note_move_off_stream(cdh_handle h, int64_t k, double d, bool ref_takes_nan) {
+// Coordinate k of the iterate moved by d in a kernel that leaves r alone: r owes the move, and the cache learns of it
+// (CacheState::moved: carried -- g has the move already -- or off_stream).  ref_takes_nan: the reference takes a NaN move
+// as well (the device loop's moves, as they always have); otherwise it skips it.
+inline void note_move_off_stream(cdh_handle h, int64_t k, double d, cdh::MoveKind kind, bool ref_takes_nan) {
     h->rs.moved(k, d);
-    if (h->gc.beta_ok && (ref_takes_nan || d == d)) h->gc.beta_ref[(size_t)k] += d;
+    h->gc.st.moved(k, d, kind, ref_takes_nan);
 }
 // the staged results of visit i become real: SparseIterate writes, the move noted for r, maxH
 void cov_apply_visit(cdh_handle h, int64_t k, int i) {
@@ -349,7 +342,7 @@ void cov_apply_visit(cdh_handle h, int64_t k, int i) {
     h->x.set(k, h->h_newval[i]);
     const double hv = h->h_hs[i];
     if (hv == 0.0) return;
-    note_move_off_stream(h, k, hv, false);
+    note_move_off_stream(h, k, hv, cdh::MoveKind::carried, false);
 }
 // the chunk is accepted: maxH, r'r, the counters; `have_g_new`: c.g_new is the gradient after the chunk
 void cov_accept_tail(cdh_handle h, int m, double* maxH, bool have_g_new) {
@@ -357,10 +350,10 @@ void cov_accept_tail(cdh_handle h, int m, double* maxH, bool have_g_new) {
     const double mh = h->h_ctrl->maxH;
     if (mh > *maxH) *maxH = mh;
     if (h->h_ctrl->domain_error) h->domain_error = true;
-    if (h->loss == CDH_SQRT) c.q = h->h_ctrl->q_carry;
-    if (have_g_new) { c.g.swap(c.g_new); c.g_host_ok = true; }
+    if (h->loss == CDH_SQRT) c.st.q_carried(h->h_ctrl->q_carry);
+    if (have_g_new) { c.g.swap(c.g_new); c.st.host_g_fetched(); }
     c.n_cov += m;
-    c.cov_since_ref += m;
+    c.st.cov_visited(m);
     bool nan = false;
     for (int i = 0; i < m; ++i) nan = nan || (h->h_hs[i] != h->h_hs[i]);
     if (nan) gc_invalidate(h, false);   // r turns NaN at the catch-up, as in the reference; the cache knows nothing any more
@@ -382,13 +375,13 @@ int32_t cov_reject(cdh_handle h, const int64_t* idx0, int m) {
     hipLaunchKernelGGL(k_scatter_f64, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, h->beta, h->d_idx, h->d_hs, m);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    c.g_host_ok = true; c.g_dev_ok = false;
+    c.st.dev_g_rejected();
     return CDH_OK;
 }
 
 // g = X'r and a = diag(X'X) (with observation weights: X'Wr, diag(X'WX)) from one dots-only pass over all of X: the
-// new reference point
-int32_t gc_validate(cdh_handle h) {
+// new reference point.  beta_known: CacheState::referenced
+int32_t gc_validate(cdh_handle h, bool beta_known) {
     GradCache& c = h->gc;
     std::vector<double> cd;
     if (h->rs.can_adopt_dots(h->has_w, h->p)) {
@@ -403,11 +396,8 @@ int32_t gc_validate(cdh_handle h) {
         h->rs.dots_taken(cd, h->has_w);
     }
     for (int64_t k = 0; k < h->p; ++k) { c.g[(size_t)k] = cd[(size_t)(2 * k)]; c.a[(size_t)k] = cd[(size_t)(2 * k + 1)]; }
-    c.moved.clear();
-    c.valid = true;
-    c.g_host_ok = true; c.g_dev_ok = false; c.a_dev_ok = false;
+    c.st.referenced(beta_known);
     c.n_validate += 1;
-    c.cov_since_ref = 0;
     return CDH_OK;
 }
 
@@ -419,16 +409,10 @@ int32_t gc_adopt_dots(cdh_handle h, const std::vector<double>& cd) {
     if (!gc_applicable(h) || c.mode == 0 || (int64_t)cd.size() != 2 * h->p) return CDH_OK;
     CHK(gc_size(h));
     if (c.mode == 0 || c.g.empty()) return CDH_OK;
-    const bool beta_known = c.beta_ok;
-    std::vector<double> beta_keep;
-    if (beta_known) beta_keep = c.beta_ref;
+    const bool beta_known = c.st.beta_known();
     gc_invalidate(h, false);
     for (int64_t k = 0; k < h->p; ++k) { c.g[(size_t)k] = cd[(size_t)(2 * k)]; c.a[(size_t)k] = cd[(size_t)(2 * k + 1)]; }
-    c.valid = true;
-    c.g_host_ok = true; c.g_dev_ok = false; c.a_dev_ok = false;
-    c.cov_since_ref = 0;
-    c.beta_ok = beta_known;
-    if (beta_known) c.beta_ref.swap(beta_keep);
+    c.st.referenced(beta_known);
     return CDH_OK;
 }
 
@@ -438,21 +422,17 @@ int32_t gc_adopt_dots(cdh_handle h, const std::vector<double>& cd) {
 // describe the same residual; what is known about beta is kept (g will describe the same residual, freshly summed).
 int32_t gc_rereference(cdh_handle h) {
     GradCache& c = h->gc;
-    const bool beta_known = c.beta_ok;
-    std::vector<double> beta_keep;
-    if (beta_known) beta_keep = c.beta_ref;
-    bool comparable = c.valid;
+    const bool beta_known = c.st.beta_known();
+    bool comparable = c.st.valid();
     if (comparable)
-        for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) comparable = false;
+        for (int64_t j : c.st.moved()) if (c.slot[(size_t)j] < 0) comparable = false;
     std::vector<double> carried;
     if (comparable) { gc_fold(h); CHK(gc_need_host_g(h)); carried = c.g; }
     gc_invalidate(h, false);
-    CHK(gc_validate(h));
-    c.beta_ok = beta_known;
-    if (beta_known) c.beta_ref.swap(beta_keep);
+    CHK(gc_validate(h, beta_known));
     if (comparable && h->ctrl.lambda0 > 0.0) {
         double scale = h->ctrl.lambda0 * (double)h->n_total;
-        if (h->loss == CDH_SQRT) { CHK(gc_ensure_q(h)); scale = h->ctrl.lambda0 * std::sqrt(c.q); }
+        if (h->loss == CDH_SQRT) { CHK(gc_ensure_q(h)); scale = h->ctrl.lambda0 * std::sqrt(c.st.q()); }
         double worst = 0.0;
         for (int64_t k = 0; k < h->p; ++k) {
             const double thr = scale * (h->has_omega ? h->h_omega[(size_t)k] : 1.0);
@@ -556,10 +536,11 @@ int32_t gc_fetch(cdh_handle h, const std::vector<int64_t>& cols) {
 bool gc_fold_device(cdh_handle h) {
     GradCache& c = h->gc;
     if (!c.cov || !c.d_G || !c.h_g_pin || c.dev_slots != (int64_t)c.G.size()) return false;
-    const int64_t M = (int64_t)c.moved.size();
+    const cdh::MoveLedger& moved = c.st.moved();
+    const int64_t M = (int64_t)moved.size();
     if (M > h->cap) return false;
     if (gc_need_dev_g(h) != CDH_OK) { (void)hipGetLastError(); return false; }
-    for (int64_t i = 0; i < M; ++i) { h->h_idx[i] = c.moved[(size_t)i]; h->h_hs[i] = c.moved.value(c.moved[(size_t)i]); }
+    for (int64_t i = 0; i < M; ++i) { h->h_idx[i] = moved[(size_t)i]; h->h_hs[i] = moved.value(moved[(size_t)i]); }
     bool ok = hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)M, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
               hipMemcpyAsync(h->d_hs, h->h_hs, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, h->stream) == hipSuccess;
     for (int64_t pos0 = 0; ok && pos0 < M; pos0 += 64)
@@ -568,33 +549,33 @@ bool gc_fold_device(cdh_handle h) {
     ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;   // the staging arrays are reused
     if (!ok) {                        // a HIP failure mid-fold: the device copy is void
         (void)hipGetLastError();
-        if (c.g_host_ok) c.g_dev_ok = false;      // c.g (host) is still the unfolded gradient: the host loop folds it
+        if (c.st.host_g_current()) c.st.dev_g_dropped();   // c.g (host) is still the unfolded gradient: the host loop folds it
         else gc_invalidate(h, false);             // no copy left: the next full pass takes g afresh from X
         return false;
     }
-    c.g_host_ok = false;              // g stays where the next pass wants it
+    c.st.dev_g_moved_on();            // g stays where the next pass wants it
     return true;
 }
 
 void gc_fold(cdh_handle h) {
     GradCache& c = h->gc;
-    if (c.moved.empty()) return;
+    if (c.st.moved().empty()) return;
     // (the host copy is needed only for the host-side fallback; when the device folds, it is merely marked stale)
     const bool on_device = gc_fold_device(h);
     if (!on_device) {
-        if (!c.valid) return;                     // invalidated by a failed device fold (moved is already empty)
+        if (!c.st.valid()) return;                // invalidated by a failed device fold (moved is already empty)
         (void)gc_need_host_g(h);
-        c.g_dev_ok = false;
+        c.st.dev_g_dropped();
     }
-    for (int64_t j : c.moved) {
-        const double d = c.moved.value(j);
+    for (int64_t j : c.st.moved()) {
+        const double d = c.st.moved().value(j);
         if (!on_device && d != 0.0) {
             (void)gc_host_column(h, c.slot[(size_t)j]);
             const std::vector<double>& col = c.G[(size_t)c.slot[(size_t)j]];
             for (int64_t k = 0; k < h->p; ++k) c.g[(size_t)k] -= d * col[(size_t)k];
         }
     }
-    c.moved.clear();
+    c.st.folded();
 }
 
 int32_t run_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH);
@@ -607,7 +588,7 @@ struct GcThresholds {
     int32_t sync_rnorm() {
         if (h->loss != CDH_SQRT) return CDH_OK;
         CHK(gc_ensure_q(h));
-        rnorm = std::sqrt(h->gc.q);
+        rnorm = std::sqrt(h->gc.st.q());
         return CDH_OK;
     }
     double thr_of(int64_t k) const {
@@ -639,7 +620,7 @@ void gc_back_off(cdh_handle h) {
 }
 
 int32_t gc_check_moved_columns(cdh_handle h) {
-    for (int64_t j : h->gc.moved)
+    for (int64_t j : h->gc.st.moved())
         if (h->gc.slot[(size_t)j] < 0) return fail(h, CDH_BAD_ARG, "gradient cache: a moved coordinate has no Gram column");
     return CDH_OK;
 }
@@ -681,12 +662,12 @@ enum { kDevDone = 0, kDevPlain = 1, kDevWalk = 2 };
 int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH, const GcThresholds& T, int* outcome) {
     GradCache& c = h->gc;
     *outcome = kDevWalk;
-    if (!c.cov || !c.d_G || !c.d_scan || !c.moved.empty() || c.dev_slots != (int64_t)c.G.size() || m > h->cap) return CDH_OK;
-    if (h->loss == CDH_SQRT && !c.q_valid) return CDH_OK;
+    if (!c.cov || !c.d_G || !c.d_scan || !c.st.moved().empty() || c.dev_slots != (int64_t)c.G.size() || m > h->cap) return CDH_OK;
+    if (h->loss == CDH_SQRT && !c.st.q_usable()) return CDH_OK;
     note_duplicates(h, idx0, (int)m);
     if (h->chunk_dup) return CDH_OK;            // a caller-made list that repeats a coordinate: positions are not unique
     CHK(gc_need_dev_g(h));
-    const bool host_ok_before = c.g_host_ok;
+    const bool host_ok_before = c.st.host_g_current();
     if ((int64_t)c.pass_idx_host.size() != m || std::memcmp(c.pass_idx_host.data(), idx0, sizeof(int64_t) * (size_t)m) != 0) {
         std::memcpy(h->h_idx, idx0, sizeof(int64_t) * (size_t)m);
         HIPCHK(h, hipMemcpyAsync(c.d_pass_idx, h->h_idx, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, h->stream));
@@ -697,7 +678,7 @@ int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* max
         cdh_handle h;
         ~ForcedGuard() {
             GradCache& c = h->gc;
-            if (c.forced_dirty) { (void)hipMemsetAsync(c.d_forced, 0, (size_t)h->p, h->stream); c.forced_dirty = false; }
+            if (c.st.forced_marks_dirty()) { (void)hipMemsetAsync(c.d_forced, 0, (size_t)h->p, h->stream); c.st.forced_marks_wiped(); }
         }
     } forced_guard{h};
     int cnt = 0;
@@ -705,7 +686,7 @@ int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* max
     for (int attempt = 0;; ++attempt) {
         h->ctrl.maxH = 0.0;
         h->ctrl.domain_error = 0;
-        h->ctrl.q_carry = c.q;
+        h->ctrl.q_carry = c.st.q();
         h->ctrl.cert_abs = T.cert_abs;
         CHK(upload_ctrl(h));
         hipLaunchKernelGGL(k_cov_scan, dim3(1), dim3(1024), 0, h->stream, c.d_g, c.d_a, h->beta, h->omega, h->d_ctrl, c.d_pass_idx, (int)m,
@@ -741,21 +722,21 @@ int32_t gc_pass_device(cdh_handle h, const int64_t* idx0, int64_t m, double* max
         // windowed walk that takes over are exercised on every problem of the suite, not only where a certificate breaks)
         const int every = h->knobs.gc_inject_rollback;
         const bool injected = every > 0 && (++c.inject_count % every) == 0;
-        if ((int64_t)c.h_scan->bad_pos < m) c.forced_dirty = true;     // (marks were set: wiped when this function returns)
+        if ((int64_t)c.h_scan->bad_pos < m) c.st.forced_marks_set();    // (marks were set: wiped when this function returns)
         if ((int64_t)c.h_scan->bad_pos < m || injected) {       // a skipped certificate did not survive the pass's own moves: undo
             hipLaunchKernelGGL(k_cov_restore, dim3((unsigned)((h->p + 255) / 256)), dim3(256), 0, h->stream, c.d_g, h->beta, c.d_g_snap,
                                c.d_beta_snap, h->p);
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipStreamSynchronize(h->stream));
-            c.g_host_ok = host_ok_before;           // d_g is the gradient of the pass's start again
+            c.st.dev_g_rolled_back(host_ok_before); // d_g is the gradient of the pass's start again
             // coordinates that crossed their threshold through the pass's own moves (the first full pass after lambda has changed,
             // on large supports: benchmark/cd_bench.jl's shape has them in most full passes beyond ~200 non-zeros): the same pass
             // again with those on the visit list -- a device pass, not the windowed walk
-            if (!injected && round < kMaxForcedRounds) { c.forced_dirty = true; c.n_forced_rounds += 1; continue; }
+            if (!injected && round < kMaxForcedRounds) { c.st.forced_marks_set(); c.n_forced_rounds += 1; continue; }
             c.n_rollbacks += 1;
             return CDH_OK;                          // -> the windowed walk
         }
-        c.g_host_ok = false;
+        c.st.dev_g_moved_on();
     } else {
         *h->h_ctrl = h->ctrl;                       // nothing ran: maxH 0, no domain error, r'r as it was
     }
@@ -785,18 +766,18 @@ int32_t gc_prepare_full(cdh_handle h, bool* go, double* cert_abs_out, bool fold 
     // mode 1 buys the Gram columns of the support (1.5 passes over X per 32 of them) only after the handle has
     // paid that much in plain full passes on the same data: at most twice the cost of having known in advance
     const int64_t rent = std::max<int64_t>(kGcEngage, 1 + (3 * h->x.nnz()) / 64);
-    if (!gc_applicable(h) || (c.mode == 1 && !c.valid && c.full_seen <= rent)) return CDH_OK;
+    if (!gc_applicable(h) || (c.mode == 1 && !c.st.valid() && c.full_seen <= rent)) return CDH_OK;
     // the support has outgrown what the cache pays for (gc_support_outgrown, cdhip.hip: long columns only)
     if (gc_support_outgrown(h)) {
-        if (c.valid) gc_invalidate(h, false);
+        if (c.st.valid()) gc_invalidate(h, false);
         return CDH_OK;
     }
     // g has been carried through this many covariance-form updates without looking at X: it is taken afresh
     // below (rounding only ever accumulates in g; one dots-only pass resets it), or dropped if this pass turns
     // out to run the plain way -- the active passes that follow must not keep carrying it either
-    const bool refresh_due = c.valid && c.cov_since_ref > h->knobs.gc_refresh;
+    const bool refresh_due = c.st.valid() && c.st.cov_since_ref() > h->knobs.gc_refresh;
     if (h->x.nnz() > gc_max_support(h)) { if (refresh_due) gc_invalidate(h, false); return CDH_OK; }
-    if (c.cooldown > 0) { c.cooldown -= 1; if (c.valid) gc_invalidate(h, false); return CDH_OK; }
+    if (c.cooldown > 0) { c.cooldown -= 1; if (c.st.valid()) gc_invalidate(h, false); return CDH_OK; }
     CHK(gc_size(h));
     if (c.mode == 0) return CDH_OK;
     double cert_abs = 0.0;            // fp32 storage: what the certificates allow for the residual's rounding
@@ -806,16 +787,16 @@ int32_t gc_prepare_full(cdh_handle h, bool* go, double* cert_abs_out, bool fold 
     //    reference yet, or the carried one is due): one dots-only pass over X gives a fresh g instead
     //    (re-referencing keeps what is known about beta: g will describe the same residual, only freshly summed)
     std::vector<int64_t> want;
-    if (c.valid && !refresh_due) {
-        for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) want.push_back(j);
+    if (c.st.valid() && !refresh_due) {
+        for (int64_t j : c.st.moved()) if (c.slot[(size_t)j] < 0) want.push_back(j);
         if ((int)want.size() > kGcMaxFetch) { gc_invalidate(h, false); want.clear(); }
     }
-    if (!c.valid || refresh_due) CHK(gc_rereference(h));
+    if (!c.st.valid() || refresh_due) CHK(gc_rereference(h));
     for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_)       // the support moves in every pass: its columns first
         if (c.slot[(size_t)h->x.coord(s_)] < 0) want.push_back(h->x.coord(s_));
     if (!want.empty()) {
         // the last batch of 32 filled with whatever has no column yet, certificate or not
-        if (want.size() % kCrossB != 0 && c.moved.empty()) {
+        if (want.size() % kCrossB != 0 && c.st.moved().empty()) {
             CHK(gc_need_host_g(h));
             GcThresholds T(h, cert_abs);
             CHK(T.sync_rnorm());
@@ -826,7 +807,7 @@ int32_t gc_prepare_full(cdh_handle h, bool* go, double* cert_abs_out, bool fold 
     }
     CHK(gc_check_moved_columns(h));
     if (fold) gc_fold(h);
-    if (!c.valid) return CDH_OK;      // (a device fold that failed hard leaves no gradient: the pass runs the plain way)
+    if (!c.st.valid()) return CDH_OK; // (a device fold that failed hard leaves no gradient: the pass runs the plain way)
     gc_q_guard(h);
     if (h->loss == CDH_SQRT) CHK(gc_ensure_q(h));
     *go = true;
@@ -840,7 +821,7 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
     double cert_abs = 0.0;
     {
         bool go = false;
-        if (c.prep_state) { go = c.prep_state == 1; cert_abs = c.prep_cert_abs; c.prep_state = 0; }   // cov_solve has prepared this pass
+        if (c.st.prepared()) go = c.st.take_prepared(&cert_abs);   // cov_solve has prepared this pass
         else CHK(gc_prepare_full(h, &go, &cert_abs));
         if (!go) return CDH_OK;
     }
@@ -853,7 +834,7 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
         CHK(gc_pass_device(h, idx0, m, maxH, T, &outcome));
         if (outcome == kDevDone) { *handled = true; c.n_passes += 1; return CDH_OK; }
         if (outcome == kDevPlain) return CDH_OK;
-        if (!c.valid) return CDH_OK;
+        if (!c.st.valid()) return CDH_OK;
     }
     CHK(gc_need_host_g(h));
     // 2'. inactive coordinates about to move: many of them means the pass is mostly real visits anyway
@@ -892,7 +873,7 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
         // a settled coordinate's certificate was read BEFORE the chunk's moves, it is re-checked afterwards
         // against the gradient as it stood when its turn came (the movers' columns are at hand).  A certificate
         // that no longer holds -- rare -- rolls the chunk back and reruns it up to that position.
-        if (c.cov && c.moved.empty() && c.d_G && c.dev_slots == (int64_t)c.G.size() && (h->loss != CDH_SQRT || c.q_valid)) {
+        if (c.cov && c.st.moved().empty() && c.d_G && c.dev_slots == (int64_t)c.G.size() && (h->loss != CDH_SQRT || c.st.q_usable())) {
             std::vector<int64_t> upos;
             int64_t wend = pos;
             bool have_all = true;
@@ -910,7 +891,7 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
                     CHK(cov_run(h, vis.data(), mv, true));
                     // re-check the skipped positions in visit order, carrying g through the chunk's moves
                     std::vector<double> gv(c.g);
-                    double q_run = c.q;                  // sqrt-lasso: ||r|| moves with every visit, and the thresholds with it
+                    double q_run = c.st.q();                 // sqrt-lasso: ||r|| moves with every visit, and the thresholds with it
                     const double rnorm_before = T.rnorm;
                     int64_t bad = -1;
                     size_t iu = 0;
@@ -940,7 +921,7 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
                             else { replay_settled(h, kq, c.g[(size_t)kq] != 0.0); c.n_certified += 1; }
                         }
                         cov_accept_tail(h, mv, maxH, true);
-                        if (h->loss == CDH_SQRT) T.rnorm = std::sqrt(c.q);
+                        if (h->loss == CDH_SQRT) T.rnorm = std::sqrt(c.st.q());
                         break;
                     }
                     CHK(cov_reject(h, vis.data(), mv));
@@ -949,7 +930,7 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
                     while (!upos.empty() && upos.back() >= bad) upos.pop_back();
                 }
                 pos = wend;
-                if (!c.valid) { *handled = true; break; }
+                if (!c.st.valid()) { *handled = true; break; }
                 continue;
             }
         }
@@ -961,10 +942,10 @@ int32_t gc_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH,
         else CHK(run_chunk(h, idx0 + pos, (int)(end - pos), maxH));
         c.n_exact += end - pos;
         pos = end;
-        if (!c.valid) { *handled = true; break; }     // a NaN step: finish below the plain way
-        if (!c.moved.empty()) {
+        if (!c.st.valid()) { *handled = true; break; }     // a NaN step: finish below the plain way
+        if (!c.st.moved().empty()) {
             std::vector<int64_t> miss;
-            for (int64_t j : c.moved) if (c.slot[(size_t)j] < 0) miss.push_back(j);
+            for (int64_t j : c.st.moved()) if (c.slot[(size_t)j] < 0) miss.push_back(j);
             if (!miss.empty()) { CHK(gc_fetch(h, miss)); if (c.mode == 0) break; }
             gc_fold(h);
             CHK(T.sync_rnorm());

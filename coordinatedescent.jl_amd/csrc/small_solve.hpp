@@ -612,18 +612,16 @@ int32_t small_solve(cdh_handle h, const cdh_options* o, const double* lambdas, i
     // reads r) and, for a gradient cache that holds a reference, pending moves like those of any other visit
     GradCache& c = h->gc;
     if (from_c) {                      // r was never read and is not touched: it stands for the new iterate, to be formed on demand
-        if (c.valid || c.beta_ok) gc_invalidate(h, false);
+        if (c.st.tracks_r()) gc_invalidate(h, false);
     } else {
         h->rs.iterate_moved();         // (also where no coordinate did: the stash is not kept across a solve)
     }
     for (int64_t k = 0; k < h->p && !from_c; ++k) {
         const double d = sp.h_beta[k] - h->x.get(k);
         if (d == 0.0) continue;
-        note_move_off_stream(h, k, d, false);
-        if (d != d) { if (c.valid || c.beta_ok) gc_invalidate(h, false); continue; }   // a NaN move: the cache knows nothing any more
-        if (c.valid) c.moved.add(k, d);
+        note_move_off_stream(h, k, d, cdh::MoveKind::off_stream, false);     // (a NaN move: the cache knows nothing any more)
     }
-    c.q_valid = false;
+    c.st.q_void();
     h->x.clear();
     for (int32_t s_ = 0; s_ < ctl.nnz; ++s_) h->x.set(sp.h_sup[s_], sp.h_beta[sp.h_sup[s_]]);
     if (from_c) h->rs.left_lazy(h->x);
