@@ -10,7 +10,7 @@ The directory name contains a dot, so import it through the root-level shim:
   sharded.py   row-sharded multi-process driver (torch.distributed + RCCL)
 """
 from . import _lib
-from ._lib import build, declared_symbols, needs_build, SO_PATH, CDH_QUAD_MAX_P  # noqa: F401
+from ._lib import build, declared_symbols, needs_build, SO_PATH, CDH_QUAD_MAX_P, CDH_VC_GRAM_MAX_COLS  # noqa: F401
 from .api import *  # noqa: F401,F403
 from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSquaresLoss,  # noqa: F401
                   CDSqrtLassoLoss, CDWeightedLSLoss, CDQuadraticLoss, CoordinateDifferentiableFunction,
@@ -20,4 +20,6 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
                   get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
                   getSigma, findInitResiduals_,
+                  locpoly, lvocv_locpoly, split_locpoly, refit_locpolyl1, getStandardError, getStandardErrorHEW,
+                  get_beta_, getResiduals_,
                   DimensionMismatch, ArgumentError, DomainError, HipError)

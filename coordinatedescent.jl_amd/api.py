@@ -578,6 +578,33 @@ class CDVaryingCoefficientLoss(CDWeightedLSLoss):
         check(self._L.cdh_vc_set_point_loo(self._h, kernel._kind, kernel.h, int(row), _vp(std), _vp(scores)), self._h)
         return std, scores
 
+    def expanded_gram(self, kernel, z0=0.0, *, leave_out=None, wpow=1, e=None, base_cols=None, rhs=True):
+        """_expand_Xt_w_X! / _expand_Xt_w_Y! (src/varying_coefficient_lasso.jl:572-647) of the listed base columns around z0,
+        straight from the resident base design (cdh_vc_gram): -> (G, c, Σω), G the ep x ep weighted Gram matrix of the expanded
+        design, ep = len(base_cols) (degree + 1), c its right-hand side (None with rhs=False), ω_i = K(z_i, z0)^wpow · e_i.
+        `leave_out` (a 0-based row) moves z0 to the stored z[row] (the z0 given is then ignored) and gives that row weight zero; `base_cols` are 0-based base
+        columns (default: all; at most 64), `e` an optional n-vector.  A read-only query: the handle's weights, expanded
+        columns, residual, cache and iterate stay as they are."""
+        _check_kernel(kernel)
+        cols = np.arange(self.p_base) if base_cols is None else np.atleast_1d(np.asarray(base_cols))
+        if cols.dtype == bool:
+            cols = np.nonzero(cols)[0]
+        idx1 = np.ascontiguousarray(cols.astype(np.int64) + 1)
+        mb = idx1.shape[0]
+        ep = mb * (self.degree + 1)
+        ee = None
+        if e is not None:
+            ee = np.ascontiguousarray(np.asarray(e), dtype=self.dtype)
+            if ee.shape != (self.n,):
+                raise DimensionMismatch("length(e) != size(X, 1)")
+        G = np.zeros((ep, ep), order="F")
+        c = np.zeros(ep) if rhs else None
+        sw = C.c_double()
+        check(self._L.cdh_vc_gram(self._h, kernel._kind, kernel.h, 0.0 if leave_out is not None else float(z0),
+                                  -1 if leave_out is None else int(leave_out),
+                                  int(wpow), _vp(ee), mb, _vp(idx1), _vp(G), _vp(c), C.byref(sw)), self._h)
+        return G, c, sw.value
+
 
 class CDQuadraticLoss(CoordinateDifferentiableFunction):
     """CDQuadraticLoss(A, b): x'Ax/2 + x'b (src/cd_differentiable_function.jl:299-348), behind one cdh_quad handle.
@@ -1275,3 +1302,209 @@ def lvocv_locpolyl1(X, z, y, degree, hArr, kernelType, lambda0, options=None):
         if f is not X:
             f.close()
     return MSE
+
+
+# --------------------------------------------------------------------------------------
+# Local polynomial regression in low dimensions (src/varying_coefficient_lasso.jl:197-476)
+# --------------------------------------------------------------------------------------
+def _solve_scaled(G, c):
+    """G \\ c from the symmetrically scaled normal equations (unit diagonal), as _vc_refit solves its block."""
+    d = np.sqrt(np.diag(G))
+    return np.linalg.solve(G / np.outer(d, d), c / d) / d
+
+
+def _inv_scaled(G):
+    d = np.sqrt(np.diag(G))
+    return np.linalg.inv(G / np.outer(d, d)) / np.outer(d, d)
+
+
+def _check_kernel(kernel):
+    if not isinstance(kernel, SmoothingKernel) or kernel._kind is None:
+        raise TypeError("MethodError: kernel::SmoothingKernel")
+    return kernel
+
+
+def _locpoly_loss(X, z, y, degree):
+    """-> (loss, built here): X is either a resident CDVaryingCoefficientLoss (z, y and degree are then its own) or the
+    reference's X::Matrix{T}, z::Vector{T}, y::Vector{T}; y may be None where the reference takes none."""
+    if isinstance(X, CDVaryingCoefficientLoss):
+        return X, False
+    X, z = np.asarray(X), np.asarray(z)
+    if X.ndim != 2 or X.dtype not in (np.float64, np.float32) or z.ndim != 1 or z.dtype != X.dtype:
+        raise TypeError("MethodError: X::Matrix{T}, z::Vector{T}, y::Vector{T}, T<:AbstractFloat")
+    y = np.zeros(X.shape[0], dtype=X.dtype) if y is None else np.asarray(y)
+    if y.ndim != 1 or y.dtype != X.dtype:
+        raise TypeError("MethodError: X::Matrix{T}, z::Vector{T}, y::Vector{T}, T<:AbstractFloat")
+    if z.shape[0] != X.shape[0]:
+        raise DimensionMismatch("length(z) != size(X, 1)")
+    if y.shape[0] != X.shape[0]:
+        raise DimensionMismatch("length(y) != size(X, 1)")
+    if not isinstance(degree, (int, np.integer)) or isinstance(degree, bool):
+        raise TypeError("MethodError: degree::Int64")
+    if X.shape[1] > _lib.CDH_VC_GRAM_MAX_COLS:
+        raise ArgumentError("locpoly on the device takes at most 64 base columns per call")
+    return CDVaryingCoefficientLoss(y, X, z, degree), True
+
+
+def locpoly(X, z, y, z0, degree, kernel=None):
+    """locpoly(X, z, y, z0, degree, kernel) and locpoly(X, z, y, zgrid, degree, kernel) (src/varying_coefficient_lasso.jl:
+    212-235; kernel defaults to GaussianKernel(1)): the local polynomial fit around a point -> p (degree + 1) coefficients,
+    or around every point of a grid -> a p (degree + 1) x length(zgrid) array.  The reference solves each point by QR of
+    √w · expandX (:206-209); here the weighted normal equations come from one pass over the base design on the device
+    (cdh_vc_gram) and are solved on the host after scaling them to unit diagonal -- the route of the reference's own
+    commented-out locpoly_alt (:322-344), which squares the condition number.  At most 64 base columns.  X may be a resident
+    CDVaryingCoefficientLoss; z, y and degree are then its own."""
+    kernel = GaussianKernel(1.0) if kernel is None else _check_kernel(kernel)
+    f, owned = _locpoly_loss(X, z, y, degree)
+    try:
+        if np.ndim(z0) == 0:
+            G, c, _ = f.expanded_gram(kernel, z0)
+            return _solve_scaled(G, c)
+        zgrid = np.asarray(z0, dtype=np.float64)
+        if zgrid.ndim != 1:
+            raise TypeError("MethodError: zgrid::Vector{T}")
+        out = np.zeros((f.p, zgrid.shape[0]))
+        for ind, zz in enumerate(zgrid):
+            G, c, _ = f.expanded_gram(kernel, zz)
+            out[:, ind] = _solve_scaled(G, c)
+        return out
+    finally:
+        if owned:
+            f.close()
+
+
+def lvocv_locpoly(X, z, y, degree, hArr, kernelType):
+    """lvocv_locpoly(X, z, y, degree, hArr, kernelType) (src/varying_coefficient_lasso.jl:348-380) -> MSE per bandwidth: the
+    sum over the observations i of (Yh_i - y_i)², Yh_i the prediction at z0 = z[i] of the local polynomial fit that left
+    observation i out.  The reference deletes row i; here it gets weight zero in the device's pass (its own commented-out
+    formulation, :413-444), and the prediction row X[i, :] is read back from the base columns (cdh_get_X_row)."""
+    hArr = np.atleast_1d(np.asarray(hArr, dtype=np.float64))
+    kernels = [createKernel(kernelType, h) for h in hArr]
+    f, owned = _locpoly_loss(X, z, y, degree)
+    try:
+        Q1 = f.degree + 1
+        yv = f.y.astype(np.float64)
+        base = np.ascontiguousarray(np.arange(f.p_base, dtype=np.int64) * Q1 + 1)
+        xrow = np.zeros(f.p_base)
+        MSE = np.zeros(hArr.shape[0])
+        for indH, kernel in enumerate(kernels):
+            for i in range(f.n):
+                G, c, _ = f.expanded_gram(kernel, leave_out=i)
+                hbeta = _solve_scaled(G, c)
+                check(f._L.cdh_get_X_row(f._h, i, f.p_base, _vp(base), _vp(xrow)), f._h)
+                MSE[indH] += (float(xrow @ hbeta[::Q1]) - yv[i]) ** 2
+        return MSE
+    finally:
+        if owned:
+            f.close()
+
+
+def get_beta_(out, zgrid, beta_grid, z0):
+    """get_beta!(out, zgrid, beta_grid, z0) (src/varying_coefficient_lasso.jl:454-476): the coefficients at z0 from the two
+    closest grid points, with the reference's weights exactly as written -- α = (z0 - z1) / (z2 - z1) multiplies the LEFT
+    point's column, 1 - α the right one's.  z0 outside the grid indexes out of bounds, as in the reference."""
+    zgrid = np.asarray(zgrid)
+    id1 = int(np.searchsorted(zgrid, z0, side="right"))          # searchsortedlast, 1-based
+    id2 = int(np.searchsorted(zgrid, z0, side="left")) + 1       # searchsortedfirst, 1-based
+    if id1 < 1 or id2 > zgrid.shape[0]:
+        raise IndexError("BoundsError: z0 lies outside zgrid")
+    if id1 == id2:
+        out[:] = beta_grid[:, id1 - 1]
+    else:
+        alpha = (z0 - zgrid[id1 - 1]) / (zgrid[id2 - 1] - zgrid[id1 - 1])
+        out[:] = alpha * beta_grid[:, id1 - 1] + (1 - alpha) * beta_grid[:, id2 - 1]
+    return out
+
+
+def split_locpoly(X, z, y, Xtest, ztest, ytest, zgrid, degree, hArr, kernelType):
+    """split_locpoly(X, z, y, Xtest, ztest, ytest, zgrid, degree, hArr, kernelType) (src/varying_coefficient_lasso.jl:383-409)
+    -> MSE per bandwidth of the grid fit's interpolated predictions (get_beta!) on the test split.  As written in the
+    reference, the loop over the test observations runs to size(X, 1), the TRAINING row count."""
+    hArr = np.atleast_1d(np.asarray(hArr, dtype=np.float64))
+    kernels = [createKernel(kernelType, h) for h in hArr]
+    Xtest, ztest, ytest = np.asarray(Xtest), np.asarray(ztest), np.asarray(ytest)
+    f, owned = _locpoly_loss(X, z, y, degree)
+    try:
+        Q1 = f.degree + 1
+        MSE = np.zeros(hArr.shape[0])
+        bi = np.zeros(f.p)
+        for indH, kernel in enumerate(kernels):
+            bhat = locpoly(f, None, None, zgrid, f.degree, kernel)
+            for i in range(f.n):                                  # :400, n = size(X, 1)
+                get_beta_(bi, zgrid, bhat, ztest[i])
+                MSE[indH] += (float(ytest[i]) - float(Xtest[i, :] @ bi[::Q1])) ** 2
+        return MSE
+    finally:
+        if owned:
+            f.close()
+
+
+def getResiduals_(ehat, X, z, y, zgrid, betahat, degree, kernel=None):
+    """getResiduals!(ϵhat, X, z, y, zgrid, βhat, degree, kernel) (src/varying_coefficient_lasso.jl:237-255): ϵhat[i] =
+    y[i] - X[i, :] · β(z[i])[1:(degree+1):ep], β(z[i]) interpolated by get_beta!.  Host numpy, n p work."""
+    X, z, y = np.asarray(X), np.asarray(z), np.asarray(y)
+    n, p = X.shape
+    if z.shape[0] != n or y.shape[0] != n or ehat.shape[0] != n:
+        raise DimensionMismatch("ϵhat, z and y need size(X, 1) entries")
+    betahat = np.asarray(betahat)
+    if betahat.shape[0] != p * (degree + 1):
+        raise DimensionMismatch("size(βhat, 1) != p * (degree + 1)")
+    bi = np.zeros(p * (degree + 1))
+    for i in range(n):
+        get_beta_(bi, zgrid, betahat, z[i])
+        ehat[i] = y[i] - X[i, :] @ bi[::degree + 1]
+    return ehat
+
+
+def _sandwich(f, z0, kernel, e):
+    """diag of A · (X'W Ψ W X) · A at the power-0 coefficients, A = inv(X'WX) (:272-283, :303-314); the products on the host."""
+    XtwX, _, _ = f.expanded_gram(kernel, z0, rhs=False)
+    XtwwX, _, _ = f.expanded_gram(kernel, z0, wpow=2, e=e, rhs=False)
+    A = _inv_scaled(XtwX)
+    return np.diag(A @ XtwwX @ A)[::f.degree + 1].copy()
+
+
+def getStandardError(X, z, sigma2, z0, degree, kernel):
+    """getStandardError(X, z, σ2, z0, degree, kernel) (src/varying_coefficient_lasso.jl:257-286) -> for every base column the
+    diagonal entry of inv(X'WX) · X'W²X · inv(X'WX) at its power-0 coefficient.  σ2 is accepted and, as in the reference,
+    not used.  Both Gram matrices come from the device (wpow 1 and 2)."""
+    _check_kernel(kernel)
+    f, owned = _locpoly_loss(X, z, None, degree)
+    try:
+        return _sandwich(f, z0, kernel, None)
+    finally:
+        if owned:
+            f.close()
+
+
+def getStandardErrorHEW(X, z, eps_sqr, z0, degree, kernel):
+    """getStandardErrorHEW(X, z, ϵ_sqr, z0, degree, kernel) (src/varying_coefficient_lasso.jl:288-317): the same with
+    X'W Ψ W X, Ψ = diag(ϵ_sqr), in the middle (wpow 2 and e = ϵ_sqr)."""
+    _check_kernel(kernel)
+    f, owned = _locpoly_loss(X, z, None, degree)
+    try:
+        eps_sqr = np.asarray(eps_sqr)
+        if eps_sqr.shape != (f.n,):
+            raise DimensionMismatch("length(ϵ_sqr) != size(X, 1)")
+        return _sandwich(f, z0, kernel, eps_sqr)
+    finally:
+        if owned:
+            f.close()
+
+
+def refit_locpolyl1(X, z, y, z0, degree, kernel, beta):
+    """refit_locpolyl1(X, z, y, z0, degree, kernel, β) (src/varying_coefficient_lasso.jl:139-154) -> (βr, S): S the base
+    columns whose group of β holds a non-zero (get_nonzero_coordinates(β, p, degree, false)), βr = locpoly(X[:, S], ...)."""
+    _check_kernel(kernel)
+    f, owned = _locpoly_loss(X, z, y, degree)
+    try:
+        S = get_nonzero_coordinates(beta, f.p_base, f.degree, False)
+        if not S.any():
+            return np.zeros(0), S
+        if int(S.sum()) > _lib.CDH_VC_GRAM_MAX_COLS:
+            raise ArgumentError("refit support larger than 64 base columns")
+        G, c, _ = f.expanded_gram(kernel, z0, base_cols=S)
+        return _solve_scaled(G, c), S
+    finally:
+        if owned:
+            f.close()

@@ -18,6 +18,7 @@
 #include "kernels.hpp"
 #include "gram_kernels.hpp"
 #include "vc_kernels.hpp"
+#include "vc_gram.hpp"
 #include "p2p_exchange.hpp"
 #include "sparse_iterate.hpp"
 #include "resid_state.hpp"
@@ -256,6 +257,17 @@ struct SmallPath {
 // best.  Where a setting seeds state that the ABI or a fallback changes later (the cache's mode, the device loop, the
 // one-launch solve), the handle's state starts from it; the rest is read from here.
 constexpr int64_t kGcCovRefresh = 200000;   // covariance-form visits after which g is re-read from X
+// What cdh_vc_gram needs besides the handle's data (vc_gram.hpp): the partial records and their sums, the listed columns, the
+// optional extra weights e, and pinned staging.  Allocated together by the first call, or not at all.
+struct VcGramScratch {
+    DevBuf<double> partials, out;
+    DevBuf<int64_t> cols;
+    DevBuf<void> e;
+    PinBuf<double> h_out;
+    PinBuf<int64_t> h_cols;
+    bool ready = false;
+};
+
 struct Knobs {
     int lt = 2;                      // CDH_LT: k_gramstep's operand loads transposed through LDS: 0 off, 1 on, 2 by size
     int ks = 0;                      // CDH_KS: chunk length of that path: 0 by shard length, 1 short, 2 long
@@ -307,6 +319,7 @@ struct cdh_handle_s {
     DevBuf<void> vc_z;
     int64_t vc_pbase = 0;
     int vc_degree = -1;           // -1: not in varying-coefficient mode
+    VcGramScratch vg;
     DevBuf<double> beta, omega;
     DevBuf<Ctrl> d_ctrl;
     DevBuf<int64_t> d_idx;
@@ -1934,6 +1947,66 @@ int32_t cdh_vc_set_point_loo(cdh_handle h, int32_t kernel_kind, double bandwidth
     if (row0 < 0 || row0 >= h->n) return fail(h, CDH_BAD_ARG, "the left-out row is outside 0 .. n - 1");
     if (!h->y_set) return fail(h, CDH_BAD_ARG, "the screening scores need y: cdh_set_y first");
     return vc_point(h, kernel_kind, bandwidth, 0.0, row0, out_std, out_scores);
+}); }
+
+// The weighted Gram matrix and right-hand side of the expanded design around one point, straight from the base design
+// (_expand_Xt_w_X!, _expand_Xt_w_Y!: varying_coefficient_lasso.jl:572-647): one pass over the listed base columns, z and y.
+// Reads the handle's data and writes only its own scratch: residual, cache, weights, expanded columns and iterate stay.
+static int32_t vc_gram_scratch(cdh_handle h) {
+    VcGramScratch& g = h->vg;
+    if (g.ready) return CDH_OK;
+    VcGramScratch s;                     // complete before the handle changes
+    const size_t nrec = (size_t)vc_gram_rec(kVgMaxDegree, kVgMaxCols).n;
+    HIPCHK(h, s.partials.alloc(sizeof(double) * (size_t)kVgPartialDoubles));
+    HIPCHK(h, s.out.alloc(sizeof(double) * nrec));
+    HIPCHK(h, s.cols.alloc(sizeof(int64_t) * kVgMaxCols));
+    HIPCHK(h, s.e.alloc((size_t)h->ld * h->esz));
+    HIPCHK(h, s.h_out.alloc(sizeof(double) * nrec));
+    HIPCHK(h, s.h_cols.alloc(sizeof(int64_t) * kVgMaxCols));
+    s.ready = true;
+    g = std::move(s);
+    return CDH_OK;
+}
+
+int32_t cdh_vc_gram(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, int64_t leave_out_row0, int32_t wpow,
+                    const void* host_e, int64_t mb, const int64_t* base_idx1, double* out_G, double* out_c,
+                    double* out_sum_w) { return guarded(h, [&]() -> int32_t {
+    NEED_P(h, out_G);
+    NEED_P(h, base_idx1);
+    CHK(vc_refuse_shards(h));
+    if (const char* bad = vc_gram_check(h->vc_degree, h->y_set, out_c != nullptr, h->vc_pbase, h->n, kernel_kind, bandwidth, z0,
+                                        leave_out_row0, wpow, mb, base_idx1))
+        return fail(h, CDH_BAD_ARG, bad);
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(vc_gram_scratch(h));
+    VcGramScratch& g = h->vg;
+    const int Q = h->vc_degree;
+    const VcGramRec R = vc_gram_rec(Q, mb);
+    const int G = vc_gram_grid(h->n, Q, mb);
+    if ((int64_t)G * R.n > kVgPartialDoubles) return fail(h, CDH_BAD_ARG, "cdh_vc_gram: partial buffer too small for this grid");
+    for (int64_t i = 0; i < mb; ++i) g.h_cols[i] = (base_idx1[i] - 1) * (Q + 1);     // base column j sits at column j (Q + 1)
+    HIPCHK(h, hipMemcpyAsync(g.cols, g.h_cols, sizeof(int64_t) * (size_t)mb, hipMemcpyHostToDevice, h->stream));
+    if (host_e) HIPCHK(h, hipMemcpyAsync(g.e, host_e, (size_t)h->n * h->esz, hipMemcpyHostToDevice, h->stream));
+    CHK(dispatch(h, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3(kVgThreads), 0, h->stream, (const T*)h->X, h->ld, h->n,
+                               (const T*)h->vc_z, out_c ? (const T*)h->y : (const T*)nullptr,
+                               host_e ? (const T*)g.e : (const T*)nullptr, (const int64_t*)g.cols, (int)mb, (int)kernel_kind,
+                               bandwidth, z0, (int)wpow, leave_out_row0, (double*)g.partials);
+        };
+        if (Q == 0) go(k_vc_moments<T, 0>); else if (Q == 1) go(k_vc_moments<T, 1>);
+        else if (Q == 2) go(k_vc_moments<T, 2>); else go(k_vc_moments<T, 3>);
+        return CDH_OK;
+    }));
+    hipLaunchKernelGGL(k_vc_moments_reduce, dim3((unsigned)((R.n + kVgThreads - 1) / kVgThreads)), dim3(kVgThreads), 0, h->stream,
+                       (const double*)g.partials, G, R.n, (double*)g.out);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(g.h_out, g.out, sizeof(double) * (size_t)R.n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    vc_gram_scatter(Q, mb, g.h_out, out_G, out_c);
+    if (out_sum_w) *out_sum_w = g.h_out[R.off_w];
+    return CDH_OK;
 }); }
 
 // _getSigma(w, r) (utils.jl:167-175): sum w, sum w r^2 at the current residual

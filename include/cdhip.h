@@ -156,6 +156,30 @@ int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, do
  * before cdh_set_y. */
 int32_t cdh_vc_set_point_loo(cdh_handle h, int32_t kernel_kind, double bandwidth, int64_t row0, double *out_std,
                              double *out_scores);
+/* The low-dimensional half of local-polynomial regression (locpoly, lvocv_locpoly, getStandardError, getStandardErrorHEW:
+ * varying_coefficient_lasso.jl:197-235, 257-317, 348-380) rests on the weighted Gram matrix and right-hand side of the
+ * expanded design, _expand_Xt_w_X! (varying_coefficient_lasso.jl:572-620) and _expand_Xt_w_Y! (:622-647).  cdh_vc_gram takes
+ * both straight from the base design in one pass over the listed base columns, z and y -- nothing is expanded or written:
+ *   out_G[(j,a),(k,b)] = sum_i om_i x_ij x_ik d_i^(a+b),   out_c[(j,a)] = sum_i om_i x_ij y_i d_i^a,   *out_sum_w = sum_i om_i,
+ * d_i = z_i - z0 (formed in T, as cdh_vc_set_point forms it), om_i = K(z_i, z0)^wpow (K evaluated in double and rounded once to
+ * T, as cdh_vc_set_point's weights) times host_e[i] when host_e is given (n values of T: eps^2 of getStandardErrorHEW, :306),
+ * wpow 1 or 2 (:275).  With leave_out_row0 >= 0, z0 is the stored z[leave_out_row0] and that row's om is 0 (the commented-out
+ * lvocv_locpoly's formulation, :432-436); -1 for none.  base_idx1 lists mb BASE columns (1-based, any order, repeats allowed),
+ * 1 <= mb <= CDH_VC_GRAM_MAX_COLS; out_G is column-major ep x ep, ep = mb (degree + 1), both triangles filled, in the expanded
+ * order (j, a) -> j (degree + 1) + a of the listed columns; out_c (ep values) and out_sum_w may be NULL.  Powers, products and
+ * sums are taken in double, in a fixed order: results are bit-identical run to run.
+ *
+ * A read-only query: the handle's residual, gradient cache, weights, expanded columns and iterate are left as they were.
+ * CDH_BAD_ARG: a call before cdh_vc_set_data; out_c given before cdh_set_y; mb outside 1 .. 64; a column outside 1 .. p_base;
+ * bandwidth <= 0; an unknown kernel; wpow outside {1, 2}; a row outside 0 .. n - 1; a row-sharded handle; NULL out_G or
+ * base_idx1. */
+#define CDH_VC_GRAM_MAX_COLS 64
+int32_t cdh_vc_gram(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0,
+                    int64_t leave_out_row0,      /* -1: none; else z0 := stored z[row], om[row] = 0 */
+                    int32_t wpow,                /* 1 or 2 */
+                    const void *host_e,          /* NULL, or n values of T multiplied into om */
+                    int64_t mb, const int64_t *base_idx1,   /* 1-based BASE columns, any order */
+                    double *out_G, double *out_c, double *out_sum_w);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects
