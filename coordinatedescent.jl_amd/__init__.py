@@ -10,7 +10,7 @@ The directory name contains a dot, so import it through the root-level shim:
   sharded.py   row-sharded multi-process driver (torch.distributed + RCCL)
 """
 from . import _lib
-from ._lib import build, declared_symbols, needs_build, SO_PATH, CDH_QUAD_MAX_P, CDH_VC_GRAM_MAX_COLS  # noqa: F401
+from ._lib import build, declared_symbols, needs_build, SO_PATH, CDH_QUAD_MAX_P, CDH_VC_GRAM_MAX_COLS, CDH_VC_GRAM_MAX_POINTS  # noqa: F401
 from .api import *  # noqa: F401,F403
 from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSquaresLoss,  # noqa: F401
                   CDSqrtLassoLoss, CDWeightedLSLoss, CDQuadraticLoss, CoordinateDifferentiableFunction,

@@ -29,6 +29,7 @@ CDH_LS, CDH_SQRT, CDH_WLS = 0, 1, 2
 CDH_SWEEP_COORD, CDH_SWEEP_BLOCK = 0, 1
 CDH_VC_GAUSSIAN, CDH_VC_EPANECHNIKOV = 0, 1
 CDH_VC_GRAM_MAX_COLS = 64   # include/cdhip.h; kVgMaxCols in csrc/vc_gram_types.hpp
+CDH_VC_GRAM_MAX_POINTS = 65536   # include/cdhip.h; kVgbMaxPoints in csrc/vc_gram_batch_types.hpp
 CDH_QUAD_MAX_P = 2559    # include/cdhip.h; derived in csrc/quad_solve_types.hpp (tests/test_quad_host.py holds the three together)
 
 
@@ -139,6 +140,7 @@ def lib():
         "cdh_vc_set_point": [vp, i32, f64, f64, vp],
         "cdh_vc_set_point_loo": [vp, i32, f64, i64, vp, vp],
         "cdh_vc_gram": [vp, i32, f64, f64, i64, i32, vp, i64, vp, vp, vp, P(f64)],
+        "cdh_vc_gram_batch": [vp, i32, i64, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp],
         "cdh_resid_wmoments": [vp, P(f64), P(f64)],
         "cdh_get_X_row": [vp, i64, i64, vp, vp],
         "cdh_resid_std": [vp, P(f64), P(f64)],

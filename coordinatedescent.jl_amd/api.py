@@ -605,6 +605,53 @@ class CDVaryingCoefficientLoss(CDWeightedLSLoss):
                                   int(wpow), _vp(ee), mb, _vp(idx1), _vp(G), _vp(c), C.byref(sw)), self._h)
         return G, c, sw.value
 
+    def expanded_gram_batch(self, kernel, h, z0=None, *, leave_out=None, wpow=1, e=None, base_cols=None, rhs=True):
+        """expanded_gram around m points in one call (cdh_vc_gram_batch): -> (G[m, ep, ep], c[m, ep] or None, Σω[m]), point t
+        bit-identical to expanded_gram(kernelType(h[t]), z0[t], leave_out=leave_out[t], ...).  `kernel` is a kernel type
+        (GaussianKernel, EpanechnikovKernel), a kernel (its type is taken; the bandwidths are `h`) or a cdh_vc_kernel code;
+        `h`, `z0` and `leave_out` are scalars or length-m vectors, broadcast against each other; an entry of `leave_out`
+        is a 0-based row or -1 for none.  `wpow`, `e` and `base_cols` are shared by the points.  At most
+        CDH_VC_GRAM_MAX_POINTS points per call.  A read-only query, as expanded_gram."""
+        kind = _kernel_kind(kernel)
+        args = [np.asarray(h, dtype=np.float64)]
+        if z0 is not None:
+            args.append(np.asarray(z0, dtype=np.float64))
+        if leave_out is not None:
+            lo = np.asarray(leave_out)
+            if lo.dtype.kind not in "iu":
+                raise TypeError("MethodError: leave_out::Vector{Int64}")
+            args.append(lo.astype(np.int64))
+        if any(a.ndim > 1 for a in args):
+            raise TypeError("MethodError: h, z0 and leave_out are scalars or vectors")
+        try:
+            shape = np.broadcast_shapes(*[a.shape for a in args])
+        except ValueError:
+            raise DimensionMismatch("h, z0 and leave_out do not broadcast to one length") from None
+        m = int(shape[0]) if shape else 1
+        if not 1 <= m <= _lib.CDH_VC_GRAM_MAX_POINTS:
+            raise ArgumentError(f"cdh_vc_gram_batch: need 1 <= m <= {_lib.CDH_VC_GRAM_MAX_POINTS} points")
+        full = [np.ascontiguousarray(np.broadcast_to(a, (m,))) for a in args]
+        hh = full[0]
+        zz = full[1] if z0 is not None else None
+        ll = full[-1] if leave_out is not None else None
+        cols = np.arange(self.p_base) if base_cols is None else np.atleast_1d(np.asarray(base_cols))
+        if cols.dtype == bool:
+            cols = np.nonzero(cols)[0]
+        idx1 = np.ascontiguousarray(cols.astype(np.int64) + 1)
+        mb = idx1.shape[0]
+        ep = mb * (self.degree + 1)
+        ee = None
+        if e is not None:
+            ee = np.ascontiguousarray(np.asarray(e), dtype=self.dtype)
+            if ee.shape != (self.n,):
+                raise DimensionMismatch("length(e) != size(X, 1)")
+        G = np.zeros((m, ep, ep))
+        c = np.zeros((m, ep)) if rhs else None
+        sw = np.zeros(m)
+        check(self._L.cdh_vc_gram_batch(self._h, kind, m, _vp(hh), _vp(zz), _vp(ll), int(wpow), _vp(ee), mb, _vp(idx1),
+                                        _vp(G), _vp(c), _vp(sw)), self._h)
+        return G.transpose(0, 2, 1), c, sw          # a block is column-major: G[t] is what expanded_gram returns
+
 
 class CDQuadraticLoss(CoordinateDifferentiableFunction):
     """CDQuadraticLoss(A, b): x'Ax/2 + x'b (src/cd_differentiable_function.jl:299-348), behind one cdh_quad handle.
@@ -1324,6 +1371,39 @@ def _check_kernel(kernel):
     return kernel
 
 
+def _kernel_kind(kernel):
+    """The cdh_vc_kernel code of a kernel type, of a kernel, or the code itself."""
+    if isinstance(kernel, type) and issubclass(kernel, SmoothingKernel) and kernel._kind is not None:
+        return int(kernel._kind)
+    if isinstance(kernel, SmoothingKernel) and kernel._kind is not None:
+        return int(kernel._kind)
+    if isinstance(kernel, (int, np.integer)) and not isinstance(kernel, bool):
+        return int(kernel)
+    raise TypeError("MethodError: kernel::Type{<:SmoothingKernel}")
+
+
+def _solve_scaled_stack(G, c):
+    """_solve_scaled of every block of G[m, ep, ep], c[m, ep]: the same scaling to unit diagonal per point, one stacked solve."""
+    d = np.sqrt(np.diagonal(G, axis1=1, axis2=2))
+    return np.linalg.solve(G / (d[:, :, None] * d[:, None, :]), (c / d)[:, :, None])[:, :, 0] / d
+
+
+_LOCPOLY_BATCH = 4096          # points per cdh_vc_gram_batch call of the front ends: 4096 blocks of ep x ep stay modest on the host
+
+
+def _locpoly_batch(f, kind, h, z0, leave_out):
+    """The local polynomial fits around m points -> (m, ep): cdh_vc_gram_batch in pieces of _LOCPOLY_BATCH points, each
+    followed by the stacked solve of its scaled normal equations.  h, z0 (or None) and leave_out (or None) are m-vectors."""
+    m = h.shape[0]
+    out = np.zeros((m, f.p))
+    for s in range(0, m, _LOCPOLY_BATCH):
+        t = slice(s, min(m, s + _LOCPOLY_BATCH))
+        G, c, _ = f.expanded_gram_batch(kind, h[t], None if z0 is None else z0[t],
+                                        leave_out=None if leave_out is None else leave_out[t])
+        out[t] = _solve_scaled_stack(G, c)
+    return out
+
+
 def _locpoly_loss(X, z, y, degree):
     """-> (loss, built here): X is either a resident CDVaryingCoefficientLoss (z, y and degree are then its own) or the
     reference's X::Matrix{T}, z::Vector{T}, y::Vector{T}; y may be None where the reference takes none."""
@@ -1352,8 +1432,9 @@ def locpoly(X, z, y, z0, degree, kernel=None):
     or around every point of a grid -> a p (degree + 1) x length(zgrid) array.  The reference solves each point by QR of
     √w · expandX (:206-209); here the weighted normal equations come from one pass over the base design on the device
     (cdh_vc_gram) and are solved on the host after scaling them to unit diagonal -- the route of the reference's own
-    commented-out locpoly_alt (:322-344), which squares the condition number.  At most 64 base columns.  X may be a resident
-    CDVaryingCoefficientLoss; z, y and degree are then its own."""
+    commented-out locpoly_alt (:322-344), which squares the condition number.  A grid is one batch of points
+    (cdh_vc_gram_batch) and one stacked solve; its columns equal the single-point results bit for bit.  At most 64 base
+    columns.  X may be a resident CDVaryingCoefficientLoss; z, y and degree are then its own."""
     kernel = GaussianKernel(1.0) if kernel is None else _check_kernel(kernel)
     f, owned = _locpoly_loss(X, z, y, degree)
     try:
@@ -1363,11 +1444,9 @@ def locpoly(X, z, y, z0, degree, kernel=None):
         zgrid = np.asarray(z0, dtype=np.float64)
         if zgrid.ndim != 1:
             raise TypeError("MethodError: zgrid::Vector{T}")
-        out = np.zeros((f.p, zgrid.shape[0]))
-        for ind, zz in enumerate(zgrid):
-            G, c, _ = f.expanded_gram(kernel, zz)
-            out[:, ind] = _solve_scaled(G, c)
-        return out
+        if zgrid.shape[0] == 0:
+            return np.zeros((f.p, 0))
+        return np.ascontiguousarray(_locpoly_batch(f, kernel._kind, np.full(zgrid.shape[0], kernel.h), zgrid, None).T)
     finally:
         if owned:
             f.close()
@@ -1377,22 +1456,28 @@ def lvocv_locpoly(X, z, y, degree, hArr, kernelType):
     """lvocv_locpoly(X, z, y, degree, hArr, kernelType) (src/varying_coefficient_lasso.jl:348-380) -> MSE per bandwidth: the
     sum over the observations i of (Yh_i - y_i)², Yh_i the prediction at z0 = z[i] of the local polynomial fit that left
     observation i out.  The reference deletes row i; here it gets weight zero in the device's pass (its own commented-out
-    formulation, :413-444), and the prediction row X[i, :] is read back from the base columns (cdh_get_X_row)."""
+    formulation, :413-444).  The points are all (bandwidth, observation) pairs, sent to the device in batches
+    (cdh_vc_gram_batch) and solved stacked; the predictions come from the base columns, fetched once (the caller's X, or
+    columns j (degree + 1) of a resident loss), and the MSE of a bandwidth is accumulated over its observations in index order."""
     hArr = np.atleast_1d(np.asarray(hArr, dtype=np.float64))
     kernels = [createKernel(kernelType, h) for h in hArr]
     f, owned = _locpoly_loss(X, z, y, degree)
     try:
-        Q1 = f.degree + 1
+        Q1, n = f.degree + 1, f.n
         yv = f.y.astype(np.float64)
-        base = np.ascontiguousarray(np.arange(f.p_base, dtype=np.int64) * Q1 + 1)
-        xrow = np.zeros(f.p_base)
+        if owned:
+            Xb = np.asarray(X, dtype=np.float64)
+        else:
+            Xb = np.concatenate([f.X_cols(j * Q1, 1) for j in range(f.p_base)], axis=1).astype(np.float64)
         MSE = np.zeros(hArr.shape[0])
-        for indH, kernel in enumerate(kernels):
-            for i in range(f.n):
-                G, c, _ = f.expanded_gram(kernel, leave_out=i)
-                hbeta = _solve_scaled(G, c)
-                check(f._L.cdh_get_X_row(f._h, i, f.p_base, _vp(base), _vp(xrow)), f._h)
-                MSE[indH] += (float(xrow @ hbeta[::Q1]) - yv[i]) ** 2
+        if not kernels or n == 0:
+            return MSE
+        pair = np.arange(len(kernels) * n)
+        indH, obs = pair // n, pair % n
+        hbeta = _locpoly_batch(f, kernels[0]._kind, hArr[indH], None, obs)
+        sq = (np.einsum("ij,ij->i", Xb[obs], hbeta[:, ::Q1]) - yv[obs]) ** 2
+        for k, v in zip(indH.tolist(), sq.tolist()):
+            MSE[k] += v
         return MSE
     finally:
         if owned:

@@ -267,6 +267,15 @@ struct VcGramScratch {
     PinBuf<int64_t> h_cols;
     bool ready = false;
 };
+// What cdh_vc_gram_batch adds to it (vc_gram_batch_types.hpp: vgb_scratch_*_bytes): the partial records of a launch group, its
+// summed records on the device and pinned, and the group's points.  Allocated together by the first batch call, or not at all.
+struct VcGramBatchScratch {
+    DevBuf<double> partials, out;
+    DevBuf<VcGramPoint> pts;
+    PinBuf<double> h_out;
+    PinBuf<VcGramPoint> h_pts;
+    bool ready = false;
+};
 
 struct Knobs {
     int lt = 2;                      // CDH_LT: k_gramstep's operand loads transposed through LDS: 0 off, 1 on, 2 by size
@@ -320,6 +329,7 @@ struct cdh_handle_s {
     int64_t vc_pbase = 0;
     int vc_degree = -1;           // -1: not in varying-coefficient mode
     VcGramScratch vg;
+    VcGramBatchScratch vgb;
     DevBuf<double> beta, omega;
     DevBuf<Ctrl> d_ctrl;
     DevBuf<int64_t> d_idx;
@@ -1987,6 +1997,7 @@ int32_t cdh_vc_gram(cdh_handle h, int32_t kernel_kind, double bandwidth, double 
     for (int64_t i = 0; i < mb; ++i) g.h_cols[i] = (base_idx1[i] - 1) * (Q + 1);     // base column j sits at column j (Q + 1)
     HIPCHK(h, hipMemcpyAsync(g.cols, g.h_cols, sizeof(int64_t) * (size_t)mb, hipMemcpyHostToDevice, h->stream));
     if (host_e) HIPCHK(h, hipMemcpyAsync(g.e, host_e, (size_t)h->n * h->esz, hipMemcpyHostToDevice, h->stream));
+    if (h->prof) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     CHK(dispatch(h, [&](auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         auto go = [&](auto kernel) {
@@ -2002,10 +2013,113 @@ int32_t cdh_vc_gram(cdh_handle h, int32_t kernel_kind, double bandwidth, double 
     hipLaunchKernelGGL(k_vc_moments_reduce, dim3((unsigned)((R.n + kVgThreads - 1) / kVgThreads)), dim3(kVgThreads), 0, h->stream,
                        (const double*)g.partials, G, R.n, (double*)g.out);
     HIPCHK(h, hipGetLastError());
+    if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     HIPCHK(h, hipMemcpyAsync(g.h_out, g.out, sizeof(double) * (size_t)R.n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->prof) {                       // cdh_profile_begin/end: the device time of the two launches
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        h->prof_ms += ms;
+        h->prof_launches += 2;
+    }
     vc_gram_scatter(Q, mb, g.h_out, out_G, out_c);
     if (out_sum_w) *out_sum_w = g.h_out[R.off_w];
+    return CDH_OK;
+}); }
+
+// A batch of points per launch: point t is cdh_vc_gram at (bandwidth[t], z0[t], leave_out_row0[t]), bit for bit
+// (vc_gram.hpp: k_vc_moments_batch; the loops of locpoly on a grid, lvocv_locpoly and split_locpoly,
+// varying_coefficient_lasso.jl:217-235, 348-380, 383-409, over :572-647).  The plan of the call is vc_gram_batch_types.hpp's.
+static_assert(kVgbMaxPoints == CDH_VC_GRAM_MAX_POINTS && kVgMaxCols == CDH_VC_GRAM_MAX_COLS, "cdhip.h names the limits the headers derive");
+static int32_t vc_gram_batch_scratch(cdh_handle h) {
+    VcGramBatchScratch& g = h->vgb;
+    if (g.ready) return CDH_OK;
+    VcGramBatchScratch s;                // complete before the handle changes
+    HIPCHK(h, s.partials.alloc(sizeof(double) * (size_t)kVgbPartialDoubles));
+    HIPCHK(h, s.out.alloc(sizeof(double) * (size_t)kVgbOutDoubles));
+    HIPCHK(h, s.pts.alloc(sizeof(VcGramPoint) * (size_t)kVgbMaxGroupPoints));
+    HIPCHK(h, s.h_out.alloc(sizeof(double) * (size_t)kVgbOutDoubles));
+    HIPCHK(h, s.h_pts.alloc(sizeof(VcGramPoint) * (size_t)kVgbMaxGroupPoints));
+    s.ready = true;
+    g = std::move(s);
+    return CDH_OK;
+}
+
+int32_t cdh_vc_gram_batch(cdh_handle h, int32_t kernel_kind, int64_t m, const double* bandwidth, const double* z0,
+                          const int64_t* leave_out_row0, int32_t wpow, const void* host_e, int64_t mb,
+                          const int64_t* base_idx1, double* out_G, double* out_c, double* out_sum_w) { return guarded(h, [&]() -> int32_t {
+    if (!out_G) return fail(h, CDH_BAD_ARG, "cdh_vc_gram_batch: out_G is NULL");
+    CHK(vc_refuse_shards(h));
+    int64_t bad_point = -1;
+    if (const char* bad = vc_gram_batch_check(h->vc_degree, h->y_set, out_c != nullptr, h->vc_pbase, h->n, kernel_kind, m,
+                                              bandwidth, z0, leave_out_row0, wpow, mb, base_idx1, &bad_point)) {
+        char buf[256];
+        if (bad_point < 0) return fail(h, CDH_BAD_ARG, bad);
+        snprintf(buf, sizeof buf, "cdh_vc_gram_batch: point %lld: %s", (long long)bad_point, bad);
+        return fail(h, CDH_BAD_ARG, buf);
+    }
+    // every point has passed; nothing has been launched or allocated before this line
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(vc_gram_scratch(h));
+    CHK(vc_gram_batch_scratch(h));
+    VcGramScratch& g = h->vg;
+    VcGramBatchScratch& b = h->vgb;
+    const int Q = h->vc_degree;
+    const int64_t n = h->n, Q1 = Q + 1, ep = mb * Q1;
+    const VcGramRec R = vc_gram_rec(Q, mb);
+    const int G = vc_gram_grid(n, Q, mb);
+    const bool resident = vgb_resident(n, Q, mb);
+    for (int64_t i = 0; i < mb; ++i) g.h_cols[i] = (base_idx1[i] - 1) * Q1;          // base column j sits at column j (Q + 1)
+    HIPCHK(h, hipMemcpyAsync(g.cols, g.h_cols, sizeof(int64_t) * (size_t)mb, hipMemcpyHostToDevice, h->stream));
+    if (host_e) HIPCHK(h, hipMemcpyAsync(g.e, host_e, (size_t)n * h->esz, hipMemcpyHostToDevice, h->stream));   // once per call
+    const int64_t ngroups = vgb_groups(n, Q, mb, m);
+    for (int64_t grp = 0; grp < ngroups; ++grp) {
+        const int64_t first = vgb_group_first(n, Q, mb, grp), pts = vgb_group_size(n, Q, mb, m, grp);
+        const int64_t per = vgb_share_points(n, Q, mb, pts), gy = vgb_grid_y(n, Q, mb, pts);
+        if (pts < 1 || vgb_rec_offset(n, Q, mb, pts, 0) > kVgbPartialDoubles || pts * R.n > kVgbOutDoubles ||
+            pts > kVgbMaxGroupPoints || gy < 1 || gy > 65535 || vgb_share_begin(n, Q, mb, pts, gy) != pts)
+            return fail(h, CDH_BAD_ARG, "cdh_vc_gram_batch: the plan of this call does not fit its scratch");
+        for (int64_t t = 0; t < pts; ++t) {
+            const int64_t lo = leave_out_row0 ? leave_out_row0[first + t] : -1;
+            b.h_pts[t] = VcGramPoint{lo >= 0 ? 0.0 : z0[first + t], bandwidth[first + t], lo};
+        }
+        HIPCHK(h, hipMemcpyAsync(b.pts, b.h_pts, sizeof(VcGramPoint) * (size_t)pts, hipMemcpyHostToDevice, h->stream));
+        if (h->prof) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+        CHK(dispatch(h, [&](auto* t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            auto go = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)G, (unsigned)gy), dim3(kVgThreads), 0, h->stream, (const T*)h->X, h->ld, n,
+                                   (const T*)h->vc_z, out_c ? (const T*)h->y : (const T*)nullptr,
+                                   host_e ? (const T*)g.e : (const T*)nullptr, (const int64_t*)g.cols, (int)mb, (int)kernel_kind,
+                                   (int)wpow, (const VcGramPoint*)b.pts, (int)pts, (int)per, (double*)b.partials);
+            };
+            if (resident) {
+                if (Q == 0) go(k_vc_moments_batch<T, 0, true>); else if (Q == 1) go(k_vc_moments_batch<T, 1, true>);
+                else if (Q == 2) go(k_vc_moments_batch<T, 2, true>); else go(k_vc_moments_batch<T, 3, true>);
+            } else {
+                if (Q == 0) go(k_vc_moments_batch<T, 0, false>); else if (Q == 1) go(k_vc_moments_batch<T, 1, false>);
+                else if (Q == 2) go(k_vc_moments_batch<T, 2, false>); else go(k_vc_moments_batch<T, 3, false>);
+            }
+            return CDH_OK;
+        }));
+        hipLaunchKernelGGL(k_vc_moments_reduce, dim3((unsigned)((R.n + kVgThreads - 1) / kVgThreads), (unsigned)pts), dim3(kVgThreads),
+                           0, h->stream, (const double*)b.partials, G, R.n, (double*)b.out);
+        HIPCHK(h, hipGetLastError());
+        if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        HIPCHK(h, hipMemcpyAsync(b.h_out, b.out, sizeof(double) * (size_t)(pts * R.n), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->prof) {
+            float ms = 0.f;
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            h->prof_ms += ms;
+            h->prof_launches += 2;
+        }
+        for (int64_t t = 0; t < pts; ++t) {
+            const double* rec = b.h_out + t * R.n;
+            vc_gram_scatter(Q, mb, rec, out_G + (first + t) * ep * ep, out_c ? out_c + (first + t) * ep : nullptr);
+            if (out_sum_w) out_sum_w[first + t] = rec[R.off_w];
+        }
+    }
     return CDH_OK;
 }); }
 

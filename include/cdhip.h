@@ -180,6 +180,41 @@ int32_t cdh_vc_gram(cdh_handle h, int32_t kernel_kind, double bandwidth, double 
                     const void *host_e,          /* NULL, or n values of T multiplied into om */
                     int64_t mb, const int64_t *base_idx1,   /* 1-based BASE columns, any order */
                     double *out_G, double *out_c, double *out_sum_w);
+/* Many points in one launch.  The reference's grid and leave-one-out loops call the two routines above once per point:
+ * locpoly on a grid (varying_coefficient_lasso.jl:217-235), lvocv_locpoly (:348-380) and split_locpoly (:383-409), each over
+ * _expand_Xt_w_X! / _expand_Xt_w_Y! (:572-647).  cdh_vc_gram_batch serves m such points with one launch per group of points
+ * instead of m round trips.  Point t is exactly
+ *   cdh_vc_gram(h, kernel_kind, bandwidth[t], z0[t], leave_out_row0[t], wpow, host_e, mb, base_idx1, ...)
+ * -- d_i formed in T, K evaluated in double and rounded once to T, the left-out row moving z0 to the stored z[row], the
+ * (j, a) -> j (degree + 1) + a order, both triangles filled, powers, products and sums in double -- and BIT-IDENTICAL to it:
+ * every output entry goes through the same additions in the same order (the same deal of row chunks to workgroups, the
+ * same slices, the same sums over slices and workgroups), so a point's result does not depend on what else is in the batch,
+ * where it stands in it, or how the call is cut into launches.  No atomics; bit-identical run to run.
+ * A batch may mix points with and without a left-out row, and bandwidths; the kernel kind, wpow, host_e and the column list
+ * are shared.  z0 may be NULL when every point leaves a row out; leave_out_row0 may be NULL when none does, else it holds
+ * -1 or a 0-based row per point.  out_G receives m blocks of ep x ep (column-major, point after point), out_c (NULL, or m
+ * blocks of ep) and out_sum_w (NULL, or m values) likewise.
+ *
+ * Two regimes.  Where every workgroup of the single-point launch holds one chunk of 64 rows (n <= 32768, fewer for the
+ * largest records) a workgroup stages its rows once and walks a share of the points: the design is read from memory once
+ * per workgroup, not once per point.  Otherwise a (workgroup, point) does what cdh_vc_gram's workgroup does and the base
+ * columns are re-read per point out of cache.  Scratch of its own (allocated by the first call, all or nothing): 128 MiB
+ * of partial records and 32 MiB of summed records on the device, 32 MiB pinned; the call is cut into as many launch groups
+ * as that allows.  host_e is uploaded once per call.
+ *
+ * A read-only query, like cdh_vc_gram.  CDH_BAD_ARG, before anything is launched: whatever cdh_vc_gram refuses, for any
+ * point (the message names the point); m outside 1 .. CDH_VC_GRAM_MAX_POINTS; NULL bandwidth, out_G or base_idx1; NULL z0
+ * while some point has no left-out row; a non-finite z0 at such a point; a row-sharded handle. */
+#define CDH_VC_GRAM_MAX_POINTS 65536
+int32_t cdh_vc_gram_batch(cdh_handle h, int32_t kernel_kind, int64_t m,
+                          const double *bandwidth,        /* m values, each > 0 */
+                          const double *z0,               /* m values; may be NULL when every point leaves a row out */
+                          const int64_t *leave_out_row0,  /* NULL: none; else m entries, -1 or a 0-based row */
+                          int32_t wpow, const void *host_e,
+                          int64_t mb, const int64_t *base_idx1,
+                          double *out_G,                  /* m blocks of ep x ep, column-major, point after point */
+                          double *out_c,                  /* NULL, or m blocks of ep */
+                          double *out_sum_w);             /* NULL, or m values */
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects

@@ -622,6 +622,74 @@ function CoordinateDescent.lvocv_locpolyl1(D::HipVaryingDesign{T}, y::Vector{T},
   MSE
 end
 
+# ---- locpoly on a grid and lvocv_locpoly (src/varying_coefficient_lasso.jl:217-235, 348-380) -----------------------------
+# The reference forms w, expandX and a QR per point.  cdh_vc_gram_batch takes _expand_Xt_w_X! / _expand_Xt_w_Y! (:572-647)
+# of many points in one launch straight from the resident base design -- point t bit-identical to cdh_vc_gram at that
+# point -- and the ep x ep systems are solved here from the symmetrically scaled normal equations.
+const VC_GRAM_BATCH = 4096          # points per call: the host blocks of one call stay modest
+
+"G (ep x ep x m), c (ep x m) and Σω (m) around m points: bandwidths bw, points z0 and/or left-out rows (1-based, 0 for none)"
+function vc_gram_batch(D::HipVaryingDesign{T}, kind::Int32, bw::Vector{Float64}, z0::Union{Nothing,Vector{Float64}},
+                       leave_out::Union{Nothing,Vector{Int}}) where {T}
+  m, ep = length(bw), D.p * (D.degree + 1)
+  (z0 === nothing || length(z0) == m) && (leave_out === nothing || length(leave_out) == m) || throw(DimensionMismatch())
+  G = Array{Float64}(undef, ep, ep, m); c = Matrix{Float64}(undef, ep, m); sw = Vector{Float64}(undef, m)
+  idx = collect(Int64, 1:D.p)
+  lo = leave_out === nothing ? Int64[] : Int64.(leave_out .- 1)
+  zz = z0 === nothing ? Float64[] : z0
+  GC.@preserve zz lo check(D.handle, ccall((:cdh_vc_gram_batch, libcdhip), Int32,
+        (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Int32, Ptr{Cvoid}, Int64, Ptr{Int64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        D.handle, kind, m, bw, z0 === nothing ? C_NULL : pointer(zz), leave_out === nothing ? C_NULL : pointer(lo),
+        1, C_NULL, D.p, idx, G, c, sw))
+  G, c, sw
+end
+
+"the local polynomial fits around m points, ep x m: batches of VC_GRAM_BATCH points, each system scaled to unit diagonal"
+function locpoly_points(D::HipVaryingDesign, kind::Int32, bw::Vector{Float64}, z0, leave_out)
+  m, ep = length(bw), D.p * (D.degree + 1)
+  out = Matrix{Float64}(undef, ep, m)
+  for s in 1:VC_GRAM_BATCH:m
+    t = s:min(m, s + VC_GRAM_BATCH - 1)
+    G, c, _ = vc_gram_batch(D, kind, bw[t], z0 === nothing ? nothing : z0[t], leave_out === nothing ? nothing : leave_out[t])
+    for (k, pt) in enumerate(t)
+      d = sqrt.([G[i, i, k] for i in 1:ep])
+      out[:, pt] .= ((view(G, :, :, k) ./ (d * d')) \ (view(c, :, k) ./ d)) ./ d
+    end
+  end
+  out
+end
+
+"locpoly(X, z, y, zgrid, degree, kernel) (:217-235) for a design in HBM: ep x length(zgrid)"
+function CoordinateDescent.locpoly(D::HipVaryingDesign{T}, y::Vector{T}, zgrid::Vector{T},
+                                   kernel::CoordinateDescent.SmoothingKernel{T}) where {T}
+  length(y) == D.n || throw(DimensionMismatch())
+  GC.@preserve y check(D.handle, ccall((:cdh_set_y, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), D.handle, y))
+  T.(locpoly_points(D, kernel_code(kernel), fill(Float64(kernel.h), length(zgrid)), Float64.(zgrid), nothing))
+end
+
+"lvocv_locpoly(X, z, y, degree, hArr, kernelType) (:348-380) for a design in HBM: the left-out row gets weight zero (:432-436)"
+function CoordinateDescent.lvocv_locpoly(D::HipVaryingDesign{T}, y::Vector{T}, hArr::Vector{T},
+                                         kernelType::Type{<:CoordinateDescent.SmoothingKernel}) where {T}
+  length(y) == D.n || throw(DimensionMismatch())
+  h, n, Q1 = D.handle, D.n, D.degree + 1
+  GC.@preserve y check(h, ccall((:cdh_set_y, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), h, y))
+  Xb = Matrix{T}(undef, n, D.p)                                   # the base columns, fetched once: column (j-1)(degree+1)+1
+  GC.@preserve Xb for j in 1:D.p
+    check(h, ccall((:cdh_get_X_cols, libcdhip), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64),
+                   h, (j - 1) * Q1, 1, pointer(Xb, (j - 1) * n + 1), n))
+  end
+  kind = kernel_code(CoordinateDescent.createKernel(kernelType, hArr[1]))
+  bw = repeat(Float64.(hArr), inner=n)                            # all (bandwidth, observation) pairs
+  hbeta = locpoly_points(D, kind, bw, nothing, repeat(collect(1:n), outer=length(hArr)))
+  MSE = zeros(length(hArr))
+  for indH in 1:length(hArr), i in 1:n                            # in index order per bandwidth (:362-376)
+    Yh = dot(Float64.(view(Xb, i, :)), view(hbeta, 1:Q1:size(hbeta, 1), (indH - 1) * n + i))
+    MSE[indH] += (Yh - y[i])^2
+  end
+  MSE
+end
+
 # Optional knobs (no reference counterpart): blocked sweep width, screened full passes, the gradient
 # cache of repeated solves, hipGraph replay, reuse of the carried residual by warm starts (what LassoPath
 # wants: src/lasso.jl:250-252).
