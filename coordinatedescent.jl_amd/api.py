@@ -578,14 +578,9 @@ class CDVaryingCoefficientLoss(CDWeightedLSLoss):
         check(self._L.cdh_vc_set_point_loo(self._h, kernel._kind, kernel.h, int(row), _vp(std), _vp(scores)), self._h)
         return std, scores
 
-    def expanded_gram(self, kernel, z0=0.0, *, leave_out=None, wpow=1, e=None, base_cols=None, rhs=True):
-        """_expand_Xt_w_X! / _expand_Xt_w_Y! (src/varying_coefficient_lasso.jl:572-647) of the listed base columns around z0,
-        straight from the resident base design (cdh_vc_gram): -> (G, c, Σω), G the ep x ep weighted Gram matrix of the expanded
-        design, ep = len(base_cols) (degree + 1), c its right-hand side (None with rhs=False), ω_i = K(z_i, z0)^wpow · e_i.
-        `leave_out` (a 0-based row) moves z0 to the stored z[row] (the z0 given is then ignored) and gives that row weight zero; `base_cols` are 0-based base
-        columns (default: all; at most 64), `e` an optional n-vector.  A read-only query: the handle's weights, expanded
-        columns, residual, cache and iterate stay as they are."""
-        _check_kernel(kernel)
+    def _gram_columns_and_e(self, base_cols, e):
+        """What expanded_gram and expanded_gram_batch share: -> (the listed base columns 1-based, their number mb,
+        ep = mb (degree + 1), e as an n-vector of the design's type or None)."""
         cols = np.arange(self.p_base) if base_cols is None else np.atleast_1d(np.asarray(base_cols))
         if cols.dtype == bool:
             cols = np.nonzero(cols)[0]
@@ -597,6 +592,17 @@ class CDVaryingCoefficientLoss(CDWeightedLSLoss):
             ee = np.ascontiguousarray(np.asarray(e), dtype=self.dtype)
             if ee.shape != (self.n,):
                 raise DimensionMismatch("length(e) != size(X, 1)")
+        return idx1, mb, ep, ee
+
+    def expanded_gram(self, kernel, z0=0.0, *, leave_out=None, wpow=1, e=None, base_cols=None, rhs=True):
+        """_expand_Xt_w_X! / _expand_Xt_w_Y! (src/varying_coefficient_lasso.jl:572-647) of the listed base columns around z0,
+        straight from the resident base design (cdh_vc_gram): -> (G, c, Σω), G the ep x ep weighted Gram matrix of the expanded
+        design, ep = len(base_cols) (degree + 1), c its right-hand side (None with rhs=False), ω_i = K(z_i, z0)^wpow · e_i.
+        `leave_out` (a 0-based row) moves z0 to the stored z[row] (the z0 given is then ignored) and gives that row weight zero; `base_cols` are 0-based base
+        columns (default: all; at most 64), `e` an optional n-vector.  A read-only query: the handle's weights, expanded
+        columns, residual, cache and iterate stay as they are."""
+        _check_kernel(kernel)
+        idx1, mb, ep, ee = self._gram_columns_and_e(base_cols, e)
         G = np.zeros((ep, ep), order="F")
         c = np.zeros(ep) if rhs else None
         sw = C.c_double()
@@ -634,17 +640,7 @@ class CDVaryingCoefficientLoss(CDWeightedLSLoss):
         hh = full[0]
         zz = full[1] if z0 is not None else None
         ll = full[-1] if leave_out is not None else None
-        cols = np.arange(self.p_base) if base_cols is None else np.atleast_1d(np.asarray(base_cols))
-        if cols.dtype == bool:
-            cols = np.nonzero(cols)[0]
-        idx1 = np.ascontiguousarray(cols.astype(np.int64) + 1)
-        mb = idx1.shape[0]
-        ep = mb * (self.degree + 1)
-        ee = None
-        if e is not None:
-            ee = np.ascontiguousarray(np.asarray(e), dtype=self.dtype)
-            if ee.shape != (self.n,):
-                raise DimensionMismatch("length(e) != size(X, 1)")
+        idx1, mb, ep, ee = self._gram_columns_and_e(base_cols, e)
         G = np.zeros((m, ep, ep))
         c = np.zeros((m, ep)) if rhs else None
         sw = np.zeros(m)

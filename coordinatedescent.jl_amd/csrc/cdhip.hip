@@ -257,18 +257,23 @@ struct SmallPath {
 // best.  Where a setting seeds state that the ABI or a fallback changes later (the cache's mode, the device loop, the
 // one-launch solve), the handle's state starts from it; the rest is read from here.
 constexpr int64_t kGcCovRefresh = 200000;   // covariance-form visits after which g is re-read from X
-// What cdh_vc_gram needs besides the handle's data (vc_gram.hpp): the partial records and their sums, the listed columns, the
-// optional extra weights e, and pinned staging.  Allocated together by the first call, or not at all.
+// The scratch of cdh_vc_gram and cdh_vc_gram_batch besides the handle's data (vc_gram.hpp), in two tiers, each allocated together
+// by the first call that needs it, or not at all.  Who owns what:
+//   VcGramScratch       the first call of either export.  Its input block (the listed columns with one point behind them: one copy
+//                       takes both to the device) and e serve both exports; partials (16 MiB), out and h_out (one summed record) and
+//                       the block's point are cdh_vc_gram's alone, so a handle that never calls the batch allocates no more.
+//   VcGramBatchScratch  the first cdh_vc_gram_batch (vc_gram_batch_types.hpp: vgb_scratch_*_bytes): the partial records of a launch
+//                       group, its summed records on the device and pinned, and the group's points.
+// vc_gram_run works in a VcGramBufs: the five buffers in which the tiers differ.
+struct VcGramInput { int64_t cols[kVgMaxCols]; VcGramPoint pt; };
 struct VcGramScratch {
     DevBuf<double> partials, out;
-    DevBuf<int64_t> cols;
+    DevBuf<VcGramInput> in;
     DevBuf<void> e;
     PinBuf<double> h_out;
-    PinBuf<int64_t> h_cols;
+    PinBuf<VcGramInput> h_in;
     bool ready = false;
 };
-// What cdh_vc_gram_batch adds to it (vc_gram_batch_types.hpp: vgb_scratch_*_bytes): the partial records of a launch group, its
-// summed records on the device and pinned, and the group's points.  Allocated together by the first batch call, or not at all.
 struct VcGramBatchScratch {
     DevBuf<double> partials, out;
     DevBuf<VcGramPoint> pts;
@@ -276,6 +281,7 @@ struct VcGramBatchScratch {
     PinBuf<VcGramPoint> h_pts;
     bool ready = false;
 };
+struct VcGramBufs { double *partials, *out, *h_out; VcGramPoint *pts, *h_pts; };
 
 struct Knobs {
     int lt = 2;                      // CDH_LT: k_gramstep's operand loads transposed through LDS: 0 off, 1 on, 2 by size
@@ -1962,6 +1968,10 @@ int32_t cdh_vc_set_point_loo(cdh_handle h, int32_t kernel_kind, double bandwidth
 // The weighted Gram matrix and right-hand side of the expanded design around one point, straight from the base design
 // (_expand_Xt_w_X!, _expand_Xt_w_Y!: varying_coefficient_lasso.jl:572-647): one pass over the listed base columns, z and y.
 // Reads the handle's data and writes only its own scratch: residual, cache, weights, expanded columns and iterate stay.
+// A batch of points per launch (the loops of locpoly on a grid, lvocv_locpoly and split_locpoly,
+// varying_coefficient_lasso.jl:217-235, 348-380, 383-409, over :572-647) is the same body over more points: point t of
+// cdh_vc_gram_batch is cdh_vc_gram at (bandwidth[t], z0[t], leave_out_row0[t]), bit for bit.
+static_assert(kVgbMaxPoints == CDH_VC_GRAM_MAX_POINTS && kVgMaxCols == CDH_VC_GRAM_MAX_COLS, "cdhip.h names the limits the headers derive");
 static int32_t vc_gram_scratch(cdh_handle h) {
     VcGramScratch& g = h->vg;
     if (g.ready) return CDH_OK;
@@ -1969,68 +1979,14 @@ static int32_t vc_gram_scratch(cdh_handle h) {
     const size_t nrec = (size_t)vc_gram_rec(kVgMaxDegree, kVgMaxCols).n;
     HIPCHK(h, s.partials.alloc(sizeof(double) * (size_t)kVgPartialDoubles));
     HIPCHK(h, s.out.alloc(sizeof(double) * nrec));
-    HIPCHK(h, s.cols.alloc(sizeof(int64_t) * kVgMaxCols));
+    HIPCHK(h, s.in.alloc(sizeof(VcGramInput)));
     HIPCHK(h, s.e.alloc((size_t)h->ld * h->esz));
     HIPCHK(h, s.h_out.alloc(sizeof(double) * nrec));
-    HIPCHK(h, s.h_cols.alloc(sizeof(int64_t) * kVgMaxCols));
+    HIPCHK(h, s.h_in.alloc(sizeof(VcGramInput)));
     s.ready = true;
     g = std::move(s);
     return CDH_OK;
 }
-
-int32_t cdh_vc_gram(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, int64_t leave_out_row0, int32_t wpow,
-                    const void* host_e, int64_t mb, const int64_t* base_idx1, double* out_G, double* out_c,
-                    double* out_sum_w) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, out_G);
-    NEED_P(h, base_idx1);
-    CHK(vc_refuse_shards(h));
-    if (const char* bad = vc_gram_check(h->vc_degree, h->y_set, out_c != nullptr, h->vc_pbase, h->n, kernel_kind, bandwidth, z0,
-                                        leave_out_row0, wpow, mb, base_idx1))
-        return fail(h, CDH_BAD_ARG, bad);
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(vc_gram_scratch(h));
-    VcGramScratch& g = h->vg;
-    const int Q = h->vc_degree;
-    const VcGramRec R = vc_gram_rec(Q, mb);
-    const int G = vc_gram_grid(h->n, Q, mb);
-    if ((int64_t)G * R.n > kVgPartialDoubles) return fail(h, CDH_BAD_ARG, "cdh_vc_gram: partial buffer too small for this grid");
-    for (int64_t i = 0; i < mb; ++i) g.h_cols[i] = (base_idx1[i] - 1) * (Q + 1);     // base column j sits at column j (Q + 1)
-    HIPCHK(h, hipMemcpyAsync(g.cols, g.h_cols, sizeof(int64_t) * (size_t)mb, hipMemcpyHostToDevice, h->stream));
-    if (host_e) HIPCHK(h, hipMemcpyAsync(g.e, host_e, (size_t)h->n * h->esz, hipMemcpyHostToDevice, h->stream));
-    if (h->prof) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    CHK(dispatch(h, [&](auto* t) {
-        using T = std::remove_pointer_t<decltype(t)>;
-        auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3(kVgThreads), 0, h->stream, (const T*)h->X, h->ld, h->n,
-                               (const T*)h->vc_z, out_c ? (const T*)h->y : (const T*)nullptr,
-                               host_e ? (const T*)g.e : (const T*)nullptr, (const int64_t*)g.cols, (int)mb, (int)kernel_kind,
-                               bandwidth, z0, (int)wpow, leave_out_row0, (double*)g.partials);
-        };
-        if (Q == 0) go(k_vc_moments<T, 0>); else if (Q == 1) go(k_vc_moments<T, 1>);
-        else if (Q == 2) go(k_vc_moments<T, 2>); else go(k_vc_moments<T, 3>);
-        return CDH_OK;
-    }));
-    hipLaunchKernelGGL(k_vc_moments_reduce, dim3((unsigned)((R.n + kVgThreads - 1) / kVgThreads)), dim3(kVgThreads), 0, h->stream,
-                       (const double*)g.partials, G, R.n, (double*)g.out);
-    HIPCHK(h, hipGetLastError());
-    if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipMemcpyAsync(g.h_out, g.out, sizeof(double) * (size_t)R.n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->prof) {                       // cdh_profile_begin/end: the device time of the two launches
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        h->prof_ms += ms;
-        h->prof_launches += 2;
-    }
-    vc_gram_scatter(Q, mb, g.h_out, out_G, out_c);
-    if (out_sum_w) *out_sum_w = g.h_out[R.off_w];
-    return CDH_OK;
-}); }
-
-// A batch of points per launch: point t is cdh_vc_gram at (bandwidth[t], z0[t], leave_out_row0[t]), bit for bit
-// (vc_gram.hpp: k_vc_moments_batch; the loops of locpoly on a grid, lvocv_locpoly and split_locpoly,
-// varying_coefficient_lasso.jl:217-235, 348-380, 383-409, over :572-647).  The plan of the call is vc_gram_batch_types.hpp's.
-static_assert(kVgbMaxPoints == CDH_VC_GRAM_MAX_POINTS && kVgMaxCols == CDH_VC_GRAM_MAX_COLS, "cdhip.h names the limits the headers derive");
 static int32_t vc_gram_batch_scratch(cdh_handle h) {
     VcGramBatchScratch& g = h->vgb;
     if (g.ready) return CDH_OK;
@@ -2045,6 +2001,105 @@ static int32_t vc_gram_batch_scratch(cdh_handle h) {
     return CDH_OK;
 }
 
+// The body of both exports, after their checks and their scratch: the points t < m in `ngroups` launch groups, each laid out
+// by group(h, m, mb, grp, &L) (CDH_OK, or the export's refusal), in the buffers b and the regime the export names.  Per call
+// the columns and e go to the device once; per group the points, k_vc_moments, k_vc_moments_reduce, one copy back, one
+// synchronise.  Where b's point is the one behind the columns (cdh_vc_gram), one copy takes columns and point `together`.
+struct VcGramGroup { int64_t first, pts, per, gy; };   // points first .. first + pts - 1 on a grid (G, gy), `per` a share (resident)
+typedef int32_t (*VcGramPlan)(cdh_handle h, int64_t m, int64_t mb, int64_t grp, VcGramGroup* L);
+static int32_t vc_gram_run(cdh_handle h, int32_t kernel_kind, int64_t m, const double* bandwidth, const double* z0,
+                           const int64_t* leave_out_row0, int32_t wpow, const void* host_e, int64_t mb, const int64_t* base_idx1,
+                           double* out_G, double* out_c, double* out_sum_w, const VcGramBufs& b, bool resident, int64_t ngroups,
+                           VcGramPlan group) {
+    VcGramScratch& g = h->vg;
+    VcGramInput* const d_in = g.in;
+    const int Q = h->vc_degree;
+    const int64_t n = h->n, Q1 = Q + 1, ep = mb * Q1;
+    const VcGramRec R = vc_gram_rec(Q, mb);
+    const int G = vc_gram_grid(n, Q, mb);
+    const bool together = b.h_pts == &g.h_in->pt;
+    for (int64_t i = 0; i < mb; ++i) g.h_in->cols[i] = (base_idx1[i] - 1) * Q1;      // base column j sits at column j (Q + 1)
+    if (!together)
+        HIPCHK(h, hipMemcpyAsync(d_in->cols, g.h_in->cols, sizeof(int64_t) * (size_t)mb, hipMemcpyHostToDevice, h->stream));
+    if (host_e) HIPCHK(h, hipMemcpyAsync(g.e, host_e, (size_t)n * h->esz, hipMemcpyHostToDevice, h->stream));   // once per call
+    for (int64_t grp = 0; grp < ngroups; ++grp) {
+        VcGramGroup L;
+        CHK(group(h, m, mb, grp, &L));
+        for (int64_t t = 0; t < L.pts; ++t) {
+            const int64_t lo = leave_out_row0 ? leave_out_row0[L.first + t] : -1;
+            b.h_pts[t] = VcGramPoint{lo >= 0 ? 0.0 : z0[L.first + t], bandwidth[L.first + t], lo};
+        }
+        if (together) HIPCHK(h, hipMemcpyAsync(d_in, g.h_in, sizeof(VcGramInput), hipMemcpyHostToDevice, h->stream));
+        else HIPCHK(h, hipMemcpyAsync(b.pts, b.h_pts, sizeof(VcGramPoint) * (size_t)L.pts, hipMemcpyHostToDevice, h->stream));
+        if (h->prof) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+        CHK(dispatch(h, [&](auto* t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            auto go = [&](auto streamed, auto res) {
+                hipLaunchKernelGGL(resident ? res : streamed, dim3((unsigned)G, (unsigned)L.gy), dim3(kVgThreads), 0, h->stream,
+                                   (const T*)h->X, h->ld, n, (const T*)h->vc_z, out_c ? (const T*)h->y : (const T*)nullptr,
+                                   host_e ? (const T*)g.e : (const T*)nullptr, (const int64_t*)d_in->cols, (int)mb, (int)kernel_kind,
+                                   (int)wpow, (const VcGramPoint*)b.pts, (int)L.pts, (int)L.per, b.partials);
+            };
+            if (Q == 0) go(k_vc_moments<T, 0, false>, k_vc_moments<T, 0, true>);
+            else if (Q == 1) go(k_vc_moments<T, 1, false>, k_vc_moments<T, 1, true>);
+            else if (Q == 2) go(k_vc_moments<T, 2, false>, k_vc_moments<T, 2, true>);
+            else go(k_vc_moments<T, 3, false>, k_vc_moments<T, 3, true>);
+            return CDH_OK;
+        }));
+        hipLaunchKernelGGL(k_vc_moments_reduce, dim3((unsigned)((R.n + kVgThreads - 1) / kVgThreads), (unsigned)L.pts), dim3(kVgThreads),
+                           0, h->stream, (const double*)b.partials, G, R.n, b.out);
+        HIPCHK(h, hipGetLastError());
+        if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        HIPCHK(h, hipMemcpyAsync(b.h_out, b.out, sizeof(double) * (size_t)(L.pts * R.n), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->prof) {                   // cdh_profile_begin/end: the device time of the two launches
+            float ms = 0.f;
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            h->prof_ms += ms;
+            h->prof_launches += 2;
+        }
+        for (int64_t t = 0; t < L.pts; ++t) {
+            const double* rec = b.h_out + t * R.n;
+            vc_gram_scatter(Q, mb, rec, out_G + (L.first + t) * ep * ep, out_c ? out_c + (L.first + t) * ep : nullptr);
+            if (out_sum_w) out_sum_w[L.first + t] = rec[R.off_w];
+        }
+    }
+    return CDH_OK;
+}
+
+// One point: a batch of one in the small tier, always in the streamed regime (vc_gram_batch_types.hpp: vgb_resident)
+static int32_t vc_gram_one_group(cdh_handle, int64_t, int64_t, int64_t, VcGramGroup* L) {
+    *L = VcGramGroup{0, 1, 1, 1};
+    return CDH_OK;
+}
+int32_t cdh_vc_gram(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, int64_t leave_out_row0, int32_t wpow,
+                    const void* host_e, int64_t mb, const int64_t* base_idx1, double* out_G, double* out_c,
+                    double* out_sum_w) { return guarded(h, [&]() -> int32_t {
+    NEED_P(h, out_G);
+    NEED_P(h, base_idx1);
+    CHK(vc_refuse_shards(h));
+    if (const char* bad = vc_gram_check(h->vc_degree, h->y_set, out_c != nullptr, h->vc_pbase, h->n, kernel_kind, bandwidth, z0,
+                                        leave_out_row0, wpow, mb, base_idx1))
+        return fail(h, CDH_BAD_ARG, bad);
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(vc_gram_scratch(h));
+    VcGramScratch& g = h->vg;
+    if (vc_gram_grid(h->n, h->vc_degree, mb) * vc_gram_rec(h->vc_degree, mb).n > kVgPartialDoubles)
+        return fail(h, CDH_BAD_ARG, "cdh_vc_gram: partial buffer too small for this grid");
+    return vc_gram_run(h, kernel_kind, 1, &bandwidth, &z0, &leave_out_row0, wpow, host_e, mb, base_idx1, out_G, out_c, out_sum_w,
+                       VcGramBufs{g.partials, g.out, g.h_out, &g.in->pt, &g.h_in->pt}, false, 1, vc_gram_one_group);
+}); }
+
+// Many points: the plan of the call is vc_gram_batch_types.hpp's
+static int32_t vc_gram_batch_group(cdh_handle h, int64_t m, int64_t mb, int64_t grp, VcGramGroup* L) {
+    const int Q = h->vc_degree;
+    const int64_t n = h->n, pts = vgb_group_size(n, Q, mb, m, grp), gy = vgb_grid_y(n, Q, mb, pts);
+    *L = VcGramGroup{vgb_group_first(n, Q, mb, grp), pts, vgb_share_points(n, Q, mb, pts), gy};
+    if (pts < 1 || vgb_rec_offset(n, Q, mb, pts, 0) > kVgbPartialDoubles || pts * vc_gram_rec(Q, mb).n > kVgbOutDoubles ||
+        pts > kVgbMaxGroupPoints || gy < 1 || gy > 65535 || vgb_share_begin(n, Q, mb, pts, gy) != pts)
+        return fail(h, CDH_BAD_ARG, "cdh_vc_gram_batch: the plan of this call does not fit its scratch");
+    return CDH_OK;
+}
 int32_t cdh_vc_gram_batch(cdh_handle h, int32_t kernel_kind, int64_t m, const double* bandwidth, const double* z0,
                           const int64_t* leave_out_row0, int32_t wpow, const void* host_e, int64_t mb,
                           const int64_t* base_idx1, double* out_G, double* out_c, double* out_sum_w) { return guarded(h, [&]() -> int32_t {
@@ -2062,65 +2117,10 @@ int32_t cdh_vc_gram_batch(cdh_handle h, int32_t kernel_kind, int64_t m, const do
     HIPCHK(h, hipSetDevice(h->device));
     CHK(vc_gram_scratch(h));
     CHK(vc_gram_batch_scratch(h));
-    VcGramScratch& g = h->vg;
     VcGramBatchScratch& b = h->vgb;
-    const int Q = h->vc_degree;
-    const int64_t n = h->n, Q1 = Q + 1, ep = mb * Q1;
-    const VcGramRec R = vc_gram_rec(Q, mb);
-    const int G = vc_gram_grid(n, Q, mb);
-    const bool resident = vgb_resident(n, Q, mb);
-    for (int64_t i = 0; i < mb; ++i) g.h_cols[i] = (base_idx1[i] - 1) * Q1;          // base column j sits at column j (Q + 1)
-    HIPCHK(h, hipMemcpyAsync(g.cols, g.h_cols, sizeof(int64_t) * (size_t)mb, hipMemcpyHostToDevice, h->stream));
-    if (host_e) HIPCHK(h, hipMemcpyAsync(g.e, host_e, (size_t)n * h->esz, hipMemcpyHostToDevice, h->stream));   // once per call
-    const int64_t ngroups = vgb_groups(n, Q, mb, m);
-    for (int64_t grp = 0; grp < ngroups; ++grp) {
-        const int64_t first = vgb_group_first(n, Q, mb, grp), pts = vgb_group_size(n, Q, mb, m, grp);
-        const int64_t per = vgb_share_points(n, Q, mb, pts), gy = vgb_grid_y(n, Q, mb, pts);
-        if (pts < 1 || vgb_rec_offset(n, Q, mb, pts, 0) > kVgbPartialDoubles || pts * R.n > kVgbOutDoubles ||
-            pts > kVgbMaxGroupPoints || gy < 1 || gy > 65535 || vgb_share_begin(n, Q, mb, pts, gy) != pts)
-            return fail(h, CDH_BAD_ARG, "cdh_vc_gram_batch: the plan of this call does not fit its scratch");
-        for (int64_t t = 0; t < pts; ++t) {
-            const int64_t lo = leave_out_row0 ? leave_out_row0[first + t] : -1;
-            b.h_pts[t] = VcGramPoint{lo >= 0 ? 0.0 : z0[first + t], bandwidth[first + t], lo};
-        }
-        HIPCHK(h, hipMemcpyAsync(b.pts, b.h_pts, sizeof(VcGramPoint) * (size_t)pts, hipMemcpyHostToDevice, h->stream));
-        if (h->prof) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-        CHK(dispatch(h, [&](auto* t) {
-            using T = std::remove_pointer_t<decltype(t)>;
-            auto go = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, dim3((unsigned)G, (unsigned)gy), dim3(kVgThreads), 0, h->stream, (const T*)h->X, h->ld, n,
-                                   (const T*)h->vc_z, out_c ? (const T*)h->y : (const T*)nullptr,
-                                   host_e ? (const T*)g.e : (const T*)nullptr, (const int64_t*)g.cols, (int)mb, (int)kernel_kind,
-                                   (int)wpow, (const VcGramPoint*)b.pts, (int)pts, (int)per, (double*)b.partials);
-            };
-            if (resident) {
-                if (Q == 0) go(k_vc_moments_batch<T, 0, true>); else if (Q == 1) go(k_vc_moments_batch<T, 1, true>);
-                else if (Q == 2) go(k_vc_moments_batch<T, 2, true>); else go(k_vc_moments_batch<T, 3, true>);
-            } else {
-                if (Q == 0) go(k_vc_moments_batch<T, 0, false>); else if (Q == 1) go(k_vc_moments_batch<T, 1, false>);
-                else if (Q == 2) go(k_vc_moments_batch<T, 2, false>); else go(k_vc_moments_batch<T, 3, false>);
-            }
-            return CDH_OK;
-        }));
-        hipLaunchKernelGGL(k_vc_moments_reduce, dim3((unsigned)((R.n + kVgThreads - 1) / kVgThreads), (unsigned)pts), dim3(kVgThreads),
-                           0, h->stream, (const double*)b.partials, G, R.n, (double*)b.out);
-        HIPCHK(h, hipGetLastError());
-        if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-        HIPCHK(h, hipMemcpyAsync(b.h_out, b.out, sizeof(double) * (size_t)(pts * R.n), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->prof) {
-            float ms = 0.f;
-            HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            h->prof_ms += ms;
-            h->prof_launches += 2;
-        }
-        for (int64_t t = 0; t < pts; ++t) {
-            const double* rec = b.h_out + t * R.n;
-            vc_gram_scatter(Q, mb, rec, out_G + (first + t) * ep * ep, out_c ? out_c + (first + t) * ep : nullptr);
-            if (out_sum_w) out_sum_w[first + t] = rec[R.off_w];
-        }
-    }
-    return CDH_OK;
+    return vc_gram_run(h, kernel_kind, m, bandwidth, z0, leave_out_row0, wpow, host_e, mb, base_idx1, out_G, out_c, out_sum_w,
+                       VcGramBufs{b.partials, b.out, b.h_out, b.pts, b.h_pts}, vgb_resident(h->n, h->vc_degree, mb),
+                       vgb_groups(h->n, h->vc_degree, mb, m), vc_gram_batch_group);
 }); }
 
 // _getSigma(w, r) (utils.jl:167-175): sum w, sum w r^2 at the current residual

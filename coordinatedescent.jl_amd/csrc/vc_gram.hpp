@@ -34,15 +34,16 @@
 // is the longest chain of sequential additions any output entry goes through (G workgroups, S slices, nchunks chunks of
 // kVgRows rows: vc_gram_chain): a thread's rows, the S slices, the reduce kernel's G / 4 records and its last two additions.
 //
-// A batch of points per launch (cdh_vc_gram_batch, vc_gram_batch_types.hpp).  k_vc_moments_batch serves the loops that call
-// the above once per point -- locpoly on a grid (varying_coefficient_lasso.jl:217-235), lvocv_locpoly (:348-380),
-// split_locpoly (:383-409), each over _expand_Xt_w_X! / _expand_Xt_w_Y! (:572-647) -- with the points' (z0, h, left-out row)
-// read from a device array and the partial records laid out [point][workgroup][entry].  Every entry of a point goes through
-// the additions of k_vc_moments in their order (the pieces below are shared, not restated): the same deal of chunks to
+// A batch of points per launch (cdh_vc_gram_batch, vc_gram_batch_types.hpp).  k_vc_moments takes a list of points, so it also
+// serves the loops that call the above once per point -- locpoly on a grid (varying_coefficient_lasso.jl:217-235),
+// lvocv_locpoly (:348-380), split_locpoly (:383-409), each over _expand_Xt_w_X! / _expand_Xt_w_Y! (:572-647) -- with the
+// points' (z0, h, left-out row) read from a device array and the partial records laid out [point][workgroup][entry].  In
+// either regime every entry of a point goes through the additions above in their order: the same deal of chunks to
 // workgroups, the same slices, the same slice-order sum, and k_vc_moments_reduce per point -- so a point's result is
-// bit-identical to cdh_vc_gram's, wherever it stands in a batch.  Two regimes, one launch per group of points either way:
-//   streamed  <.., false>: workgroups walk several chunks; grid.y = the points, and a (workgroup, point) is k_vc_moments' body.
-//             The base columns are re-read per point, out of L2 / Infinity Cache for the designs this is for.
+// bit-identical wherever it stands in a batch.  Two regimes, one launch per group of points either way:
+//   streamed  <.., false>: workgroups walk several chunks; grid.y = the points, and a (workgroup, point) is
+//             vg_point_over_chunks.  The base columns are re-read per point, out of L2 / Infinity Cache for the designs this is
+//             for.  A single-point call (cdh_vc_gram) is this instantiation on a grid (G, 1), whatever n is.
 //   resident  <.., true>: every workgroup of the single-point deal holds ONE chunk (vc_gram_chunks(n) <= vc_gram_grid(n, Q, mb):
 //             n <= 32768 rows, fewer where the partial buffer caps the grid).  grid.x = the chunks, grid.y = shares of the point
 //             list.  A workgroup stages its 64 rows of the listed columns, y and the ones once, keeps z and e of its rows in
@@ -53,7 +54,7 @@
 //             LDS: 34 KiB rows + 8 KiB tables + 32 KiB slice sums = 74.5 KiB, two workgroups per CU at most.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; no scratch in any instantiation; fp32 within 3 registers of fp64):
 //                          Q = 0        Q = 1        Q = 2              Q = 3               LDS
-//   k_vc_moments, streamed 100 VGPRs    168          240                256 + 41 AGPRs      38.5 KiB
+//   streamed               100 VGPRs    168          240                256 + 41 AGPRs      38.5 KiB
 //   resident               147          213          255 + 28 AGPRs     256 + 90 AGPRs      74.5 KiB
 // (the accumulators alone are 32 (2Q + 1) VGPRs: 224 at Q = 3.)  Waves per SIMD: 4, 3, 2, 1 streamed; 2, 2, 1, 1 resident --
 // at Q >= 2 the resident kernel's registers, not its LDS, hold a CU to one workgroup.
@@ -72,7 +73,7 @@ constexpr int kVgWs = 8;      // doubles per row of the weight table: w d^s, s =
 static_assert(vc_gram_groups(kVgMaxCols) * kVgTile <= kVgLd && 2 * kVgMaxDegree + 1 <= kVgWs, "");
 static_assert(kVgTile * kVgTile * kVgThreads <= kVgRows * kVgLd, "the slices' sums of one order fit the staging area");
 
-// ---- the pieces k_vc_moments and k_vc_moments_batch are both made of ------------------------------------------------------------
+// ---- the pieces of k_vc_moments -------------------------------------------------------------------------------------------
 // what a thread works on: slice `slice` of the pair (bj, bk) of column groups, bj <= bk
 struct VgThread {
     int NB, NP, S, slice, pair, bj, bk;
@@ -204,8 +205,8 @@ __device__ __forceinline__ void vg_write_rec(const double (&acc)[kVgTile][kVgTil
         }
 }
 
-// One point over the chunks blockIdx.x, blockIdx.x + gridDim.x, ..: the whole of k_vc_moments, and of a (workgroup, point) of
-// the streamed batch.  scol has been written by the caller (the first barrier below covers it).
+// One point over the chunks blockIdx.x, blockIdx.x + gridDim.x, ..: the whole of a (workgroup, point) of the streamed regime.
+// scol has been written by the caller (the first barrier below covers it).
 template <typename T, int Q>
 __device__ __forceinline__ void vg_point_over_chunks(const T* __restrict__ X, int64_t ld, int64_t n, const T* __restrict__ z,
                                                      const T* __restrict__ y, const T* __restrict__ e, const int64_t* scol, int mb,
@@ -243,30 +244,16 @@ __device__ __forceinline__ void vg_point_over_chunks(const T* __restrict__ X, in
     if (t.slice == 0) vg_write_rec<Q>(acc, rec, mb, t);
 }
 
-template <typename T, int Q>
-__global__ __launch_bounds__(kVgThreads) void k_vc_moments(const T* __restrict__ X, int64_t ld, int64_t n,
-                                                           const T* __restrict__ z, const T* __restrict__ y,
-                                                           const T* __restrict__ e, const int64_t* __restrict__ cols,
-                                                           int mb, int kind, double h, double z0, int wpow, int64_t leave_out,
-                                                           double* __restrict__ partials) {
-    __shared__ __attribute__((aligned(16))) double xs[kVgRows * kVgLd];
-    __shared__ __attribute__((aligned(16))) double ws[kVgRows * kVgWs];
-    __shared__ int64_t scol[kVgMaxCols];
-    if ((int)threadIdx.x < mb) scol[threadIdx.x] = cols[threadIdx.x];
-    vg_point_over_chunks<T, Q>(X, ld, n, z, y, e, scol, mb, kind, h, z0, wpow, leave_out,
-                               partials + (int64_t)blockIdx.x * vc_gram_rec(Q, mb).n, xs, ws);
-}
-
 // The points pts[0 .. npts) of one launch group; the record of (point, workgroup) at partials + (point gridDim.x + blockIdx.x) nrec.
 // RES = false: grid (G, npts), `per` unused.  RES = true: grid (G, shares), G workgroups of one chunk each, share blockIdx.y walks
 // points blockIdx.y per .. min(npts, (blockIdx.y + 1) per) - 1 (vc_gram_batch_types.hpp: vgb_share_points, vgb_share_begin).
 template <typename T, int Q, bool RES>
-__global__ __launch_bounds__(kVgThreads) void k_vc_moments_batch(const T* __restrict__ X, int64_t ld, int64_t n,
-                                                                 const T* __restrict__ z, const T* __restrict__ y,
-                                                                 const T* __restrict__ e, const int64_t* __restrict__ cols,
-                                                                 int mb, int kind, int wpow,
-                                                                 const VcGramPoint* __restrict__ pts, int npts, int per,
-                                                                 double* __restrict__ partials) {
+__global__ __launch_bounds__(kVgThreads) void k_vc_moments(const T* __restrict__ X, int64_t ld, int64_t n,
+                                                           const T* __restrict__ z, const T* __restrict__ y,
+                                                           const T* __restrict__ e, const int64_t* __restrict__ cols,
+                                                           int mb, int kind, int wpow,
+                                                           const VcGramPoint* __restrict__ pts, int npts, int per,
+                                                           double* __restrict__ partials) {
     constexpr int NS = 2 * Q + 1, TL = kVgTile;
     __shared__ __attribute__((aligned(16))) double xs[kVgRows * kVgLd];
     __shared__ __attribute__((aligned(16))) double ws[(RES ? 2 : 1) * kVgRows * kVgWs];

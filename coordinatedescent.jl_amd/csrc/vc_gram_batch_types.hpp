@@ -1,4 +1,4 @@
-// vc_gram_batch_types.hpp -- the host-only arithmetic of cdh_vc_gram_batch (vc_gram.hpp: k_vc_moments_batch): the argument
+// vc_gram_batch_types.hpp -- the host-only arithmetic of cdh_vc_gram_batch (vc_gram.hpp: k_vc_moments): the argument
 // check of a batch of points and the plan of a call -- which regime applies, how the batch is cut into launch groups, how a
 // group's points are dealt to the workgroups, and where every partial record sits.  No HIP in here:
 // tests/test_vc_gram_batch_host.py compiles it with g++ (a shim for ctypes, and a stand-alone program under the host
@@ -30,7 +30,10 @@ struct VcGramPoint {
 };
 
 // ---- the plan: all of it functions of (n, Q, mb, m) ---------------------------------------------------------------------------
-// resident: every workgroup of the single-point deal holds one chunk, so a workgroup can stage it once and walk many points
+// resident: every workgroup of the single-point deal holds one chunk, so a workgroup can stage it once and walk many points.
+// This is the batch's question: cdh_vc_gram does not ask it and passes "streamed" at every n.  With one point a workgroup stages
+// its chunk once either way, and the streamed instantiation keeps its smaller footprint (38.5 against 74.5 KiB of LDS, fewer
+// registers: vc_gram.hpp), so the single point runs as it always has.
 constexpr bool vgb_resident(int64_t n, int Q, int64_t mb) { return vc_gram_chunks(n) <= vc_gram_grid(n, Q, mb); }
 // points of a full launch group: what the partial buffer, the summed-record buffer and kVgbMaxGroupPoints allow (>= 8: vc_gram_grid
 // keeps G records within kVgPartialDoubles = kVgbPartialDoubles / 8)

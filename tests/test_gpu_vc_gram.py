@@ -1,5 +1,5 @@
-"""cdh_vc_gram (csrc/vc_gram.hpp: k_vc_moments, k_vc_moments_reduce) and the locpoly front ends on the device, against the
-long-double yardstick of tests/_vc_gram_numpy.py.
+"""cdh_vc_gram (csrc/vc_gram.hpp: k_vc_moments' streamed instantiation on one point, k_vc_moments_reduce) and the locpoly front
+ends on the device, against the long-double yardstick of tests/_vc_gram_numpy.py.
 
 Exact sums.  Epanechnikov h = 1 around z0 = 0.5 with z in {0, 0.5, 1}: d in {0, +-0.5}, K in {0.75, 0.5625}.  With |x| <= 3,
 |y| <= 4, e in 0 .. 3 every term is a multiple of 2^-14 (K^2: 2^-8, d^6: 2^-6) below 2^5, so every partial sum over fewer

@@ -1,9 +1,12 @@
-"""cdh_vc_gram_batch (csrc/vc_gram.hpp: k_vc_moments_batch) on the device.  The export promises that point t of a batch IS
+"""cdh_vc_gram_batch (csrc/vc_gram.hpp: k_vc_moments) on the device.  The export promises that point t of a batch IS
 cdh_vc_gram at that point, addition for addition, so the yardstick of most tests here is the single-point export itself,
-compared with tobytes() and no tolerance; tests/test_gpu_vc_gram.py pins that export to the long-double yardstick.  The exact
-sums of section 3 go straight to the yardstick (tests/_vc_gram_numpy.py) with the exactness argument of that file: every term
-a multiple of 2^-14 below 2^5, fewer than 2^20 rows.  Shapes come from the plan restated in tests/_vc_gram_batch_plan.py and
-every case asserts the regime it is named for."""
+compared with tobytes() and no tolerance; tests/test_gpu_vc_gram.py pins that export to the long-double yardstick.  The two
+exports run one body, and cdh_vc_gram always launches k_vc_moments' streamed instantiation on one point: in the streamed cases
+batch and single are the same code, in the resident cases (and wherever the shared scratch could carry state from one call to
+the next: section 2b) they are two code paths compared byte for byte.  The exact sums of section 3 go straight to the
+yardstick (tests/_vc_gram_numpy.py) with the exactness argument of that file: every term a multiple of 2^-14 below 2^5,
+fewer than 2^20 rows.  Shapes come from the plan restated in tests/_vc_gram_batch_plan.py and every case asserts the regime it
+is named for."""
 import ctypes as C
 
 import numpy as np
@@ -134,6 +137,41 @@ def test_a_points_bytes_do_not_depend_on_where_it_stands():
     e1 = pl2[0]["edges"][1]
     batch(m2, [0, e1 - 1, e1, e1 + 1, m2 - 1])
     f.close()
+
+
+# ---- 2b. the two exports share a scratch and leave nothing in it for each other ------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("Q,mb,wpow,kind", [(1, 5, 2, "gaussian"), (3, 64, 1, "epanechnikov")])
+def test_single_and_batch_calls_on_one_handle_leave_each_other_nothing(dtype, Q, mb, wpow, kind):
+    """n = 65: two chunks, the second of one row.  The single-point call keeps its point behind the columns in one block, the
+    batch has a point list of its own, and both read the columns and e from the same buffers: a single call after a batch must
+    not see the batch's e or a stale point, and a batch after a single call must not depend on it."""
+    n = R + 1
+    X, z, y, e = _random_data(40 + Q, n, mb, dtype)
+    h, z0, lo = _points(n, z)
+    h, z0, lo = np.append(h, [0.45, 0.3]), np.append(z0, [0.2, 0.8]), np.append(lo, [-1, -1])
+    assert h.shape[0] == 9 and {0, R - 1, R} <= set(lo.tolist()) and lo[0] == -1
+    pl = BP.plan(n, Q, mb, 9)
+    assert pl["resident"] and pl["G"] == 2 and len(pl["groups"]) == 1 and (VG.launch(n, Q, mb)["S"] > 1) == (mb == 5)
+    k0 = KIND[kind](float(h[0]))
+
+    f = cd.CDVaryingCoefficientLoss(y, X, z, Q)
+    first = f.expanded_gram(k0, float(z0[0]), wpow=wpow)
+    batch = f.expanded_gram_batch(KIND[kind], h, z0, leave_out=lo, wpow=wpow, e=e)
+    again = f.expanded_gram(k0, float(z0[0]), wpow=wpow)
+    with_e = f.expanded_gram(k0, float(z0[0]), wpow=wpow, e=e)
+    f.close()
+    assert all(_same(u, v) for u, v in zip(again, first))            # neither the batch's e nor a stale point is picked up
+    assert not _same(with_e[0], first[0])                            # (e does change the result)
+    assert all(_same(u[0], v) for u, v in zip(batch, with_e))        # the resident batch's entry is the streamed single point
+
+    g = cd.CDVaryingCoefficientLoss(y, X, z, Q)                      # a fresh handle: the batch first, then the single point
+    batch2 = g.expanded_gram_batch(KIND[kind], h, z0, leave_out=lo, wpow=wpow, e=e)
+    first2 = g.expanded_gram(k0, float(z0[0]), wpow=wpow)
+    with_e2 = g.expanded_gram(k0, float(z0[0]), wpow=wpow, e=e)
+    g.close()
+    assert all(_same(u, v) for u, v in zip(batch2, batch))
+    assert all(_same(u, v) for u, v in zip(first2, first)) and all(_same(u, v) for u, v in zip(with_e2, with_e))
 
 
 # ---- 3. exact sums against the yardstick -------------------------------------------------------------------------------------

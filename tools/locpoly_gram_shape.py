@@ -2,7 +2,8 @@
 """locpoly over a grid of 20 points at n = 1 000 000, p in {10, 50}, degree 1 and 2, fp64, Gaussian kernel, two routes on the
 same handle, interleaved:
 
- A. cdh_vc_gram (k_vc_moments: one pass over the p base columns, z and y) + the host solve of the scaled normal equations;
+ A. cdh_vc_gram (k_vc_moments, streamed, on one point: one pass over the p base columns, z and y) + the host solve of the scaled
+    normal equations;
  B. the best route the C ABI offered before it: cdh_vc_set_point (writes the p Q expanded columns) + cdh_initialize (r = y) +
     cdh_gram_weighted over all p (Q + 1) columns (<= 64 per launch, pairs of 32-column groups beyond) + the same host solve;
 
