@@ -209,27 +209,10 @@ struct GradCache {
 
 // The one-launch solve of problems that fit on chip (small_solve.hpp): the full Gram matrix of the resident X, the
 // control block of the solve kernel, pinned staging for what comes back.
-constexpr int kSmallMaxP = 1024;
-constexpr int kSmallMaxLam = 64;                 // solves per launch (a cold start's numSteps + 1 = 51 by default)
+#include "small_plan.hpp"   // SmallCtl, kSmallMaxP, kSmallMaxLam; the kernel's LDS plan, unroll width and io offsets: host-only arithmetic
 // How much X the Gram form is worth building for is a cost comparison (small_worth_building, small_solve.hpp); X that fits
 // kSmallAlwaysBytes takes it regardless (the reference's own test and benchmark shapes).
 constexpr size_t kSmallAlwaysBytes = (size_t)16 << 20;
-
-struct SmallCtl {
-    double lambdas[kSmallMaxLam];
-    int32_t nlam, randomize, loss, has_omega;
-    int64_t maxIter;
-    double optTol, n_total;
-    uint64_t rng;                // splitmix64 state of the substitute RandomIterator: in / out
-    int32_t nnz_in, g_from_c;   // g_from_c: `ga` holds (X'y, a) and g = X'y - G beta is formed in the kernel; else ga holds (X'r, a)
-    // out
-    int64_t passes, full_passes, visits;
-    int32_t converged, domain_error;
-    double maxH;
-    int32_t nnz, precision_lost;
-    int64_t steps;               // visit steps taken (each settles a run of positions and makes at most one move)
-    uint64_t cycles, ticks;      // shader cycles (s_memtime) and 100 MHz ticks (s_memrealtime) the kernel ran for
-};
 
 struct SmallPath {
     bool enabled = true;             // Knobs::small_path, cdh_set_small_path

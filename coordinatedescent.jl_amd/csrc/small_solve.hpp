@@ -436,9 +436,7 @@ __global__ __launch_bounds__(64) void k_solve_small(SmallCtl* ctl, int p, int nc
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-inline size_t small_sup_off() { return (sizeof(SmallCtl) + 15) / 16 * 16; }
-inline size_t small_beta_off(int64_t p) { return small_sup_off() + ((size_t)p * sizeof(int32_t) + 15) / 16 * 16; }
-inline size_t small_io_bytes(int64_t p) { return small_beta_off(p) + (size_t)p * sizeof(double); }
+// (small_sup_off, small_beta_off, small_io_bytes -- the block that crosses the bus per solve -- are small_plan.hpp's)
 
 // Is the full Gram matrix worth building for this X?  X that fits kSmallAlwaysBytes: always (the build is a fraction of
 // a millisecond: the reference's own shapes).  Beyond that it is rent or buy.  A solve on the streamed kernels is cheap where
@@ -500,6 +498,19 @@ int32_t small_prepare(cdh_handle h) {     // buffers, X'y and diag(G) of the cur
     if (!sp.d_io) {
         CHK(gc_size(h));                  // k_cross's scratch (d_cross, d_cross_part, d_cols) is the gradient cache's
         if (!c.d_cross) { sp.enabled = false; return CDH_OK; }
+        // dynamic LDS of the solve kernel: the p-sized state, then as many Gram columns as the rest of the CU's LDS holds
+        // (the whole 160 KB when the runtime grants it, else what fits the default 64 KB)
+        size_t budget = kSmallLdsWide;
+        auto widen = [&](auto kernel) {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)budget) == hipSuccess;
+        };
+        if (!(widen(&k_solve_small<false, 4>) && widen(&k_solve_small<true, 4>) && widen(&k_solve_small<false, 8>) &&
+              widen(&k_solve_small<true, 8>) && widen(&k_solve_small<false, 16>) && widen(&k_solve_small<true, 16>))) {
+            (void)hipGetLastError();
+            budget = kSmallLdsDefault;
+        }
+        const SmallPlan plan = small_plan(h->p, budget);
+        if (!plan.fits) { sp.enabled = false; return CDH_OK; }     // (p >= 964 on 64 KB: the state alone is larger; nothing is allocated)
         DevBuf<double> G, ca; DevBuf<char> d_io; PinBuf<char> h_io;
         bool fits = G.alloc(sizeof(double) * (size_t)h->p * (size_t)h->p) == hipSuccess &&
                     ca.alloc(sizeof(double) * (2 * (size_t)h->p + 1)) == hipSuccess &&
@@ -509,25 +520,12 @@ int32_t small_prepare(cdh_handle h) {     // buffers, X'y and diag(G) of the cur
         if (!fits) { sp.enabled = false; return CDH_OK; }
         sp.d_G = std::move(G); sp.d_ca = std::move(ca); sp.d_io = std::move(d_io); sp.h_io = std::move(h_io);
         sp.d_ctl = (SmallCtl*)sp.d_io; sp.h_ctl = (SmallCtl*)sp.h_io;
+        sp.ncache = plan.ncache; sp.lds_bytes = plan.lds_bytes;
         void* dev_view = nullptr;          // the pinned block as the device addresses it (zero-copy solves)
         if (hipHostGetDevicePointer(&dev_view, sp.h_io, 0) == hipSuccess) sp.hd_io = static_cast<char*>(dev_view);
         else (void)hipGetLastError();
         sp.d_sup = reinterpret_cast<int32_t*>(sp.d_io + small_sup_off()); sp.h_sup = reinterpret_cast<int32_t*>(sp.h_io + small_sup_off());
         sp.d_beta = reinterpret_cast<double*>(sp.d_io + small_beta_off(h->p)); sp.h_beta = reinterpret_cast<double*>(sp.h_io + small_beta_off(h->p));
-        // dynamic LDS of the solve kernel: the p-sized state, then as many Gram columns as the rest of the CU's LDS holds
-        // (the whole 160 KB when the runtime grants it, else what fits the default 64 KB)
-        const size_t state = (size_t)h->p * (4 * sizeof(double) + 9 * sizeof(int32_t)) + 2 * sizeof(int32_t);
-        size_t budget = (size_t)160 * 1024;
-        auto widen = [&](auto kernel) {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)budget) == hipSuccess;
-        };
-        if (!(widen(&k_solve_small<false, 4>) && widen(&k_solve_small<true, 4>) && widen(&k_solve_small<false, 8>) &&
-              widen(&k_solve_small<true, 8>) && widen(&k_solve_small<false, 16>) && widen(&k_solve_small<true, 16>))) {
-            (void)hipGetLastError();
-            budget = (size_t)64 * 1024;
-        }
-        sp.ncache = (int)std::min<size_t>(256, (budget - state) / ((size_t)h->p * sizeof(double)));
-        sp.lds_bytes = (unsigned)(state + (size_t)sp.ncache * (size_t)h->p * sizeof(double));
     }
     if (!sp.c_valid) {                // c = X'y (X'Wy), a = diag(G), y'y: one dots pass over X with y in r's place, once per y
         CHK(col_dots(h, 0, h->p, h->y, h->has_w));
@@ -597,9 +595,11 @@ int32_t small_solve(cdh_handle h, const cdh_options* o, const double* lambdas, i
                            h->omega, qin, h->beta, k_sup, k_beta);
     };
     const bool sq = h->loss == CDH_SQRT;
-    if (h->p <= 256) { if (sq) go(k_solve_small<true, 4>); else go(k_solve_small<false, 4>); }
-    else if (h->p <= 512) { if (sq) go(k_solve_small<true, 8>); else go(k_solve_small<false, 8>); }
-    else { if (sq) go(k_solve_small<true, 16>); else go(k_solve_small<false, 16>); }
+    switch (small_unroll(h->p)) {
+        case 4: if (sq) go(k_solve_small<true, 4>); else go(k_solve_small<false, 4>); break;
+        case 8: if (sq) go(k_solve_small<true, 8>); else go(k_solve_small<false, 8>); break;
+        default: if (sq) go(k_solve_small<true, 16>); else go(k_solve_small<false, 16>); break;
+    }
     HIPCHK(h, hipGetLastError());
     if (!zc) HIPCHK(h, hipMemcpyAsync(sp.h_io, sp.d_io, small_io_bytes(h->p), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
