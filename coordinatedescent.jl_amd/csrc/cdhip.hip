@@ -145,7 +145,7 @@ class GraphCache {
 // only.  Same iterates as visiting one by one: a coordinate is skipped only when the exact path would have
 // left it at zero (1e-9 relative margin, as for the dots-only screens), everything else is visited by the
 // same kernels.  fp64 storage, no observation weights.
-#include "cov_solve_types.hpp"   // CovSolveCtl, CovSolveBufs (the kernel and its host side: cov_solve.hpp, below)
+#include "cov_plan.hpp"   // CovSolveCtl, CovSolveBufs (cov_solve_types.hpp) and the host-only arithmetic of the device loop: its launch plan and layouts
 struct GradCache {
     int mode = 1;                   // 0 off, 1 rent-or-buy, 2 from the first full pass (both only where the host-side
                                     // fold is cheaper than reading X), 3 from the first full pass, unconditionally
@@ -171,7 +171,7 @@ struct GradCache {
     std::vector<int64_t> pass_idx_host;   // ... and what it holds
     DevBuf<int32_t> d_pos_of; int32_t* d_upos = nullptr;
     DevBuf<uint8_t> d_setflag; uint8_t* d_forced = nullptr;   // (d_forced: the second half of d_setflag's allocation)
-    int64_t n_forced_rounds = 0, n_cs_forced_rounds = 0, n_cs_crew_passes = 0, n_cs_crew_jobs = 0;
+    int64_t n_forced_rounds = 0;    // full passes of the host's device pass run again with forced coordinates (gc_pass_device)
     // the scan's counters sit at the head of the buffer of unsettled positions (one copy brings both back); the results of
     // a pass come back through k_cov_pack's block
     DevBuf<int32_t> d_scanbuf; PinBuf<int32_t> h_scanbuf;   // [CovScanOut: 4 int32][positions: cap]
@@ -189,22 +189,26 @@ struct GradCache {
     int64_t n_drift = 0;
     int64_t n_validate = 0, n_batches = 0, n_columns = 0, n_certified = 0, n_exact = 0, n_passes = 0, n_cov = 0,
             n_reconcile = 0;
-    // the device-resident pass loop (cov_solve.hpp): its scratch, the pinned block it reads from and writes into, the bound's M_k
-    bool cs_enabled = true;          // Knobs::cov_solve, cdh_set_device_loop
-    bool cs_big = false;             // a visit list has outgrown the loop's LDS block on this handle: launches use the instantiation with the table and the helpers
-    int cs_helpers = 31;             // helper workgroups a launch that expects large visit lists brings (Knobs::cs_crew, cdh_set_device_loop; 0: none)
-    bool cs_shuffle_ok = true;
-    size_t cs_lds_budget = 0;
-    DevBuf<char> cs_dev; PinBuf<char> cs_pin; char* cs_pin_dev = nullptr;
-    CovSolveBufs cs_bufs{};
-    CovSolveCtl* cs_ctl = nullptr;
-    int32_t *cs_in_sup = nullptr, *cs_out_sup_idx = nullptr, *cs_out_moved_idx = nullptr, *cs_out_list = nullptr;
-    double *cs_out_sup_val = nullptr, *cs_out_moved_val = nullptr, *d_colmax = nullptr;
-    int64_t colmax_slots = 0;        // columns of the device store already folded into d_colmax
-    std::vector<double> cs_old;      // scratch: the iterate's values before a launch, by coordinate (zero between launches)
-    int64_t n_cs_launches = 0, n_cs_passes = 0, n_cs_folds = 0, n_cs_exact = 0, n_cs_table_passes = 0, n_cs_table_rows = 0;
-    int32_t cs_tepoch = 0;           // the kernel's Gram table: the epoch of its carried gradients
-    int64_t cs_ticks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+// The device-resident pass loop of cache-served solves (cov_solve.hpp): its scratch, the pinned block it reads from and writes
+// into, the bound's M_k, its counters.  What a launch looks like is cov_plan.hpp's to say.
+struct CovSolvePath {
+    bool enabled = true;             // Knobs::cov_solve, cdh_set_device_loop
+    bool big = false;                // a visit list has outgrown the loop's LDS block on this handle: launches use the instantiation with the table and the helpers
+    int helpers = 31;                // helper workgroups a launch that expects large visit lists brings (Knobs::cs_crew, cdh_set_device_loop; 0: none)
+    size_t lds_budget = 0;           // dynamic LDS the runtime grants the kernel (0: not asked yet)
+    DevBuf<char> dev; PinBuf<char> pin;   // the scratch and the pinned block: allocated together (cs_alloc), or not at all
+    CovSolveBufs bufs{};             // what the kernel gets: the scratch carved, the pinned block as the device addresses it
+    CsPinView io;                    // the pinned block as the host addresses it
+    CovSolveCtl* ctl_dev = nullptr;  // ... and its head as the device does
+    double* colmax = nullptr;        // = bufs.colmax
+    int64_t colmax_slots = 0;        // columns of the device store already folded into colmax
+    std::vector<double> old;         // scratch: the iterate's values before a launch, by coordinate (zero between launches)
+    int32_t tepoch = 0;              // the kernel's Gram table: the epoch of its carried gradients
+    int64_t ticks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t n_launches = 0, n_passes = 0, n_folds = 0, n_exact = 0, n_table_passes = 0, n_table_rows = 0;
+    int64_t n_forced_rounds = 0, n_crew_passes = 0, n_crew_jobs = 0;
 };
 
 // The one-launch solve of problems that fit on chip (small_solve.hpp): the full Gram matrix of the resident X, the
@@ -371,6 +375,7 @@ struct cdh_handle_s {
     size_t h_xchg_doubles = 0;
     // profile
     GradCache gc;
+    CovSolvePath cs;
     SmallPath small;
     bool prof = false;
     double prof_ms = 0.0, prof_bytes = 0.0;
@@ -645,7 +650,7 @@ void gc_invalidate(cdh_handle h, bool columns) {
     if (columns) {
         c.G.clear(); c.G.shrink_to_fit();
         std::fill(c.slot.begin(), c.slot.end(), -1);     // (d_slot still names the old columns until the next upload)
-        c.colmax_slots = 0;
+        h->cs.colmax_slots = 0;
         c.dev_slots = 0;                 // the device store is refilled from slot 0 (its memory is kept)
         c.full_seen = 0;
     }
@@ -1201,8 +1206,8 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
         h->knobs = read_knobs();
         h->gc.mode = h->knobs.gradient_cache;
         h->gc.cov = h->knobs.gc_cov;
-        h->gc.cs_enabled = h->knobs.cov_solve;
-        h->gc.cs_helpers = h->knobs.cs_crew;
+        h->cs.enabled = h->knobs.cov_solve;
+        h->cs.helpers = h->knobs.cs_crew;
         h->small.enabled = h->knobs.small_path;
         const int64_t want = (h->nvec + (int64_t)kBlock * kUnroll - 1) / ((int64_t)kBlock * kUnroll);
         h->step_grid = balanced_grid(want, std::min<int64_t>((int64_t)kMaxStepGrid, (int64_t)cus * kStepGridPerCU));
@@ -2281,23 +2286,23 @@ int32_t cdh_cache_gram_column(cdh_handle h, int64_t k1, double* out_p, double* o
 }); }
 
 int32_t cdh_set_device_loop(cdh_handle h, int32_t on) { return guarded(h, [&]() -> int32_t {
-    h->gc.cs_enabled = on != 0;
-    if (on == 2) h->gc.cs_helpers = 0;                 // the loop without its helper workgroups
-    else if (on > 2) h->gc.cs_helpers = std::min(kCsCrewMax, on);
+    h->cs.enabled = on != 0;
+    if (on == 2) h->cs.helpers = 0;                 // the loop without its helper workgroups
+    else if (on > 2) h->cs.helpers = std::min(kCsCrewMax, on);
     return CDH_OK;
 }); }
 
 int32_t cdh_device_loop_stats(cdh_handle h, int64_t* out12) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out12);
-    out12[0] = h->gc.n_cs_launches; out12[1] = h->gc.n_cs_passes; out12[2] = h->gc.n_cs_folds; out12[3] = h->gc.n_cs_exact;
-    for (int i = 0; i < 8; ++i) out12[4 + i] = h->gc.cs_ticks[i];
+    out12[0] = h->cs.n_launches; out12[1] = h->cs.n_passes; out12[2] = h->cs.n_folds; out12[3] = h->cs.n_exact;
+    for (int i = 0; i < 8; ++i) out12[4 + i] = h->cs.ticks[i];
     return CDH_OK;
 }); }
 
 int32_t cdh_device_loop_table(cdh_handle h, int64_t* out6 /* eight values by now */) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out6);
-    out6[0] = h->gc.n_cs_table_passes; out6[1] = h->gc.n_cs_table_rows; out6[2] = h->gc.st.table_entries(); out6[3] = kCsTableCap;
-    out6[4] = h->gc.n_forced_rounds; out6[5] = h->gc.n_cs_forced_rounds; out6[6] = h->gc.n_cs_crew_passes; out6[7] = h->gc.n_cs_crew_jobs;
+    out6[0] = h->cs.n_table_passes; out6[1] = h->cs.n_table_rows; out6[2] = h->gc.st.table_entries(); out6[3] = kCsTableCap;
+    out6[4] = h->gc.n_forced_rounds; out6[5] = h->cs.n_forced_rounds; out6[6] = h->cs.n_crew_passes; out6[7] = h->cs.n_crew_jobs;
     return CDH_OK;
 }); }
 

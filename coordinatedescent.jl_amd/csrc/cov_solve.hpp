@@ -50,17 +50,9 @@
 // fuzz, tests/test_gpu_cov_solve.py).
 #pragma once
 
-constexpr int kCsThreads = 256;          // 4 waves, one per SIMD: gram_scalar_body<4> holds a 64-entry Gram column per lane (128 VGPRs) next to the loops' state
+// kCsThreads, the LDS budget and what fits it, the table's size: cov_plan.hpp (host-only; cdhip.hip includes it ahead of the handle)
 constexpr int kCsWaves = kCsThreads / 64;
 constexpr int kCsNearMax = 96;           // inactive coordinates failing the bound beyond which the kernel folds and scans again
-constexpr int64_t kCsShuffleMaxP = 5600;    // the shuffle's six (p + 1)-sized int arrays must fit the kernel's dynamic LDS
-constexpr size_t kCsLdsBudget = (size_t)134 * 1024;   // dynamic LDS next to ~24 KB of static arrays (160 KB per CU)
-constexpr int kCsTrackedMargin = 24;     // room in the tracked list for entering and near-threshold coordinates next to the support
-constexpr int kCsTableCap = 1536;        // coordinates the Gram table of large visit lists holds (1536^2 doubles = 18.9 MB of device memory)
-constexpr int kCsTableMargin = 160;      // ... of which this many are left to entering and near-threshold coordinates next to the support
-constexpr size_t kCsTableLds = 2688 + 64 * 64 + 640;    // doubles of dynamic LDS table mode and crew passes use (a GramRec<4> record rounded up, a tile, a block's moves)
-constexpr int kCsUcapMax = 176;          // tracked coordinates whose Gram block is kept in LDS: symmetric, upper triangle packed (176 x 177 / 2 doubles = 122 KB)
-__host__ __device__ constexpr size_t cs_tri_doubles(size_t u) { return u * (u + 1) / 2; }
 // index of G_UU[i][j], i <= j, in the packed upper triangle of a cnt x cnt block (row i starts after rows 0 .. i - 1)
 __device__ __forceinline__ int cs_tri(int i, int j, int cnt) { return i * cnt - (i * (i - 1)) / 2 + (j - i); }
 
@@ -249,7 +241,7 @@ struct CsTracked {
     double *beta, *om, *gx, *hs, *nv, *qs, *tv;
     int32_t* tch;
 };
-constexpr size_t kCsTrackedBytes = 3 * 8 + 7 * 8 + 4;      // per tracked coordinate
+static_assert(kCsTrackedBytes == 3 * sizeof(int64_t) + 7 * sizeof(double) + sizeof(int32_t), "CsTracked, per tracked coordinate: what cs_lds_bytes charges for");
 
 // Two instantiations.  BIG = false is the loop as the common case needs it -- visit lists that fit the LDS block: no table, no helpers,
 // no call, no scratch (a kernel that asks for scratch makes the runtime map it for every wave slot of the chip on its first launch:
@@ -262,7 +254,7 @@ __global__ __launch_bounds__(kCsThreads) void k_cov_solve(CovSolveCtl* ctl, CovS
     using R = GramRec<4>;
     constexpr int B = R::B;
     constexpr int E = kCsE;
-    extern __shared__ double s_dynamic[];        // [G_UU: upper triangle of ucap x ucap doubles, packed; a shuffle's scratch overlays it][tracked arrays: 84 ucap bytes]
+    extern __shared__ double s_dynamic[];        // [G_UU: upper triangle of ucap x ucap doubles, packed; a shuffle's scratch overlays it][tracked arrays: 84 ucap bytes carved, 92 charged (cov_plan.hpp)]
     __shared__ double s_rec[R::N];
     __shared__ int s_mu[B];
     __shared__ int s_mu2[2][B], s_cid2[2][B];      // table mode: two blocks in flight
@@ -703,9 +695,9 @@ __global__ __launch_bounds__(kCsThreads) void k_cov_solve(CovSolveCtl* ctl, CovS
             // forced[], cw->bad) -- one job behind, never waited for inside the pass.
             const int nch = (cnt + B - 1) / B;
             auto recb = [&](int which) -> double* { return which ? s_dynamic : s_rec; };
-            static_assert(R::N <= 2688, "the second block record");
-            double* s_tile = s_dynamic + 2688;                                       // [64 moves][64 coordinates] of the block about to be visited
-            int64_t* s_off2 = reinterpret_cast<int64_t*>(s_dynamic + 6784);           // crew: [2][B] column offsets of a block's moves
+            static_assert(R::N <= kCsTableRec && B * B == kCsTableTile && 7 * B <= kCsTableJobs, "kCsTableLds: the second block record, the tile, the jobs' [2][B] arrays (7 B doubles)");
+            double* s_tile = s_dynamic + kCsTableRec;                                       // [64 moves][64 coordinates] of the block about to be visited
+            int64_t* s_off2 = reinterpret_cast<int64_t*>(s_dynamic + kCsTableRec + kCsTableTile);           // crew: [2][B] column offsets of a block's moves
             double* s_q2 = reinterpret_cast<double*>(s_off2 + 2 * B);                //       [2][B] r'r after each move
             int* s_pos2 = reinterpret_cast<int*>(s_q2 + 2 * B);                      //       [2][B] visit index of each move
             int64_t* s_v2 = reinterpret_cast<int64_t*>(s_pos2 + 2 * B);              //       [2][B] column offsets of a block's coordinates
@@ -1237,115 +1229,76 @@ __global__ __launch_bounds__(256) void k_cov_colmax(double* __restrict__ colmax,
 // ---- host side ---------------------------------------------------------------------------------------------------
 enum { kCsNotNow = 0, kCsFinished = 1, kCsAgain = 2 };
 
-inline size_t cs_align(size_t v) { return (v + 255) / 256 * 256; }
-
-// dynamic LDS of k_cov_solve for `ucap` tracked coordinates: their Gram block (upper triangle, packed) and arrays (a shuffle's
-// scratch overlays them), and the most tracked coordinates a budget of that many bytes holds
-inline size_t cs_lds_bytes(int ucap) { return 8 * cs_tri_doubles((size_t)ucap) + (kCsTrackedBytes + 8) * (size_t)ucap; }
-inline int cs_ucap(size_t budget) {
-    int ucap = kCsUcapMax;
-    while (ucap > 8 && cs_lds_bytes(ucap) > budget) ucap -= 4;
-    return ucap;
-}
-
-// scratch of the kernel (122 p bytes of device memory) and the pinned block it reads the support from and writes its
-// results into (zero-copy, as the one-launch solve's: nothing is copied around the launch)
-int32_t cs_alloc(cdh_handle h) {
-    GradCache& c = h->gc;
-    if (c.cs_dev || !c.cs_enabled) return CDH_OK;
-    const size_t p = (size_t)h->p;
-    const size_t tc = (size_t)kCsTableCap;
-    const size_t dev_bytes = 11 * cs_align(8 * p) + 5 * cs_align(8 * p) + 12 * cs_align(4 * p) + 3 * cs_align(p) + cs_align(8 * p) /* colmax */ +
-                             cs_align(8 * tc * tc) + 2 * cs_align(8 * tc) + cs_align(4 * tc) + 3 * cs_align(4 * p) /* the Gram table */ +
-                             cs_align(sizeof(CsCrew)) + cs_align(8 * p) /* the crew: jobs, g's snapshot */;
-    const size_t pin_bytes = cs_align(sizeof(CovSolveCtl)) + 4 * cs_align(4 * p) + 2 * cs_align(8 * p);
-    DevBuf<char> dev; PinBuf<char> pin;
-    void* dev_view = nullptr;
-    bool fits = dev.alloc(dev_bytes) == hipSuccess && pin.alloc(pin_bytes) == hipSuccess &&
-                hipHostGetDevicePointer(&dev_view, pin, 0) == hipSuccess;
-    if (!fits) (void)hipGetLastError();   // (a refused device view: a failed alloc has cleared its own)
-    CHK(all_ranks_agree(h, fits, &fits));
-    if (!fits) { c.cs_enabled = false; return CDH_OK; }
-    CovSolveBufs b = c.cs_bufs;
-    char* d = dev;
-    auto take = [&](size_t bytes) { char* q = d; d += cs_align(bytes); return q; };
-    b.p = h->p;
-    b.gx = (double*)take(8 * p); b.bfold = (double*)take(8 * p); b.bsnap = (double*)take(8 * p); b.hs = (double*)take(8 * p);
-    b.newval = (double*)take(8 * p); b.qs = (double*)take(8 * p); b.tv = (double*)take(8 * p); b.pendv = (double*)take(8 * p);
-    b.ubeta = (double*)take(8 * p); b.uom = (double*)take(8 * p); b.ugx = (double*)take(8 * p);
-    b.uk = (int64_t*)take(8 * p); b.poff = (int64_t*)take(8 * p); b.voff = (int64_t*)take(8 * p); b.uprev = (int64_t*)take(8 * p); b.iota = (int64_t*)take(8 * p);
-    b.touched = (int32_t*)take(4 * p); b.s2i = (int32_t*)take(4 * p); b.i2s = (int32_t*)take(4 * p); b.list = (int32_t*)take(4 * p);
-    b.vb = (int32_t*)take(4 * p); b.moved = (int32_t*)take(4 * p); b.holes = (int32_t*)take(4 * p); b.fills = (int32_t*)take(4 * p);
-    b.gxp = (int32_t*)take(4 * p); b.upos = (int32_t*)take(4 * p); b.aidx = (int32_t*)take(4 * p); b.occ = (int32_t*)take(4 * p);
-    b.setflag = (uint8_t*)take(p); b.inmoved = (uint8_t*)take(p); b.forced = (uint8_t*)take(p);
-    double* const colmax = (double*)take(8 * p); b.colmax = colmax;
-    b.Gc = (double*)take(8 * tc * tc); b.gxc = (double*)take(8 * tc); b.cidk = (int64_t*)take(8 * tc); b.gxe = (int32_t*)take(4 * tc);
-    b.cidof = (int32_t*)take(4 * p); b.ucid = (int32_t*)take(4 * p); b.newc = (int32_t*)take(4 * p);
-    b.crew = (CsCrew*)take(sizeof(CsCrew)); b.g_snap = (double*)take(8 * p);
-    char* const pin_dev = static_cast<char*>(dev_view);   // the pinned block as the device addresses it
-    size_t o = cs_align(sizeof(CovSolveCtl));
-    auto at = [&](size_t bytes) { const size_t q = o; o += cs_align(bytes); return q; };
-    const size_t o_in = at(4 * p), o_si = at(4 * p), o_mi = at(4 * p), o_li = at(4 * p), o_sv = at(8 * p), o_mv = at(8 * p);
-    b.in_sup = reinterpret_cast<const int32_t*>(pin_dev + o_in);
-    b.out_sup_idx = reinterpret_cast<int32_t*>(pin_dev + o_si); b.out_moved_idx = reinterpret_cast<int32_t*>(pin_dev + o_mi);
-    b.out_list = reinterpret_cast<int32_t*>(pin_dev + o_li);
-    b.out_sup_val = reinterpret_cast<double*>(pin_dev + o_sv); b.out_moved_val = reinterpret_cast<double*>(pin_dev + o_mv);
-    // (on the handle's own stream: the first operation on the NULL stream of a process creates its queue -- 10 ms measured)
-    HIPCHK(h, hipMemsetAsync(b.forced, 0, p, h->stream));
-    c.cs_dev = std::move(dev); c.cs_pin = std::move(pin); c.cs_pin_dev = pin_dev;   // all there: the handle takes the group
-    c.cs_bufs = b; c.d_colmax = colmax;
-    c.st.table_allocated();
-    c.cs_ctl = (CovSolveCtl*)c.cs_pin;
-    c.cs_in_sup = reinterpret_cast<int32_t*>(c.cs_pin + o_in);
-    c.cs_out_sup_idx = reinterpret_cast<int32_t*>(c.cs_pin + o_si); c.cs_out_moved_idx = reinterpret_cast<int32_t*>(c.cs_pin + o_mi);
-    c.cs_out_list = reinterpret_cast<int32_t*>(c.cs_pin + o_li);
-    c.cs_out_sup_val = reinterpret_cast<double*>(c.cs_pin + o_sv); c.cs_out_moved_val = reinterpret_cast<double*>(c.cs_pin + o_mv);
-    c.cs_old.assign(p, 0.0);
-    c.colmax_slots = 0;
-    // dynamic LDS: the tracked coordinates' Gram block and, for shuffled sweeps, the shuffle's two p-sized arrays
-    c.cs_lds_budget = kCsLdsBudget;
+// The dynamic LDS the runtime grants the kernel (the tracked coordinates' Gram block and arrays; a shuffle's scratch overlays them):
+// asked once per handle, before the first plan.  Allocates nothing.
+void cs_probe_lds(CovSolvePath& cp) {
+    if (cp.lds_budget) return;
+    cp.lds_budget = kCsLdsBudget;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_solve<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCsLdsBudget) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCsLdsBudget) != hipSuccess) {
         (void)hipGetLastError();
-        c.cs_lds_budget = (size_t)36 * 1024;          // what the default 64 KB leave next to the kernel's static arrays
+        cp.lds_budget = kCsLdsFallback;
     }
-    c.cs_shuffle_ok = true;
+}
+
+// scratch of the kernel and the pinned block it reads the support from and writes its results into (cov_plan.hpp lays both out)
+int32_t cs_alloc(cdh_handle h) {
+    CovSolvePath& cp = h->cs;
+    if (cp.dev || !cp.enabled) return CDH_OK;
+    const size_t p = (size_t)h->p;
+    DevBuf<char> dev; PinBuf<char> pin;
+    void* dev_view = nullptr;
+    bool fits = dev.alloc(cs_dev_bytes(p)) == hipSuccess && pin.alloc(cs_pin_layout(p).bytes) == hipSuccess &&
+                hipHostGetDevicePointer(&dev_view, pin, 0) == hipSuccess;
+    if (!fits) (void)hipGetLastError();   // (a refused device view: a failed alloc has cleared its own)
+    CHK(all_ranks_agree(h, fits, &fits));
+    if (!fits) { cp.enabled = false; return CDH_OK; }
+    CovSolveBufs b = cp.bufs;
+    b.p = h->p;
+    cs_dev_carve(b, p, dev);
+    const CsPinView io_dev = cs_pin_view(static_cast<char*>(dev_view), p);   // the pinned block as the device addresses it
+    b.in_sup = io_dev.in_sup; b.out_sup_idx = io_dev.out_sup_idx; b.out_moved_idx = io_dev.out_moved_idx; b.out_list = io_dev.out_list;
+    b.out_sup_val = io_dev.out_sup_val; b.out_moved_val = io_dev.out_moved_val;
+    // (on the handle's own stream: the first operation on the NULL stream of a process creates its queue -- 10 ms measured)
+    HIPCHK(h, hipMemsetAsync(b.forced, 0, p, h->stream));
+    cp.dev = std::move(dev); cp.pin = std::move(pin);   // all there: the handle takes the group
+    cp.bufs = b; cp.ctl_dev = io_dev.ctl; cp.colmax = const_cast<double*>(b.colmax);
+    cp.io = cs_pin_view(cp.pin, p);
+    h->gc.st.table_allocated();
+    cp.old.assign(p, 0.0);
+    cp.colmax_slots = 0;
     return CDH_OK;
 }
 
 // M_k of the kernel's bound, brought up to date with the columns the device store holds
 int32_t cs_update_colmax(cdh_handle h) {
     GradCache& c = h->gc;
-    if (c.colmax_slots > c.dev_slots) c.colmax_slots = 0;          // the store was refilled from slot 0
-    if (c.colmax_slots == c.dev_slots) return CDH_OK;
-    if (c.colmax_slots == 0) HIPCHK(h, hipMemsetAsync(c.d_colmax, 0, sizeof(double) * (size_t)h->p, h->stream));
-    hipLaunchKernelGGL(k_cov_colmax, dim3((unsigned)((h->p + 255) / 256)), dim3(256), 0, h->stream, c.d_colmax, c.d_G, c.d_slot,
-                       c.colmax_slots, c.dev_slots, h->p);
+    CovSolvePath& cp = h->cs;
+    if (cp.colmax_slots > c.dev_slots) cp.colmax_slots = 0;          // the store was refilled from slot 0
+    if (cp.colmax_slots == c.dev_slots) return CDH_OK;
+    if (cp.colmax_slots == 0) HIPCHK(h, hipMemsetAsync(cp.colmax, 0, sizeof(double) * (size_t)h->p, h->stream));
+    hipLaunchKernelGGL(k_cov_colmax, dim3((unsigned)((h->p + 255) / 256)), dim3(256), 0, h->stream, cp.colmax, c.d_G, c.d_slot,
+                       cp.colmax_slots, c.dev_slots, h->p);
     HIPCHK(h, hipGetLastError());
-    c.colmax_slots = c.dev_slots;
+    cp.colmax_slots = c.dev_slots;
     return CDH_OK;
 }
 
-// The passes of a solve from `*iter` on, on the device, as far as the gradient cache can serve them.
-//   kCsFinished  the solve is over (converged, or maxIter passes done): statistics and the iterate are up to date
-//   kCsAgain     the kernel stopped for something the host has now supplied (Gram columns, a fresh g): call again
-//   kCsNotNow    the next pass runs the round-3 way (solve() below): the cache is not engaged, or the kernel undid a pass
-int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched, cdh_stats* st, bool* prev_conv, bool* conv,
-                  int64_t* iter, int* outcome) {
+// Whether the cache is engaged for the pass at hand (`*go`), and what its certificates allow for the residual's rounding.
+int32_t cs_gate(cdh_handle h, const cdh_options* o, bool full, bool* go, double* cert_abs_out) {
     GradCache& c = h->gc;
-    *outcome = kCsNotNow;
+    *go = false;
     c.st.unprepared();
-    if (!c.cs_enabled || !c.cov || !gc_applicable(h) || c.mode == 0 || h->p < kScreenMinPass || h->p > ((int64_t)1 << 26)) return CDH_OK;
+    if (!h->cs.enabled || !c.cov || !gc_applicable(h) || c.mode == 0 || h->p < kScreenMinPass || h->p > ((int64_t)1 << 26)) return CDH_OK;
     if (o->randomize && h->p > kCsShuffleMaxP) return CDH_OK;
-    const bool full = *conv;
     double cert_abs = 0.0;
     if (full) {
         // (the gate of run_pass: full passes over dense iterates are not screened at all)
         if (!h->screening || h->x.nnz() * 4 > h->p) return CDH_OK;
-        bool go = false;
-        CHK(gc_prepare_full(h, &go, &cert_abs, false));             // the moves still pending on g go into the kernel with it
-        c.st.prepared(go, cert_abs);                                // gc_full_pass, if it comes to that, does not prepare twice
-        if (!go) { gc_fold(h); return CDH_OK; }
+        bool prepared = false;
+        CHK(gc_prepare_full(h, &prepared, &cert_abs, false));       // the moves still pending on g go into the kernel with it
+        c.st.prepared(prepared, cert_abs);                          // gc_full_pass, if it comes to that, does not prepare twice
+        if (!prepared) { gc_fold(h); return CDH_OK; }
     } else {
         if (!c.st.valid() || !c.d_G) return CDH_OK;
         if (gc_support_outgrown(h)) { gc_invalidate(h, false); return CDH_OK; }
@@ -1355,36 +1308,85 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
         if (h->loss == CDH_SQRT) CHK(gc_ensure_q(h));
         CHK(gc_cert_abs(h, &cert_abs));
     }
+    *cert_abs_out = cert_abs;
+    *go = true;
+    return CDH_OK;
+}
+
+// What a launch leaves behind, taken over by the host: the iterate, the cache, the statistics.
+void cs_absorb(cdh_handle h, cdh::VisitScheduler& sched, cdh_stats* st, bool* prev_conv, bool* conv, int64_t* iter) {
+    GradCache& c = h->gc;
+    CovSolvePath& cp = h->cs;
+    const CovSolveCtl& ctl = *cp.io.ctl;
+    // ---- the iterate: the support in its new slot order; what changed becomes pending residual updates ----
+    const int64_t nnz_old = h->x.nnz();
+    std::vector<int64_t> old_idx((size_t)nnz_old);
+    for (int64_t s_ = 0; s_ < nnz_old; ++s_) { old_idx[(size_t)s_] = h->x.coord(s_); cp.old[(size_t)h->x.coord(s_)] = h->x.slot_value(s_); }
+    auto note_move = [&](int64_t k, double d) { if (d != 0.0) note_move_off_stream(h, k, d, cdh::MoveKind::carried, true); };
+    h->x.clear();
+    for (int32_t s_ = 0; s_ < ctl.nnz; ++s_) {
+        const int64_t k = cp.io.out_sup_idx[s_];
+        const double v = cp.io.out_sup_val[s_];
+        if (v == 0.0) { h->x.set(k, 1.0); h->x.set(k, 0.0); }     // a stored zero keeps its slot (the caller put it there)
+        else h->x.set(k, v);
+        note_move(k, v - cp.old[(size_t)k]);
+        cp.old[(size_t)k] = 0.0;
+    }
+    for (int64_t k : old_idx) { if (cp.old[(size_t)k] != 0.0) note_move(k, -cp.old[(size_t)k]); cp.old[(size_t)k] = 0.0; }
+    // ---- the cache: moves still pending on g, r'r, the counters ----
+    c.st.pending_replaced(cp.io.out_moved_idx, cp.io.out_moved_val, ctl.n_moved);   // what went in is in the kernel's list (or folded)
+    c.st.table_holds(ctl.ncid); cp.tepoch = ctl.tepoch; cp.n_table_passes += ctl.table_passes; cp.n_table_rows += ctl.table_rows;
+    cp.n_forced_rounds += ctl.forced_rounds; cp.n_crew_passes += ctl.crew_passes; cp.n_crew_jobs += ctl.crew_jobs;
+    if (ctl.crew_passes > 0 || ctl.folds > 0) c.st.dev_g_moved_on();   // the helpers, or a fold in the loop
+    if (h->loss == CDH_SQRT) c.st.q_carried(ctl.q);
+    c.inject_count = ctl.inject_count;
+    c.n_passes += ctl.full_passes; c.n_dev_passes += ctl.full_passes; c.n_certified += ctl.settled;
+    c.n_cov += ctl.cov_visits; c.st.cov_visited(ctl.cov_visits); cp.n_passes += ctl.passes; cp.n_folds += ctl.folds; cp.n_exact += ctl.exact_rechecks;
+    for (int i = 0; i < 8; ++i) cp.ticks[i] += ctl.ticks[i];
+    c.n_exact += ctl.cov_visits_full;
+    if (ctl.domain_error) h->domain_error = true;
+    sched.set_state(ctl.rng);
+    *prev_conv = ctl.prev_conv != 0; *conv = ctl.conv != 0; *iter += ctl.passes;
+    st->passes += ctl.passes; st->full_passes += ctl.full_passes; st->visits += ctl.visits;
+    if (ctl.passes > 0) st->maxH = ctl.maxH;
+}
+
+// The passes of a solve from `*iter` on, on the device, as far as the gradient cache can serve them.
+//   kCsFinished  the solve is over (converged, or maxIter passes done): statistics and the iterate are up to date
+//   kCsAgain     the kernel stopped for something the host has now supplied (Gram columns, a fresh g): call again
+//   kCsNotNow    the next pass runs the round-3 way (solve() below): the cache is not engaged, or the kernel undid a pass
+int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched, cdh_stats* st, bool* prev_conv, bool* conv,
+                  int64_t* iter, int* outcome) {
+    GradCache& c = h->gc;
+    CovSolvePath& cp = h->cs;
+    *outcome = kCsNotNow;
+    // ---- the gate ----
+    bool go = false;
+    double cert_abs = 0.0;
+    CHK(cs_gate(h, o, *conv, &go, &cert_abs));
+    if (!go) return CDH_OK;
     // (from here on a "not now" hands the pass to the round-3 code, which expects the pending moves folded into g)
     auto not_now = [&]() -> int32_t { gc_fold(h); return CDH_OK; };
     if (!c.d_G || !c.d_scan || c.dev_slots != (int64_t)c.G.size() || (int64_t)c.st.moved().size() > h->p) return not_now();
     for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) if (c.slot[(size_t)h->x.coord(s_)] < 0) return not_now();
     if (h->x.nnz() > gc_max_support(h)) return not_now();
-    // The LDS of workgroup 0 holds the Gram block of ~170 tracked coordinates (ucap); longer visit lists run from the Gram table
-    // and with the helpers (see the header).
-    int ucap = cs_ucap(c.cs_lds_budget ? c.cs_lds_budget : kCsLdsBudget);      // (cs_alloc, below, sets the budget)
-    // (visit lists beyond that run in the kernel's table mode, up to the table's rows)
-    const int64_t support_cap = kCsTableCap - kCsTableMargin;
-    if (h->x.nnz() > support_cap) return not_now();
+    // ---- the launch shape, once, for the LDS the launch will really have ----
+    cs_probe_lds(cp);
+    CsPlanIn in{};
+    in.p = h->p; in.nnz = h->x.nnz(); in.full = *conv; in.randomize = o->randomize != 0;
+    in.lds_budget = cp.lds_budget; in.ucap_limit = h->knobs.cs_ucap; in.helpers = cp.helpers; in.big = cp.big;
+    in.support_limit = gc_max_support(h);
+    if (!(c.mode == 3 || gc_short_columns(h))) in.support_limit = std::min<int64_t>(in.support_limit, h->n_total / gc_rows_per_nnz(h));
+    const CsPlan plan = cs_plan(in);
+    if (!plan.run()) return not_now();
     CHK(cs_alloc(h));
-    if (!c.cs_enabled) return not_now();
-    // Full passes of large supports stay with the host's device pass (gc_pass_device): certifying the inactive coordinates takes g
-    // for all p after every block of moves -- p x moves gathers per pass, which twenty workgroups do in microseconds and one does not
-    // (the bound of the loop's certificates is useless there: M_k TV exceeds the thresholds themselves once hundreds of coordinates move)
-    // ... unless the launch brings helpers (the crew, above): then they do that work beside the visits, inside the loop
-    const int ucap_limit = h->knobs.cs_ucap;
-    const int ucap_lists = ucap_limit > 0 ? std::min(ucap, ucap_limit) : ucap;
-    const int lds_margin = std::min(kCsTrackedMargin, ucap_lists / 4);
-    const int nhelp = (c.cs_helpers > 0 && h->x.nnz() + lds_margin / 2 > ucap_lists - lds_margin) ? std::min(c.cs_helpers, kCsCrewMax) : 0;
-    const int32_t full_cap = nhelp > 0 ? 0x7fffffff : ucap_lists - lds_margin;
-    if (full && h->x.nnz() > full_cap) return not_now();
+    if (!cp.enabled) return not_now();
+    // ---- the launch ----
     if (c.st.table_void()) {         // a new X: the table's entries are void
-        HIPCHK(h, hipMemsetAsync(c.cs_bufs.cidof, 0xff, sizeof(int32_t) * (size_t)h->p, h->stream));
+        HIPCHK(h, hipMemsetAsync(cp.bufs.cidof, 0xff, sizeof(int32_t) * (size_t)h->p, h->stream));
         c.st.table_reset_done();
     }
-    // a fold is p x (pending moves) gathers: beyond a few moves the chip does it (gc_fold's kernel), not the one workgroup of the loop
-    const int32_t fold_limit = (int32_t)std::max<int64_t>(16, 120000 / h->p);
-    if ((int64_t)c.st.moved().size() > fold_limit) gc_fold(h);
+    if ((int64_t)c.st.moved().size() > plan.fold_limit) gc_fold(h);
     if (!c.st.dev_slot_current()) {           // the columns were dropped since the map last went down (a new X): the kernel asks d_slot who has one
         HIPCHK(h, hipMemcpyAsync(c.d_slot, c.slot.data(), sizeof(int32_t) * (size_t)h->p, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1394,75 +1396,30 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     CHK(gc_need_dev_g(h));
     c.st.unprepared();                                              // from here on the state moves: a later pass prepares afresh
 
-    CovSolveCtl& ctl = *c.cs_ctl;
+    CovSolveCtl& ctl = *cp.io.ctl;
     ctl.lambda0 = h->ctrl.lambda0; ctl.n_total = (double)h->n_total; ctl.optTol = o->optTol; ctl.cert_abs = cert_abs;
     ctl.max_passes = o->maxIter - *iter;
     ctl.cov_budget = std::max<int64_t>(0, h->knobs.gc_refresh - c.st.cov_since_ref());
     ctl.loss = h->loss; ctl.has_omega = h->has_omega ? 1 : 0; ctl.randomize = o->randomize ? 1 : 0;
-    {
-        int64_t lim = gc_max_support(h);
-        if (!(c.mode == 3 || gc_short_columns(h))) lim = std::min<int64_t>(lim, h->n_total / gc_rows_per_nnz(h));
-        ctl.nnz_limit = (int32_t)std::min<int64_t>({lim, support_cap, (int64_t)0x7fffffff});
-    }
-    ctl.busy_limit = kGcBusy; ctl.inject_every = h->knobs.gc_inject_rollback; ctl.fold_limit = fold_limit;
-    ctl.tcap = kCsTableCap; ctl.ncid = c.st.table_entries(); ctl.tepoch = c.cs_tepoch; ctl.full_cap = full_cap; ctl.ucap_limit = ucap_limit;
+    ctl.nnz_limit = plan.nnz_limit; ctl.busy_limit = kGcBusy; ctl.inject_every = h->knobs.gc_inject_rollback; ctl.fold_limit = plan.fold_limit;
+    ctl.tcap = plan.tcap; ctl.ncid = c.st.table_entries(); ctl.tepoch = cp.tepoch; ctl.full_cap = plan.full_cap; ctl.ucap_limit = in.ucap_limit;
     ctl.rng = sched.state(); ctl.q = c.st.q(); ctl.q_floor = h->loss == CDH_SQRT ? kGcQGuard * c.st.q_exact() : 0.0;
     ctl.nnz = (int32_t)h->x.nnz(); ctl.prev_conv = *prev_conv ? 1 : 0; ctl.conv = *conv ? 1 : 0; ctl.inject_count = c.inject_count;
     ctl.status = -1; ctl.n_list = 0;
     const cdh::MoveLedger& moved = c.st.moved();
     ctl.n_moved = (int32_t)moved.size();        // in: the moves still pending on g (out: those pending when the kernel stops)
-    for (size_t m = 0; m < moved.size(); ++m) { c.cs_out_moved_idx[m] = (int32_t)moved[m]; c.cs_out_moved_val[m] = moved.value(moved[m]); }
-    for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) c.cs_in_sup[s_] = (int32_t)h->x.coord(s_);
-    CovSolveBufs b = c.cs_bufs;
+    for (size_t m = 0; m < moved.size(); ++m) { cp.io.out_moved_idx[m] = (int32_t)moved[m]; cp.io.out_moved_val[m] = moved.value(moved[m]); }
+    for (int64_t s_ = 0; s_ < h->x.nnz(); ++s_) cp.io.in_sup[s_] = (int32_t)h->x.coord(s_);
+    CovSolveBufs b = cp.bufs;
     b.g = c.d_g; b.Gcols = c.d_G; b.slot = c.d_slot; b.a = c.d_a; b.omega = h->omega; b.beta = h->beta;
-    ucap = cs_ucap(c.cs_lds_budget);                // (the budget cs_alloc has settled on)
-    // (table mode keeps a second block record and a 64 x 64 tile where the LDS Gram block of small lists would be: kCsTableLds doubles)
-    if (cs_tri_doubles((size_t)ucap) < kCsTableLds) ctl.tcap = 0;
-    if (ctl.tcap == 0 && h->x.nnz() > ucap - kCsTrackedMargin) return not_now();     // (the budget the runtime really granted is smaller)
-    const unsigned lds = (unsigned)cs_lds_bytes(ucap);
-    if (o->randomize && 24 * ((size_t)h->p + 1) > (size_t)lds) return not_now();   // the shuffle's scratch overlays the dynamic LDS
-    const int nh = ctl.tcap > 0 ? nhelp : 0;
-    // the instantiation with the large-list paths once a list has outgrown the LDS block on this handle (or is about to: helpers are coming)
-    const bool big = ctl.tcap > 0 && (c.cs_big || nh > 0 || h->x.nnz() + lds_margin / 2 > ucap_lists - lds_margin);
-    if (nh > 0) HIPCHK(h, hipMemsetAsync(b.crew, 0, offsetof(CsCrew, ring), h->stream));      // the counters and flags (the jobs are written before they are posted)
-    if (big) hipLaunchKernelGGL(k_cov_solve<true>, dim3(1 + nh), dim3(kCsThreads), lds, h->stream, reinterpret_cast<CovSolveCtl*>(c.cs_pin_dev), b, ucap);
-    else hipLaunchKernelGGL(k_cov_solve<false>, dim3(1), dim3(kCsThreads), lds, h->stream, reinterpret_cast<CovSolveCtl*>(c.cs_pin_dev), b, ucap);
+    if (plan.nhelp > 0) HIPCHK(h, hipMemsetAsync(b.crew, 0, offsetof(CsCrew, ring), h->stream));      // the counters and flags (the jobs are written before they are posted)
+    if (plan.big) hipLaunchKernelGGL(k_cov_solve<true>, dim3(1 + plan.nhelp), dim3(kCsThreads), plan.lds_bytes, h->stream, cp.ctl_dev, b, plan.ucap);
+    else hipLaunchKernelGGL(k_cov_solve<false>, dim3(1), dim3(kCsThreads), plan.lds_bytes, h->stream, cp.ctl_dev, b, plan.ucap);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    c.n_cs_launches += 1;
+    cp.n_launches += 1;
     if (ctl.status < 0) return fail(h, CDH_HIP_ERROR, "the device-resident solve returned no status");
-
-    // ---- the iterate: the support in its new slot order; what changed becomes pending residual updates ----
-    const int64_t nnz_old = h->x.nnz();
-    std::vector<int64_t> old_idx((size_t)nnz_old);
-    for (int64_t s_ = 0; s_ < nnz_old; ++s_) { old_idx[(size_t)s_] = h->x.coord(s_); c.cs_old[(size_t)h->x.coord(s_)] = h->x.slot_value(s_); }
-    auto note_move = [&](int64_t k, double d) { if (d != 0.0) note_move_off_stream(h, k, d, cdh::MoveKind::carried, true); };
-    h->x.clear();
-    for (int32_t s_ = 0; s_ < ctl.nnz; ++s_) {
-        const int64_t k = c.cs_out_sup_idx[s_];
-        const double v = c.cs_out_sup_val[s_];
-        if (v == 0.0) { h->x.set(k, 1.0); h->x.set(k, 0.0); }     // a stored zero keeps its slot (the caller put it there)
-        else h->x.set(k, v);
-        note_move(k, v - c.cs_old[(size_t)k]);
-        c.cs_old[(size_t)k] = 0.0;
-    }
-    for (int64_t k : old_idx) { if (c.cs_old[(size_t)k] != 0.0) note_move(k, -c.cs_old[(size_t)k]); c.cs_old[(size_t)k] = 0.0; }
-    // ---- the cache: moves still pending on g, r'r, the counters ----
-    c.st.pending_replaced(c.cs_out_moved_idx, c.cs_out_moved_val, ctl.n_moved);   // what went in is in the kernel's list (or folded)
-    c.st.table_holds(ctl.ncid); c.cs_tepoch = ctl.tepoch; c.n_cs_table_passes += ctl.table_passes; c.n_cs_table_rows += ctl.table_rows;
-    c.n_cs_forced_rounds += ctl.forced_rounds; c.n_cs_crew_passes += ctl.crew_passes; c.n_cs_crew_jobs += ctl.crew_jobs;
-    if (ctl.crew_passes > 0 || ctl.folds > 0) c.st.dev_g_moved_on();   // the helpers, or a fold in the loop
-    if (h->loss == CDH_SQRT) c.st.q_carried(ctl.q);
-    c.inject_count = ctl.inject_count;
-    c.n_passes += ctl.full_passes; c.n_dev_passes += ctl.full_passes; c.n_certified += ctl.settled;
-    c.n_cov += ctl.cov_visits; c.st.cov_visited(ctl.cov_visits); c.n_cs_passes += ctl.passes; c.n_cs_folds += ctl.folds; c.n_cs_exact += ctl.exact_rechecks;
-    for (int i = 0; i < 8; ++i) c.cs_ticks[i] += ctl.ticks[i];
-    c.n_exact += ctl.cov_visits_full;
-    if (ctl.domain_error) h->domain_error = true;
-    sched.set_state(ctl.rng);
-    *prev_conv = ctl.prev_conv != 0; *conv = ctl.conv != 0; *iter += ctl.passes;
-    st->passes += ctl.passes; st->full_passes += ctl.full_passes; st->visits += ctl.visits;
-    if (ctl.passes > 0) st->maxH = ctl.maxH;
+    cs_absorb(h, sched, st, prev_conv, conv, iter);
 
     switch (ctl.status) {
     case kCsConverged: st->converged = 1; *outcome = kCsFinished; return CDH_OK;
@@ -1475,7 +1432,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     case kCsCrewLost: return fail(h, CDH_HIP_ERROR, "the device-resident solve lost its helper workgroups (a wait ran into its 20 s bound)");
     case kCsNeedBig:                                                // a visit list has outgrown the LDS block: the instantiation that knows what to do
         if (ctl.tcap == 0) return CDH_OK;                           // (no room for its scratch in LDS: the host's passes)
-        c.cs_big = true; *outcome = kCsAgain; return CDH_OK;
+        cp.big = true; *outcome = kCsAgain; return CDH_OK;
     case kCsHostFull: return CDH_OK;                                // the next (full) pass runs the pass-by-pass way
     case kCsBusy:     // many inactive coordinates about to move: back off, as gc_pass_device does
         gc_back_off(h);
@@ -1484,7 +1441,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     case kCsNeedColumns: {
         if (c.st.stalled_twice(ctl.passes == 0)) return CDH_OK;     // (twice in a row without progress: the old way)
         c.backoff = 1;
-        std::vector<int64_t> enter(c.cs_out_list, c.cs_out_list + ctl.n_list);
+        std::vector<int64_t> enter(cp.io.out_list, cp.io.out_list + ctl.n_list);
         CHK(gc_check_moved_columns(h));
         gc_fold(h);
         if (!c.st.valid()) return CDH_OK;
