@@ -136,6 +136,7 @@ def lib():
         "cdh_xt_r_cols": [vp, i64, vp, vp],
         "cdh_gram_weighted": [vp, i64, vp, vp, vp, P(f64)],
         "cdh_col_wrms": [vp, vp],
+        "cdh_loadings": [vp, vp],
         "cdh_vc_set_data": [vp, i64, i32, vp, i64, vp],
         "cdh_vc_set_point": [vp, i32, f64, f64, vp],
         "cdh_vc_set_point_loo": [vp, i32, f64, i64, vp, vp],

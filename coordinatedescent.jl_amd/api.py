@@ -14,7 +14,7 @@ Reference files mirrored (relative to the reference's src/):
   cd_differentiable_function.jl      the loss operators and the 4-function plugin API
   coordinate_descent.jl              coordinateDescent!, _findLambdaMax
   atom_iterator.jl                   OrderedIterator, RandomIterator
-  lasso.jl                           lasso, sqrtLasso, scaledLasso!, LassoPath
+  lasso.jl                           lasso, sqrtLasso, scaledLasso!, feasibleLasso!, LassoPath, refitLassoPath
   varying_coefficient_lasso.jl       the smoothing kernels, locpolyl1, lvocv_locpolyl1, get_nonzero_coordinates
   ProximalBase 0.3.0 (not vendored)  ProxL1, SparseIterate (contract: SURVEY.md App. B)
 """
@@ -1004,6 +1004,14 @@ def stdX(f, weighted=False):
     return out
 
 
+def getLoadings(f):
+    """_getLoadings!(out, X, e) (src/utils.jl:153-164) at e = f.r: Γ_j = sqrt(Σ_i (X_ij r_i)² / n) for the X resident behind
+    loss f, one pass over X on the device (cdh_loadings).  Read-only on the handle."""
+    out = np.zeros(f.p)
+    check(f._L.cdh_loadings(f._h, _vp(out)), f._h)
+    return out
+
+
 def objective(f, g=None, problem=0):
     """f(β) + λ0 Σ ω|β| at the handle's current state (src/coordinate_descent.jl:1-3)."""
     if isinstance(f, CDQuadraticLoss):       # x'Ax/2 + x'b = sum_k x_k (g_k + b_k) / 2 with g = Ax + b as the handle holds it
@@ -1086,12 +1094,29 @@ def sqrtLasso(X, y, lam, omega=None, options=None, standardizeX=True):
     return LassoSolution(x, f.r, g, _std_resid(f))
 
 
-def _find_init_sigma(f, s):
-    """_findInitSigma! (src/utils.jl:60-77, 96-106): std of the OLS residuals on the s
-    columns most correlated with y.  Everything n-sized stays in HBM: the screening scores
-    X'y and the s x s normal equations (X_S'X_S, X_S'y) come from one pass each over the
-    columns involved, the host solves the s x s system, and the residual y - X_S b is formed
-    by initialize! on the device (s is 5 by default)."""
+def _ols_on_columns(f, idx1):
+    """X[:, S] \\ y for the 1-based column list idx1 of a handle that stands at β = 0 (r = y), with nothing n-sized on the
+    host: cdh_gram gives (X_S'X_S, X_S'y), the host solves the |S| x |S| system and refines it against X_S'(y - X_S b),
+    which initialize! and one pass over the |S| columns evaluate on the device.  The handle is left at the last refinement's
+    iterate; the caller sets what it wants and drops f._synced."""
+    L, m = f._L, idx1.shape[0]
+    G, c = np.zeros((m, m)), np.zeros(m)
+    check(L.cdh_gram(f._h, m, _vp(idx1), _vp(G), _vp(c), None), f._h)
+
+    def normal_residual(b):                  # Xs'(y - Xs b): initialize! forms the residual, one pass over the s columns dots it
+        check(L.cdh_initialize(f._h, f.p, m, _vp(idx1), _vp(np.ascontiguousarray(b))), f._h)
+        out = np.zeros(m)
+        check(L.cdh_xt_r_cols(f._h, m, _vp(idx1), _vp(out)), f._h)
+        return out
+
+    return solve_screening_ols(G, c, normal_residual)      # Xs \ y
+
+
+def _find_init_residuals(f, s):
+    """_findInitResiduals! (src/utils.jl:65-77, 96-106): leaves r = y - X_S (X_S \\ y) on the device, S the s columns most
+    correlated with y.  Everything n-sized stays in HBM: the screening scores X'y and the s x s normal equations
+    (X_S'X_S, X_S'y) come from one pass each over the columns involved, the host solves the s x s system, and the residual
+    y - X_S b is formed by initialize! on the device (s is 5 by default)."""
     L = f._L
     check(L.cdh_initialize(f._h, f.p, 0, None, None), f._h)  # beta = 0, r = y: X'r == X'y
     f._synced = None
@@ -1103,20 +1128,15 @@ def _find_init_sigma(f, s):
     if len(S) > 4096:
         raise ArgumentError("screening set larger than 4096 columns")
     idx1 = np.ascontiguousarray(S + 1, dtype=np.int64)
-    G, c = np.zeros((len(S), len(S))), np.zeros(len(S))
-    check(L.cdh_gram(f._h, len(S), _vp(idx1), _vp(G), _vp(c), None), f._h)
-
-    def normal_residual(b):                  # Xs'(y - Xs b): initialize! forms the residual, one pass over the s columns dots it
-        check(L.cdh_initialize(f._h, f.p, len(S), _vp(idx1), _vp(np.ascontiguousarray(b))), f._h)
-        out = np.zeros(len(S))
-        check(L.cdh_xt_r_cols(f._h, len(S), _vp(idx1), _vp(out)), f._h)
-        return out
-
-    coef = solve_screening_ols(G, c, normal_residual)      # Xs \ y
+    coef = _ols_on_columns(f, idx1)
     check(L.cdh_initialize(f._h, f.p, len(S), _vp(idx1), _vp(np.ascontiguousarray(coef))), f._h)
-    sigma = _std_resid(f)                    # std(y - Xs * (Xs \ y))
     f._synced = None
-    return sigma
+
+
+def _find_init_sigma(f, s):
+    """_findInitSigma! (src/utils.jl:60-64): std of the OLS residuals on the s columns most correlated with y."""
+    _find_init_residuals(f, s)
+    return _std_resid(f)                     # std(y - Xs * (Xs \ y))
 
 
 def scaledLasso_(x, X, y, lam, omega, options=None):
@@ -1146,11 +1166,71 @@ def scaledLasso_(x, X, y, lam, omega, options=None):
     return LassoSolution(x, f.r, g, _std_resid(f))
 
 
+def feasibleLasso_(x, X, y, lam0, options=None):
+    """feasibleLasso!(x, X, y, λ0, options) (src/lasso.jl:154-194): the lasso with the heteroscedasticity-robust penalty
+    loadings Γ_j = sqrt(Σ_i (X_ij r_i)² / n), re-estimated from the residual after every solve until
+    max|Γold - Γ| / max Γ < optTol.  X may also be an existing CDLeastSquaresLoss; y is then ignored.
+
+    This is the behaviour the reference intends: its own function cannot run on Julia >= 1.0, because `Array{T}(p)`
+    (:164-165) is no longer a constructor (as in sqrtLasso) and `LassoSolution(x, f.r, g, std(f.r))`
+    (:193) names an outer constructor the struct does not have (:7-17 define `LassoSolution{T, S}(...)` only).
+
+    One quirk is kept: `g = ProxL1(λ0, Γ)` (:181) aliases Γ, which `_getLoadings!` (:186) overwrites in place, so the
+    penalty of the returned LassoSolution carries the loadings computed AFTER the last solve, not the ones it used.
+
+    The loadings are one pass over X on the device per round (cdh_loadings); only the p-vector comes to the host, where the
+    stopping statistic is taken.  Nothing n-sized leaves HBM inside the loop."""
+    o = options or IterLassoOptions()
+    f = _as_loss(CDLeastSquaresLoss, X, y)
+    if o.initProcedure == "Screening":
+        _find_init_residuals(f, o.sinit)                     # :169
+    elif o.initProcedure == "InitStd":
+        coordinateDescent_(x, f, ProxL1(lam0 * o.sigmainit, stdX(f)), o.optionsCD)   # :171-173
+    elif o.initProcedure == "WarmStart":
+        initialize_(f, x)                                    # :175
+    else:
+        raise ArgumentError("Incorrect initialization Symbol")  # :177
+    gamma = getLoadings(f)                                   # :179
+    for _ in range(o.maxIter):
+        gamma_old = gamma
+        coordinateDescent_(x, f, ProxL1(lam0, gamma), o.optionsCD)
+        gamma = getLoadings(f)                               # :186
+        if np.max(np.abs(gamma_old - gamma)) / np.max(gamma) < o.optTol:   # :188
+            break
+    return LassoSolution(x, f.r, ProxL1(lam0, gamma), _std_resid(f))
+
+
 @dataclass
 class LassoPathResult:
     """LassoPath{T} (src/lasso.jl:201-204)."""
     lambdapath: list
     betapath: list
+
+
+def refitLassoPath(path, X, Y):
+    """refitLassoPath(path, X, Y) (src/lasso.jl:208-225): for every distinct support S along the path, the least-squares
+    coefficients X[:, S] \\ Y.  Returns a dict from the sorted 1-based support (a tuple) to a float64 array; a support already
+    seen is skipped, and the empty support maps to an empty array.  X may also be an existing CDLeastSquaresLoss; Y is then
+    ignored.
+
+    Per support the handle is initialised at β = 0 (r = y), cdh_gram gives (X_S'X_S, X_S'y), and the host solves the
+    |S| x |S| system with the refinement _findInitResiduals! uses -- nothing n-sized on the host.  cdh_gram takes up to 4096
+    columns: a larger support raises ArgumentError.  The handle is left at β = 0 with r = y (an iterate synced to it before
+    the call is pushed again by its next use)."""
+    f = _as_loss(CDLeastSquaresLoss, X, Y)
+    out = {}
+    for beta in path.betapath:
+        S = tuple(int(k) + 1 for k in np.nonzero(beta.dense())[0])   # findall(!iszero, β)
+        if S in out:
+            continue
+        if len(S) > 4096:
+            raise ArgumentError("support larger than 4096 columns")
+        check(f._L.cdh_initialize(f._h, f.p, 0, None, None), f._h)
+        f._synced = None
+        out[S] = _ols_on_columns(f, np.array(S, dtype=np.int64)) if S else np.zeros(0)
+    check(f._L.cdh_initialize(f._h, f.p, 0, None, None), f._h)
+    f._synced = None
+    return out
 
 
 def LassoPath(X, Y, lambdapath, options=None, max_hat_s=np.inf, standardizeX=True, reuse_residual=True):

@@ -587,6 +587,30 @@ int32_t col_dots(cdh_handle h, int64_t j0, int64_t nc, const void* rvec, bool us
     return CDH_OK;
 }
 
+// ---- column loadings at the current residual: d_colout[j] = sum_i (x_ij r_i)^2 for all p columns (all shards) ----
+// col_dots's batches and row chunks; read-only on the handle apart from bringing r up to date.
+int32_t col_loadings(cdh_handle h) {
+    CHK(sync_r(h));
+    for (int64_t b0 = 0; b0 < h->p; b0 += kColBatch) {
+        const int64_t bc = std::min<int64_t>(kColBatch, h->p - b0);
+        const int64_t groups = (bc + kColGroup - 1) / kColGroup;
+        const int chunks = col_dots_chunks(h, bc);
+        if ((size_t)groups * chunks * kColGroup > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partials too small");
+        dim3 grid(chunks, (unsigned)groups);
+        CHK(dispatch(h, [&](auto* t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            hipLaunchKernelGGL(k_col_loadings<T>, grid, dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
+                               h->nvec, (const T*)h->r, b0, (int)bc, h->d_partials);
+            return CDH_OK;
+        }));
+        hipLaunchKernelGGL(k_col_loadings_reduce, dim3((unsigned)bc), dim3(64), 0, h->stream,
+                           h->d_partials, chunks, h->d_colout + b0);
+        HIPCHK(h, hipGetLastError());
+    }
+    CHK(allreduce(h, h->d_colout, (size_t)h->p));
+    return CDH_OK;
+}
+
 int32_t resid_moments_dev(cdh_handle h, const void* vec = nullptr, double shift = 0.0, bool sum_w = false) {  // -> d_red[0..2] = sum v (sum_w: sum w; needs weights), sum v^2, sum w v^2 (v = r unless given; minus shift)
     if (!vec) { CHK(sync_r(h)); vec = h->r; }
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (h->nvec + kBlock - 1) / kBlock));
@@ -1688,6 +1712,16 @@ int32_t cdh_col_rms(cdh_handle h, double* out_p) { return guarded(h, [&]() -> in
     HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(cd[(size_t)(2 * j + 1)] / (double)h->n_total);
+    return CDH_OK;
+}); }
+
+int32_t cdh_loadings(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
+    NEED_P(h, out_p);
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(col_loadings(h));
+    HIPCHK(h, hipMemcpyAsync(out_p, h->d_colout, sizeof(double) * h->p, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(out_p[j] / (double)h->n_total);
     return CDH_OK;
 }); }
 

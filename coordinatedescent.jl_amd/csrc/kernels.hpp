@@ -9,6 +9,7 @@
 //   k_init_resid  initialize!               :59-72 (A_mul_B_row)
 //   k_col_dots    gradient / _findLambdaMax / _stdX!   :75-76, coordinate_descent.jl:118-149,
 //                                           utils.jl:127-138
+//   k_col_loadings  _getLoadings!           utils.jl:153-164
 //   k_blockstep / k_block_finalize          the same visit arithmetic, B visits per launch
 //
 // Everything here is HBM-bound BLAS-1/2 work: 16-byte coalesced loads of
@@ -722,6 +723,62 @@ __global__ __launch_bounds__(64) void k_col_dots_reduce(const double* __restrict
     }
     s0 = wave_sum(s0); s1 = wave_sum(s1);
     if (threadIdx.x == 0) { out[2 * col] = s0; out[2 * col + 1] = s1; }
+}
+
+// ---------------------------------------------------------------------------------
+// Column loadings (_getLoadings!, utils.jl:153-164): out_j = sum_i (x_ij r_i)^2 for every column at the current residual, on
+// k_col_dots's grid and at its bytes (X once, r once per kColGroup columns).  One fp64 accumulator per column: per row the
+// product t = x r in double (exact for fp32 storage), then acc = fma(t, t, acc).  The zero pad of X beyond n adds nothing.
+// partials[(group * nchunks + chunk) * kColGroup + i], summed in a fixed order by k_col_loadings_reduce.
+// ---------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_col_loadings(const T* __restrict__ X, int64_t ld, int64_t nvec,
+                                                         const T* __restrict__ r, int64_t j0, int ncols,
+                                                         double* __restrict__ partials) {
+    using V = typename VecOf<T>::V;
+    constexpr int NV = VecOf<T>::N;
+    __shared__ double lds[kColGroup * (kBlock / 64)];
+    const int c0 = blockIdx.y * kColGroup;
+    const V* cv[kColGroup];
+#pragma unroll
+    for (int i = 0; i < kColGroup; ++i)    // columns past the end alias the group's first (discarded)
+        cv[i] = reinterpret_cast<const V*>(X + (j0 + (c0 + i < ncols ? c0 + i : c0)) * ld);
+    const V* rv = reinterpret_cast<const V*>(r);
+    double acc[kColGroup];
+#pragma unroll
+    for (int i = 0; i < kColGroup; ++i) acc[i] = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < nvec; j += stride) {
+        V xv[kColGroup];
+#pragma unroll
+        for (int i = 0; i < kColGroup; ++i) xv[i] = ld_stream<true>(cv[i] + j);
+        const V rr = rv[j];
+#pragma unroll
+        for (int e = 0; e < NV; ++e) {
+            const double re = (double)rr[e];
+#pragma unroll
+            for (int i = 0; i < kColGroup; ++i) {
+                const double t = (double)xv[i][e] * re;
+                acc[i] = fma(t, t, acc[i]);
+            }
+        }
+    }
+    block_sum<kColGroup>(acc, lds);
+    if (threadIdx.x == 0) {
+        double* out = partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kColGroup;
+#pragma unroll
+        for (int i = 0; i < kColGroup; ++i) out[i] = acc[i];
+    }
+}
+// one wave per column: out[col] = sum over chunks
+__global__ __launch_bounds__(64) void k_col_loadings_reduce(const double* __restrict__ partials, int nchunks,
+                                                            double* __restrict__ out) {
+    const int col = blockIdx.x, grp = col / kColGroup, i = col % kColGroup;
+    const double* pr = partials + (int64_t)grp * nchunks * kColGroup + i;
+    double s = 0.0;
+    for (int c = threadIdx.x; c < nchunks; c += 64) s += pr[(int64_t)c * kColGroup];
+    s = wave_sum(s);
+    if (threadIdx.x == 0) out[col] = s;
 }
 
 // sum (r - shift), sum (r - shift)^2 (+ sum w (r - shift)^2 when w) -> partials[(block, 4)]; rows beyond n (the zero pad of

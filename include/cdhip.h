@@ -272,6 +272,11 @@ int32_t cdh_get_residual(cdh_handle h, void *out_n_local);               /* f.r 
 int32_t cdh_col_rms(cdh_handle h, double *out_p);
 /* _stdX!(out, w, X) (utils.jl:140-151): out_j = sqrt(sum_i w_i X_ij^2 / n_total); CDH_WLS with weights set, else CDH_BAD_ARG. */
 int32_t cdh_col_wrms(cdh_handle h, double *out_p);
+/* _getLoadings!(out, X, e) (utils.jl:153-164) at e = the current residual: out_j = sqrt(sum_i (X_ij r_i)^2 / n_total), the
+ * penalty loadings of feasibleLasso! (lasso.jl:179,186).  One pass over X, summed in double in a fixed order (bit-identical
+ * run to run) over all shards; a function of X and r only, so any loss.  Read-only: beta, the penalty, the weights and the
+ * gradient cache are left as they are (r catches up with pending moves first, as for every reader of r). */
+int32_t cdh_loadings(cdh_handle h, double *out_p);
 /* out_j = X_j' r for every column at the current r (At_mul_B_row for all j: the
  * screening scores of _findLargestCorrelations, utils.jl:96-106; KKT checks). */
 int32_t cdh_xt_r(cdh_handle h, double *out_p);

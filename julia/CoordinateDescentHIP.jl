@@ -5,9 +5,10 @@
 # box.  It is deliberately a thin ccall shim with no arithmetic beyond an s x s solve: every number
 # comes from the library.  tests/test_binding_call_sequence.py replays, with plain ctypes and nothing
 # else in between, the exact sequence of C calls each method below makes (function by function) and
-# checks the results against the oracle -- that is the executable evidence for this file.
+# checks the results against the oracle -- that is the executable evidence for this file.  (feasibleLasso! and
+# refitLassoPath are replayed the same way in tests/test_binding_feasible_sequence.py.)
 #
-# lasso(), sqrtLasso(), scaledLasso!, LassoPath, CDOptions, IterLassoOptions, ProxL1, SparseIterate and
+# lasso(), sqrtLasso(), scaledLasso!, feasibleLasso!, LassoPath, refitLassoPath, CDOptions, IterLassoOptions, ProxL1, SparseIterate and
 # the loss constructors are untouched: the user passes a HipMatrix where a Matrix went, and multiple
 # dispatch picks the methods below (each strictly more specific than the reference's generic one).
 #
@@ -19,6 +20,10 @@
 #                                         (cdh_resid_moments), the residual copied back ONCE at the end
 #   LassoPath(X, Y, λpath)     :229-260   LassoPath(X::HipMatrix, ...) below: same loop, nothing n-sized moves
 #                                         between the λ (carried residual reused, gradient cache from the start)
+#   feasibleLasso!(x, X, y, λ0) :154-194  feasibleLasso!(x, X::HipMatrix, ...) below: the loop the reference intends, the
+#                                         loadings of every round from one pass over X on the device (cdh_loadings)
+#   refitLassoPath(path, X, Y) :208-225   refitLassoPath(path, X::HipMatrix, Y) below: X[:, S] \ Y per distinct support
+#                                         from the s x s normal equations (cdh_gram), as the screening init solves them
 # The generic front-ends still work on a HipMatrix through the operator methods (_findInitResiduals!,
 # initialize!, coordinateDescent!, _stdX!), at the price of one n-sized device -> host copy per solve because
 # their bodies read `f.r` on the host (lasso.jl:134); the two methods above exist to take that copy out of
@@ -32,7 +37,7 @@ using DataStructures: nlargest
 import CoordinateDescent: coordinateDescent!, initialize!, gradient, descendCoordinate!,
                           numCoordinates, CDOptions, CDLeastSquaresLoss, CDSqrtLassoLoss, CDWeightedLSLoss,
                           _stdX!, _findInitResiduals!, _findLargestCorrelations,
-                          scaledLasso!, LassoPath, LassoSolution, IterLassoOptions
+                          scaledLasso!, feasibleLasso!, LassoPath, refitLassoPath, LassoSolution, IterLassoOptions
 
 const libcdhip = get(ENV, "LIBCDHIP", "libcdhip.so")
 
@@ -394,6 +399,50 @@ function scaledLasso!(x::SparseIterate{T}, X::HipMatrix{T}, y::AbstractVector{T}
   LassoSolution{T, typeof(g)}(x, f.r, g, T(resid_std(X)))
 end
 
+"_getLoadings!(out, X, e) (utils.jl:153-164) at e = the residual the device holds: out[j] = sqrt(sum_i (X[i,j] r[i])^2 / n),
+one pass over X in HBM; the handle is left as it was."
+function device_loadings!(out::Vector{T}, X::HipMatrix{T}) where {T<:AbstractFloat}
+  length(out) == X.p || throw(DimensionMismatch())
+  buf = Vector{Float64}(undef, X.p)
+  check(X.handle, ccall((:cdh_loadings, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Float64}), X.handle, buf))
+  out .= T.(buf)
+  out
+end
+
+"feasibleLasso!(x, X, y, λ0, options) (lasso.jl:154-194) for a design in HBM, as the reference intends it: its own body stops
+at `Array{T}(p)` (:164-165) and at `LassoSolution(x, f.r, g, std(f.r))` (:193, no such outer constructor) on Julia >= 1.0.
+g aliases Γ as in the reference (:181), so the returned penalty carries the loadings computed after the last solve.
+Nothing n-sized crosses the bus inside the loop; `f.r` comes back once, for the LassoSolution."
+function feasibleLasso!(x::SparseIterate{T}, X::HipMatrix{T}, y::AbstractVector{T}, λ0::T,
+                        options::IterLassoOptions=IterLassoOptions()) where {T<:AbstractFloat}
+  p = X.p
+  f = CDLeastSquaresLoss(y, X)
+  Γ = Array{T}(undef, p)
+  Γold = Array{T}(undef, p)
+  if options.initProcedure == :Screening
+    S = _findLargestCorrelations(X, y, options.sinit)      # leaves y on the device, loss kind LS, r = y
+    screening_ols!(X, Int64.(findall(S)))                  # r = y - Xs (Xs \ y) stays on the device
+    X.owner = f.r                     # the device holds exactly this loss's y and kind: no second upload
+  elseif options.initProcedure == :InitStd
+    _stdX!(Γ, X)
+    solve_resident!(x, f, ProxL1(λ0 * options.σinit, Γ), options.optionsCD)
+  elseif options.initProcedure == :WarmStart
+    bind!(f); push_iterate!(f, x, true)
+  else
+    throw(ArgumentError("Incorrect initialization Symbol"))
+  end
+  device_loadings!(Γ, X)
+  g = ProxL1(λ0, Γ)
+  for iter = 1:options.maxIter
+    copyto!(Γold, Γ)
+    solve_resident!(x, f, g, options.optionsCD)
+    device_loadings!(Γ, X)
+    maximum(abs.(Γold - Γ)) / maximum(Γ) < options.optTol && break
+  end
+  pull_residual!(f)
+  LassoSolution{T, typeof(g)}(x, f.r, g, T(resid_std(X)))
+end
+
 "LassoPath(X, Y, λpath, options; max_hat_s, standardizeX) (lasso.jl:229-260) for a design in HBM: one x and one f
 for all λ as in the reference; warm starts keep the carried residual (it already equals Y - X x) and the gradient
 cache is engaged from the first full pass for the duration of the path (whatever the caller set otherwise stays)."
@@ -423,6 +472,27 @@ function LassoPath(X::HipMatrix{T}, Y::StridedVector{T}, λpath::Vector{T}, opti
     mode_before == 1 && set_gradient_cache!(X, 1)
   end
   LassoPath{T}(copy(λpath), βpath)
+end
+
+"refitLassoPath(path, X, Y) (lasso.jl:208-225) for a design in HBM: X[:, S] \ Y for every distinct support S along the path,
+from the normal equations of the S columns at r = Y (cdh_gram) with the refinement of screening_ols!; supports already
+seen are skipped.  More than 4096 columns in one support: ArgumentError.  The handle is left at β = 0 with r = Y."
+function refitLassoPath(path::LassoPath{T}, X::HipMatrix{T}, Y::StridedVector{T}) where {T<:AbstractFloat}
+  out = Dict{Vector{Int64},Vector{Float64}}()
+  set_loss!(X, CDH_LS)
+  upload_y!(X, Y)
+  X.owner = nothing
+  for i = 1:length(path.λpath)
+    S = findall(!iszero, path.βpath[i])
+    haskey(out, S) && continue
+    check(X.handle, ccall((:cdh_initialize, libcdhip), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                          X.handle, X.p, 0, C_NULL, C_NULL))
+    out[S] = isempty(S) ? Float64[] : screening_ols!(X, Int64.(S))
+  end
+  check(X.handle, ccall((:cdh_initialize, libcdhip), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                        X.handle, X.p, 0, C_NULL, C_NULL))
+  X.synced = false                     # the handle's iterate is zero now, nobody's x
+  out
 end
 
 # ---- locpolyl1 with the design expanded on the device (src/varying_coefficient_lasso.jl:30-79) ----------------
