@@ -17,7 +17,7 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   OrderedIterator, RandomIterator, reset_, numCoordinates, initialize_, gradient,
                   descendCoordinate_, coordinateDescent_, cdPass_, findLambdaMax, stdX, objective,
                   lasso, sqrtLasso, scaledLasso_, LassoPath, LassoSolution, LassoPathResult,
-                  getLoadings, feasibleLasso_, refitLassoPath,
+                  getLoadings, feasibleLasso_, refitLassoPath, cvLassoPath, CVLassoPathResult,
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
                   get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
                   getSigma, findInitResiduals_,

@@ -116,6 +116,9 @@ def lib():
         "cdh_set_obs_weights": [vp, vp],
         "cdh_get_obs_weights": [vp, vp],
         "cdh_set_loss": [vp, i32],
+        "cdh_set_folds": [vp, vp, i32, vp],
+        "cdh_set_fold_weights": [vp, i32],
+        "cdh_path_sse": [vp, i32, i64, vp, i64, vp, i64, vp, vp],
         "cdh_generate": [vp, C.c_uint64, i64, f64, vp],
         "cdh_set_penalty": [vp, f64, vp, i64],
         "cdh_num_coordinates": [vp, P(i64)],

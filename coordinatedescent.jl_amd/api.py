@@ -430,6 +430,39 @@ class _HipLoss(CoordinateDifferentiableFunction):
         check(self._L.cdh_profile_end(self._h, C.byref(ms), C.byref(nl), C.byref(by)), self._h)
         return ms.value, nl.value, by.value
 
+    # -- cross-validation folds (cdh_set_folds, cdh_set_fold_weights, cdh_path_sse) ---------
+    def set_folds(self, folds, K):
+        """Keep the 0-based fold id of every row on the device (folds=None: drop them); returns the fold sizes."""
+        if folds is None:
+            check(self._L.cdh_set_folds(self._h, None, 0, None), self._h)
+            return None
+        ids = np.ascontiguousarray(folds, dtype=np.int32)
+        if ids.shape != (self.n,):
+            raise ArgumentError("folds must hold one id per row")
+        count = np.zeros(max(int(K), 1), dtype=np.int64)
+        check(self._L.cdh_set_folds(self._h, _vp(ids), int(K), _vp(count)), self._h)
+        return count
+
+    def set_fold_weights(self, k):
+        """f.w = (fold != k) written on the device (k = -1: all ones); the handle is left as an upload of those weights
+        would leave it."""
+        check(self._L.cdh_set_fold_weights(self._h, int(k)), self._h)
+        self._synced = None
+
+    def path_sse(self, k, idx1, B, held=True, train=True):
+        """Σ_i (y_i - Σ_t X[i, idx1[t]] B[t, j])² for every column j of B (len(idx1) x m) over the rows of fold k and over
+        the other rows, in one pass over the listed columns (k = -1: every row is a training row).  Returns
+        (held, train); an output that was not asked for is None.  Read-only on the handle."""
+        idx1 = np.ascontiguousarray(idx1, dtype=np.int64)
+        B = np.asfortranarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != idx1.shape[0]:
+            raise DimensionMismatch("B must have one row per listed coordinate")
+        s, m = B.shape
+        oh = np.zeros(m) if held else None
+        ot = np.zeros(m) if train else None
+        check(self._L.cdh_path_sse(self._h, int(k), s, _vp(idx1), m, _vp(B), max(s, 1), _vp(oh), _vp(ot)), self._h)
+        return oh, ot
+
     # -- sync helpers ----------------------------------------------------------------------
     def _set_penalty(self, g):
         if not isinstance(g, ProxL1):
@@ -1238,6 +1271,12 @@ def LassoPath(X, Y, lambdapath, options=None, max_hat_s=np.inf, standardizeX=Tru
     one x and one f shared by all λ (warm starts), βpath[i] = copy(x)."""
     f = _as_loss(CDLeastSquaresLoss, X, Y)
     sx = stdX(f) if standardizeX else np.ones(f.p)
+    return _solve_path(f, lambdapath, sx, options, max_hat_s, reuse_residual)
+
+
+def _solve_path(f, lambdapath, sx, options, max_hat_s, reuse_residual):
+    """The loop of LassoPath (src/lasso.jl:250-257) on whatever loss f is by now, with the penalty scales sx: a fresh x
+    warm-started along λ.  LassoPath and the folds of cvLassoPath run it."""
     x = SparseIterate(f.p)
     lambdapath = list(lambdapath)
     betapath = []
@@ -1261,6 +1300,132 @@ def LassoPath(X, Y, lambdapath, options=None, max_hat_s=np.inf, standardizeX=Tru
         if mode_before == 1:
             check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
     return LassoPathResult(lambdapath, betapath)
+
+
+@dataclass
+class CVLassoPathResult:
+    """What cvLassoPath returns.  fold_mse[k, j] is the mean squared prediction error of λ_j on the rows of fold k by the
+    path fitted without them, train_mse[k, j] the same on the rows it was fitted on; cvm and cvsd weight the folds by their
+    sizes; the two indices are 0-based positions in lambdapath."""
+    lambdapath: np.ndarray
+    fold_sizes: np.ndarray
+    fold_mse: np.ndarray
+    train_mse: np.ndarray
+    cvm: np.ndarray
+    cvsd: np.ndarray
+    index_min: int
+    lambda_min: float
+    index_1se: int
+    lambda_1se: float
+    path: LassoPathResult = None
+    fold_paths: list = None
+
+
+def _cv_fold_ids(n, K, folds, seed):
+    """The 0-based fold of every row, checked on the host: a caller's array, or default_rng(seed).permutation(n) % K."""
+    K = int(K)
+    if K < 2 or K > 255 or K > n:
+        raise ArgumentError("need 2 <= K <= 255 folds, and K <= n")
+    if folds is None:
+        ids = np.random.default_rng(seed).permutation(n) % K
+    else:
+        ids = np.asarray(folds)
+        if ids.shape != (n,):
+            raise ArgumentError("folds must hold one id per row")
+        if not np.issubdtype(ids.dtype, np.integer):
+            if not np.all(ids == np.floor(ids)):
+                raise ArgumentError("fold ids must be integers")
+        if ids.min() < 0 or ids.max() >= K:
+            raise ArgumentError("fold ids must lie in 0 .. K - 1")
+    ids = ids.astype(np.int32)
+    sizes = np.bincount(ids, minlength=K)
+    if np.any(sizes == 0):
+        raise ArgumentError("fold %d is empty" % int(np.nonzero(sizes == 0)[0][0]))
+    return ids, sizes
+
+
+def _cv_select(lam, sizes, fold_mse):
+    """cvm, cvsd and the two selection rules from the folds' errors."""
+    n, K = sizes.sum(), len(sizes)
+    wt = sizes / n
+    cvm = wt @ fold_mse
+    cvsd = np.sqrt(wt @ (fold_mse - cvm) ** 2 / (K - 1))
+    imin = int(np.argmin(cvm))
+    ok = np.nonzero(cvm <= cvm[imin] + cvsd[imin])[0]
+    i1se = int(ok[np.argmax(lam[ok])])           # the largest λ within one standard error; argmax takes the lowest index of a tie
+    return cvm, cvsd, imin, i1se
+
+
+def cvLassoPath(X, Y, lambdapath, K=10, folds=None, options=None, standardizeX=True, seed=0, full_path=True,
+                keep_fold_paths=False):
+    """K-fold cross-validation of LassoPath(X, Y, λpath, options; standardizeX) (src/lasso.jl:229-260) on the device; no
+    reference counterpart.  X may also be an existing CDLeastSquaresLoss (Y is then ignored); the design is uploaded once.
+
+    A fold is a 0/1 observation weight: LassoPath on the n_k training rows of fold k has the same iterates as the weighted
+    loss on all n rows with ω = _stdX!(w, X) and λ·sqrt(n_k / n) (standardizeX=False: ω = 1 and λ·n_k / n).  So per fold
+    the weights are written on the device from the resident fold ids (cdh_set_fold_weights), the whole path is solved
+    warm-started along λ exactly as LassoPath solves it, and one pass over the union support of the fold's path
+    (cdh_path_sse) gives the held-out and training errors of every λ.  Nothing n-sized moves after the upload.
+
+    folds: 0-based ids, one per row; otherwise np.random.default_rng(seed).permutation(n) % K.  There is no max_hat_s: the
+    folds would be truncated at different λ.  A handle that was passed in is switched to the weighted loss for the folds
+    and is back on least squares, without folds, when the call returns or raises (an iterate synced to it before the call
+    is pushed again by its next use).  `path` is LassoPath on all rows (None with full_path=False), `fold_paths` the K
+    fold paths as LassoPathResult (None unless keep_fold_paths)."""
+    if isinstance(X, CoordinateDifferentiableFunction) and not isinstance(X, CDLeastSquaresLoss):
+        raise TypeError("MethodError: cvLassoPath takes a matrix or a CDLeastSquaresLoss")
+    lam = np.array(list(lambdapath), dtype=np.float64)
+    if lam.size == 0:
+        raise ArgumentError("lambdapath is empty")
+    n = X.n if isinstance(X, _HipLoss) else np.shape(X)[0]
+    ids, sizes = _cv_fold_ids(int(n), K, folds, seed)
+    if isinstance(X, _HipLoss):
+        return _cv_lasso_path(X, lam, ids, sizes, options, standardizeX, full_path, keep_fold_paths)
+    f = CDLeastSquaresLoss(Y, X)
+    try:
+        return _cv_lasso_path(f, lam, ids, sizes, options, standardizeX, full_path, keep_fold_paths)
+    finally:
+        f.close()                  # the handle this call made goes with it, also when a fold raises
+
+
+def _cv_lasso_path(f, lam, ids, sizes, options, standardizeX, full_path, keep_fold_paths):
+    n, K, m = f.n, len(sizes), lam.size
+    if f.n_total != f.n:
+        raise ArgumentError("cvLassoPath does not run on row-sharded handles")
+    fold_mse, train_mse = np.zeros((K, m)), np.zeros((K, m))
+    fold_paths = [] if keep_fold_paths else None
+    try:
+        check(f._L.cdh_set_loss(f._h, CDH_WLS), f._h)
+        f._synced = None
+        f.set_folds(ids, K)
+        for k in range(K):
+            f.set_fold_weights(k)
+            nk = n - sizes[k]
+            sx = stdX(f, weighted=True) if standardizeX else np.ones(f.p)
+            scale = np.sqrt(nk / n) if standardizeX else nk / n
+            res = _solve_path(f, lam * scale, sx, options, np.inf, True)
+            beta = np.stack([b.dense() for b in res.betapath], axis=1)         # p x m
+            S = np.nonzero(np.any(beta != 0.0, axis=1))[0]
+            if len(S) > 4096:
+                raise ArgumentError("union support of a fold's path larger than 4096 columns")
+            if len(S) == 0:
+                S, B = np.zeros(1, dtype=np.int64), np.zeros((1, m))          # held-out SSE = Σ y² over the fold
+            else:
+                B = beta[S, :]
+            for j0 in range(0, m, 1024):
+                held, train = f.path_sse(k, S + 1, B[:, j0:j0 + 1024])
+                fold_mse[k, j0:j0 + 1024] = held / sizes[k]
+                train_mse[k, j0:j0 + 1024] = train / nk
+            if keep_fold_paths:
+                fold_paths.append(LassoPathResult(list(lam), res.betapath))
+    finally:
+        f._synced = None
+        f.set_folds(None, 0)
+        check(f._L.cdh_set_loss(f._h, CDH_LS), f._h)
+    cvm, cvsd, imin, i1se = _cv_select(lam, sizes, fold_mse)
+    path = LassoPath(f, None, lam, options, standardizeX=standardizeX) if full_path else None
+    return CVLassoPathResult(lam, sizes, fold_mse, train_mse, cvm, cvsd, imin, float(lam[imin]), i1se, float(lam[i1se]),
+                             path, fold_paths)
 
 
 # --------------------------------------------------------------------------------------

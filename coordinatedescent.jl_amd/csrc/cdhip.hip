@@ -270,6 +270,19 @@ struct VcGramBatchScratch {
 };
 struct VcGramBufs { double *partials, *out, *h_out; VcGramPoint *pts, *h_pts; };
 
+// Cross-validation folds (cv_path.hpp).  The fold ids of the rows -- a byte each, resident from cdh_set_folds until it drops them
+// -- and the scratch of cdh_path_sse, allocated by its first call: the workgroups' partial records, the summed record, the
+// 0-based coordinates of a call and the packed image of its B (cv_plan.hpp: sizes and layouts; the image grows with the calls).
+#include "cv_plan.hpp"
+struct CvState {
+    DevBuf<uint8_t> fold;
+    int K = 0;                 // 0: no folds set
+    DevBuf<double> partials, out, B;
+    DevBuf<int64_t> idx;
+    int64_t b_cap = 0;
+    bool ready = false;
+};
+
 struct Knobs {
     int lt = 2;                      // CDH_LT: k_gramstep's operand loads transposed through LDS: 0 off, 1 on, 2 by size
     int ks = 0;                      // CDH_KS: chunk length of that path: 0 by shard length, 1 short, 2 long
@@ -323,6 +336,7 @@ struct cdh_handle_s {
     int vc_degree = -1;           // -1: not in varying-coefficient mode
     VcGramScratch vg;
     VcGramBatchScratch vgb;
+    CvState cv;
     DevBuf<double> beta, omega;
     DevBuf<Ctrl> d_ctrl;
     DevBuf<int64_t> d_idx;
@@ -1007,6 +1021,7 @@ constexpr int kScreenMinPass = 16;   // screens / the cache: passes over fewer c
 #include "small_solve.hpp"  // small_applicable, small_prepare, small_solve
 #include "cov_solve.hpp"    // k_cov_solve, cov_solve: the pass loop of a cache-served solve on the device
 #include "quad_solve.hpp"   // k_quad_solve, k_quad_init: a batch of CDQuadraticLoss problems, one workgroup each
+#include "cv_path.hpp"      // k_fold_weights, k_path_sse: the folds of a cross-validated path and its errors in one pass
 
 // _cdPass! (coordinate_descent.jl:94-110)
 // Screening of a FULL pass (exact, no reference counterpart).  A visit of a coordinate with
@@ -1859,6 +1874,27 @@ int32_t cdh_col_wrms(cdh_handle h, double* out_p) { return guarded(h, [&]() -> i
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(cd[(size_t)(2 * j + 1)] / (double)h->n_total);
     return CDH_OK;
+}); }
+
+// ---- cross-validation of a lasso path (cv_path.hpp; the solves are lasso.jl:229-260 on 0/1 weights, utils.jl:140-151) ------
+int32_t cdh_set_folds(cdh_handle h, const int32_t* fold_of_row, int32_t K, int64_t* out_count) { return guarded(h, [&]() -> int32_t {
+    return cv_set_folds(h, fold_of_row, K, out_count);
+}); }
+
+// leaves the handle as cdh_set_obs_weights with the same values would
+int32_t cdh_set_fold_weights(cdh_handle h, int32_t k) { return guarded(h, [&]() -> int32_t {
+    CHK(cv_check_fold_weights(h, k));
+    CHK(design_changes(h, false));
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(ensure_weights_buffer(h));
+    CHK(cv_write_fold_weights(h, k));
+    h->has_w = true;
+    return CDH_OK;
+}); }
+
+int32_t cdh_path_sse(cdh_handle h, int32_t k, int64_t s, const int64_t* idx1, int64_t m, const double* B, int64_t ldb,
+                     double* out_held, double* out_train) { return guarded(h, [&]() -> int32_t {
+    return cv_path_sse(h, k, s, idx1, m, B, ldb, out_held, out_train);
 }); }
 
 // ---- varying-coefficient mode (varying_coefficient_lasso.jl:30-79) -------------------------------------------------

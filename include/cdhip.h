@@ -215,6 +215,38 @@ int32_t cdh_vc_gram_batch(cdh_handle h, int32_t kernel_kind, int64_t m,
                           double *out_G,                  /* m blocks of ep x ep, column-major, point after point */
                           double *out_c,                  /* NULL, or m blocks of ep */
                           double *out_sum_w);             /* NULL, or m values */
+/* ---- K-fold cross-validation of a lasso path (no reference counterpart) -----------------------------------------------
+ * LassoPath (lasso.jl:229-260) on the training rows of a fold is the weighted loss on all rows with w_i = 1 on the training
+ * rows and 0 on the others: with standardizeX the scales are _stdX!(w, X) (utils.jl:140-151; cdh_col_wrms) and lambda is
+ * multiplied by sqrt(n_k / n), n_k the training rows; without, the scales are 1 and lambda is multiplied by n_k / n.  The
+ * iterates are the same, so a resident X serves every fold, and nothing n-sized moves.
+ *
+ * cdh_set_folds keeps the fold of every row on the device, a byte each: fold_of_row holds n values in 0 .. K - 1,
+ * 2 <= K <= 255 and K <= n, every fold non-empty (CDH_BAD_ARG otherwise; the message names the fold that is empty); out_count
+ * (K values, may be NULL) receives the fold sizes.  fold_of_row == NULL with K == 0 drops the folds.  Nothing else on the
+ * handle changes; a refused call leaves the folds it had.
+ *
+ * cdh_set_fold_weights writes the observation weights of fold k on the device: w_i = (fold_i == k ? 0 : 1) in the handle's
+ * dtype, k == -1: all ones.  It leaves the handle exactly as cdh_set_obs_weights with those values would (the residual's
+ * consistency, the gradient cache and the one-launch solve's Gram matrix are void; cdh_get_obs_weights returns the values).
+ * CDH_BAD_ARG: not CDH_WLS; k >= 0 without folds, or k >= K; k < -1.
+ *
+ * cdh_path_sse evaluates the coefficients of a whole path against the rows in one pass over the listed columns: B is s x m,
+ * column-major with leading dimension ldb >= s, row t belonging to coordinate idx1[t] (1-based; a coordinate may repeat, its
+ * terms add), and
+ *   out_held[j]  = sum over rows i with fold_i == k of (y_i - sum_t X[i, idx1[t]] B[t, j])^2,
+ *   out_train[j] = the same sum over the other rows.
+ * k == -1 counts every row as training (out_held is all zero; folds need not be set).  1 <= s <= 4096, 1 <= m <= 1024, y set;
+ * either out pointer may be NULL, not both.  Storage values are converted to double and every product and sum is taken in
+ * double, in a fixed order: bit-identical run to run.  A function of X, y and the fold ids only -- any loss kind, either
+ * storage type -- and read-only: r does not catch up, and beta, the penalty, the weights, the residual's state, the gradient
+ * cache and the one-launch solve's Gram matrix are left as they are.  Scratch of its own, allocated by the first call.
+ *
+ * All three refuse row-sharded handles (n_local != n_total, or any exchange installed) with CDH_BAD_ARG. */
+int32_t cdh_set_folds(cdh_handle h, const int32_t *fold_of_row, int32_t K, int64_t *out_count);
+int32_t cdh_set_fold_weights(cdh_handle h, int32_t k);
+int32_t cdh_path_sse(cdh_handle h, int32_t k, int64_t s, const int64_t *idx1, int64_t m, const double *B, int64_t ldb,
+                     double *out_held, double *out_train);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects
