@@ -18,6 +18,8 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   descendCoordinate_, coordinateDescent_, cdPass_, findLambdaMax, stdX, objective,
                   lasso, sqrtLasso, scaledLasso_, LassoPath, LassoSolution, LassoPathResult,
                   getLoadings, feasibleLasso_, refitLassoPath, cvLassoPath, CVLassoPathResult,
+                  CDLogisticLoss, IRLSOptions, logisticLasso_, logisticLasso, logisticLambdaMax, LogisticLassoPath,
+                  LogisticLassoSolution, LogisticLassoPathResult,
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
                   get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
                   getSigma, findInitResiduals_,

@@ -511,6 +511,51 @@ class CDWeightedLSLoss(_HipLoss):
         super().__init__(y, X, w, **kw)
 
 
+class CDLogisticLoss(CDWeightedLSLoss):
+    """CDLogisticLoss(y, X): (1/n) Σ [log(1 + e^η_i) - y_i η_i], η = Xβ, labels y_i in [0, 1]; no reference counterpart.
+    Minimised by IRLS: a round is the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the
+    working response z and weights w, which the handle's y and w hold from one irls_step to the next; the labels live in a
+    buffer of their own (cdh_glm_set_labels).  fp64 only, one device."""
+
+    def __init__(self, y, X, *, device=0):
+        X = np.asarray(X)
+        labels = np.ascontiguousarray(y, dtype=np.float64)
+        if X.dtype != np.float64 or X.ndim != 2:
+            raise TypeError("MethodError: CDLogisticLoss takes X::AbstractMatrix{Float64}")
+        if labels.ndim != 1 or labels.shape[0] != X.shape[0]:
+            raise DimensionMismatch("length(y) != size(X, 1)")
+        n, p = X.shape
+        self._create(X.dtype, n, p, device, None, 0)
+        step = max(1, (64 << 20) // max(1, n * X.itemsize))
+        for j0 in range(0, p, step):
+            blk = np.asfortranarray(X[:, j0:j0 + step])
+            check(self._L.cdh_set_X_cols(self._h, j0, blk.shape[1], _vp(blk), n), self._h)
+        check(self._L.cdh_glm_set_labels(self._h, 0, _vp(labels)), self._h)
+
+    @property
+    def labels(self):
+        out = np.zeros(self.n)
+        check(self._L.cdh_glm_get_labels(self._h, _vp(out)), self._h)
+        return out
+
+    def irls_step(self, apply=True, wmin=1e-5):
+        """One IRLS step at the iterate the handle holds (cdh_glm_irls).  apply=True turns the handle's y, w and r into the
+        working response, the working weights (clamped below at wmin) and their residual; apply=False only reads.  Returns
+        {"nll": (1/n) Σ nll_i, "sum_w": Σ w_i, "clamped": rows whose weight was clamped}."""
+        out = np.zeros(3)
+        check(self._L.cdh_glm_irls(self._h, 1 if apply else 0, float(wmin), out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        return {"nll": float(out[0]) / self.n, "sum_w": float(out[1]), "clamped": int(out[2])}
+
+    def objective(self, g=None):
+        """F(β) = (1/n) Σ nll_i + λ0 Σ ω_j |β_j| at the handle's iterate, read-only (apply=0)."""
+        val = self.irls_step(apply=False, wmin=0.25)["nll"]       # (the sum of nll does not depend on wmin)
+        if g is not None:
+            beta = np.zeros(self.p)
+            check(self._L.cdh_get_beta(self._h, _vp(beta)), self._h)
+            val += g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
+        return val
+
+
 # --------------------------------------------------------------------------------------
 # Smoothing kernels (src/varying_coefficient_lasso.jl:3-21)
 # --------------------------------------------------------------------------------------
@@ -1058,6 +1103,8 @@ def objective(f, g=None, problem=0):
             om = np.ones(x.nnz) if g.lam is None else g.lam[k]
             val += g.lambda0 * float(np.sum(np.abs(x._val[: x.nnz]) * om))
         return val
+    if isinstance(f, CDLogisticLoss):        # F itself, not the weighted least squares of the round the handle is in
+        return f.objective(g)
     if g is not None:
         f._set_penalty(g)
     out = C.c_double()
@@ -1426,6 +1473,191 @@ def _cv_lasso_path(f, lam, ids, sizes, options, standardizeX, full_path, keep_fo
     path = LassoPath(f, None, lam, options, standardizeX=standardizeX) if full_path else None
     return CVLassoPathResult(lam, sizes, fold_mse, train_mse, cvm, cvsd, imin, float(lam[imin]), i1se, float(lam[i1se]),
                              path, fold_paths)
+
+
+# --------------------------------------------------------------------------------------
+# l1-penalised logistic regression by IRLS (no reference counterpart)
+# --------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class IRLSOptions:
+    """The outer loop of logisticLasso_: at most maxIter rounds, stopped when max_j |Δβ_j| < optTol between two rounds; the
+    working weights are clamped below at wmin (only the weights: the fixed point keeps the KKT conditions of F)."""
+    maxIter: int = 25
+    optTol: float = 1e-7
+    wmin: float = 1e-5
+
+
+@dataclass
+class LogisticLassoSolution:
+    """What logisticLasso_ and logisticLasso return.  nll is (1/n) Σ [log(1 + e^η) - y η] at the final β; monotone is False
+    if the penalised objective F rose between two rounds by more than 1e-10 max(1, F) (there is no step halving: the rise is
+    only reported); intercept is None unless one was fitted."""
+    x: SparseIterate
+    nll: float
+    rounds: int
+    converged: bool
+    monotone: bool
+    intercept: float = None
+    penalty: ProxL1 = None
+
+
+@dataclass
+class LogisticLassoPathResult(LassoPathResult):
+    """LassoPathResult with, per λ, the nll at the solution, the IRLS rounds taken, convergence and the intercept."""
+    nll: list = None
+    rounds: list = None
+    converged: list = None
+    intercepts: list = None
+
+
+def _penalty_value(g, beta):
+    return g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
+
+
+def logisticLasso_(x, f, g, options=None, irls=None):
+    """Minimise F(β) = (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ0 Σ ω_j |β_j| over the CDLogisticLoss f by IRLS, warm-started
+    from x (updated in place).  A round is one f.irls_step -- working weights, working response and their residual formed on
+    the device from the linear predictor the handle holds, nothing n-sized on the host -- and one coordinateDescent_ of the
+    weighted lasso they define, which keeps the residual the step left (cdh_set_reuse_residual for the duration)."""
+    if not isinstance(f, CDLogisticLoss):
+        raise TypeError("MethodError: logisticLasso_ takes a CDLogisticLoss")
+    options = options or CDOptions()
+    irls = irls or IRLSOptions()
+    if not options.warmStart:
+        raise ArgumentError("the rounds of IRLS are warm starts: options.warmStart must be true")
+    _check_dims(x, f, g)
+    f._ensure_synced(x)
+    check(f._L.cdh_set_reuse_residual(f._h, 1), f._h)
+    rounds, converged, monotone, F_prev = 0, False, True, None
+
+    def rose(F):
+        return F_prev is not None and F - F_prev > 1e-10 * max(1.0, F_prev)
+
+    try:
+        beta = x.dense()
+        for _ in range(int(irls.maxIter)):
+            F = f.irls_step(True, irls.wmin)["nll"] + _penalty_value(g, beta)      # F at the iterate this round starts from
+            monotone, F_prev = monotone and not rose(F), F
+            coordinateDescent_(x, f, g, options)
+            rounds += 1
+            beta, old = x.dense(), beta
+            if float(np.max(np.abs(beta - old))) < irls.optTol:
+                converged = True
+                break
+        f._ensure_synced(x)
+        nll = f.irls_step(False, irls.wmin)["nll"]
+        monotone = monotone and not rose(nll + _penalty_value(g, beta))
+    finally:
+        check(f._L.cdh_set_reuse_residual(f._h, 0), f._h)
+    return LogisticLassoSolution(x, nll, rounds, converged, monotone, None, g)
+
+
+def _logit_start(labels):
+    ybar = float(np.mean(labels))
+    if not 0.0 < ybar < 1.0:
+        raise ArgumentError("fit_intercept needs labels of both kinds: the null model's intercept is infinite")
+    return float(np.log(ybar / (1.0 - ybar)))
+
+
+def _logistic_loss(X, y, fit_intercept):
+    """-> (f, owned): a CDLogisticLoss over X (with a trailing column of ones when an intercept is fitted)."""
+    if isinstance(X, CDLogisticLoss):
+        if fit_intercept:
+            raise ArgumentError("fit_intercept appends a column of ones: pass the matrix, not a loss")
+        return X, False
+    if isinstance(X, CoordinateDifferentiableFunction):
+        raise TypeError("MethodError: takes a matrix or a CDLogisticLoss")
+    X = np.asarray(X)
+    if fit_intercept:
+        X = np.asfortranarray(np.hstack([X, np.ones((X.shape[0], 1), dtype=X.dtype)]))
+    return CDLogisticLoss(y, X), True
+
+
+def _split_intercept(x, p):
+    """x of length p + 1 -> (its first p coordinates as a SparseIterate, the last)."""
+    beta = x.dense()
+    return SparseIterate(p, beta[:p]), float(beta[p])
+
+
+def logisticLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=False):
+    """ℓ1-penalised logistic regression (glmnet's family = "binomial"): the minimiser of
+    (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ Σ ω_j |β_j|, η = Xβ (+ b with fit_intercept: a column of ones appended as
+    coordinate p + 1 with ω = 0, started at log(ȳ / (1 - ȳ)) and returned apart from x, which has length p).  X may also be
+    an existing CDLogisticLoss (y is then ignored; no intercept)."""
+    f, owned = _logistic_loss(X, y, fit_intercept)
+    try:
+        p = f.p - (1 if fit_intercept else 0)
+        om = None if omega is None else np.asarray(omega, dtype=np.float64)
+        x = SparseIterate(f.p)
+        if fit_intercept:
+            om = np.r_[np.ones(p) if om is None else om, 0.0]
+            x[p + 1] = _logit_start(np.asarray(y, dtype=np.float64))
+        sol = logisticLasso_(x, f, ProxL1(lam, om), options, irls)
+        if fit_intercept:
+            sol.x, sol.intercept = _split_intercept(x, p)
+        return sol
+    finally:
+        if owned:
+            f.close()
+
+
+def logisticLambdaMax(f, omega=None, fit_intercept=False):
+    """The smallest λ at which every penalised coordinate of the logistic lasso is zero: max_j |X_j'(y - p̂)| / (n ω_j) at the
+    null model (β = 0; with fit_intercept the last column of f is the column of ones, its coordinate log(ȳ / (1 - ȳ)) and
+    left out of the maximum).  One irls_step at the null model and one cdh_xt_r: the step leaves r = (y - p̂) / w, and at
+    the null model every row has the same weight w̄ = Σw / n, so X'(y - p̂) = w̄ X'r.  The handle is left at the null model."""
+    if not isinstance(f, CDLogisticLoss):
+        raise TypeError("MethodError: logisticLambdaMax takes a CDLogisticLoss")
+    p = f.p - (1 if fit_intercept else 0)
+    x = SparseIterate(f.p)
+    if fit_intercept:
+        x[p + 1] = _logit_start(f.labels)
+    f._push(x, rebuild=True)
+    f._synced = None
+    wbar = f.irls_step(True, 1e-12)["sum_w"] / f.n
+    out = np.zeros(f.p)
+    check(f._L.cdh_xt_r(f._h, _vp(out)), f._h)
+    t = np.abs(out[:p]) * wbar / f.n
+    if omega is not None:
+        t = t / np.asarray(omega, dtype=np.float64)[:p]
+    return float(t.max())
+
+
+def LogisticLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, fit_intercept=False):
+    """LassoPath's loop (src/lasso.jl:229-260) with logisticLasso_ per λ: one handle, one x warm-started along λ,
+    ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p."""
+    f, owned = _logistic_loss(X, y, fit_intercept)
+    try:
+        p = f.p - (1 if fit_intercept else 0)
+        sx = stdX(f) if standardizeX else np.ones(f.p)
+        x = SparseIterate(f.p)
+        if fit_intercept:
+            sx[p] = 0.0
+            x[p + 1] = _logit_start(f.labels)
+        lambdapath = list(lambdapath)
+        res = LogisticLassoPathResult(lambdapath, [], [], [], [], [])
+        mode_before = f.gradient_cache_mode()          # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
+        try:
+            for i, lam in enumerate(lambdapath):
+                sol = logisticLasso_(x, f, ProxL1(lam, sx), options, irls)
+                b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
+                res.betapath.append(b)
+                res.nll.append(sol.nll)
+                res.rounds.append(sol.rounds)
+                res.converged.append(sol.converged)
+                res.intercepts.append(b0)
+                if b.nnz > max_hat_s:
+                    res.lambdapath = lambdapath[: i + 1]
+                    break
+        finally:
+            if mode_before == 1:
+                check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
+        return res
+    finally:
+        if owned:
+            f.close()
 
 
 # --------------------------------------------------------------------------------------

@@ -283,6 +283,15 @@ struct CvState {
     bool ready = false;
 };
 
+// The logistic loss (glm_kernels.hpp): the labels of the rows, resident from cdh_glm_set_labels on in a buffer of the handle's
+// own -- y holds the working response of the IRLS round, not the labels.  glm_plan.hpp: the grid and the rows of a workgroup.
+#include "glm_plan.hpp"
+struct GlmState {
+    DevBuf<double> labels;
+    int family = 0;            // 0: binomial
+    bool set = false;
+};
+
 struct Knobs {
     int lt = 2;                      // CDH_LT: k_gramstep's operand loads transposed through LDS: 0 off, 1 on, 2 by size
     int ks = 0;                      // CDH_KS: chunk length of that path: 0 by shard length, 1 short, 2 long
@@ -294,6 +303,7 @@ struct Knobs {
     bool cov_solve = true;           // CDH_COV_SOLVE: the device-resident pass loop
     int cs_crew = 31;                // CDH_CS_CREW: its helper workgroups (0: none)
     int cs_ucap = 0;                 // CDH_CS_UCAP (tests): visit lists longer than this leave the loop's LDS block
+    int64_t glm_grid = kGlmMaxGrid;  // CDH_GLM_GRID (tests): cap of k_glm_irls' grid, so that a short vector gives a workgroup a second stride
     bool small_path = true;          // CDH_SMALL_PATH: the one-launch solve
     int64_t small_max_bytes = -1;    // CDH_SMALL_MAX_BYTES: a fixed limit on n p sz instead of rent-or-buy (-1: none)
     int64_t small_always_bytes = (int64_t)kSmallAlwaysBytes;   // CDH_SMALL_ALWAYS_BYTES (tests: 0 makes every handle rent first)
@@ -315,6 +325,7 @@ Knobs read_knobs() {
     k.cov_solve = num("CDH_COV_SOLVE", 1) != 0;
     k.cs_crew = (int)std::max(0LL, std::min((long long)kCsCrewMax, num("CDH_CS_CREW", k.cs_crew)));
     k.cs_ucap = (int)std::max(0LL, num("CDH_CS_UCAP", 0));
+    k.glm_grid = glm_grid_cap(num("CDH_GLM_GRID", k.glm_grid));
     k.small_path = num("CDH_SMALL_PATH", 1) != 0;
     k.small_max_bytes = num("CDH_SMALL_MAX_BYTES", k.small_max_bytes);
     k.small_always_bytes = num("CDH_SMALL_ALWAYS_BYTES", k.small_always_bytes);
@@ -337,6 +348,7 @@ struct cdh_handle_s {
     VcGramScratch vg;
     VcGramBatchScratch vgb;
     CvState cv;
+    GlmState glm;
     DevBuf<double> beta, omega;
     DevBuf<Ctrl> d_ctrl;
     DevBuf<int64_t> d_idx;
@@ -1022,6 +1034,7 @@ constexpr int kScreenMinPass = 16;   // screens / the cache: passes over fewer c
 #include "cov_solve.hpp"    // k_cov_solve, cov_solve: the pass loop of a cache-served solve on the device
 #include "quad_solve.hpp"   // k_quad_solve, k_quad_init: a batch of CDQuadraticLoss problems, one workgroup each
 #include "cv_path.hpp"      // k_fold_weights, k_path_sse: the folds of a cross-validated path and its errors in one pass
+#include "glm_kernels.hpp"  // k_glm_irls: the step between two IRLS rounds of the logistic loss
 
 // _cdPass! (coordinate_descent.jl:94-110)
 // Screening of a FULL pass (exact, no reference counterpart).  A visit of a coordinate with
@@ -1737,6 +1750,38 @@ int32_t cdh_loadings(cdh_handle h, double* out_p) { return guarded(h, [&]() -> i
     HIPCHK(h, hipMemcpyAsync(out_p, h->d_colout, sizeof(double) * h->p, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(out_p[j] / (double)h->n_total);
+    return CDH_OK;
+}); }
+
+// ---- l1-penalised logistic regression by IRLS (glm_kernels.hpp; no reference counterpart: a round's solve is the weighted lasso of
+// CDWeightedLSLoss, cd_differentiable_function.jl:118-194) ---------------------------------------------------------------------
+// stands in for cdh_set_y of n zeros, the labels kept beside it
+int32_t cdh_glm_set_labels(cdh_handle h, int32_t family, const void* host_labels) { return guarded(h, [&]() -> int32_t {
+    return glm_set_labels(h, family, host_labels);
+}); }
+
+int32_t cdh_glm_get_labels(cdh_handle h, void* host_labels) { return guarded(h, [&]() -> int32_t {
+    return glm_get_labels(h, host_labels);
+}); }
+
+// stands in for cdh_get_residual, w and z on the host, cdh_set_y, cdh_set_obs_weights and cdh_initialize between two rounds
+int32_t cdh_glm_irls(cdh_handle h, int32_t apply, double wmin, double* out3) { return guarded(h, [&]() -> int32_t {
+    CHK(glm_check_irls(h, apply, wmin, out3));
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(glm_catch_up(h));
+    if (!apply) return glm_launch(h, false, wmin, out3);      // read-only from here
+    // what cdh_set_obs_weights and cdh_set_y void, through their own calls: the residual's consistency and the stashed dots,
+    // the gradient cache with its Gram columns, y'y, the one-launch solve's G and c
+    CHK(design_changes(h, false));
+    gc_invalidate(h, false);
+    h->gc.st.yy_void();
+    h->small.c_valid = false;
+    CHK(ensure_weights_buffer(h));
+    CHK(glm_launch(h, true, wmin, out3));
+    // r = d / w IS z - X beta of the iterate, but not the bits initialize! would write: consistent, not pristine
+    h->rs.rewritten_as_residual();
+    gc_after_rebuild(h, h->x);           // (as after cdh_initialize: the cache's reference iterate is the handle's)
+    h->has_w = true;
     return CDH_OK;
 }); }
 

@@ -1,0 +1,157 @@
+// glm_kernels.hpp -- the step between two rounds of IRLS for l1-penalised logistic regression (no reference counterpart; a
+// round's solve is the weighted lasso of CDWeightedLSLoss, cd_differentiable_function.jl:118-194): from the linear predictor
+// the handle's residual stands for, the working weights, the working response and the new residual in one pass over the
+// rows, with the sums a caller needs of it.  Included by cdhip.hip inside its anonymous namespace, after the handle; the
+// grid and the rows of a workgroup are glm_plan.hpp's.
+
+// One row, every quantity in double and every operation rounded on its own (no contraction into FMAs: tests/_logistic_numpy.py
+// writes the same lines).  eta = yw - r;  a = |eta|, e = exp(-a);  p = 1 / (1 + e) or e / (1 + e) by the sign of eta and
+// q = 1 - p from the OTHER branch, never as a difference;  w = max(e / (1 + e)^2, wmin);  d = y q - (1 - y) p, which is
+// y - p without cancellation;  r_new = d / w, z = eta + r_new;  nll = max(eta, 0) + log1p(e) - y eta.
+struct GlmRow { double w, z, r, nll; bool clamped; };
+__device__ __forceinline__ GlmRow glm_row(double label, double yw, double r, double wmin) {
+#pragma clang fp contract(off)
+    const double eta = yw - r;
+    const double a = fabs(eta), e = exp(-a);
+    const double ope = 1.0 + e;
+    const double big = 1.0 / ope, small = e / ope;
+    const double p = eta >= 0.0 ? big : small, q = eta >= 0.0 ? small : big;
+    const double w_raw = e / (ope * ope);
+    GlmRow o;
+    o.clamped = w_raw < wmin;
+    o.w = o.clamped ? wmin : w_raw;
+    const double d = label * q - (1.0 - label) * p;
+    o.r = d / o.w;
+    o.z = eta + o.r;
+    o.nll = (fmax(eta, 0.0) + log1p(e)) - label * eta;
+    return o;
+}
+
+// Workgroup b walks tiles b, b + gridDim.x, ... of kGlmRows rows; a lane holds one 16-byte vector of each of the three
+// streams per trip.  Rows n .. ld - 1 (the pad rows every other kernel relies on being zero) are WRITTEN as
+// zeros in w, y and r with APPLY and add nothing to the sums -- eta = 0 there would otherwise give w = 0.25.  The lanes'
+// sums go through block_sum (wave butterflies, the four waves in order) into the workgroup's record
+// partials[b kGlmVals + {0, 1, 2}] = (sum nll, sum w, clamped rows); k_gram_reduce adds the records in block order.  No
+// atomics: bit-identical run to run.  With APPLY = false nothing is written but the record.
+template <bool APPLY>
+__global__ __launch_bounds__(kGlmBlock) void k_glm_irls(const double* __restrict__ label, double* __restrict__ y,
+                                                        double* __restrict__ r, double* __restrict__ w, int64_t n,
+                                                        int64_t vecs, double wmin, double* __restrict__ partials) {
+    __shared__ double s_red[kGlmVals * (kGlmBlock / 64)];
+    const dvec2* lv = reinterpret_cast<const dvec2*>(label);
+    dvec2* yv = reinterpret_cast<dvec2*>(y);
+    dvec2* rv = reinterpret_cast<dvec2*>(r);
+    dvec2* wv = reinterpret_cast<dvec2*>(w);
+    double acc[kGlmVals] = {0.0, 0.0, 0.0};
+    const int64_t stride = (int64_t)gridDim.x * kGlmBlock;
+    for (int64_t j = (int64_t)blockIdx.x * kGlmBlock + threadIdx.x; j < vecs; j += stride) {
+        const dvec2 ll = lv[j], yy = yv[j], rr = rv[j];
+        dvec2 wn, zn, rn;
+#pragma unroll
+        for (int e = 0; e < kGlmVec; ++e) {
+            const bool live = j * kGlmVec + e < n;
+            const GlmRow o = glm_row(ll[e], yy[e], rr[e], wmin);
+            wn[e] = live ? o.w : 0.0;
+            zn[e] = live ? o.z : 0.0;
+            rn[e] = live ? o.r : 0.0;
+            acc[0] += live ? o.nll : 0.0;
+            acc[1] += live ? o.w : 0.0;
+            acc[2] += (live && o.clamped) ? 1.0 : 0.0;
+        }
+        if constexpr (APPLY) { wv[j] = wn; yv[j] = zn; rv[j] = rn; }
+    }
+    block_sum<kGlmVals>(acc, s_red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kGlmVals; ++i) partials[(int64_t)blockIdx.x * kGlmVals + i] = acc[i];
+    }
+}
+static_assert(kGlmBlock == kBlock && kGlmVec == VecOf<double>::N, "block_sum and dvec2 are kernels.hpp's");
+
+// what the three exports refuse of the handle itself, before anything is touched (the style of vc_refuse_shards)
+int32_t glm_refuse(cdh_handle h) {
+    if (h->n != h->n_total || h->xs.sharded())
+        return fail(h, CDH_BAD_ARG, "the logistic loss does not run on row-sharded handles");
+    if (h->dtype != CDH_F64) return fail(h, CDH_BAD_ARG, "the logistic loss needs fp64 storage (CDH_F64)");
+    if (h->loss != CDH_WLS) return fail(h, CDH_BAD_ARG, "the logistic loss needs the CDH_WLS loss");
+    return CDH_OK;
+}
+
+// leaves the handle exactly as cdh_set_y of n zeros would (what that export voids is voided here, in its order)
+int32_t glm_set_labels(cdh_handle h, int32_t family, const void* host_labels) {
+    if (family != 0) return fail(h, CDH_BAD_ARG, "unknown family: 0 (binomial) is the only one");
+    CHK(glm_refuse(h));
+    NEED_P(h, host_labels);
+    const double* lab = (const double*)host_labels;
+    for (int64_t i = 0; i < h->n; ++i)
+        if (!(lab[i] >= 0.0 && lab[i] <= 1.0)) {      // (a NaN fails both comparisons)
+            char buf[128];
+            snprintf(buf, sizeof buf, "labels[%lld] = %g is outside [0, 1]", (long long)i, lab[i]);
+            return fail(h, CDH_BAD_ARG, buf);
+        }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t colbytes = (size_t)h->ld * sizeof(double);
+    DevBuf<double> fresh;                // complete before the handle changes: a failed allocation leaves it as it was
+    if (!h->glm.labels) {
+        HIPCHK(h, fresh.alloc(colbytes));
+        HIPCHK(h, hipMemsetAsync(fresh, 0, colbytes, h->stream));
+    }
+    h->rs.overwritten_with_y();          // r = copy(y) = 0 below
+    gc_invalidate(h, false);
+    h->gc.st.yy_void();
+    h->small.c_valid = false;
+    if (!h->glm.labels) h->glm.labels = std::move(fresh);
+    HIPCHK(h, hipMemcpyAsync(h->glm.labels, lab, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->y, 0, colbytes, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->r, 0, colbytes, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->y_set = true;
+    h->glm.family = family;
+    h->glm.set = true;
+    return CDH_OK;
+}
+
+int32_t glm_get_labels(cdh_handle h, void* host_labels) {
+    NEED_P(h, host_labels);
+    if (!h->glm.set) return fail(h, CDH_BAD_ARG, "no labels are set: call cdh_glm_set_labels first");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(host_labels, h->glm.labels, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CDH_OK;
+}
+
+// what cdh_glm_irls refuses, before the handle is touched
+int32_t glm_check_irls(cdh_handle h, int32_t apply, double wmin, const double* out3) {
+    CHK(glm_refuse(h));
+    if (!h->glm.set) return fail(h, CDH_BAD_ARG, "cdh_glm_irls needs labels: call cdh_glm_set_labels first");
+    if (apply != 0 && apply != 1) return fail(h, CDH_BAD_ARG, "apply must be 0 or 1");
+    if (!(wmin > 0.0 && wmin <= 0.25)) return fail(h, CDH_BAD_ARG, "need 0 < wmin <= 0.25");
+    NEED_P(h, out3);
+    if ((size_t)(glm_plan(h->ld, h->knobs.glm_grid).records * kGlmVals) > h->partials_doubles)
+        return fail(h, CDH_BAD_ARG, "partials too small");
+    return CDH_OK;
+}
+
+// eta = y - r holds of the residual the handle STANDS FOR at its iterate: r first catches up with what it owes, as for every
+// reader of r (cdh_loadings' catch-up); a residual that is not its iterate's is rebuilt through the body cdh_initialize runs
+int32_t glm_catch_up(cdh_handle h) {
+    if (!h->rs.consistent()) return rebuild_residual(h);
+    return sync_r(h);
+}
+
+// the pass and its sums: out3 = (sum nll, sum w, clamped rows)
+int32_t glm_launch(cdh_handle h, bool apply, double wmin, double* out3) {
+    const GlmPlan pl = glm_plan(h->ld, h->knobs.glm_grid);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid), dim3(kGlmBlock), 0, h->stream, (const double*)h->glm.labels,
+                           (double*)h->y, (double*)h->r, (double*)h->w, h->n, pl.vecs, wmin, (double*)h->d_partials);
+    };
+    if (apply) go(k_glm_irls<true>); else go(k_glm_irls<false>);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_gram_reduce, dim3((kGlmVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
+                       (const double*)h->d_partials, (int)pl.records, (int)kGlmVals, (double*)h->d_red);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out3, h->d_red, sizeof(double) * kGlmVals, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CDH_OK;
+}

@@ -95,6 +95,10 @@ public:
     void rebuilt_from(const SupportList& x) { consistent_ = true; pristine_ = true; x_pristine_ = x; }
     // the buffer already held what initialize!(x) writes (rebuild_is_noop): keeps the stash, the residual stood for is the same
     void rebuild_skipped() { roundings_ = 1; consistent_ = true; n_rebuild_skipped_ += 1; }
+    // a kernel has just written y, W and r together so that r IS y - X x of the current iterate (cdh_glm_irls: r = d / w under
+    // the new working response), after r had caught up: consistent, but NOT the bits initialize! would write -- a later
+    // rebuild must run -- and nothing taken of the old r, y or W holds
+    void rewritten_as_residual() { overwritten(); roundings_ = 1; consistent_ = true; }
     // r = copy(y) under a new y: whatever the iterate is, r is not its residual
     void overwritten_with_y() { consistent_ = false; overwritten(); }
     // X and y regenerated with r = y; keeps `consistent`: the generator zeroes the iterate, so r IS its residual -- a

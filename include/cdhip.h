@@ -247,6 +247,39 @@ int32_t cdh_set_folds(cdh_handle h, const int32_t *fold_of_row, int32_t K, int64
 int32_t cdh_set_fold_weights(cdh_handle h, int32_t k);
 int32_t cdh_path_sse(cdh_handle h, int32_t k, int64_t s, const int64_t *idx1, int64_t m, const double *B, int64_t ldb,
                      double *out_held, double *out_train);
+/* ---- l1-penalised logistic regression by IRLS (no reference counterpart) ----------------------------------------------
+ * F(beta) = (1/n) sum_i [log(1 + e^eta_i) - y_i eta_i] + lambda0 sum_j omega_j |beta_j|, eta = X beta, labels y_i in [0, 1].
+ * One round of IRLS solves the weighted lasso sum_i w_i (z_i - x_i'beta)^2 / (2n) + lambda0 sum_j omega_j |beta_j| -- the
+ * loss of CDWeightedLSLoss (cd_differentiable_function.jl:118-194), so the solver and the resident X are unchanged -- and the
+ * step between two rounds forms w, z and the residual z - X beta from the current linear predictor.  That step is
+ * cdh_glm_irls: one elementwise pass on the device where the exports below would move three n-sized vectors across the host.
+ * Per row, every quantity in double: eta = y_w - r (y_w the working response the handle holds, r the residual it stands
+ * for), a = |eta|, e = exp(-a); p = 1/(1+e) if eta >= 0, else e/(1+e), and q = 1 - p taken from the other branch;
+ * w = max(e/(1+e)^2, wmin); d = y q - (1-y) p; r_new = d / w; z = eta + r_new; nll = max(eta, 0) + log1p(e) - y eta.
+ * Only w is clamped, so the fixed point's KKT conditions are those of F: X_j'W r = X_j'(y - p) whatever W is.
+ *
+ * cdh_glm_set_labels (stands in for cdh_set_y: the labels are kept beside y, which becomes the working response) stores n
+ * doubles in a buffer the handle owns (allocated all-or-nothing) and zeroes the working response: the handle is left
+ * exactly as cdh_set_y of n zeros would leave it.  family 0 = binomial.  CDH_BAD_ARG, the handle unchanged: another family;
+ * not CDH_WLS; not CDH_F64 (eta = y_w - r in fp32 loses eta once |z| grows); row-sharded (n_local != n_total, or any
+ * exchange installed); a label that is not finite or outside [0, 1] (the message names the row).  cdh_glm_get_labels copies
+ * the labels back.
+ *
+ * cdh_glm_irls (stands in for cdh_get_residual, w and z formed on the host, cdh_set_y, cdh_set_obs_weights and
+ * cdh_initialize) needs labels, CDH_WLS, fp64, apply in {0, 1} and 0 < wmin <= 0.25.  out3 = {sum_i nll_i, sum_i w_i,
+ * number of rows whose weight was clamped} at the iterate the handle holds, summed in a fixed order: bit-identical run to
+ * run.  Before the pass r catches up with what it owes, as for every reader of r (cdh_loadings); a residual that is not
+ * the iterate's (after cdh_set_iterate, cdh_set_y, cdh_glm_set_labels, ...) is rebuilt as cdh_initialize would.
+ *   apply = 0 reads only: beta, the penalty, the weights, y, r's state, the gradient cache and the one-launch solve's Gram
+ *     data are left as they are.
+ *   apply = 1 writes w to the observation weights, z to y and r_new to r, rows n .. ld - 1 as zeros, and leaves the handle
+ *     as cdh_set_y(z), cdh_set_obs_weights(w) and cdh_initialize(beta) would: the gradient cache, the stashed dots, y'y
+ *     and the one-launch solve's Gram matrix and X'Wy are void, cdh_get_obs_weights returns w; r is the iterate's residual
+ *     (a warm start with cdh_set_reuse_residual may keep it) but not the bits cdh_initialize writes, so a later
+ *     cdh_initialize is executed, not skipped. */
+int32_t cdh_glm_set_labels(cdh_handle h, int32_t family, const void *host_labels);
+int32_t cdh_glm_get_labels(cdh_handle h, void *host_labels);
+int32_t cdh_glm_irls(cdh_handle h, int32_t apply, double wmin, double *out3);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects

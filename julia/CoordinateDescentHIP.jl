@@ -495,6 +495,33 @@ function refitLassoPath(path::LassoPath{T}, X::HipMatrix{T}, Y::StridedVector{T}
   out
 end
 
+# ---- l1-penalised logistic regression by IRLS (no reference counterpart) --------------------------------------
+# A round solves the weighted lasso of CDWeightedLSLoss (cd_differentiable_function.jl:118-194) on the working response
+# and weights; the step between two rounds runs on the device (cdh_glm_irls), so nothing n-sized moves per round.
+"the 0/1 labels (proportions in [0, 1] allowed) of a Float64 design under the weighted loss; the working response is zeroed"
+function glm_set_labels!(X::HipMatrix{Float64}, labels::Vector{Float64})
+  length(labels) == X.n || throw(DimensionMismatch())
+  set_loss!(X, CDH_WLS)
+  check(X.handle, ccall((:cdh_glm_set_labels, libcdhip), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}), X.handle, Int32(0), labels))
+  X.owner = nothing
+  X.synced = false
+  X
+end
+
+function glm_get_labels(X::HipMatrix{Float64})
+  out = Vector{Float64}(undef, X.n)
+  check(X.handle, ccall((:cdh_glm_get_labels, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), X.handle, out))
+  out
+end
+
+"one IRLS step at the iterate the handle holds: (Σ nll, Σ w, clamped rows); apply=false reads only"
+function glm_irls!(X::HipMatrix{Float64}; apply::Bool=true, wmin::Float64=1e-5)
+  out = Vector{Float64}(undef, 3)
+  check(X.handle, ccall((:cdh_glm_irls, libcdhip), Int32, (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}),
+                        X.handle, Int32(apply), wmin, out))
+  (nll = out[1] / X.n, sum_w = out[2], clamped = Int(out[3]))
+end
+
 # ---- locpolyl1 with the design expanded on the device (src/varying_coefficient_lasso.jl:30-79) ----------------
 # The reference rebuilds w, expandX and stdX on the host for every z0 (:63-65).  A HipVaryingDesign keeps the base
 # design and z in HBM; cdh_vc_set_point regenerates all three there, and the refit (:71-76) reads its weighted normal
