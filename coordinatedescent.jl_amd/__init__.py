@@ -19,7 +19,7 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   lasso, sqrtLasso, scaledLasso_, LassoPath, LassoSolution, LassoPathResult,
                   getLoadings, feasibleLasso_, refitLassoPath, cvLassoPath, CVLassoPathResult,
                   CDLogisticLoss, IRLSOptions, logisticLasso_, logisticLasso, logisticLambdaMax, LogisticLassoPath,
-                  LogisticLassoSolution, LogisticLassoPathResult,
+                  LogisticLassoSolution, LogisticLassoPathResult, cvLogisticLassoPath, CVLogisticLassoPathResult,
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
                   get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
                   getSigma, findInitResiduals_,

@@ -538,13 +538,23 @@ class CDLogisticLoss(CDWeightedLSLoss):
         check(self._L.cdh_glm_get_labels(self._h, _vp(out)), self._h)
         return out
 
-    def irls_step(self, apply=True, wmin=1e-5):
+    def irls_step(self, apply=True, wmin=1e-5, fold=None):
         """One IRLS step at the iterate the handle holds (cdh_glm_irls).  apply=True turns the handle's y, w and r into the
         working response, the working weights (clamped below at wmin) and their residual; apply=False only reads.  Returns
-        {"nll": (1/n) Σ nll_i, "sum_w": Σ w_i, "clamped": rows whose weight was clamped}."""
-        out = np.zeros(3)
-        check(self._L.cdh_glm_irls(self._h, 1 if apply else 0, float(wmin), out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
-        return {"nll": float(out[0]) / self.n, "sum_w": float(out[1]), "clamped": int(out[2])}
+        {"nll": (1/n) Σ nll_i, "sum_w": Σ w_i, "clamped": rows whose weight was clamped}.
+
+        fold=k (cdh_glm_irls_fold, after set_folds): the rows of fold k are held out -- w = 0, z = η, r = 0 -- and the three
+        sums run over the other rows; the dict gains "held_nll" = Σ nll_i and "held_miss" = Σ y_i [η_i <= 0] + (1 - y_i) [η_i > 0]
+        over the held-out rows (sums, not means).  "nll" stays (1/n) Σ over the training rows: the handle's objective."""
+        po = C.POINTER(C.c_double)
+        if fold is None:
+            out = np.zeros(3)
+            check(self._L.cdh_glm_irls(self._h, 1 if apply else 0, float(wmin), out.ctypes.data_as(po)), self._h)
+            return {"nll": float(out[0]) / self.n, "sum_w": float(out[1]), "clamped": int(out[2])}
+        out = np.zeros(5)
+        check(self._L.cdh_glm_irls_fold(self._h, int(fold), 1 if apply else 0, float(wmin), out.ctypes.data_as(po)), self._h)
+        return {"nll": float(out[0]) / self.n, "sum_w": float(out[1]), "clamped": int(out[2]),
+                "held_nll": float(out[3]), "held_miss": float(out[4])}
 
     def objective(self, g=None):
         """F(β) = (1/n) Σ nll_i + λ0 Σ ω_j |β_j| at the handle's iterate, read-only (apply=0)."""
@@ -1499,6 +1509,8 @@ class LogisticLassoSolution:
     monotone: bool
     intercept: float = None
     penalty: ProxL1 = None
+    held_nll: float = None       # with fold=k: Σ nll_i and Σ misclassification over the held-out rows at the final β
+    held_miss: float = None
 
 
 @dataclass
@@ -1514,11 +1526,15 @@ def _penalty_value(g, beta):
     return g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
 
 
-def logisticLasso_(x, f, g, options=None, irls=None):
+def logisticLasso_(x, f, g, options=None, irls=None, fold=None):
     """Minimise F(β) = (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ0 Σ ω_j |β_j| over the CDLogisticLoss f by IRLS, warm-started
     from x (updated in place).  A round is one f.irls_step -- working weights, working response and their residual formed on
     the device from the linear predictor the handle holds, nothing n-sized on the host -- and one coordinateDescent_ of the
-    weighted lasso they define, which keeps the residual the step left (cdh_set_reuse_residual for the duration)."""
+    weighted lasso they define, which keeps the residual the step left (cdh_set_reuse_residual for the duration).
+
+    fold=k: every step, the final read-only one included, holds the rows of fold k out (irls_step(fold=k), after
+    f.set_folds); the minimised F is then (1/n) Σ over the training rows, and the solution carries the held-out rows'
+    held_nll and held_miss at the final β."""
     if not isinstance(f, CDLogisticLoss):
         raise TypeError("MethodError: logisticLasso_ takes a CDLogisticLoss")
     options = options or CDOptions()
@@ -1536,7 +1552,7 @@ def logisticLasso_(x, f, g, options=None, irls=None):
     try:
         beta = x.dense()
         for _ in range(int(irls.maxIter)):
-            F = f.irls_step(True, irls.wmin)["nll"] + _penalty_value(g, beta)      # F at the iterate this round starts from
+            F = f.irls_step(True, irls.wmin, fold)["nll"] + _penalty_value(g, beta)      # F at the iterate this round starts from
             monotone, F_prev = monotone and not rose(F), F
             coordinateDescent_(x, f, g, options)
             rounds += 1
@@ -1545,11 +1561,12 @@ def logisticLasso_(x, f, g, options=None, irls=None):
                 converged = True
                 break
         f._ensure_synced(x)
-        nll = f.irls_step(False, irls.wmin)["nll"]
+        last = f.irls_step(False, irls.wmin, fold)
+        nll = last["nll"]
         monotone = monotone and not rose(nll + _penalty_value(g, beta))
     finally:
         check(f._L.cdh_set_reuse_residual(f._h, 0), f._h)
-    return LogisticLassoSolution(x, nll, rounds, converged, monotone, None, g)
+    return LogisticLassoSolution(x, nll, rounds, converged, monotone, None, g, last.get("held_nll"), last.get("held_miss"))
 
 
 def _logit_start(labels):
@@ -1628,36 +1645,170 @@ def LogisticLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.in
     ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p."""
     f, owned = _logistic_loss(X, y, fit_intercept)
     try:
-        p = f.p - (1 if fit_intercept else 0)
-        sx = stdX(f) if standardizeX else np.ones(f.p)
-        x = SparseIterate(f.p)
-        if fit_intercept:
-            sx[p] = 0.0
-            x[p + 1] = _logit_start(f.labels)
-        lambdapath = list(lambdapath)
-        res = LogisticLassoPathResult(lambdapath, [], [], [], [], [])
-        mode_before = f.gradient_cache_mode()          # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
-        if mode_before == 1:
-            check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
-        try:
-            for i, lam in enumerate(lambdapath):
-                sol = logisticLasso_(x, f, ProxL1(lam, sx), options, irls)
-                b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
-                res.betapath.append(b)
-                res.nll.append(sol.nll)
-                res.rounds.append(sol.rounds)
-                res.converged.append(sol.converged)
-                res.intercepts.append(b0)
-                if b.nnz > max_hat_s:
-                    res.lambdapath = lambdapath[: i + 1]
-                    break
-        finally:
-            if mode_before == 1:
-                check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
-        return res
+        return _logistic_path_on(f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept)
     finally:
         if owned:
             f.close()
+
+
+def _logistic_path_on(f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, labels=None):
+    """LogisticLassoPath on the loss f (its last column the column of ones when an intercept is fitted; labels: the host's
+    copy of f.labels, where the caller still has it)."""
+    p = f.p - (1 if fit_intercept else 0)
+    sx = stdX(f) if standardizeX else np.ones(f.p)
+    x = SparseIterate(f.p)
+    if fit_intercept:
+        sx[p] = 0.0
+        x[p + 1] = _logit_start(f.labels if labels is None else labels)
+    lambdapath = list(lambdapath)
+    res = LogisticLassoPathResult(lambdapath, [], [], [], [], [])
+    mode_before = f.gradient_cache_mode()          # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
+    if mode_before == 1:
+        check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
+    try:
+        for i, lam in enumerate(lambdapath):
+            sol = logisticLasso_(x, f, ProxL1(lam, sx), options, irls)
+            b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
+            res.betapath.append(b)
+            res.nll.append(sol.nll)
+            res.rounds.append(sol.rounds)
+            res.converged.append(sol.converged)
+            res.intercepts.append(b0)
+            if b.nnz > max_hat_s:
+                res.lambdapath = lambdapath[: i + 1]
+                break
+    finally:
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
+    return res
+
+
+@dataclass
+class CVLogisticLassoPathResult:
+    """What cvLogisticLassoPath returns.  Per fold k and λ_j, by the path fitted without the rows of fold k:
+    fold_deviance[k, j] = 2 Σ nll_i / size_k and fold_class[k, j] = misclassified rows / size_k over the held-out rows,
+    train_deviance[k, j] = 2 Σ nll_i / n_k over the rows it was fitted on, rounds and converged of its IRLS loop.  cvm, cvsd
+    and the two selections (0-based positions in lambdapath) are taken from `measure`, the folds weighted by their sizes."""
+    lambdapath: np.ndarray
+    fold_sizes: np.ndarray
+    fold_deviance: np.ndarray
+    train_deviance: np.ndarray
+    fold_class: np.ndarray
+    rounds: np.ndarray
+    converged: np.ndarray
+    measure: str
+    cvm: np.ndarray
+    cvsd: np.ndarray
+    index_min: int
+    lambda_min: float
+    index_1se: int
+    lambda_1se: float
+    path: LogisticLassoPathResult = None
+    fold_paths: list = None
+
+
+_CV_LOGISTIC_MEASURES = ("deviance", "class")
+
+
+def cvLogisticLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, fit_intercept=False,
+                        seed=0, measure="deviance", full_path=True, keep_fold_paths=False):
+    """K-fold cross-validation of LogisticLassoPath(X, y, λpath, options, irls; standardizeX, fit_intercept) on the device
+    (glmnet's cv.glmnet(family = "binomial")); no reference counterpart.  X may also be an existing CDLogisticLoss (y is then
+    ignored; no intercept); the design is uploaded once.
+
+    A fold is a 0/1 observation weight, as in cvLassoPath: the logistic lasso on the n_k training rows of fold k has the
+    iterates of IRLS on all n rows with the held-out rows at w = 0, z = η (irls_step(fold=k): cdh_glm_irls_fold), ω =
+    _stdX!(w, X) of the 0/1 weights and λ·sqrt(n_k / n) (standardizeX=False: ω = 1 and λ·n_k / n).  Per fold the path is
+    LogisticLassoPath's loop, warm-started along λ, and the read-only step that ends every solve returns the held-out
+    deviance and class error of that λ.  Nothing n-sized moves after the upload.
+
+    folds: 0-based ids, one per row; otherwise np.random.default_rng(seed).permutation(n) % K.  measure: "deviance" or
+    "class" -- what cvm, cvsd and the selections are taken from.  There is no max_hat_s: the folds would be truncated at
+    different λ.  With fit_intercept every fold starts at the logit of its own training rows' mean label.  The folds are
+    dropped when the call returns or raises.  `path` is LogisticLassoPath on all rows (None with full_path=False): from a
+    matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was passed
+    in it runs after them, so that the loss comes back with the weights of all rows.  `fold_paths`: the K fold paths as LogisticLassoPathResult (None unless keep_fold_paths)."""
+    if measure not in _CV_LOGISTIC_MEASURES:
+        raise ArgumentError('measure must be "deviance" or "class"')
+    if isinstance(X, CoordinateDifferentiableFunction) and not isinstance(X, CDLogisticLoss):
+        raise TypeError("MethodError: cvLogisticLassoPath takes a matrix or a CDLogisticLoss")
+    lam = np.array(list(lambdapath), dtype=np.float64)
+    if lam.size == 0:
+        raise ArgumentError("lambdapath is empty")
+    n = X.n if isinstance(X, _HipLoss) else np.shape(X)[0]
+    ids, sizes = _cv_fold_ids(int(n), K, folds, seed)
+    labels = None
+    if fit_intercept and not isinstance(X, _HipLoss):
+        labels = np.ascontiguousarray(y, dtype=np.float64)
+        for k in range(len(sizes)):                     # before the upload: a fold whose start would be infinite
+            _logit_start(labels[ids != k])
+    f, owned = _logistic_loss(X, y, fit_intercept)
+    try:
+        return _cv_logistic_path(f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, labels, measure,
+                                 full_path, keep_fold_paths)
+    finally:
+        if owned:
+            f.close()                  # the handle this call made goes with it, also when a fold raises
+
+
+def _cv_logistic_path(f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, labels, measure, full_path,
+                      keep_fold_paths):
+    n, K, m = f.n, len(sizes), lam.size
+    if f.n_total != f.n:
+        raise ArgumentError("cvLogisticLassoPath does not run on row-sharded handles")
+    p = f.p - (1 if fit_intercept else 0)
+    dev, tdev, cls = np.zeros((K, m)), np.zeros((K, m)), np.zeros((K, m))
+    rounds, conv = np.zeros((K, m), dtype=np.int64), np.zeros((K, m), dtype=bool)
+    fold_paths = [] if keep_fold_paths else None
+    if fit_intercept and labels is None:
+        labels = f.labels                                # (a loss that was passed in has no intercept: not reached in practice)
+    # The path on all rows.  On the handle this call has just made it runs FIRST: the very calls LogisticLassoPath makes on a
+    # fresh handle, so the same bits (after the folds an intercept's start η = b0 would be read as y - (y - b0) off the working
+    # response they left, and the handle's cache policy has a history).  A loss that was passed in gets it LAST, and comes
+    # back as LogisticLassoPath leaves it: the weights of all rows, no folds.
+    path = None
+    if full_path and owned:
+        path = _logistic_path_on(f, lam, options, irls, np.inf, standardizeX, fit_intercept, labels)
+    mode_before = f.gradient_cache_mode()                # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
+    try:
+        f.set_folds(ids, K)
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
+        for k in range(K):
+            f.set_fold_weights(k)
+            nk = n - sizes[k]
+            sx = stdX(f, weighted=True) if standardizeX else np.ones(f.p)     # while w still holds the 0/1 weights
+            scale = np.sqrt(nk / n) if standardizeX else nk / n
+            x = SparseIterate(f.p)
+            if fit_intercept:
+                sx[p] = 0.0
+                x[p + 1] = _logit_start(labels[ids != k])
+            res = LogisticLassoPathResult(list(lam), [], [], [], [], [])
+            for j in range(m):
+                sol = logisticLasso_(x, f, ProxL1(lam[j] * scale, sx), options, irls, fold=k)
+                dev[k, j] = 2.0 * sol.held_nll / sizes[k]
+                tdev[k, j] = 2.0 * n * sol.nll / nk
+                cls[k, j] = sol.held_miss / sizes[k]
+                rounds[k, j], conv[k, j] = sol.rounds, sol.converged
+                if keep_fold_paths:
+                    b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
+                    res.betapath.append(b)
+                    res.nll.append(sol.nll * n / nk)
+                    res.rounds.append(sol.rounds)
+                    res.converged.append(sol.converged)
+                    res.intercepts.append(b0)
+            if keep_fold_paths:
+                fold_paths.append(res)
+    finally:
+        f._synced = None
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
+        f.set_folds(None, 0)
+    cvm, cvsd, imin, i1se = _cv_select(lam, sizes, dev if measure == "deviance" else cls)
+    if full_path and not owned:
+        path = _logistic_path_on(f, lam, options, irls, np.inf, standardizeX, fit_intercept)
+    return CVLogisticLassoPathResult(lam, sizes, dev, tdev, cls, rounds, conv, measure, cvm, cvsd, imin, float(lam[imin]),
+                                     i1se, float(lam[i1se]), path, fold_paths)
 
 
 # --------------------------------------------------------------------------------------

@@ -1785,6 +1785,26 @@ int32_t cdh_glm_irls(cdh_handle h, int32_t apply, double wmin, double* out3) { r
     return CDH_OK;
 }); }
 
+// the same step inside a fold of a cross-validated path (cv_path.hpp; the solves are LassoPath's, lasso.jl:229-260, on the
+// weighted loss): held-out rows keep weight zero through every round, and their deviance and class error come out of the pass
+int32_t cdh_glm_irls_fold(cdh_handle h, int32_t k, int32_t apply, double wmin, double* out5) { return guarded(h, [&]() -> int32_t {
+    CHK(glm_check_irls_fold(h, k, apply, wmin, out5));
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(glm_catch_up(h));
+    if (!apply) return glm_launch_fold(h, k, false, wmin, out5);      // read-only from here
+    // what cdh_glm_irls(apply = 1) voids, through the same calls in the same order
+    CHK(design_changes(h, false));
+    gc_invalidate(h, false);
+    h->gc.st.yy_void();
+    h->small.c_valid = false;
+    CHK(ensure_weights_buffer(h));
+    CHK(glm_launch_fold(h, k, true, wmin, out5));
+    h->rs.rewritten_as_residual();
+    gc_after_rebuild(h, h->x);
+    h->has_w = true;
+    return CDH_OK;
+}); }
+
 int32_t cdh_xt_r(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_p);
     HIPCHK(h, hipSetDevice(h->device));

@@ -68,6 +68,67 @@ __global__ __launch_bounds__(kGlmBlock) void k_glm_irls(const double* __restrict
 }
 static_assert(kGlmBlock == kBlock && kGlmVec == VecOf<double>::N, "block_sum and dvec2 are kernels.hpp's");
 
+// The step of a cross-validated path (cv_path.hpp: a fold is a 0/1 observation weight on the resident X; the solves are
+// LassoPath's, lasso.jl:229-260, on the weighted loss): k_glm_irls' grid, tiles, vectors and sums, with the fold id of every
+// row -- one byte, n of them, not ld -- deciding what the row becomes.  A training row (fold_i != k) is k_glm_irls' row.  A
+// held-out row (fold_i == k) gets w = 0 exactly (never clamped up to wmin), z = eta and r = 0: its row of X enters no
+// gradient, and eta = y - r stays recoverable from the two stored vectors after the solver's residual updates, so the next
+// step finds its linear predictor where it finds everybody's.  Its nll and its misclassification at the current iterate
+// (label [eta <= 0] + (1 - label) [eta > 0]: eta = 0 predicts class 0) go into sums of their own.  The record is
+// partials[b kGlmFoldVals + {0 .. 4}] = (nll of training rows, sum w, clamped training rows, nll of held-out rows, held-out
+// rows misclassified); lane sums, block_sum and k_gram_reduce take every value in k_glm_irls' order, so with no fold
+// (fold == nullptr or k < 0) w, y, r and the first three sums are k_glm_irls' bit for bit and the last two are zero.
+// A lane's vector covers two rows and the last one may lie at or beyond n: the id's address is clamped to n - 1 and the load
+// unconditional (as k_path_sse's), so no byte at or beyond n is read; `live` keeps such a row out of everything.  (Measured
+// and dropped: both ids in one 2-byte load where both rows lie below n, the clamped byte load elsewhere -- 1.12x the plain
+// step against 1.08x for the two byte loads, interleaved at n = 1e7.)
+template <bool APPLY>
+__global__ __launch_bounds__(kGlmBlock) void k_glm_irls_fold(const double* __restrict__ label, double* __restrict__ y,
+                                                             double* __restrict__ r, double* __restrict__ w,
+                                                             const uint8_t* __restrict__ fold, int k, int64_t n,
+                                                             int64_t vecs, double wmin, double* __restrict__ partials) {
+    __shared__ double s_red[kGlmFoldVals * (kGlmBlock / 64)];
+    const dvec2* lv = reinterpret_cast<const dvec2*>(label);
+    dvec2* yv = reinterpret_cast<dvec2*>(y);
+    dvec2* rv = reinterpret_cast<dvec2*>(r);
+    dvec2* wv = reinterpret_cast<dvec2*>(w);
+    const bool folded = fold != nullptr && k >= 0;           // (uniform over the launch)
+    double acc[kGlmFoldVals] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const int64_t stride = (int64_t)gridDim.x * kGlmBlock;
+    for (int64_t j = (int64_t)blockIdx.x * kGlmBlock + threadIdx.x; j < vecs; j += stride) {
+        const dvec2 ll = lv[j], yy = yv[j], rr = rv[j];
+        int id[kGlmVec];
+#pragma unroll
+        for (int e = 0; e < kGlmVec; ++e) {
+            const int64_t i = j * kGlmVec + e;
+            id[e] = folded ? (int)fold[i < n ? i : n - 1] : -1;
+        }
+        dvec2 wn, zn, rn;
+#pragma unroll
+        for (int e = 0; e < kGlmVec; ++e) {
+            const bool live = j * kGlmVec + e < n;
+            const bool held = live && folded && id[e] == k;
+            const bool train = live && !held;
+            const GlmRow o = glm_row(ll[e], yy[e], rr[e], wmin);
+            const double eta = yy[e] - rr[e];                // (glm_row's own first line)
+            wn[e] = train ? o.w : 0.0;
+            zn[e] = train ? o.z : (held ? eta : 0.0);
+            rn[e] = train ? o.r : 0.0;
+            acc[0] += train ? o.nll : 0.0;
+            acc[1] += train ? o.w : 0.0;
+            acc[2] += (train && o.clamped) ? 1.0 : 0.0;
+            acc[3] += held ? o.nll : 0.0;
+            acc[4] += held ? (eta > 0.0 ? 1.0 - ll[e] : ll[e]) : 0.0;
+        }
+        if constexpr (APPLY) { wv[j] = wn; yv[j] = zn; rv[j] = rn; }
+    }
+    block_sum<kGlmFoldVals>(acc, s_red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kGlmFoldVals; ++i) partials[(int64_t)blockIdx.x * kGlmFoldVals + i] = acc[i];
+    }
+}
+
 // what the three exports refuse of the handle itself, before anything is touched (the style of vc_refuse_shards)
 int32_t glm_refuse(cdh_handle h) {
     if (h->n != h->n_total || h->xs.sharded())
@@ -132,6 +193,17 @@ int32_t glm_check_irls(cdh_handle h, int32_t apply, double wmin, const double* o
     return CDH_OK;
 }
 
+// what cdh_glm_irls_fold refuses, before the handle is touched: all of the above, and of k what cdh_set_fold_weights refuses
+int32_t glm_check_irls_fold(cdh_handle h, int32_t k, int32_t apply, double wmin, const double* out5) {
+    CHK(glm_check_irls(h, apply, wmin, out5));
+    if (k < -1) return fail(h, CDH_BAD_ARG, "k must be a fold, or -1 for all ones");
+    if (k >= 0 && h->cv.K == 0) return fail(h, CDH_BAD_ARG, "k >= 0 needs cdh_set_folds first");
+    if (k >= h->cv.K && k >= 0) return fail(h, CDH_BAD_ARG, "k must be below the K of cdh_set_folds");
+    if ((size_t)(glm_plan(h->ld, h->knobs.glm_grid).records * kGlmFoldVals) > h->partials_doubles)
+        return fail(h, CDH_BAD_ARG, "partials too small");
+    return CDH_OK;
+}
+
 // eta = y - r holds of the residual the handle STANDS FOR at its iterate: r first catches up with what it owes, as for every
 // reader of r (cdh_loadings' catch-up); a residual that is not its iterate's is rebuilt through the body cdh_initialize runs
 int32_t glm_catch_up(cdh_handle h) {
@@ -152,6 +224,26 @@ int32_t glm_launch(cdh_handle h, bool apply, double wmin, double* out3) {
                        (const double*)h->d_partials, (int)pl.records, (int)kGlmVals, (double*)h->d_red);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out3, h->d_red, sizeof(double) * kGlmVals, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CDH_OK;
+}
+
+// the fold-aware pass and its sums: out5 = (nll of training rows, sum w, clamped rows, nll of held-out rows, held-out rows
+// misclassified); k = -1: no row is held out and the fold ids are not read
+int32_t glm_launch_fold(cdh_handle h, int32_t k, bool apply, double wmin, double* out5) {
+    const GlmPlan pl = glm_plan(h->ld, h->knobs.glm_grid);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid), dim3(kGlmBlock), 0, h->stream, (const double*)h->glm.labels,
+                           (double*)h->y, (double*)h->r, (double*)h->w,
+                           k >= 0 ? (const uint8_t*)h->cv.fold : (const uint8_t*)nullptr, (int)k, h->n, pl.vecs, wmin,
+                           (double*)h->d_partials);
+    };
+    if (apply) go(k_glm_irls_fold<true>); else go(k_glm_irls_fold<false>);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_gram_reduce, dim3((kGlmFoldVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
+                       (const double*)h->d_partials, (int)pl.records, (int)kGlmFoldVals, (double*)h->d_red);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out5, h->d_red, sizeof(double) * kGlmFoldVals, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
 }

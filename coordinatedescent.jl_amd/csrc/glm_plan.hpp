@@ -15,6 +15,9 @@ constexpr int kGlmVec = 2;                                // doubles per 16-byte
 constexpr int64_t kGlmRows = (int64_t)kGlmBlock * kGlmVec; // a workgroup's share of rows per stride
 constexpr int64_t kGlmMaxGrid = 1024;                     // four workgroups per CU of 256
 constexpr int kGlmVals = 3;
+// the record of the fold-aware step (k_glm_irls_fold): (nll of the training rows, sum w, clamped rows, nll of the held-out
+// rows, misclassified held-out rows); same grid, same tiles, one record per workgroup
+constexpr int kGlmFoldVals = 5;
 
 struct GlmPlan {
     int64_t vecs;      // 16-byte vectors over the ld rows

@@ -280,6 +280,26 @@ int32_t cdh_path_sse(cdh_handle h, int32_t k, int64_t s, const int64_t *idx1, in
 int32_t cdh_glm_set_labels(cdh_handle h, int32_t family, const void *host_labels);
 int32_t cdh_glm_get_labels(cdh_handle h, void *host_labels);
 int32_t cdh_glm_irls(cdh_handle h, int32_t apply, double wmin, double *out3);
+/* cdh_glm_irls_fold: the step of cdh_glm_irls inside fold k of a cross-validated logistic path (no reference counterpart; it
+ * joins the two sections above: a round's solve is the weighted lasso of CDWeightedLSLoss, cd_differentiable_function.jl:118-194,
+ * and the path over the training rows is LassoPath's loop, lasso.jl:229-260, on 0/1 observation weights).  cdh_glm_irls
+ * writes the weight of every row, so the first round of a fold would turn its held-out rows into training rows again; here
+ * the fold ids of cdh_set_folds decide per row, in the same single pass:
+ *   a training row (fold_i != k) is cdh_glm_irls' row: w (clamped below at wmin), z and r_new;
+ *   a held-out row (fold_i == k) gets w = 0 exactly (never clamped), z = eta and r = 0, so that its row of X enters no
+ *     gradient and eta = y_w - r stays what the next step reads after the solver's updates of r;
+ *   rows n .. ld - 1 are written as zeros.
+ * out5 = {sum of nll_i over the training rows, sum of w_i, training rows whose weight was clamped, sum of nll_i over the
+ * held-out rows, sum over the held-out rows of y_i [eta_i <= 0] + (1 - y_i) [eta_i > 0]} at the iterate the handle holds --
+ * the last is the number of misclassified held-out rows for 0/1 labels, eta = 0 predicting class 0 (glmnet's type.measure =
+ * "class") -- each summed in a fixed order: bit-identical run to run.  With standardised penalty scales omega = _stdX!(w, X)
+ * (utils.jl:140-151) of the 0/1 weights and lambda sqrt(n_k / n), the rounds are those of the logistic lasso on the n_k
+ * training rows alone.
+ * k == -1: no row is held out, folds need not be set, and w, z, r and out5[0..2] are cdh_glm_irls' bit for bit;
+ * out5[3] = out5[4] = 0.  The catch-up of r before the pass, apply = 0 (read-only) and the state apply = 1 leaves are
+ * cdh_glm_irls'; cdh_get_obs_weights returns the written weights, zeros included.  CDH_BAD_ARG, the handle unchanged:
+ * everything cdh_glm_irls refuses; k < -1; k >= 0 without folds; k >= K. */
+int32_t cdh_glm_irls_fold(cdh_handle h, int32_t k, int32_t apply, double wmin, double *out5);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects

@@ -522,6 +522,14 @@ function glm_irls!(X::HipMatrix{Float64}; apply::Bool=true, wmin::Float64=1e-5)
   (nll = out[1] / X.n, sum_w = out[2], clamped = Int(out[3]))
 end
 
+"the same step inside fold k (0-based, -1: none) of the folds the handle holds: held-out rows get w = 0, z = η and r = 0, and their Σ nll and misclassified rows are returned beside the training rows' sums"
+function glm_irls_fold!(X::HipMatrix{Float64}, k::Integer; apply::Bool=true, wmin::Float64=1e-5)
+  out = Vector{Float64}(undef, 5)
+  check(X.handle, ccall((:cdh_glm_irls_fold, libcdhip), Int32, (Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Float64}),
+                        X.handle, Int32(k), Int32(apply), wmin, out))
+  (nll = out[1] / X.n, sum_w = out[2], clamped = Int(out[3]), held_nll = out[4], held_miss = out[5])
+end
+
 # ---- locpolyl1 with the design expanded on the device (src/varying_coefficient_lasso.jl:30-79) ----------------
 # The reference rebuilds w, expandX and stdX on the host for every z0 (:63-65).  A HipVaryingDesign keeps the base
 # design and z in HBM; cdh_vc_set_point regenerates all three there, and the refit (:71-76) reads its weighted normal
