@@ -20,6 +20,8 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   getLoadings, feasibleLasso_, refitLassoPath, cvLassoPath, CVLassoPathResult,
                   CDLogisticLoss, IRLSOptions, logisticLasso_, logisticLasso, logisticLambdaMax, LogisticLassoPath,
                   LogisticLassoSolution, LogisticLassoPathResult, cvLogisticLassoPath, CVLogisticLassoPathResult,
+                  CDPoissonLoss, poissonLasso_, poissonLasso, poissonLambdaMax, PoissonLassoPath, PoissonLassoSolution,
+                  PoissonLassoPathResult, cvPoissonLassoPath, CVPoissonLassoPathResult,
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
                   get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
                   getSigma, findInitResiduals_,

@@ -566,6 +566,75 @@ class CDLogisticLoss(CDWeightedLSLoss):
         return val
 
 
+class CDPoissonLoss(CDWeightedLSLoss):
+    """CDPoissonLoss(y, X, offset=None): (1/n) Σ [μ_i - y_i η_i], η = Xβ + o, μ = e^η, counts y_i >= 0 and offsets o_i (log
+    exposure); no reference counterpart.  Minimised by IRLS like CDLogisticLoss (a sibling, not a subclass of it): a round is
+    the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the working response and weights
+    the handle's y and w hold from one irls_step to the next.  The counts and the offset live in buffers of their own
+    (cdh_glm_set_counts), and the stored working response leaves the offset out: f.y - f.r is Xβ.  fp64 only, one device."""
+
+    def __init__(self, y, X, offset=None, *, device=0):
+        X = np.asarray(X)
+        counts = np.ascontiguousarray(y, dtype=np.float64)
+        off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64)
+        if X.dtype != np.float64 or X.ndim != 2:
+            raise TypeError("MethodError: CDPoissonLoss takes X::AbstractMatrix{Float64}")
+        if counts.ndim != 1 or counts.shape[0] != X.shape[0]:
+            raise DimensionMismatch("length(y) != size(X, 1)")
+        if off is not None and off.shape != counts.shape:
+            raise DimensionMismatch("length(offset) != size(X, 1)")
+        n, p = X.shape
+        self._create(X.dtype, n, p, device, None, 0)
+        step = max(1, (64 << 20) // max(1, n * X.itemsize))
+        for j0 in range(0, p, step):
+            blk = np.asfortranarray(X[:, j0:j0 + step])
+            check(self._L.cdh_set_X_cols(self._h, j0, blk.shape[1], _vp(blk), n), self._h)
+        check(self._L.cdh_glm_set_counts(self._h, _vp(counts), _vp(off)), self._h)
+
+    @property
+    def counts(self):
+        out = np.zeros(self.n)
+        check(self._L.cdh_glm_get_labels(self._h, _vp(out)), self._h)
+        return out
+
+    @property
+    def offset(self):
+        """The offsets (zeros when none was given)."""
+        out = np.zeros(self.n)
+        check(self._L.cdh_glm_get_offset(self._h, _vp(out)), self._h)
+        return out
+
+    def irls_step(self, apply=True, wmin=1e-5, eta_max=50.0, fold=None):
+        """One IRLS step at the iterate the handle holds (cdh_glm_poisson_irls).  apply=True turns the handle's y, w and r into
+        the working response (without the offset), the working weights (μ clamped below at wmin, η capped above at eta_max)
+        and their residual; apply=False only reads.  Returns {"nll": (1/n) Σ [μ_i - y_i η_i], "sum_w": Σ w_i, "clamped": rows
+        whose weight was clamped, "capped": rows whose η was capped, "deviance": Σ dev_i}, the sums over the training rows
+        ("capped" over all rows).
+
+        fold=k (after set_folds): the rows of fold k are held out -- w = 0, z = Xβ, r = 0 -- and the dict gains
+        "held_deviance" = Σ dev_i over them (a sum, not a mean)."""
+        out = np.zeros(6)
+        k = -1 if fold is None else int(fold)
+        if k < 0 and fold is not None:
+            raise ArgumentError("fold must be a fold id")
+        check(self._L.cdh_glm_poisson_irls(self._h, k, 1 if apply else 0, float(wmin), float(eta_max),
+                                           out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        res = {"nll": float(out[0]) / self.n, "sum_w": float(out[1]), "clamped": int(out[2]), "capped": int(out[3]),
+               "deviance": float(out[5])}
+        if fold is not None:
+            res["held_deviance"] = float(out[4])
+        return res
+
+    def objective(self, g=None):
+        """F(β) = (1/n) Σ [μ_i - y_i η_i] + λ0 Σ ω_j |β_j| at the handle's iterate, read-only (apply=0)."""
+        val = self.irls_step(apply=False)["nll"]
+        if g is not None:
+            beta = np.zeros(self.p)
+            check(self._L.cdh_get_beta(self._h, _vp(beta)), self._h)
+            val += g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
+        return val
+
+
 # --------------------------------------------------------------------------------------
 # Smoothing kernels (src/varying_coefficient_lasso.jl:3-21)
 # --------------------------------------------------------------------------------------
@@ -1491,10 +1560,13 @@ def _cv_lasso_path(f, lam, ids, sizes, options, standardizeX, full_path, keep_fo
 @dataclass(frozen=True)
 class IRLSOptions:
     """The outer loop of logisticLasso_: at most maxIter rounds, stopped when max_j |Δβ_j| < optTol between two rounds; the
-    working weights are clamped below at wmin (only the weights: the fixed point keeps the KKT conditions of F)."""
+    working weights are clamped below at wmin (only the weights: the fixed point keeps the KKT conditions of F).  etaMax
+    (the Poisson family only) caps the linear predictor before exp: a chosen guard, not a measurement -- exp and w x² stay
+    finite, and it is far beyond any fitted model."""
     maxIter: int = 25
     optTol: float = 1e-7
     wmin: float = 1e-5
+    etaMax: float = 50.0
 
 
 @dataclass
@@ -1526,19 +1598,10 @@ def _penalty_value(g, beta):
     return g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
 
 
-def logisticLasso_(x, f, g, options=None, irls=None, fold=None):
-    """Minimise F(β) = (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ0 Σ ω_j |β_j| over the CDLogisticLoss f by IRLS, warm-started
-    from x (updated in place).  A round is one f.irls_step -- working weights, working response and their residual formed on
-    the device from the linear predictor the handle holds, nothing n-sized on the host -- and one coordinateDescent_ of the
-    weighted lasso they define, which keeps the residual the step left (cdh_set_reuse_residual for the duration).
-
-    fold=k: every step, the final read-only one included, holds the rows of fold k out (irls_step(fold=k), after
-    f.set_folds); the minimised F is then (1/n) Σ over the training rows, and the solution carries the held-out rows'
-    held_nll and held_miss at the final β."""
-    if not isinstance(f, CDLogisticLoss):
-        raise TypeError("MethodError: logisticLasso_ takes a CDLogisticLoss")
+def _irls_rounds(x, f, g, options, irls, step):
+    """The outer loop logisticLasso_ and poissonLasso_ share: step(apply) is the family's f.irls_step with the caller's
+    options and fold.  -> (the dict of the read-only step that ends the solve, rounds, converged, monotone)."""
     options = options or CDOptions()
-    irls = irls or IRLSOptions()
     if not options.warmStart:
         raise ArgumentError("the rounds of IRLS are warm starts: options.warmStart must be true")
     _check_dims(x, f, g)
@@ -1552,7 +1615,7 @@ def logisticLasso_(x, f, g, options=None, irls=None, fold=None):
     try:
         beta = x.dense()
         for _ in range(int(irls.maxIter)):
-            F = f.irls_step(True, irls.wmin, fold)["nll"] + _penalty_value(g, beta)      # F at the iterate this round starts from
+            F = step(True)["nll"] + _penalty_value(g, beta)      # F at the iterate this round starts from
             monotone, F_prev = monotone and not rose(F), F
             coordinateDescent_(x, f, g, options)
             rounds += 1
@@ -1561,11 +1624,27 @@ def logisticLasso_(x, f, g, options=None, irls=None, fold=None):
                 converged = True
                 break
         f._ensure_synced(x)
-        last = f.irls_step(False, irls.wmin, fold)
-        nll = last["nll"]
-        monotone = monotone and not rose(nll + _penalty_value(g, beta))
+        last = step(False)
+        monotone = monotone and not rose(last["nll"] + _penalty_value(g, beta))
     finally:
         check(f._L.cdh_set_reuse_residual(f._h, 0), f._h)
+    return last, rounds, converged, monotone
+
+
+def logisticLasso_(x, f, g, options=None, irls=None, fold=None):
+    """Minimise F(β) = (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ0 Σ ω_j |β_j| over the CDLogisticLoss f by IRLS, warm-started
+    from x (updated in place).  A round is one f.irls_step -- working weights, working response and their residual formed on
+    the device from the linear predictor the handle holds, nothing n-sized on the host -- and one coordinateDescent_ of the
+    weighted lasso they define, which keeps the residual the step left (cdh_set_reuse_residual for the duration).
+
+    fold=k: every step, the final read-only one included, holds the rows of fold k out (irls_step(fold=k), after
+    f.set_folds); the minimised F is then (1/n) Σ over the training rows, and the solution carries the held-out rows'
+    held_nll and held_miss at the final β."""
+    if not isinstance(f, CDLogisticLoss):
+        raise TypeError("MethodError: logisticLasso_ takes a CDLogisticLoss")
+    irls = irls or IRLSOptions()
+    last, rounds, converged, monotone = _irls_rounds(x, f, g, options, irls, lambda apply: f.irls_step(apply, irls.wmin, fold))
+    nll = last["nll"]
     return LogisticLassoSolution(x, nll, rounds, converged, monotone, None, g, last.get("held_nll"), last.get("held_miss"))
 
 
@@ -1809,6 +1888,296 @@ def _cv_logistic_path(f, owned, lam, ids, sizes, options, irls, standardizeX, fi
         path = _logistic_path_on(f, lam, options, irls, np.inf, standardizeX, fit_intercept)
     return CVLogisticLassoPathResult(lam, sizes, dev, tdev, cls, rounds, conv, measure, cvm, cvsd, imin, float(lam[imin]),
                                      i1se, float(lam[i1se]), path, fold_paths)
+
+
+# --------------------------------------------------------------------------------------
+# l1-penalised Poisson regression with an offset, by the same IRLS loop (no reference counterpart)
+# --------------------------------------------------------------------------------------
+@dataclass
+class PoissonLassoSolution:
+    """What poissonLasso_ and poissonLasso return.  nll is (1/n) Σ [μ_i - y_i η_i] and deviance Σ dev_i over the training rows
+    at the final β; capped counts the rows whose η the final step capped at etaMax; monotone is False if the penalised
+    objective F rose between two rounds by more than 1e-10 max(1, F) (there is no step halving: the rise is only reported);
+    intercept is None unless one was fitted; held_deviance (with fold=k) is Σ dev_i over the held-out rows."""
+    x: SparseIterate
+    nll: float
+    deviance: float
+    rounds: int
+    converged: bool
+    monotone: bool
+    capped: int = 0
+    intercept: float = None
+    penalty: ProxL1 = None
+    held_deviance: float = None
+
+
+@dataclass
+class PoissonLassoPathResult(LassoPathResult):
+    """LassoPathResult with, per λ, the nll and the deviance at the solution, the IRLS rounds taken, convergence and the
+    intercept."""
+    nll: list = None
+    deviance: list = None
+    rounds: list = None
+    converged: list = None
+    intercepts: list = None
+
+
+def poissonLasso_(x, f, g, options=None, irls=None, fold=None):
+    """Minimise F(β) = (1/n) Σ [μ_i - y_i η_i] + λ0 Σ ω_j |β_j|, η = Xβ + o, μ = e^η, over the CDPoissonLoss f by IRLS,
+    warm-started from x (updated in place): logisticLasso_'s loop with f.irls_step of the Poisson family (irls.wmin,
+    irls.etaMax).  fold=k: every step holds the rows of fold k out, F is (1/n) Σ over the training rows, and the solution
+    carries the held-out rows' held_deviance at the final β."""
+    if not isinstance(f, CDPoissonLoss):
+        raise TypeError("MethodError: poissonLasso_ takes a CDPoissonLoss")
+    irls = irls or IRLSOptions()
+    last, rounds, converged, monotone = _irls_rounds(x, f, g, options, irls,
+                                                     lambda apply: f.irls_step(apply, irls.wmin, irls.etaMax, fold))
+    return PoissonLassoSolution(x, last["nll"], last["deviance"], rounds, converged, monotone, last["capped"], None, g,
+                                last.get("held_deviance"))
+
+
+def _poisson_start(counts, offset=None):
+    """The intercept of the null model: log(Σy / Σ e^o)."""
+    total = float(np.sum(counts))
+    if not total > 0.0:
+        raise ArgumentError("fit_intercept needs a positive count: the null model's intercept is -infinity")
+    expo = float(len(counts)) if offset is None else float(np.sum(np.exp(offset)))
+    return float(np.log(total / expo))
+
+
+def _poisson_loss(X, y, fit_intercept, offset):
+    """-> (f, owned): a CDPoissonLoss over X (with a trailing column of ones when an intercept is fitted)."""
+    if isinstance(X, CDPoissonLoss):
+        if fit_intercept:
+            raise ArgumentError("fit_intercept appends a column of ones: pass the matrix, not a loss")
+        if offset is not None:
+            raise ArgumentError("the offset belongs to the loss: pass the matrix, or a loss made with it")
+        return X, False
+    if isinstance(X, CoordinateDifferentiableFunction):
+        raise TypeError("MethodError: takes a matrix or a CDPoissonLoss")
+    X = np.asarray(X)
+    if fit_intercept:
+        X = np.asfortranarray(np.hstack([X, np.ones((X.shape[0], 1), dtype=X.dtype)]))
+    return CDPoissonLoss(y, X, offset), True
+
+
+def poissonLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=False, offset=None):
+    """ℓ1-penalised Poisson regression (glmnet's family = "poisson" with offset): the minimiser of
+    (1/n) Σ [μ_i - y_i η_i] + λ Σ ω_j |β_j|, η = Xβ + o (+ b with fit_intercept: a column of ones appended as coordinate
+    p + 1 with ω = 0, started at log(Σy / Σ e^o) and returned apart from x, which has length p).  X may also be an existing
+    CDPoissonLoss (y and offset are then its own; no intercept)."""
+    if fit_intercept and not isinstance(X, CoordinateDifferentiableFunction):
+        start = _poisson_start(np.asarray(y, dtype=np.float64), None if offset is None else np.asarray(offset, dtype=np.float64))
+    f, owned = _poisson_loss(X, y, fit_intercept, offset)
+    try:
+        p = f.p - (1 if fit_intercept else 0)
+        om = None if omega is None else np.asarray(omega, dtype=np.float64)
+        x = SparseIterate(f.p)
+        if fit_intercept:
+            om = np.r_[np.ones(p) if om is None else om, 0.0]
+            x[p + 1] = start
+        sol = poissonLasso_(x, f, ProxL1(lam, om), options, irls)
+        if fit_intercept:
+            sol.x, sol.intercept = _split_intercept(x, p)
+        return sol
+    finally:
+        if owned:
+            f.close()
+
+
+def poissonLambdaMax(f, omega=None, fit_intercept=False):
+    """The smallest λ at which every penalised coordinate of the Poisson lasso is zero: max_j |X_j'(y - μ)| / (n ω_j) at the
+    null model (β = 0, μ = e^o; with fit_intercept the last column of f is the column of ones, its coordinate
+    log(Σy / Σ e^o) and left out of the maximum).  One applied irls_step at the null model leaves r = (y - μ) / w, and the
+    weighted gradient of the handle (cdh_lambda_max: X_j'W r / n) is X_j'(y - μ) / n -- with an offset the null weights differ
+    by row, so the binomial's w̄ X'r does not hold here.  Nothing n-sized crosses the host beyond the counts and the offset of
+    an intercept's start.  The handle is left at the null model, with the penalty scales of the maximum."""
+    if not isinstance(f, CDPoissonLoss):
+        raise TypeError("MethodError: poissonLambdaMax takes a CDPoissonLoss")
+    p = f.p - (1 if fit_intercept else 0)
+    x = SparseIterate(f.p)
+    om = None if omega is None else np.asarray(omega, dtype=np.float64)[:p]
+    if fit_intercept:
+        x[p + 1] = _poisson_start(f.counts, f.offset)
+        om = np.r_[np.ones(p) if om is None else om, np.inf]        # (|g| / inf = 0: the intercept is out of the maximum)
+    f._push(x, rebuild=True)
+    f._synced = None
+    f.irls_step(True, 1e-300)
+    f._set_penalty(ProxL1(1.0, om))
+    out = C.c_double()
+    check(f._L.cdh_lambda_max(f._h, C.byref(out)), f._h)
+    return out.value
+
+
+def PoissonLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, fit_intercept=False,
+                     offset=None):
+    """LassoPath's loop (src/lasso.jl:229-260) with poissonLasso_ per λ: one handle, one x warm-started along λ,
+    ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p."""
+    start = None
+    if fit_intercept and not isinstance(X, CoordinateDifferentiableFunction):
+        start = _poisson_start(np.asarray(y, dtype=np.float64), None if offset is None else np.asarray(offset, dtype=np.float64))
+    f, owned = _poisson_loss(X, y, fit_intercept, offset)
+    try:
+        return _poisson_path_on(f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, start)
+    finally:
+        if owned:
+            f.close()
+
+
+def _poisson_path_on(f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, start=None):
+    """PoissonLassoPath on the loss f (its last column the column of ones when an intercept is fitted; start: the null
+    model's intercept, where the caller has computed it from its host copies)."""
+    p = f.p - (1 if fit_intercept else 0)
+    sx = stdX(f) if standardizeX else np.ones(f.p)
+    x = SparseIterate(f.p)
+    if fit_intercept:
+        sx[p] = 0.0
+        x[p + 1] = _poisson_start(f.counts, f.offset) if start is None else start
+    lambdapath = list(lambdapath)
+    res = PoissonLassoPathResult(lambdapath, [], [], [], [], [], [])
+    mode_before = f.gradient_cache_mode()          # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
+    if mode_before == 1:
+        check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
+    try:
+        for i, lam in enumerate(lambdapath):
+            sol = poissonLasso_(x, f, ProxL1(lam, sx), options, irls)
+            b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
+            res.betapath.append(b)
+            res.nll.append(sol.nll)
+            res.deviance.append(sol.deviance)
+            res.rounds.append(sol.rounds)
+            res.converged.append(sol.converged)
+            res.intercepts.append(b0)
+            if b.nnz > max_hat_s:
+                res.lambdapath = lambdapath[: i + 1]
+                break
+    finally:
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
+    return res
+
+
+@dataclass
+class CVPoissonLassoPathResult:
+    """What cvPoissonLassoPath returns.  Per fold k and λ_j, by the path fitted without the rows of fold k:
+    fold_deviance[k, j] = Σ dev_i / size_k over the held-out rows, train_deviance[k, j] = Σ dev_i / n_k over the rows it was
+    fitted on, rounds and converged of its IRLS loop.  cvm, cvsd and the two selections (0-based positions in lambdapath) are
+    taken from fold_deviance, the folds weighted by their sizes."""
+    lambdapath: np.ndarray
+    fold_sizes: np.ndarray
+    fold_deviance: np.ndarray
+    train_deviance: np.ndarray
+    rounds: np.ndarray
+    converged: np.ndarray
+    measure: str
+    cvm: np.ndarray
+    cvsd: np.ndarray
+    index_min: int
+    lambda_min: float
+    index_1se: int
+    lambda_1se: float
+    path: PoissonLassoPathResult = None
+    fold_paths: list = None
+
+
+def cvPoissonLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, fit_intercept=False,
+                       seed=0, measure="deviance", offset=None, full_path=True, keep_fold_paths=False):
+    """K-fold cross-validation of PoissonLassoPath(X, y, λpath, options, irls; standardizeX, fit_intercept, offset) on the
+    device (glmnet's cv.glmnet(family = "poisson", offset = ...)); no reference counterpart.  X may also be an existing
+    CDPoissonLoss (y and offset are then its own; no intercept); the design is uploaded once.
+
+    cvLogisticLassoPath's structure: a fold is a 0/1 observation weight, the held-out rows kept at w = 0, z = Xβ by
+    irls_step(fold=k), ω = _stdX!(w, X) of the 0/1 weights and λ·sqrt(n_k / n) (standardizeX=False: ω = 1 and λ·n_k / n);
+    with fit_intercept every fold starts at log(Σy / Σ e^o) of its own training rows.  The read-only step that ends every
+    solve returns the held-out Poisson deviance of that λ: the only measure.  Nothing n-sized moves after the upload.
+
+    folds: 0-based ids, one per row; otherwise np.random.default_rng(seed).permutation(n) % K.  There is no max_hat_s.  The
+    folds are dropped when the call returns or raises.  `path` is PoissonLassoPath on all rows (None with full_path=False):
+    from a matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was
+    passed in it runs after them, so that the loss comes back with the weights of all rows.  `fold_paths`: the K fold paths
+    as PoissonLassoPathResult (None unless keep_fold_paths)."""
+    if measure != "deviance":
+        raise ArgumentError('measure must be "deviance"')
+    if isinstance(X, CoordinateDifferentiableFunction) and not isinstance(X, CDPoissonLoss):
+        raise TypeError("MethodError: cvPoissonLassoPath takes a matrix or a CDPoissonLoss")
+    lam = np.array(list(lambdapath), dtype=np.float64)
+    if lam.size == 0:
+        raise ArgumentError("lambdapath is empty")
+    n = X.n if isinstance(X, _HipLoss) else np.shape(X)[0]
+    ids, sizes = _cv_fold_ids(int(n), K, folds, seed)
+    counts = off = None
+    if fit_intercept and not isinstance(X, _HipLoss):
+        counts = np.ascontiguousarray(y, dtype=np.float64)
+        off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64)
+        _poisson_start(counts, off)
+        for k in range(len(sizes)):                     # before the upload: a fold whose start would be infinite
+            _poisson_start(counts[ids != k], None if off is None else off[ids != k])
+    f, owned = _poisson_loss(X, y, fit_intercept, offset)
+    try:
+        return _cv_poisson_path(f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, counts, off, full_path,
+                                keep_fold_paths)
+    finally:
+        if owned:
+            f.close()                  # the handle this call made goes with it, also when a fold raises
+
+
+def _cv_poisson_path(f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, counts, off, full_path,
+                     keep_fold_paths):
+    n, K, m = f.n, len(sizes), lam.size
+    if f.n_total != f.n:
+        raise ArgumentError("cvPoissonLassoPath does not run on row-sharded handles")
+    p = f.p - (1 if fit_intercept else 0)
+    dev, tdev = np.zeros((K, m)), np.zeros((K, m))
+    rounds, conv = np.zeros((K, m), dtype=np.int64), np.zeros((K, m), dtype=bool)
+    fold_paths = [] if keep_fold_paths else None
+    if fit_intercept and counts is None:
+        counts, off = f.counts, f.offset                 # (a loss that was passed in has no intercept: not reached in practice)
+    # the path on all rows: first on the handle this call has just made (PoissonLassoPath's own calls on a fresh handle, so
+    # the same bits), last on a loss that was passed in (it comes back with the weights of all rows and no folds)
+    path = None
+    if full_path and owned:
+        path = _poisson_path_on(f, lam, options, irls, np.inf, standardizeX, fit_intercept,
+                                _poisson_start(counts, off) if fit_intercept else None)
+    mode_before = f.gradient_cache_mode()                # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
+    try:
+        f.set_folds(ids, K)
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
+        for k in range(K):
+            f.set_fold_weights(k)
+            nk = n - sizes[k]
+            sx = stdX(f, weighted=True) if standardizeX else np.ones(f.p)     # while w still holds the 0/1 weights
+            scale = np.sqrt(nk / n) if standardizeX else nk / n
+            x = SparseIterate(f.p)
+            if fit_intercept:
+                sx[p] = 0.0
+                x[p + 1] = _poisson_start(counts[ids != k], None if off is None else off[ids != k])
+            res = PoissonLassoPathResult(list(lam), [], [], [], [], [], [])
+            for j in range(m):
+                sol = poissonLasso_(x, f, ProxL1(lam[j] * scale, sx), options, irls, fold=k)
+                dev[k, j] = sol.held_deviance / sizes[k]
+                tdev[k, j] = sol.deviance / nk
+                rounds[k, j], conv[k, j] = sol.rounds, sol.converged
+                if keep_fold_paths:
+                    b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
+                    res.betapath.append(b)
+                    res.nll.append(sol.nll * n / nk)
+                    res.deviance.append(sol.deviance)
+                    res.rounds.append(sol.rounds)
+                    res.converged.append(sol.converged)
+                    res.intercepts.append(b0)
+            if keep_fold_paths:
+                fold_paths.append(res)
+    finally:
+        f._synced = None
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
+        f.set_folds(None, 0)
+    cvm, cvsd, imin, i1se = _cv_select(lam, sizes, dev)
+    if full_path and not owned:
+        path = _poisson_path_on(f, lam, options, irls, np.inf, standardizeX, fit_intercept)
+    return CVPoissonLassoPathResult(lam, sizes, dev, tdev, rounds, conv, "deviance", cvm, cvsd, imin, float(lam[imin]),
+                                    i1se, float(lam[i1se]), path, fold_paths)
 
 
 # --------------------------------------------------------------------------------------

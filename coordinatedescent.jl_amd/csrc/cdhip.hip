@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -287,8 +288,10 @@ struct CvState {
 // own -- y holds the working response of the IRLS round, not the labels.  glm_plan.hpp: the grid and the rows of a workgroup.
 #include "glm_plan.hpp"
 struct GlmState {
-    DevBuf<double> labels;
-    int family = 0;            // 0: binomial
+    DevBuf<double> labels;     // the labels, or the counts of the Poisson family
+    DevBuf<double> offset;     // Poisson: ld doubles, pads zero; allocated by the first cdh_glm_set_counts that brings one
+    int family = 0;            // 0: binomial, 1: Poisson (cdh_glm_set_counts)
+    bool has_offset = false;   // the offset buffer holds this handle's offset (false: the step runs without one)
     bool set = false;
 };
 
@@ -1291,6 +1294,7 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
                                                 (size_t)cus * kBlockGridPerCU * BlockRec<kMaxBlockB>::N,
                                                 (size_t)4096 * kColChunks * 2,
                                                 gram(4, GramRec<4>::N), gram(2, GramRec<2>::N), gram(1, GramRec<1>::N)});
+        static_assert((size_t)4096 * kColChunks * 2 >= (size_t)kGlmMaxGrid * kGlmPoisVals, "the widest IRLS record fits the partials");
         HIPCHK(h, h->d_partials.alloc(sizeof(double) * h->partials_doubles));
         HIPCHK(h, h->d_red.alloc(sizeof(double) * 4096));
         HIPCHK(h, h->d_colout.alloc(sizeof(double) * 2 * p));
@@ -1799,6 +1803,36 @@ int32_t cdh_glm_irls_fold(cdh_handle h, int32_t k, int32_t apply, double wmin, d
     h->small.c_valid = false;
     CHK(ensure_weights_buffer(h));
     CHK(glm_launch_fold(h, k, true, wmin, out5));
+    h->rs.rewritten_as_residual();
+    gc_after_rebuild(h, h->x);
+    h->has_w = true;
+    return CDH_OK;
+}); }
+
+// ---- the Poisson family of the same loop (k_glm_poisson; no reference counterpart: a round's solve is the weighted lasso of
+// CDWeightedLSLoss, cd_differentiable_function.jl:118-194) -------------------------------------------------------------------
+// stands in for cdh_set_y of n zeros, the counts and the offset kept beside it
+int32_t cdh_glm_set_counts(cdh_handle h, const void* host_counts, const void* host_offset) { return guarded(h, [&]() -> int32_t {
+    return glm_set_counts(h, host_counts, host_offset);
+}); }
+
+int32_t cdh_glm_get_offset(cdh_handle h, void* host_offset) { return guarded(h, [&]() -> int32_t {
+    return glm_get_offset(h, host_offset);
+}); }
+
+// cdh_glm_irls_fold's catch-up, read-only form and voided state around the Poisson pass
+int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double* out6) { return guarded(h, [&]() -> int32_t {
+    CHK(glm_check_poisson(h, k, apply, wmin, eta_max, out6));
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(glm_catch_up(h));
+    if (!apply) return glm_launch_poisson(h, k, false, wmin, eta_max, out6);      // read-only from here
+    // what cdh_glm_irls(apply = 1) voids, through the same calls in the same order
+    CHK(design_changes(h, false));
+    gc_invalidate(h, false);
+    h->gc.st.yy_void();
+    h->small.c_valid = false;
+    CHK(ensure_weights_buffer(h));
+    CHK(glm_launch_poisson(h, k, true, wmin, eta_max, out6));
     h->rs.rewritten_as_residual();
     gc_after_rebuild(h, h->x);
     h->has_w = true;

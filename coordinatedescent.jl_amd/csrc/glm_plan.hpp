@@ -18,6 +18,10 @@ constexpr int kGlmVals = 3;
 // the record of the fold-aware step (k_glm_irls_fold): (nll of the training rows, sum w, clamped rows, nll of the held-out
 // rows, misclassified held-out rows); same grid, same tiles, one record per workgroup
 constexpr int kGlmFoldVals = 5;
+// the record of the Poisson step (k_glm_poisson): (nll of the training rows, sum w, training rows clamped at wmin, live rows
+// capped at eta_max, deviance of the held-out rows, deviance of the training rows); same grid, same tiles, one record per
+// workgroup
+constexpr int kGlmPoisVals = 6;
 
 struct GlmPlan {
     int64_t vecs;      // 16-byte vectors over the ld rows

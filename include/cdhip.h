@@ -300,6 +300,39 @@ int32_t cdh_glm_irls(cdh_handle h, int32_t apply, double wmin, double *out3);
  * cdh_glm_irls'; cdh_get_obs_weights returns the written weights, zeros included.  CDH_BAD_ARG, the handle unchanged:
  * everything cdh_glm_irls refuses; k < -1; k >= 0 without folds; k >= K. */
 int32_t cdh_glm_irls_fold(cdh_handle h, int32_t k, int32_t apply, double wmin, double *out5);
+/* ---- l1-penalised Poisson regression with an offset, by the same IRLS loop (no reference counterpart: a round's solve is
+ * the weighted lasso of CDWeightedLSLoss, cd_differentiable_function.jl:118-194) ------------------------------------------
+ * F(beta) = (1/n) sum_i [mu_i - y_i eta_i] + lambda0 sum_j omega_j |beta_j|, eta = X beta + o, mu = exp(eta), counts
+ * y_i >= 0 and offsets o_i (log exposure).  The handle's working response y_w and residual r stand for eta_lin = y_w - r =
+ * X beta WITHOUT the offset, so that every other reader of y_w and r sees the linear predictor of the columns.  Per row, in
+ * double, each operation rounded on its own: eta = eta_lin + o; capped = eta > eta_max, ec = min(eta, eta_max); mu = exp(ec);
+ * clamped = mu < wmin, w = max(mu, wmin); d = y - mu; r_new = d / w; z_lin = eta_lin + r_new; nll = mu - y ec;
+ * dev = 2 ((y > 0 ? y log(y / mu) : 0) - (y - mu)).  Only w is clamped, so X'W r = X'(y - mu) and the fixed point keeps the
+ * KKT conditions of F. */
+/* cdh_glm_set_counts (no reference counterpart; the loss is that of cd_differentiable_function.jl:118-194 per round) stands
+ * in for cdh_set_y: it stores n counts where cdh_glm_set_labels stores labels (cdh_glm_get_labels returns them) and, when
+ * host_offset is not NULL, n offsets in a buffer of ld doubles the handle owns (pads zero; both buffers allocated
+ * all-or-nothing before the handle changes), makes the handle a Poisson handle and leaves it exactly as cdh_set_y of n zeros
+ * would.  CDH_BAD_ARG, the handle unchanged: what cdh_glm_set_labels refuses of the handle (not CDH_WLS, not CDH_F64,
+ * row-sharded); a count that is negative or not finite, an offset that is not finite (the message names the row).  Counts
+ * need not be integers.  cdh_glm_irls and cdh_glm_irls_fold refuse a Poisson handle; a later cdh_glm_set_labels(h, 0, ...)
+ * makes it binomial again and drops the offset. */
+int32_t cdh_glm_set_counts(cdh_handle h, const void *host_counts, const void *host_offset_or_null);
+/* cdh_glm_get_offset (no reference counterpart; see cdh_glm_set_counts, cd_differentiable_function.jl:118-194): the n
+ * offsets of a Poisson handle, zeros when none was given.  CDH_BAD_ARG without counts. */
+int32_t cdh_glm_get_offset(cdh_handle h, void *host_offset);
+/* cdh_glm_poisson_irls (no reference counterpart; a round's solve is the weighted lasso of CDWeightedLSLoss,
+ * cd_differentiable_function.jl:118-194): the step between two rounds at the iterate the handle holds, in one pass.
+ *   a training row becomes (w, y_w, r) = (w, z_lin, r_new);
+ *   a held-out row (fold id == k, after cdh_set_folds) becomes (0, eta_lin, 0): weight exactly 0, never clamped up;
+ *   rows n .. ld - 1 are written as zeros.
+ * k == -1: no row is held out and the fold ids are not read.  out6 = {sum of nll_i over the training rows, sum of w_i,
+ * training rows clamped at wmin, live rows capped at eta_max, sum of dev_i over the held-out rows, sum of dev_i over the
+ * training rows}, each summed in a fixed order: bit-identical run to run.  The catch-up of r before the pass, apply = 0
+ * (read-only) and the state apply = 1 leaves are cdh_glm_irls'.  CDH_BAD_ARG, the handle unchanged: no counts set (a binomial
+ * handle included); apply not in {0, 1}; wmin not finite or not > 0; eta_max outside (0, 700]; k < -1; k >= 0 without folds;
+ * k >= K; out6 NULL. */
+int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double *out6);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects
