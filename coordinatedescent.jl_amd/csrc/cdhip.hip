@@ -1450,6 +1450,11 @@ int32_t cdh_generate(cdh_handle h, uint64_t seed, int64_t s, double noise, doubl
     h->gc.st.yy_void();
     small_invalidate(h);
     HIPCHK(h, hipSetDevice(h->device));
+    // The handle starts over as a new one does, down to the memory of the Gram store.  The cache's gates ask whether there is
+    // a store (gc_fetch, gc_pass_device, cov_solve), not whether it holds anything: with the old X's store left over, the
+    // device loop served the first full pass on the new X where a new handle's host pass does -- the same path of solves
+    // with the same counts, and iterates a bit or two apart in the last place (tests/test_gpu_generator.py, LAB_NOTES.md)
+    { DevBuf<double> gone = std::move(h->gc.d_G); h->gc.d_G_retired.clear(); h->gc.dev_slots_cap = 0; }
     // planted coefficients: beta*_j = z_j (1 + u_j) (benchmark/cd_bench.jl:14), stream 2
     std::vector<double> bstar((size_t)std::max<int64_t>(s, 1), 0.0);
     for (int64_t j = 0; j < s; ++j) {

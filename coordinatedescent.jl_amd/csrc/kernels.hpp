@@ -844,7 +844,8 @@ struct Philox {
             k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
         }
     }
-    // two uniforms in (0,1) with 53 random bits each
+    // two uniforms in (0,1] with 53 random bits each: k + 0.5 needs 54 bits from k = 2^52 on and rounds to even, so
+    // k = 2^53 - 1 gives exactly 1 (log 1 = 0: a zero draw); the least, 2^-54, keeps |normal| <= sqrt(108 ln 2) < 8.66
     __host__ __device__ static inline void uniforms(uint64_t seed, uint64_t ctr, uint32_t col,
                                                     uint32_t stream, double& u1, double& u2) {
         uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), col, stream};

@@ -342,7 +342,10 @@ int32_t cdh_set_loss(cdh_handle h, int32_t loss);
 /* Synthetic Gaussian problem generated on the device from a counter-based
  * generator keyed (seed, global row, column), shapes of benchmark/cd_bench.jl:
  * 8-14: X_ij ~ N(0,1), beta*_j = z_j (1 + u_j) for j < s, y = X beta* + noise e.
- * out_beta_star (may be NULL) receives the s planted values. */
+ * out_beta_star (may be NULL) receives the s planted values.  0 <= s <= p, else
+ * CDH_BAD_ARG and nothing is written.  On a handle that has solved before, the
+ * handle starts over: the iterate is zero, and data and later solves are those
+ * of a new handle generated the same way, bit for bit. */
 int32_t cdh_generate(cdh_handle h, uint64_t seed, int64_t s, double noise, double *out_beta_star);
 
 /* ---- penalty: ProxL1(lambda0) / ProxL1(lambda0, omega) (ProximalBase) -------- */
