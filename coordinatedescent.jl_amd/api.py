@@ -511,32 +511,59 @@ class CDWeightedLSLoss(_HipLoss):
         super().__init__(y, X, w, **kw)
 
 
-class CDLogisticLoss(CDWeightedLSLoss):
-    """CDLogisticLoss(y, X): (1/n) Σ [log(1 + e^η_i) - y_i η_i], η = Xβ, labels y_i in [0, 1]; no reference counterpart.
-    Minimised by IRLS: a round is the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the
-    working response z and weights w, which the handle's y and w hold from one irls_step to the next; the labels live in a
-    buffer of their own (cdh_glm_set_labels).  fp64 only, one device."""
+class _GLMLoss(CDWeightedLSLoss):
+    """What CDLogisticLoss and CDPoissonLoss share: the upload of X in column chunks, the observations kept in a buffer of
+    the handle's own beside the working response, and the objective read off a read-only step.  A family adds
+    _set_observations (its export), irls_step with its own arguments, and _irls: that step as the IRLS loop calls it."""
+    _objective_step = {}                 # the arguments of objective's read-only irls_step
 
-    def __init__(self, y, X, *, device=0):
+    def __init__(self, y, X, offset=None, *, device=0):
         X = np.asarray(X)
-        labels = np.ascontiguousarray(y, dtype=np.float64)
+        obs = np.ascontiguousarray(y, dtype=np.float64)
+        off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64)
         if X.dtype != np.float64 or X.ndim != 2:
-            raise TypeError("MethodError: CDLogisticLoss takes X::AbstractMatrix{Float64}")
-        if labels.ndim != 1 or labels.shape[0] != X.shape[0]:
+            raise TypeError("MethodError: %s takes X::AbstractMatrix{Float64}" % type(self).__name__)
+        if obs.ndim != 1 or obs.shape[0] != X.shape[0]:
             raise DimensionMismatch("length(y) != size(X, 1)")
+        if off is not None and off.shape != obs.shape:
+            raise DimensionMismatch("length(offset) != size(X, 1)")
         n, p = X.shape
         self._create(X.dtype, n, p, device, None, 0)
         step = max(1, (64 << 20) // max(1, n * X.itemsize))
         for j0 in range(0, p, step):
             blk = np.asfortranarray(X[:, j0:j0 + step])
             check(self._L.cdh_set_X_cols(self._h, j0, blk.shape[1], _vp(blk), n), self._h)
-        check(self._L.cdh_glm_set_labels(self._h, 0, _vp(labels)), self._h)
+        self._set_observations(obs, off)
 
-    @property
-    def labels(self):
+    def _observations(self):
         out = np.zeros(self.n)
         check(self._L.cdh_glm_get_labels(self._h, _vp(out)), self._h)
         return out
+
+    def objective(self, g=None):
+        """F(β) = (the family's nll) + λ0 Σ ω_j |β_j| at the handle's iterate, read-only (apply=0)."""
+        val = self.irls_step(apply=False, **self._objective_step)["nll"]
+        if g is not None:
+            beta = np.zeros(self.p)
+            check(self._L.cdh_get_beta(self._h, _vp(beta)), self._h)
+            val += g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
+        return val
+
+
+class CDLogisticLoss(_GLMLoss):
+    """CDLogisticLoss(y, X): (1/n) Σ [log(1 + e^η_i) - y_i η_i], η = Xβ, labels y_i in [0, 1]; no reference counterpart.
+    Minimised by IRLS: a round is the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the
+    working response z and weights w, which the handle's y and w hold from one irls_step to the next; the labels live in a
+    buffer of their own (cdh_glm_set_labels).  fp64 only, one device."""
+    _objective_step = {"wmin": 0.25}     # (the sum of nll does not depend on wmin)
+
+    def __init__(self, y, X, *, device=0):
+        super().__init__(y, X, device=device)
+
+    def _set_observations(self, labels, _):
+        check(self._L.cdh_glm_set_labels(self._h, 0, _vp(labels)), self._h)
+
+    labels = property(_GLMLoss._observations)
 
     def irls_step(self, apply=True, wmin=1e-5, fold=None):
         """One IRLS step at the iterate the handle holds (cdh_glm_irls).  apply=True turns the handle's y, w and r into the
@@ -556,46 +583,21 @@ class CDLogisticLoss(CDWeightedLSLoss):
         return {"nll": float(out[0]) / self.n, "sum_w": float(out[1]), "clamped": int(out[2]),
                 "held_nll": float(out[3]), "held_miss": float(out[4])}
 
-    def objective(self, g=None):
-        """F(β) = (1/n) Σ nll_i + λ0 Σ ω_j |β_j| at the handle's iterate, read-only (apply=0)."""
-        val = self.irls_step(apply=False, wmin=0.25)["nll"]       # (the sum of nll does not depend on wmin)
-        if g is not None:
-            beta = np.zeros(self.p)
-            check(self._L.cdh_get_beta(self._h, _vp(beta)), self._h)
-            val += g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
-        return val
+    def _irls(self, apply, irls, fold):
+        return self.irls_step(apply, irls.wmin, fold)
 
 
-class CDPoissonLoss(CDWeightedLSLoss):
+class CDPoissonLoss(_GLMLoss):
     """CDPoissonLoss(y, X, offset=None): (1/n) Σ [μ_i - y_i η_i], η = Xβ + o, μ = e^η, counts y_i >= 0 and offsets o_i (log
     exposure); no reference counterpart.  Minimised by IRLS like CDLogisticLoss (a sibling, not a subclass of it): a round is
     the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the working response and weights
     the handle's y and w hold from one irls_step to the next.  The counts and the offset live in buffers of their own
     (cdh_glm_set_counts), and the stored working response leaves the offset out: f.y - f.r is Xβ.  fp64 only, one device."""
 
-    def __init__(self, y, X, offset=None, *, device=0):
-        X = np.asarray(X)
-        counts = np.ascontiguousarray(y, dtype=np.float64)
-        off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64)
-        if X.dtype != np.float64 or X.ndim != 2:
-            raise TypeError("MethodError: CDPoissonLoss takes X::AbstractMatrix{Float64}")
-        if counts.ndim != 1 or counts.shape[0] != X.shape[0]:
-            raise DimensionMismatch("length(y) != size(X, 1)")
-        if off is not None and off.shape != counts.shape:
-            raise DimensionMismatch("length(offset) != size(X, 1)")
-        n, p = X.shape
-        self._create(X.dtype, n, p, device, None, 0)
-        step = max(1, (64 << 20) // max(1, n * X.itemsize))
-        for j0 in range(0, p, step):
-            blk = np.asfortranarray(X[:, j0:j0 + step])
-            check(self._L.cdh_set_X_cols(self._h, j0, blk.shape[1], _vp(blk), n), self._h)
+    def _set_observations(self, counts, off):
         check(self._L.cdh_glm_set_counts(self._h, _vp(counts), _vp(off)), self._h)
 
-    @property
-    def counts(self):
-        out = np.zeros(self.n)
-        check(self._L.cdh_glm_get_labels(self._h, _vp(out)), self._h)
-        return out
+    counts = property(_GLMLoss._observations)
 
     @property
     def offset(self):
@@ -625,14 +627,8 @@ class CDPoissonLoss(CDWeightedLSLoss):
             res["held_deviance"] = float(out[4])
         return res
 
-    def objective(self, g=None):
-        """F(β) = (1/n) Σ [μ_i - y_i η_i] + λ0 Σ ω_j |β_j| at the handle's iterate, read-only (apply=0)."""
-        val = self.irls_step(apply=False)["nll"]
-        if g is not None:
-            beta = np.zeros(self.p)
-            check(self._L.cdh_get_beta(self._h, _vp(beta)), self._h)
-            val += g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
-        return val
+    def _irls(self, apply, irls, fold):
+        return self.irls_step(apply, irls.wmin, irls.etaMax, fold)
 
 
 # --------------------------------------------------------------------------------------
@@ -1594,174 +1590,6 @@ class LogisticLassoPathResult(LassoPathResult):
     intercepts: list = None
 
 
-def _penalty_value(g, beta):
-    return g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
-
-
-def _irls_rounds(x, f, g, options, irls, step):
-    """The outer loop logisticLasso_ and poissonLasso_ share: step(apply) is the family's f.irls_step with the caller's
-    options and fold.  -> (the dict of the read-only step that ends the solve, rounds, converged, monotone)."""
-    options = options or CDOptions()
-    if not options.warmStart:
-        raise ArgumentError("the rounds of IRLS are warm starts: options.warmStart must be true")
-    _check_dims(x, f, g)
-    f._ensure_synced(x)
-    check(f._L.cdh_set_reuse_residual(f._h, 1), f._h)
-    rounds, converged, monotone, F_prev = 0, False, True, None
-
-    def rose(F):
-        return F_prev is not None and F - F_prev > 1e-10 * max(1.0, F_prev)
-
-    try:
-        beta = x.dense()
-        for _ in range(int(irls.maxIter)):
-            F = step(True)["nll"] + _penalty_value(g, beta)      # F at the iterate this round starts from
-            monotone, F_prev = monotone and not rose(F), F
-            coordinateDescent_(x, f, g, options)
-            rounds += 1
-            beta, old = x.dense(), beta
-            if float(np.max(np.abs(beta - old))) < irls.optTol:
-                converged = True
-                break
-        f._ensure_synced(x)
-        last = step(False)
-        monotone = monotone and not rose(last["nll"] + _penalty_value(g, beta))
-    finally:
-        check(f._L.cdh_set_reuse_residual(f._h, 0), f._h)
-    return last, rounds, converged, monotone
-
-
-def logisticLasso_(x, f, g, options=None, irls=None, fold=None):
-    """Minimise F(β) = (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ0 Σ ω_j |β_j| over the CDLogisticLoss f by IRLS, warm-started
-    from x (updated in place).  A round is one f.irls_step -- working weights, working response and their residual formed on
-    the device from the linear predictor the handle holds, nothing n-sized on the host -- and one coordinateDescent_ of the
-    weighted lasso they define, which keeps the residual the step left (cdh_set_reuse_residual for the duration).
-
-    fold=k: every step, the final read-only one included, holds the rows of fold k out (irls_step(fold=k), after
-    f.set_folds); the minimised F is then (1/n) Σ over the training rows, and the solution carries the held-out rows'
-    held_nll and held_miss at the final β."""
-    if not isinstance(f, CDLogisticLoss):
-        raise TypeError("MethodError: logisticLasso_ takes a CDLogisticLoss")
-    irls = irls or IRLSOptions()
-    last, rounds, converged, monotone = _irls_rounds(x, f, g, options, irls, lambda apply: f.irls_step(apply, irls.wmin, fold))
-    nll = last["nll"]
-    return LogisticLassoSolution(x, nll, rounds, converged, monotone, None, g, last.get("held_nll"), last.get("held_miss"))
-
-
-def _logit_start(labels):
-    ybar = float(np.mean(labels))
-    if not 0.0 < ybar < 1.0:
-        raise ArgumentError("fit_intercept needs labels of both kinds: the null model's intercept is infinite")
-    return float(np.log(ybar / (1.0 - ybar)))
-
-
-def _logistic_loss(X, y, fit_intercept):
-    """-> (f, owned): a CDLogisticLoss over X (with a trailing column of ones when an intercept is fitted)."""
-    if isinstance(X, CDLogisticLoss):
-        if fit_intercept:
-            raise ArgumentError("fit_intercept appends a column of ones: pass the matrix, not a loss")
-        return X, False
-    if isinstance(X, CoordinateDifferentiableFunction):
-        raise TypeError("MethodError: takes a matrix or a CDLogisticLoss")
-    X = np.asarray(X)
-    if fit_intercept:
-        X = np.asfortranarray(np.hstack([X, np.ones((X.shape[0], 1), dtype=X.dtype)]))
-    return CDLogisticLoss(y, X), True
-
-
-def _split_intercept(x, p):
-    """x of length p + 1 -> (its first p coordinates as a SparseIterate, the last)."""
-    beta = x.dense()
-    return SparseIterate(p, beta[:p]), float(beta[p])
-
-
-def logisticLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=False):
-    """ℓ1-penalised logistic regression (glmnet's family = "binomial"): the minimiser of
-    (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ Σ ω_j |β_j|, η = Xβ (+ b with fit_intercept: a column of ones appended as
-    coordinate p + 1 with ω = 0, started at log(ȳ / (1 - ȳ)) and returned apart from x, which has length p).  X may also be
-    an existing CDLogisticLoss (y is then ignored; no intercept)."""
-    f, owned = _logistic_loss(X, y, fit_intercept)
-    try:
-        p = f.p - (1 if fit_intercept else 0)
-        om = None if omega is None else np.asarray(omega, dtype=np.float64)
-        x = SparseIterate(f.p)
-        if fit_intercept:
-            om = np.r_[np.ones(p) if om is None else om, 0.0]
-            x[p + 1] = _logit_start(np.asarray(y, dtype=np.float64))
-        sol = logisticLasso_(x, f, ProxL1(lam, om), options, irls)
-        if fit_intercept:
-            sol.x, sol.intercept = _split_intercept(x, p)
-        return sol
-    finally:
-        if owned:
-            f.close()
-
-
-def logisticLambdaMax(f, omega=None, fit_intercept=False):
-    """The smallest λ at which every penalised coordinate of the logistic lasso is zero: max_j |X_j'(y - p̂)| / (n ω_j) at the
-    null model (β = 0; with fit_intercept the last column of f is the column of ones, its coordinate log(ȳ / (1 - ȳ)) and
-    left out of the maximum).  One irls_step at the null model and one cdh_xt_r: the step leaves r = (y - p̂) / w, and at
-    the null model every row has the same weight w̄ = Σw / n, so X'(y - p̂) = w̄ X'r.  The handle is left at the null model."""
-    if not isinstance(f, CDLogisticLoss):
-        raise TypeError("MethodError: logisticLambdaMax takes a CDLogisticLoss")
-    p = f.p - (1 if fit_intercept else 0)
-    x = SparseIterate(f.p)
-    if fit_intercept:
-        x[p + 1] = _logit_start(f.labels)
-    f._push(x, rebuild=True)
-    f._synced = None
-    wbar = f.irls_step(True, 1e-12)["sum_w"] / f.n
-    out = np.zeros(f.p)
-    check(f._L.cdh_xt_r(f._h, _vp(out)), f._h)
-    t = np.abs(out[:p]) * wbar / f.n
-    if omega is not None:
-        t = t / np.asarray(omega, dtype=np.float64)[:p]
-    return float(t.max())
-
-
-def LogisticLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, fit_intercept=False):
-    """LassoPath's loop (src/lasso.jl:229-260) with logisticLasso_ per λ: one handle, one x warm-started along λ,
-    ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p."""
-    f, owned = _logistic_loss(X, y, fit_intercept)
-    try:
-        return _logistic_path_on(f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept)
-    finally:
-        if owned:
-            f.close()
-
-
-def _logistic_path_on(f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, labels=None):
-    """LogisticLassoPath on the loss f (its last column the column of ones when an intercept is fitted; labels: the host's
-    copy of f.labels, where the caller still has it)."""
-    p = f.p - (1 if fit_intercept else 0)
-    sx = stdX(f) if standardizeX else np.ones(f.p)
-    x = SparseIterate(f.p)
-    if fit_intercept:
-        sx[p] = 0.0
-        x[p + 1] = _logit_start(f.labels if labels is None else labels)
-    lambdapath = list(lambdapath)
-    res = LogisticLassoPathResult(lambdapath, [], [], [], [], [])
-    mode_before = f.gradient_cache_mode()          # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
-    if mode_before == 1:
-        check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
-    try:
-        for i, lam in enumerate(lambdapath):
-            sol = logisticLasso_(x, f, ProxL1(lam, sx), options, irls)
-            b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
-            res.betapath.append(b)
-            res.nll.append(sol.nll)
-            res.rounds.append(sol.rounds)
-            res.converged.append(sol.converged)
-            res.intercepts.append(b0)
-            if b.nnz > max_hat_s:
-                res.lambdapath = lambdapath[: i + 1]
-                break
-    finally:
-        if mode_before == 1:
-            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
-    return res
-
-
 @dataclass
 class CVLogisticLassoPathResult:
     """What cvLogisticLassoPath returns.  Per fold k and λ_j, by the path fitted without the rows of fold k:
@@ -1786,113 +1614,6 @@ class CVLogisticLassoPathResult:
     fold_paths: list = None
 
 
-_CV_LOGISTIC_MEASURES = ("deviance", "class")
-
-
-def cvLogisticLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, fit_intercept=False,
-                        seed=0, measure="deviance", full_path=True, keep_fold_paths=False):
-    """K-fold cross-validation of LogisticLassoPath(X, y, λpath, options, irls; standardizeX, fit_intercept) on the device
-    (glmnet's cv.glmnet(family = "binomial")); no reference counterpart.  X may also be an existing CDLogisticLoss (y is then
-    ignored; no intercept); the design is uploaded once.
-
-    A fold is a 0/1 observation weight, as in cvLassoPath: the logistic lasso on the n_k training rows of fold k has the
-    iterates of IRLS on all n rows with the held-out rows at w = 0, z = η (irls_step(fold=k): cdh_glm_irls_fold), ω =
-    _stdX!(w, X) of the 0/1 weights and λ·sqrt(n_k / n) (standardizeX=False: ω = 1 and λ·n_k / n).  Per fold the path is
-    LogisticLassoPath's loop, warm-started along λ, and the read-only step that ends every solve returns the held-out
-    deviance and class error of that λ.  Nothing n-sized moves after the upload.
-
-    folds: 0-based ids, one per row; otherwise np.random.default_rng(seed).permutation(n) % K.  measure: "deviance" or
-    "class" -- what cvm, cvsd and the selections are taken from.  There is no max_hat_s: the folds would be truncated at
-    different λ.  With fit_intercept every fold starts at the logit of its own training rows' mean label.  The folds are
-    dropped when the call returns or raises.  `path` is LogisticLassoPath on all rows (None with full_path=False): from a
-    matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was passed
-    in it runs after them, so that the loss comes back with the weights of all rows.  `fold_paths`: the K fold paths as LogisticLassoPathResult (None unless keep_fold_paths)."""
-    if measure not in _CV_LOGISTIC_MEASURES:
-        raise ArgumentError('measure must be "deviance" or "class"')
-    if isinstance(X, CoordinateDifferentiableFunction) and not isinstance(X, CDLogisticLoss):
-        raise TypeError("MethodError: cvLogisticLassoPath takes a matrix or a CDLogisticLoss")
-    lam = np.array(list(lambdapath), dtype=np.float64)
-    if lam.size == 0:
-        raise ArgumentError("lambdapath is empty")
-    n = X.n if isinstance(X, _HipLoss) else np.shape(X)[0]
-    ids, sizes = _cv_fold_ids(int(n), K, folds, seed)
-    labels = None
-    if fit_intercept and not isinstance(X, _HipLoss):
-        labels = np.ascontiguousarray(y, dtype=np.float64)
-        for k in range(len(sizes)):                     # before the upload: a fold whose start would be infinite
-            _logit_start(labels[ids != k])
-    f, owned = _logistic_loss(X, y, fit_intercept)
-    try:
-        return _cv_logistic_path(f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, labels, measure,
-                                 full_path, keep_fold_paths)
-    finally:
-        if owned:
-            f.close()                  # the handle this call made goes with it, also when a fold raises
-
-
-def _cv_logistic_path(f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, labels, measure, full_path,
-                      keep_fold_paths):
-    n, K, m = f.n, len(sizes), lam.size
-    if f.n_total != f.n:
-        raise ArgumentError("cvLogisticLassoPath does not run on row-sharded handles")
-    p = f.p - (1 if fit_intercept else 0)
-    dev, tdev, cls = np.zeros((K, m)), np.zeros((K, m)), np.zeros((K, m))
-    rounds, conv = np.zeros((K, m), dtype=np.int64), np.zeros((K, m), dtype=bool)
-    fold_paths = [] if keep_fold_paths else None
-    if fit_intercept and labels is None:
-        labels = f.labels                                # (a loss that was passed in has no intercept: not reached in practice)
-    # The path on all rows.  On the handle this call has just made it runs FIRST: the very calls LogisticLassoPath makes on a
-    # fresh handle, so the same bits (after the folds an intercept's start η = b0 would be read as y - (y - b0) off the working
-    # response they left, and the handle's cache policy has a history).  A loss that was passed in gets it LAST, and comes
-    # back as LogisticLassoPath leaves it: the weights of all rows, no folds.
-    path = None
-    if full_path and owned:
-        path = _logistic_path_on(f, lam, options, irls, np.inf, standardizeX, fit_intercept, labels)
-    mode_before = f.gradient_cache_mode()                # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
-    try:
-        f.set_folds(ids, K)
-        if mode_before == 1:
-            check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
-        for k in range(K):
-            f.set_fold_weights(k)
-            nk = n - sizes[k]
-            sx = stdX(f, weighted=True) if standardizeX else np.ones(f.p)     # while w still holds the 0/1 weights
-            scale = np.sqrt(nk / n) if standardizeX else nk / n
-            x = SparseIterate(f.p)
-            if fit_intercept:
-                sx[p] = 0.0
-                x[p + 1] = _logit_start(labels[ids != k])
-            res = LogisticLassoPathResult(list(lam), [], [], [], [], [])
-            for j in range(m):
-                sol = logisticLasso_(x, f, ProxL1(lam[j] * scale, sx), options, irls, fold=k)
-                dev[k, j] = 2.0 * sol.held_nll / sizes[k]
-                tdev[k, j] = 2.0 * n * sol.nll / nk
-                cls[k, j] = sol.held_miss / sizes[k]
-                rounds[k, j], conv[k, j] = sol.rounds, sol.converged
-                if keep_fold_paths:
-                    b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
-                    res.betapath.append(b)
-                    res.nll.append(sol.nll * n / nk)
-                    res.rounds.append(sol.rounds)
-                    res.converged.append(sol.converged)
-                    res.intercepts.append(b0)
-            if keep_fold_paths:
-                fold_paths.append(res)
-    finally:
-        f._synced = None
-        if mode_before == 1:
-            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
-        f.set_folds(None, 0)
-    cvm, cvsd, imin, i1se = _cv_select(lam, sizes, dev if measure == "deviance" else cls)
-    if full_path and not owned:
-        path = _logistic_path_on(f, lam, options, irls, np.inf, standardizeX, fit_intercept)
-    return CVLogisticLassoPathResult(lam, sizes, dev, tdev, cls, rounds, conv, measure, cvm, cvsd, imin, float(lam[imin]),
-                                     i1se, float(lam[i1se]), path, fold_paths)
-
-
-# --------------------------------------------------------------------------------------
-# l1-penalised Poisson regression with an offset, by the same IRLS loop (no reference counterpart)
-# --------------------------------------------------------------------------------------
 @dataclass
 class PoissonLassoSolution:
     """What poissonLasso_ and poissonLasso return.  nll is (1/n) Σ [μ_i - y_i η_i] and deviance Σ dev_i over the training rows
@@ -1922,18 +1643,71 @@ class PoissonLassoPathResult(LassoPathResult):
     intercepts: list = None
 
 
-def poissonLasso_(x, f, g, options=None, irls=None, fold=None):
-    """Minimise F(β) = (1/n) Σ [μ_i - y_i η_i] + λ0 Σ ω_j |β_j|, η = Xβ + o, μ = e^η, over the CDPoissonLoss f by IRLS,
-    warm-started from x (updated in place): logisticLasso_'s loop with f.irls_step of the Poisson family (irls.wmin,
-    irls.etaMax).  fold=k: every step holds the rows of fold k out, F is (1/n) Σ over the training rows, and the solution
-    carries the held-out rows' held_deviance at the final β."""
-    if not isinstance(f, CDPoissonLoss):
-        raise TypeError("MethodError: poissonLasso_ takes a CDPoissonLoss")
-    irls = irls or IRLSOptions()
-    last, rounds, converged, monotone = _irls_rounds(x, f, g, options, irls,
-                                                     lambda apply: f.irls_step(apply, irls.wmin, irls.etaMax, fold))
-    return PoissonLassoSolution(x, last["nll"], last["deviance"], rounds, converged, monotone, last["capped"], None, g,
-                                last.get("held_deviance"))
+@dataclass
+class CVPoissonLassoPathResult:
+    """What cvPoissonLassoPath returns.  Per fold k and λ_j, by the path fitted without the rows of fold k:
+    fold_deviance[k, j] = Σ dev_i / size_k over the held-out rows, train_deviance[k, j] = Σ dev_i / n_k over the rows it was
+    fitted on, rounds and converged of its IRLS loop.  cvm, cvsd and the two selections (0-based positions in lambdapath) are
+    taken from fold_deviance, the folds weighted by their sizes."""
+    lambdapath: np.ndarray
+    fold_sizes: np.ndarray
+    fold_deviance: np.ndarray
+    train_deviance: np.ndarray
+    rounds: np.ndarray
+    converged: np.ndarray
+    measure: str
+    cvm: np.ndarray
+    cvsd: np.ndarray
+    index_min: int
+    lambda_min: float
+    index_1se: int
+    lambda_1se: float
+    path: PoissonLassoPathResult = None
+    fold_paths: list = None
+
+
+def _penalty_value(g, beta):
+    return g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
+
+
+def _irls_rounds(x, f, g, options, irls, fold):
+    """The outer loop of every family: f._irls(apply, irls, fold) is the family's f.irls_step with the caller's options and
+    fold.  -> (the dict of the read-only step that ends the solve, rounds, converged, monotone)."""
+    options = options or CDOptions()
+    if not options.warmStart:
+        raise ArgumentError("the rounds of IRLS are warm starts: options.warmStart must be true")
+    _check_dims(x, f, g)
+    f._ensure_synced(x)
+    check(f._L.cdh_set_reuse_residual(f._h, 1), f._h)
+    rounds, converged, monotone, F_prev = 0, False, True, None
+
+    def rose(F):
+        return F_prev is not None and F - F_prev > 1e-10 * max(1.0, F_prev)
+
+    try:
+        beta = x.dense()
+        for _ in range(int(irls.maxIter)):
+            F = f._irls(True, irls, fold)["nll"] + _penalty_value(g, beta)      # F at the iterate this round starts from
+            monotone, F_prev = monotone and not rose(F), F
+            coordinateDescent_(x, f, g, options)
+            rounds += 1
+            beta, old = x.dense(), beta
+            if float(np.max(np.abs(beta - old))) < irls.optTol:
+                converged = True
+                break
+        f._ensure_synced(x)
+        last = f._irls(False, irls, fold)
+        monotone = monotone and not rose(last["nll"] + _penalty_value(g, beta))
+    finally:
+        check(f._L.cdh_set_reuse_residual(f._h, 0), f._h)
+    return last, rounds, converged, monotone
+
+
+def _logit_start(labels):
+    ybar = float(np.mean(labels))
+    if not 0.0 < ybar < 1.0:
+        raise ArgumentError("fit_intercept needs labels of both kinds: the null model's intercept is infinite")
+    return float(np.log(ybar / (1.0 - ybar)))
 
 
 def _poisson_start(counts, offset=None):
@@ -1945,20 +1719,312 @@ def _poisson_start(counts, offset=None):
     return float(np.log(total / expo))
 
 
-def _poisson_loss(X, y, fit_intercept, offset):
-    """-> (f, owned): a CDPoissonLoss over X (with a trailing column of ones when an intercept is fitted)."""
-    if isinstance(X, CDPoissonLoss):
+def _split_intercept(x, p):
+    """x of length p + 1 -> (its first p coordinates as a SparseIterate, the last)."""
+    beta = x.dense()
+    return SparseIterate(p, beta[:p]), float(beta[p])
+
+
+# ---- what the front ends know of a family, and the front ends written once ----------------------------------------------
+@dataclass(frozen=True)
+class _GLMFamily:
+    name: str                    # "logistic", "poisson": the front ends' names (logisticLasso_, cvLogisticLassoPath, ...)
+    loss: type
+    start: object                # (observations, offset or None) -> the null model's intercept, or the family's refusal
+    observed: object             # f -> (observations, offset or None), fetched from the loss
+    start_before_upload: bool    # a matrix's front ends refuse an infinite start before the upload (the Poisson ones), or
+                                 # find it on the way: after the upload, a path from the labels the handle returns
+    solution: object             # (x, the last read-only step's dict, rounds, converged, monotone, g) -> the Solution
+    path_result: type
+    path_fields: tuple           # the Solution's fields a path keeps per λ, between betapath and intercepts
+    cv_result: type
+    cv_measures: dict            # measure -> (sol, size_k) -> its value over the held-out rows; the first is fold_deviance
+    cv_train: object             # (sol, n, n_k) -> train_deviance
+
+
+_LOGISTIC = _GLMFamily(
+    name="logistic", loss=CDLogisticLoss, start=lambda labels, offset=None: _logit_start(labels),
+    observed=lambda f: (f.labels, None), start_before_upload=False,
+    solution=lambda x, last, rounds, converged, monotone, g: LogisticLassoSolution(
+        x, last["nll"], rounds, converged, monotone, None, g, last.get("held_nll"), last.get("held_miss")),
+    path_result=LogisticLassoPathResult, path_fields=("nll", "rounds", "converged"), cv_result=CVLogisticLassoPathResult,
+    cv_measures={"deviance": lambda sol, size: 2.0 * sol.held_nll / size, "class": lambda sol, size: sol.held_miss / size},
+    cv_train=lambda sol, n, nk: 2.0 * n * sol.nll / nk)
+
+_POISSON = _GLMFamily(
+    name="poisson", loss=CDPoissonLoss, start=_poisson_start,
+    observed=lambda f: (f.counts, f.offset), start_before_upload=True,
+    solution=lambda x, last, rounds, converged, monotone, g: PoissonLassoSolution(
+        x, last["nll"], last["deviance"], rounds, converged, monotone, last["capped"], None, g, last.get("held_deviance")),
+    path_result=PoissonLassoPathResult, path_fields=("nll", "deviance", "rounds", "converged"),
+    cv_result=CVPoissonLassoPathResult,
+    cv_measures={"deviance": lambda sol, size: sol.held_deviance / size},
+    cv_train=lambda sol, n, nk: sol.deviance / nk)
+
+
+def _glm_solve(fam, x, f, g, options, irls, fold):
+    if not isinstance(f, fam.loss):
+        raise TypeError("MethodError: %sLasso_ takes a %s" % (fam.name, fam.loss.__name__))
+    irls = irls or IRLSOptions()
+    last, rounds, converged, monotone = _irls_rounds(x, f, g, options, irls, fold)
+    return fam.solution(x, last, rounds, converged, monotone, g)
+
+
+def _glm_loss(fam, X, y, fit_intercept, offset):
+    """-> (f, owned): the family's loss over X (with a trailing column of ones when an intercept is fitted)."""
+    if isinstance(X, fam.loss):
         if fit_intercept:
             raise ArgumentError("fit_intercept appends a column of ones: pass the matrix, not a loss")
         if offset is not None:
             raise ArgumentError("the offset belongs to the loss: pass the matrix, or a loss made with it")
         return X, False
     if isinstance(X, CoordinateDifferentiableFunction):
-        raise TypeError("MethodError: takes a matrix or a CDPoissonLoss")
+        raise TypeError("MethodError: takes a matrix or a %s" % fam.loss.__name__)
     X = np.asarray(X)
     if fit_intercept:
         X = np.asfortranarray(np.hstack([X, np.ones((X.shape[0], 1), dtype=X.dtype)]))
-    return CDPoissonLoss(y, X, offset), True
+    return (fam.loss(y, X) if offset is None else fam.loss(y, X, offset)), True
+
+
+def _glm_host_start(fam, y, offset):
+    return fam.start(np.asarray(y, dtype=np.float64), None if offset is None else np.asarray(offset, dtype=np.float64))
+
+
+def _glm_early_start(fam, X, y, fit_intercept, offset):
+    if fit_intercept and fam.start_before_upload and not isinstance(X, CoordinateDifferentiableFunction):
+        return _glm_host_start(fam, y, offset)
+    return None
+
+
+def _glm_lasso(fam, X, y, lam, omega, options, irls, fit_intercept, offset=None):
+    start = _glm_early_start(fam, X, y, fit_intercept, offset)
+    f, owned = _glm_loss(fam, X, y, fit_intercept, offset)
+    try:
+        p = f.p - (1 if fit_intercept else 0)
+        om = None if omega is None else np.asarray(omega, dtype=np.float64)
+        x = SparseIterate(f.p)
+        if fit_intercept:
+            om = np.r_[np.ones(p) if om is None else om, 0.0]
+            x[p + 1] = _glm_host_start(fam, y, offset) if start is None else start
+        sol = _glm_solve(fam, x, f, ProxL1(lam, om), options, irls, None)
+        if fit_intercept:
+            sol.x, sol.intercept = _split_intercept(x, p)
+        return sol
+    finally:
+        if owned:
+            f.close()
+
+
+def _glm_path(fam, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, offset=None):
+    start = _glm_early_start(fam, X, y, fit_intercept, offset)
+    f, owned = _glm_loss(fam, X, y, fit_intercept, offset)
+    try:
+        return _glm_path_on(fam, f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, start)
+    finally:
+        if owned:
+            f.close()
+
+
+def _glm_keep(fam, res, sol, x, p, fit_intercept, nll=None):
+    """One λ of a path: β (without the intercept), the family's fields of the solution -- nll as given, where the caller
+    rescales it -- and the intercept.  -> β."""
+    b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
+    res.betapath.append(b)
+    for name in fam.path_fields:
+        getattr(res, name).append(nll if name == "nll" and nll is not None else getattr(sol, name))
+    res.intercepts.append(b0)
+    return b
+
+
+def _glm_path_on(fam, f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, start=None):
+    """The family's path on the loss f (its last column the column of ones when an intercept is fitted; start: the null
+    model's intercept, where the caller has computed it from its host copies -- otherwise from what the loss returns)."""
+    p = f.p - (1 if fit_intercept else 0)
+    sx = stdX(f) if standardizeX else np.ones(f.p)
+    x = SparseIterate(f.p)
+    if fit_intercept:
+        sx[p] = 0.0
+        x[p + 1] = fam.start(*fam.observed(f)) if start is None else start
+    lambdapath = list(lambdapath)
+    res = fam.path_result(lambdapath, [], *[[] for _ in fam.path_fields], [])
+    mode_before = f.gradient_cache_mode()          # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
+    if mode_before == 1:
+        check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
+    try:
+        for i, lam in enumerate(lambdapath):
+            sol = _glm_solve(fam, x, f, ProxL1(lam, sx), options, irls, None)
+            if _glm_keep(fam, res, sol, x, p, fit_intercept).nnz > max_hat_s:
+                res.lambdapath = lambdapath[: i + 1]
+                break
+    finally:
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
+    return res
+
+
+def _cv_glm_path(fam, X, y, lambdapath, K, folds, options, irls, standardizeX, fit_intercept, seed, measure, offset,
+                 full_path, keep_fold_paths):
+    front = "cv%sLassoPath" % fam.name.capitalize()
+    if measure not in fam.cv_measures:
+        raise ArgumentError("measure must be " + " or ".join('"%s"' % m for m in fam.cv_measures))
+    if isinstance(X, CoordinateDifferentiableFunction) and not isinstance(X, fam.loss):
+        raise TypeError("MethodError: %s takes a matrix or a %s" % (front, fam.loss.__name__))
+    lam = np.array(list(lambdapath), dtype=np.float64)
+    if lam.size == 0:
+        raise ArgumentError("lambdapath is empty")
+    n = X.n if isinstance(X, _HipLoss) else np.shape(X)[0]
+    ids, sizes = _cv_fold_ids(int(n), K, folds, seed)
+    obs = off = None
+    if fit_intercept and not isinstance(X, _HipLoss):
+        obs = np.ascontiguousarray(y, dtype=np.float64)
+        off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64)
+        fam.start(obs, off)
+        for k in range(len(sizes)):                     # before the upload: a fold whose start would be infinite
+            fam.start(obs[ids != k], None if off is None else off[ids != k])
+    f, owned = _glm_loss(fam, X, y, fit_intercept, offset)
+    try:
+        return _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, obs, off,
+                               measure, full_path, keep_fold_paths)
+    finally:
+        if owned:
+            f.close()                  # the handle this call made goes with it, also when a fold raises
+
+
+def _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, obs, off, measure,
+                    full_path, keep_fold_paths):
+    n, K, m = f.n, len(sizes), lam.size
+    if f.n_total != f.n:
+        raise ArgumentError("%s does not run on row-sharded handles" % front)
+    p = f.p - (1 if fit_intercept else 0)
+    held, tdev = {name: np.zeros((K, m)) for name in fam.cv_measures}, np.zeros((K, m))
+    rounds, conv = np.zeros((K, m), dtype=np.int64), np.zeros((K, m), dtype=bool)
+    fold_paths = [] if keep_fold_paths else None
+    if fit_intercept and obs is None:
+        obs, off = fam.observed(f)                       # (a loss that was passed in has no intercept: not reached in practice)
+    # The path on all rows.  On the handle this call has just made it runs FIRST: the very calls the family's path makes on a
+    # fresh handle, so the same bits (after the folds an intercept's start η = b0 would be read as y - (y - b0) off the working
+    # response they left, and the handle's cache policy has a history).  A loss that was passed in gets it LAST, and comes
+    # back as the family's path leaves it: the weights of all rows, no folds.
+    path = None
+    if full_path and owned:
+        path = _glm_path_on(fam, f, lam, options, irls, np.inf, standardizeX, fit_intercept,
+                            fam.start(obs, off) if fit_intercept else None)
+    mode_before = f.gradient_cache_mode()                # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
+    try:
+        f.set_folds(ids, K)
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
+        for k in range(K):
+            f.set_fold_weights(k)
+            nk = n - sizes[k]
+            sx = stdX(f, weighted=True) if standardizeX else np.ones(f.p)     # while w still holds the 0/1 weights
+            scale = np.sqrt(nk / n) if standardizeX else nk / n
+            x = SparseIterate(f.p)
+            if fit_intercept:
+                sx[p] = 0.0
+                x[p + 1] = fam.start(obs[ids != k], None if off is None else off[ids != k])
+            res = fam.path_result(list(lam), [], *[[] for _ in fam.path_fields], [])
+            for j in range(m):
+                sol = _glm_solve(fam, x, f, ProxL1(lam[j] * scale, sx), options, irls, k)
+                for name, value in fam.cv_measures.items():
+                    held[name][k, j] = value(sol, sizes[k])
+                tdev[k, j] = fam.cv_train(sol, n, nk)
+                rounds[k, j], conv[k, j] = sol.rounds, sol.converged
+                if keep_fold_paths:
+                    _glm_keep(fam, res, sol, x, p, fit_intercept, nll=sol.nll * n / nk)
+            if keep_fold_paths:
+                fold_paths.append(res)
+    finally:
+        f._synced = None
+        if mode_before == 1:
+            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
+        f.set_folds(None, 0)
+    cvm, cvsd, imin, i1se = _cv_select(lam, sizes, held[measure])
+    if full_path and not owned:
+        path = _glm_path_on(fam, f, lam, options, irls, np.inf, standardizeX, fit_intercept)
+    dev, *others = held.values()
+    return fam.cv_result(lam, sizes, dev, tdev, *others, rounds, conv, measure, cvm, cvsd, imin, float(lam[imin]), i1se,
+                         float(lam[i1se]), path, fold_paths)
+
+
+# ---- the binomial family -------------------------------------------------------------------------------------------------
+def logisticLasso_(x, f, g, options=None, irls=None, fold=None):
+    """Minimise F(β) = (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ0 Σ ω_j |β_j| over the CDLogisticLoss f by IRLS, warm-started
+    from x (updated in place).  A round is one f.irls_step -- working weights, working response and their residual formed on
+    the device from the linear predictor the handle holds, nothing n-sized on the host -- and one coordinateDescent_ of the
+    weighted lasso they define, which keeps the residual the step left (cdh_set_reuse_residual for the duration).
+
+    fold=k: every step, the final read-only one included, holds the rows of fold k out (irls_step(fold=k), after
+    f.set_folds); the minimised F is then (1/n) Σ over the training rows, and the solution carries the held-out rows'
+    held_nll and held_miss at the final β."""
+    return _glm_solve(_LOGISTIC, x, f, g, options, irls, fold)
+
+
+def logisticLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=False):
+    """ℓ1-penalised logistic regression (glmnet's family = "binomial"): the minimiser of
+    (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ Σ ω_j |β_j|, η = Xβ (+ b with fit_intercept: a column of ones appended as
+    coordinate p + 1 with ω = 0, started at log(ȳ / (1 - ȳ)) and returned apart from x, which has length p).  X may also be
+    an existing CDLogisticLoss (y is then ignored; no intercept)."""
+    return _glm_lasso(_LOGISTIC, X, y, lam, omega, options, irls, fit_intercept)
+
+
+def logisticLambdaMax(f, omega=None, fit_intercept=False):
+    """The smallest λ at which every penalised coordinate of the logistic lasso is zero: max_j |X_j'(y - p̂)| / (n ω_j) at the
+    null model (β = 0; with fit_intercept the last column of f is the column of ones, its coordinate log(ȳ / (1 - ȳ)) and
+    left out of the maximum).  One irls_step at the null model and one cdh_xt_r: the step leaves r = (y - p̂) / w, and at
+    the null model every row has the same weight w̄ = Σw / n, so X'(y - p̂) = w̄ X'r.  The handle is left at the null model."""
+    if not isinstance(f, CDLogisticLoss):
+        raise TypeError("MethodError: logisticLambdaMax takes a CDLogisticLoss")
+    p = f.p - (1 if fit_intercept else 0)
+    x = SparseIterate(f.p)
+    if fit_intercept:
+        x[p + 1] = _logit_start(f.labels)
+    f._push(x, rebuild=True)
+    f._synced = None
+    wbar = f.irls_step(True, 1e-12)["sum_w"] / f.n
+    out = np.zeros(f.p)
+    check(f._L.cdh_xt_r(f._h, _vp(out)), f._h)
+    t = np.abs(out[:p]) * wbar / f.n
+    if omega is not None:
+        t = t / np.asarray(omega, dtype=np.float64)[:p]
+    return float(t.max())
+
+
+def LogisticLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, fit_intercept=False):
+    """LassoPath's loop (src/lasso.jl:229-260) with logisticLasso_ per λ: one handle, one x warm-started along λ,
+    ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p."""
+    return _glm_path(_LOGISTIC, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept)
+
+
+def cvLogisticLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, fit_intercept=False,
+                        seed=0, measure="deviance", full_path=True, keep_fold_paths=False):
+    """K-fold cross-validation of LogisticLassoPath(X, y, λpath, options, irls; standardizeX, fit_intercept) on the device
+    (glmnet's cv.glmnet(family = "binomial")); no reference counterpart.  X may also be an existing CDLogisticLoss (y is then
+    ignored; no intercept); the design is uploaded once.
+
+    A fold is a 0/1 observation weight, as in cvLassoPath: the logistic lasso on the n_k training rows of fold k has the
+    iterates of IRLS on all n rows with the held-out rows at w = 0, z = η (irls_step(fold=k): cdh_glm_irls_fold), ω =
+    _stdX!(w, X) of the 0/1 weights and λ·sqrt(n_k / n) (standardizeX=False: ω = 1 and λ·n_k / n).  Per fold the path is
+    LogisticLassoPath's loop, warm-started along λ, and the read-only step that ends every solve returns the held-out
+    deviance and class error of that λ.  Nothing n-sized moves after the upload.
+
+    folds: 0-based ids, one per row; otherwise np.random.default_rng(seed).permutation(n) % K.  measure: "deviance" or
+    "class" -- what cvm, cvsd and the selections are taken from.  There is no max_hat_s: the folds would be truncated at
+    different λ.  With fit_intercept every fold starts at the logit of its own training rows' mean label.  The folds are
+    dropped when the call returns or raises.  `path` is LogisticLassoPath on all rows (None with full_path=False): from a
+    matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was passed
+    in it runs after them, so that the loss comes back with the weights of all rows.  `fold_paths`: the K fold paths as LogisticLassoPathResult (None unless keep_fold_paths)."""
+    return _cv_glm_path(_LOGISTIC, X, y, lambdapath, K, folds, options, irls, standardizeX, fit_intercept, seed, measure, None,
+                        full_path, keep_fold_paths)
+
+
+# ---- the Poisson family with an offset ----------------------------------------------------------------------------------------
+def poissonLasso_(x, f, g, options=None, irls=None, fold=None):
+    """Minimise F(β) = (1/n) Σ [μ_i - y_i η_i] + λ0 Σ ω_j |β_j|, η = Xβ + o, μ = e^η, over the CDPoissonLoss f by IRLS,
+    warm-started from x (updated in place): logisticLasso_'s loop with f.irls_step of the Poisson family (irls.wmin,
+    irls.etaMax).  fold=k: every step holds the rows of fold k out, F is (1/n) Σ over the training rows, and the solution
+    carries the held-out rows' held_deviance at the final β."""
+    return _glm_solve(_POISSON, x, f, g, options, irls, fold)
 
 
 def poissonLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=False, offset=None):
@@ -1966,23 +2032,7 @@ def poissonLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=F
     (1/n) Σ [μ_i - y_i η_i] + λ Σ ω_j |β_j|, η = Xβ + o (+ b with fit_intercept: a column of ones appended as coordinate
     p + 1 with ω = 0, started at log(Σy / Σ e^o) and returned apart from x, which has length p).  X may also be an existing
     CDPoissonLoss (y and offset are then its own; no intercept)."""
-    if fit_intercept and not isinstance(X, CoordinateDifferentiableFunction):
-        start = _poisson_start(np.asarray(y, dtype=np.float64), None if offset is None else np.asarray(offset, dtype=np.float64))
-    f, owned = _poisson_loss(X, y, fit_intercept, offset)
-    try:
-        p = f.p - (1 if fit_intercept else 0)
-        om = None if omega is None else np.asarray(omega, dtype=np.float64)
-        x = SparseIterate(f.p)
-        if fit_intercept:
-            om = np.r_[np.ones(p) if om is None else om, 0.0]
-            x[p + 1] = start
-        sol = poissonLasso_(x, f, ProxL1(lam, om), options, irls)
-        if fit_intercept:
-            sol.x, sol.intercept = _split_intercept(x, p)
-        return sol
-    finally:
-        if owned:
-            f.close()
+    return _glm_lasso(_POISSON, X, y, lam, omega, options, irls, fit_intercept, offset)
 
 
 def poissonLambdaMax(f, omega=None, fit_intercept=False):
@@ -2013,71 +2063,7 @@ def PoissonLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf
                      offset=None):
     """LassoPath's loop (src/lasso.jl:229-260) with poissonLasso_ per λ: one handle, one x warm-started along λ,
     ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p."""
-    start = None
-    if fit_intercept and not isinstance(X, CoordinateDifferentiableFunction):
-        start = _poisson_start(np.asarray(y, dtype=np.float64), None if offset is None else np.asarray(offset, dtype=np.float64))
-    f, owned = _poisson_loss(X, y, fit_intercept, offset)
-    try:
-        return _poisson_path_on(f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, start)
-    finally:
-        if owned:
-            f.close()
-
-
-def _poisson_path_on(f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, start=None):
-    """PoissonLassoPath on the loss f (its last column the column of ones when an intercept is fitted; start: the null
-    model's intercept, where the caller has computed it from its host copies)."""
-    p = f.p - (1 if fit_intercept else 0)
-    sx = stdX(f) if standardizeX else np.ones(f.p)
-    x = SparseIterate(f.p)
-    if fit_intercept:
-        sx[p] = 0.0
-        x[p + 1] = _poisson_start(f.counts, f.offset) if start is None else start
-    lambdapath = list(lambdapath)
-    res = PoissonLassoPathResult(lambdapath, [], [], [], [], [], [])
-    mode_before = f.gradient_cache_mode()          # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
-    if mode_before == 1:
-        check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
-    try:
-        for i, lam in enumerate(lambdapath):
-            sol = poissonLasso_(x, f, ProxL1(lam, sx), options, irls)
-            b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
-            res.betapath.append(b)
-            res.nll.append(sol.nll)
-            res.deviance.append(sol.deviance)
-            res.rounds.append(sol.rounds)
-            res.converged.append(sol.converged)
-            res.intercepts.append(b0)
-            if b.nnz > max_hat_s:
-                res.lambdapath = lambdapath[: i + 1]
-                break
-    finally:
-        if mode_before == 1:
-            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
-    return res
-
-
-@dataclass
-class CVPoissonLassoPathResult:
-    """What cvPoissonLassoPath returns.  Per fold k and λ_j, by the path fitted without the rows of fold k:
-    fold_deviance[k, j] = Σ dev_i / size_k over the held-out rows, train_deviance[k, j] = Σ dev_i / n_k over the rows it was
-    fitted on, rounds and converged of its IRLS loop.  cvm, cvsd and the two selections (0-based positions in lambdapath) are
-    taken from fold_deviance, the folds weighted by their sizes."""
-    lambdapath: np.ndarray
-    fold_sizes: np.ndarray
-    fold_deviance: np.ndarray
-    train_deviance: np.ndarray
-    rounds: np.ndarray
-    converged: np.ndarray
-    measure: str
-    cvm: np.ndarray
-    cvsd: np.ndarray
-    index_min: int
-    lambda_min: float
-    index_1se: int
-    lambda_1se: float
-    path: PoissonLassoPathResult = None
-    fold_paths: list = None
+    return _glm_path(_POISSON, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, offset)
 
 
 def cvPoissonLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, fit_intercept=False,
@@ -2096,88 +2082,8 @@ def cvPoissonLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=No
     from a matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was
     passed in it runs after them, so that the loss comes back with the weights of all rows.  `fold_paths`: the K fold paths
     as PoissonLassoPathResult (None unless keep_fold_paths)."""
-    if measure != "deviance":
-        raise ArgumentError('measure must be "deviance"')
-    if isinstance(X, CoordinateDifferentiableFunction) and not isinstance(X, CDPoissonLoss):
-        raise TypeError("MethodError: cvPoissonLassoPath takes a matrix or a CDPoissonLoss")
-    lam = np.array(list(lambdapath), dtype=np.float64)
-    if lam.size == 0:
-        raise ArgumentError("lambdapath is empty")
-    n = X.n if isinstance(X, _HipLoss) else np.shape(X)[0]
-    ids, sizes = _cv_fold_ids(int(n), K, folds, seed)
-    counts = off = None
-    if fit_intercept and not isinstance(X, _HipLoss):
-        counts = np.ascontiguousarray(y, dtype=np.float64)
-        off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64)
-        _poisson_start(counts, off)
-        for k in range(len(sizes)):                     # before the upload: a fold whose start would be infinite
-            _poisson_start(counts[ids != k], None if off is None else off[ids != k])
-    f, owned = _poisson_loss(X, y, fit_intercept, offset)
-    try:
-        return _cv_poisson_path(f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, counts, off, full_path,
-                                keep_fold_paths)
-    finally:
-        if owned:
-            f.close()                  # the handle this call made goes with it, also when a fold raises
-
-
-def _cv_poisson_path(f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, counts, off, full_path,
-                     keep_fold_paths):
-    n, K, m = f.n, len(sizes), lam.size
-    if f.n_total != f.n:
-        raise ArgumentError("cvPoissonLassoPath does not run on row-sharded handles")
-    p = f.p - (1 if fit_intercept else 0)
-    dev, tdev = np.zeros((K, m)), np.zeros((K, m))
-    rounds, conv = np.zeros((K, m), dtype=np.int64), np.zeros((K, m), dtype=bool)
-    fold_paths = [] if keep_fold_paths else None
-    if fit_intercept and counts is None:
-        counts, off = f.counts, f.offset                 # (a loss that was passed in has no intercept: not reached in practice)
-    # the path on all rows: first on the handle this call has just made (PoissonLassoPath's own calls on a fresh handle, so
-    # the same bits), last on a loss that was passed in (it comes back with the weights of all rows and no folds)
-    path = None
-    if full_path and owned:
-        path = _poisson_path_on(f, lam, options, irls, np.inf, standardizeX, fit_intercept,
-                                _poisson_start(counts, off) if fit_intercept else None)
-    mode_before = f.gradient_cache_mode()                # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
-    try:
-        f.set_folds(ids, K)
-        if mode_before == 1:
-            check(f._L.cdh_set_gradient_cache(f._h, 2), f._h)
-        for k in range(K):
-            f.set_fold_weights(k)
-            nk = n - sizes[k]
-            sx = stdX(f, weighted=True) if standardizeX else np.ones(f.p)     # while w still holds the 0/1 weights
-            scale = np.sqrt(nk / n) if standardizeX else nk / n
-            x = SparseIterate(f.p)
-            if fit_intercept:
-                sx[p] = 0.0
-                x[p + 1] = _poisson_start(counts[ids != k], None if off is None else off[ids != k])
-            res = PoissonLassoPathResult(list(lam), [], [], [], [], [], [])
-            for j in range(m):
-                sol = poissonLasso_(x, f, ProxL1(lam[j] * scale, sx), options, irls, fold=k)
-                dev[k, j] = sol.held_deviance / sizes[k]
-                tdev[k, j] = sol.deviance / nk
-                rounds[k, j], conv[k, j] = sol.rounds, sol.converged
-                if keep_fold_paths:
-                    b, b0 = _split_intercept(x, p) if fit_intercept else (x.copy(), None)
-                    res.betapath.append(b)
-                    res.nll.append(sol.nll * n / nk)
-                    res.deviance.append(sol.deviance)
-                    res.rounds.append(sol.rounds)
-                    res.converged.append(sol.converged)
-                    res.intercepts.append(b0)
-            if keep_fold_paths:
-                fold_paths.append(res)
-    finally:
-        f._synced = None
-        if mode_before == 1:
-            check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
-        f.set_folds(None, 0)
-    cvm, cvsd, imin, i1se = _cv_select(lam, sizes, dev)
-    if full_path and not owned:
-        path = _poisson_path_on(f, lam, options, irls, np.inf, standardizeX, fit_intercept)
-    return CVPoissonLassoPathResult(lam, sizes, dev, tdev, rounds, conv, "deviance", cvm, cvsd, imin, float(lam[imin]),
-                                    i1se, float(lam[i1se]), path, fold_paths)
+    return _cv_glm_path(_POISSON, X, y, lambdapath, K, folds, options, irls, standardizeX, fit_intercept, seed, measure, offset,
+                        full_path, keep_fold_paths)
 
 
 # --------------------------------------------------------------------------------------

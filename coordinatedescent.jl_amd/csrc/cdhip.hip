@@ -287,10 +287,11 @@ struct CvState {
 // The logistic loss (glm_kernels.hpp): the labels of the rows, resident from cdh_glm_set_labels on in a buffer of the handle's
 // own -- y holds the working response of the IRLS round, not the labels.  glm_plan.hpp: the grid and the rows of a workgroup.
 #include "glm_plan.hpp"
+enum class GlmData : int { Binomial = 0, Poisson = 1 };
 struct GlmState {
     DevBuf<double> labels;     // the labels, or the counts of the Poisson family
     DevBuf<double> offset;     // Poisson: ld doubles, pads zero; allocated by the first cdh_glm_set_counts that brings one
-    int family = 0;            // 0: binomial, 1: Poisson (cdh_glm_set_counts)
+    GlmData family = GlmData::Binomial;   // what `labels` holds: cdh_glm_set_labels' labels or cdh_glm_set_counts' counts
     bool has_offset = false;   // the offset buffer holds this handle's offset (false: the step runs without one)
     bool set = false;
 };
@@ -306,7 +307,7 @@ struct Knobs {
     bool cov_solve = true;           // CDH_COV_SOLVE: the device-resident pass loop
     int cs_crew = 31;                // CDH_CS_CREW: its helper workgroups (0: none)
     int cs_ucap = 0;                 // CDH_CS_UCAP (tests): visit lists longer than this leave the loop's LDS block
-    int64_t glm_grid = kGlmMaxGrid;  // CDH_GLM_GRID (tests): cap of k_glm_irls' grid, so that a short vector gives a workgroup a second stride
+    int64_t glm_grid = kGlmMaxGrid;  // CDH_GLM_GRID (tests): cap of k_glm_step's grid, so that a short vector gives a workgroup a second stride
     bool small_path = true;          // CDH_SMALL_PATH: the one-launch solve
     int64_t small_max_bytes = -1;    // CDH_SMALL_MAX_BYTES: a fixed limit on n p sz instead of rent-or-buy (-1: none)
     int64_t small_always_bytes = (int64_t)kSmallAlwaysBytes;   // CDH_SMALL_ALWAYS_BYTES (tests: 0 makes every handle rent first)
@@ -1037,7 +1038,7 @@ constexpr int kScreenMinPass = 16;   // screens / the cache: passes over fewer c
 #include "cov_solve.hpp"    // k_cov_solve, cov_solve: the pass loop of a cache-served solve on the device
 #include "quad_solve.hpp"   // k_quad_solve, k_quad_init: a batch of CDQuadraticLoss problems, one workgroup each
 #include "cv_path.hpp"      // k_fold_weights, k_path_sse: the folds of a cross-validated path and its errors in one pass
-#include "glm_kernels.hpp"  // k_glm_irls: the step between two IRLS rounds of the logistic loss
+#include "glm_kernels.hpp"  // k_glm_step: the step between two IRLS rounds of a GLM family
 
 // _cdPass! (coordinate_descent.jl:94-110)
 // Screening of a FULL pass (exact, no reference counterpart).  A visit of a coordinate with
@@ -1762,8 +1763,31 @@ int32_t cdh_loadings(cdh_handle h, double* out_p) { return guarded(h, [&]() -> i
     return CDH_OK;
 }); }
 
-// ---- l1-penalised logistic regression by IRLS (glm_kernels.hpp; no reference counterpart: a round's solve is the weighted lasso of
+// ---- l1-penalised GLMs by IRLS (glm_kernels.hpp; no reference counterpart: a round's solve is the weighted lasso of
 // CDWeightedLSLoss, cd_differentiable_function.jl:118-194) ---------------------------------------------------------------------
+// The body of cdh_glm_irls, cdh_glm_irls_fold and cdh_glm_poisson_irls: stands in for cdh_get_residual, w and z on the host,
+// cdh_set_y, cdh_set_obs_weights and cdh_initialize between two rounds.  F: the family (GlmBinomial, GlmBinomialFold, GlmPoisson).
+extern "C++" template <class F>
+static int32_t glm_step(cdh_handle h, int32_t k, int32_t apply, const GlmParams& pm, double* out) {
+    CHK(glm_check<F>(h, k, apply, pm, out));
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(glm_catch_up(h));
+    if (!apply) return glm_launch<F>(h, k, false, pm, out);      // read-only from here
+    // what cdh_set_obs_weights and cdh_set_y void, through their own calls: the residual's consistency and the stashed dots,
+    // the gradient cache with its Gram columns, y'y, the one-launch solve's G and c
+    CHK(design_changes(h, false));
+    gc_invalidate(h, false);
+    h->gc.st.yy_void();
+    h->small.c_valid = false;
+    CHK(ensure_weights_buffer(h));
+    CHK(glm_launch<F>(h, k, true, pm, out));
+    // r = d / w IS z - X beta of the iterate, but not the bits initialize! would write: consistent, not pristine
+    h->rs.rewritten_as_residual();
+    gc_after_rebuild(h, h->x);           // (as after cdh_initialize: the cache's reference iterate is the handle's)
+    h->has_w = true;
+    return CDH_OK;
+}
+
 // stands in for cdh_set_y of n zeros, the labels kept beside it
 int32_t cdh_glm_set_labels(cdh_handle h, int32_t family, const void* host_labels) { return guarded(h, [&]() -> int32_t {
     return glm_set_labels(h, family, host_labels);
@@ -1773,75 +1797,28 @@ int32_t cdh_glm_get_labels(cdh_handle h, void* host_labels) { return guarded(h, 
     return glm_get_labels(h, host_labels);
 }); }
 
-// stands in for cdh_get_residual, w and z on the host, cdh_set_y, cdh_set_obs_weights and cdh_initialize between two rounds
+// the step between two rounds (glm_step), the binomial family
 int32_t cdh_glm_irls(cdh_handle h, int32_t apply, double wmin, double* out3) { return guarded(h, [&]() -> int32_t {
-    CHK(glm_check_irls(h, apply, wmin, out3));
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(glm_catch_up(h));
-    if (!apply) return glm_launch(h, false, wmin, out3);      // read-only from here
-    // what cdh_set_obs_weights and cdh_set_y void, through their own calls: the residual's consistency and the stashed dots,
-    // the gradient cache with its Gram columns, y'y, the one-launch solve's G and c
-    CHK(design_changes(h, false));
-    gc_invalidate(h, false);
-    h->gc.st.yy_void();
-    h->small.c_valid = false;
-    CHK(ensure_weights_buffer(h));
-    CHK(glm_launch(h, true, wmin, out3));
-    // r = d / w IS z - X beta of the iterate, but not the bits initialize! would write: consistent, not pristine
-    h->rs.rewritten_as_residual();
-    gc_after_rebuild(h, h->x);           // (as after cdh_initialize: the cache's reference iterate is the handle's)
-    h->has_w = true;
-    return CDH_OK;
+    return glm_step<GlmBinomial>(h, -1, apply, GlmParams{wmin, 0.0}, out3);
 }); }
 
 // the same step inside a fold of a cross-validated path (cv_path.hpp; the solves are LassoPath's, lasso.jl:229-260, on the
 // weighted loss): held-out rows keep weight zero through every round, and their deviance and class error come out of the pass
 int32_t cdh_glm_irls_fold(cdh_handle h, int32_t k, int32_t apply, double wmin, double* out5) { return guarded(h, [&]() -> int32_t {
-    CHK(glm_check_irls_fold(h, k, apply, wmin, out5));
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(glm_catch_up(h));
-    if (!apply) return glm_launch_fold(h, k, false, wmin, out5);      // read-only from here
-    // what cdh_glm_irls(apply = 1) voids, through the same calls in the same order
-    CHK(design_changes(h, false));
-    gc_invalidate(h, false);
-    h->gc.st.yy_void();
-    h->small.c_valid = false;
-    CHK(ensure_weights_buffer(h));
-    CHK(glm_launch_fold(h, k, true, wmin, out5));
-    h->rs.rewritten_as_residual();
-    gc_after_rebuild(h, h->x);
-    h->has_w = true;
-    return CDH_OK;
+    return glm_step<GlmBinomialFold>(h, k, apply, GlmParams{wmin, 0.0}, out5);
 }); }
 
-// ---- the Poisson family of the same loop (k_glm_poisson; no reference counterpart: a round's solve is the weighted lasso of
-// CDWeightedLSLoss, cd_differentiable_function.jl:118-194) -------------------------------------------------------------------
-// stands in for cdh_set_y of n zeros, the counts and the offset kept beside it
+// the Poisson family of the same loop: stands in for cdh_set_y of n zeros, the counts and the offset kept beside it
 int32_t cdh_glm_set_counts(cdh_handle h, const void* host_counts, const void* host_offset) { return guarded(h, [&]() -> int32_t {
-    return glm_set_counts(h, host_counts, host_offset);
+    return glm_set_observations(h, GlmData::Poisson, host_counts, host_offset);
 }); }
 
 int32_t cdh_glm_get_offset(cdh_handle h, void* host_offset) { return guarded(h, [&]() -> int32_t {
     return glm_get_offset(h, host_offset);
 }); }
 
-// cdh_glm_irls_fold's catch-up, read-only form and voided state around the Poisson pass
 int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double* out6) { return guarded(h, [&]() -> int32_t {
-    CHK(glm_check_poisson(h, k, apply, wmin, eta_max, out6));
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(glm_catch_up(h));
-    if (!apply) return glm_launch_poisson(h, k, false, wmin, eta_max, out6);      // read-only from here
-    // what cdh_glm_irls(apply = 1) voids, through the same calls in the same order
-    CHK(design_changes(h, false));
-    gc_invalidate(h, false);
-    h->gc.st.yy_void();
-    h->small.c_valid = false;
-    CHK(ensure_weights_buffer(h));
-    CHK(glm_launch_poisson(h, k, true, wmin, eta_max, out6));
-    h->rs.rewritten_as_residual();
-    gc_after_rebuild(h, h->x);
-    h->has_w = true;
-    return CDH_OK;
+    return glm_step<GlmPoisson>(h, k, apply, GlmParams{wmin, eta_max}, out6);
 }); }
 
 int32_t cdh_xt_r(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {

@@ -1,9 +1,10 @@
-// glm_kernels.hpp -- the step between two rounds of IRLS for l1-penalised logistic regression (no reference counterpart; a
-// round's solve is the weighted lasso of CDWeightedLSLoss, cd_differentiable_function.jl:118-194): from the linear predictor
-// the handle's residual stands for, the working weights, the working response and the new residual in one pass over the
-// rows, with the sums a caller needs of it.  Included by cdhip.hip inside its anonymous namespace, after the handle; the
-// grid and the rows of a workgroup are glm_plan.hpp's.  The Poisson family with an offset (k_glm_poisson, further down) is
-// the same pass with its own row function and record.
+// glm_kernels.hpp -- the step between two rounds of IRLS for an l1-penalised GLM (no reference counterpart; a round's solve
+// is the weighted lasso of CDWeightedLSLoss, cd_differentiable_function.jl:118-194): from the linear predictor the handle's
+// residual stands for, the working weights, the working response and the new residual in one pass over the rows, with the
+// sums a caller needs of it.  Included by cdhip.hip inside its anonymous namespace, after the handle; the grid and the rows of
+// a workgroup are glm_plan.hpp's.  One kernel (k_glm_step) and one host body (glm_step) serve every family; a family -- the
+// binomial, the binomial inside a fold, the Poisson with an offset -- is a struct that names its row function, its record
+// and what its export refuses.
 
 // One row, every quantity in double and every operation rounded on its own (no contraction into FMAs: tests/_logistic_numpy.py
 // writes the same lines).  eta = yw - r;  a = |eta|, e = exp(-a);  p = 1 / (1 + e) or e / (1 + e) by the sign of eta and
@@ -36,108 +37,6 @@ __device__ __forceinline__ GlmRow glm_row(double label, double yw, double r, dou
     return o;
 }
 
-// Workgroup b walks tiles b, b + gridDim.x, ... of kGlmRows rows; a lane holds one 16-byte vector of each of the three
-// streams per trip.  Rows n .. ld - 1 (the pad rows every other kernel relies on being zero) are WRITTEN as
-// zeros in w, y and r with APPLY and add nothing to the sums -- eta = 0 there would otherwise give w = 0.25.  The lanes'
-// sums go through block_sum (wave butterflies, the four waves in order) into the workgroup's record
-// partials[b kGlmVals + {0, 1, 2}] = (sum nll, sum w, clamped rows); k_gram_reduce adds the records in block order.  No
-// atomics: bit-identical run to run.  With APPLY = false nothing is written but the record.
-template <bool APPLY>
-__global__ __launch_bounds__(kGlmBlock) void k_glm_irls(const double* __restrict__ label, double* __restrict__ y,
-                                                        double* __restrict__ r, double* __restrict__ w, int64_t n,
-                                                        int64_t vecs, double wmin, double* __restrict__ partials) {
-    __shared__ double s_red[kGlmVals * (kGlmBlock / 64)];
-    const dvec2* lv = reinterpret_cast<const dvec2*>(label);
-    dvec2* yv = reinterpret_cast<dvec2*>(y);
-    dvec2* rv = reinterpret_cast<dvec2*>(r);
-    dvec2* wv = reinterpret_cast<dvec2*>(w);
-    double acc[kGlmVals] = {0.0, 0.0, 0.0};
-    const int64_t stride = (int64_t)gridDim.x * kGlmBlock;
-    for (int64_t j = (int64_t)blockIdx.x * kGlmBlock + threadIdx.x; j < vecs; j += stride) {
-        const dvec2 ll = lv[j], yy = yv[j], rr = rv[j];
-        dvec2 wn, zn, rn;
-#pragma unroll
-        for (int e = 0; e < kGlmVec; ++e) {
-            const bool live = j * kGlmVec + e < n;
-            const GlmRow o = glm_row(ll[e], yy[e], rr[e], wmin);
-            wn[e] = live ? o.w : 0.0;
-            zn[e] = live ? o.z : 0.0;
-            rn[e] = live ? o.r : 0.0;
-            acc[0] += live ? o.nll : 0.0;
-            acc[1] += live ? o.w : 0.0;
-            acc[2] += (live && o.clamped) ? 1.0 : 0.0;
-        }
-        if constexpr (APPLY) { wv[j] = wn; yv[j] = zn; rv[j] = rn; }
-    }
-    block_sum<kGlmVals>(acc, s_red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < kGlmVals; ++i) partials[(int64_t)blockIdx.x * kGlmVals + i] = acc[i];
-    }
-}
-static_assert(kGlmBlock == kBlock && kGlmVec == VecOf<double>::N, "block_sum and dvec2 are kernels.hpp's");
-
-// The step of a cross-validated path (cv_path.hpp: a fold is a 0/1 observation weight on the resident X; the solves are
-// LassoPath's, lasso.jl:229-260, on the weighted loss): k_glm_irls' grid, tiles, vectors and sums, with the fold id of every
-// row -- one byte, n of them, not ld -- deciding what the row becomes.  A training row (fold_i != k) is k_glm_irls' row.  A
-// held-out row (fold_i == k) gets w = 0 exactly (never clamped up to wmin), z = eta and r = 0: its row of X enters no
-// gradient, and eta = y - r stays recoverable from the two stored vectors after the solver's residual updates, so the next
-// step finds its linear predictor where it finds everybody's.  Its nll and its misclassification at the current iterate
-// (label [eta <= 0] + (1 - label) [eta > 0]: eta = 0 predicts class 0) go into sums of their own.  The record is
-// partials[b kGlmFoldVals + {0 .. 4}] = (nll of training rows, sum w, clamped training rows, nll of held-out rows, held-out
-// rows misclassified); lane sums, block_sum and k_gram_reduce take every value in k_glm_irls' order, so with no fold
-// (fold == nullptr or k < 0) w, y, r and the first three sums are k_glm_irls' bit for bit and the last two are zero.
-// A lane's vector covers two rows and the last one may lie at or beyond n: the id's address is clamped to n - 1 and the load
-// unconditional (as k_path_sse's), so no byte at or beyond n is read; `live` keeps such a row out of everything.  (Measured
-// and dropped: both ids in one 2-byte load where both rows lie below n, the clamped byte load elsewhere -- 1.12x the plain
-// step against 1.08x for the two byte loads, interleaved at n = 1e7.)
-template <bool APPLY>
-__global__ __launch_bounds__(kGlmBlock) void k_glm_irls_fold(const double* __restrict__ label, double* __restrict__ y,
-                                                             double* __restrict__ r, double* __restrict__ w,
-                                                             const uint8_t* __restrict__ fold, int k, int64_t n,
-                                                             int64_t vecs, double wmin, double* __restrict__ partials) {
-    __shared__ double s_red[kGlmFoldVals * (kGlmBlock / 64)];
-    const dvec2* lv = reinterpret_cast<const dvec2*>(label);
-    dvec2* yv = reinterpret_cast<dvec2*>(y);
-    dvec2* rv = reinterpret_cast<dvec2*>(r);
-    dvec2* wv = reinterpret_cast<dvec2*>(w);
-    const bool folded = fold != nullptr && k >= 0;           // (uniform over the launch)
-    double acc[kGlmFoldVals] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    const int64_t stride = (int64_t)gridDim.x * kGlmBlock;
-    for (int64_t j = (int64_t)blockIdx.x * kGlmBlock + threadIdx.x; j < vecs; j += stride) {
-        const dvec2 ll = lv[j], yy = yv[j], rr = rv[j];
-        int id[kGlmVec];
-#pragma unroll
-        for (int e = 0; e < kGlmVec; ++e) {
-            const int64_t i = j * kGlmVec + e;
-            id[e] = folded ? (int)fold[i < n ? i : n - 1] : -1;
-        }
-        dvec2 wn, zn, rn;
-#pragma unroll
-        for (int e = 0; e < kGlmVec; ++e) {
-            const bool live = j * kGlmVec + e < n;
-            const bool held = live && folded && id[e] == k;
-            const bool train = live && !held;
-            const GlmRow o = glm_row(ll[e], yy[e], rr[e], wmin);
-            const double eta = yy[e] - rr[e];                // (glm_row's own first line)
-            wn[e] = train ? o.w : 0.0;
-            zn[e] = train ? o.z : (held ? eta : 0.0);
-            rn[e] = train ? o.r : 0.0;
-            acc[0] += train ? o.nll : 0.0;
-            acc[1] += train ? o.w : 0.0;
-            acc[2] += (train && o.clamped) ? 1.0 : 0.0;
-            acc[3] += held ? o.nll : 0.0;
-            acc[4] += held ? (eta > 0.0 ? 1.0 - ll[e] : ll[e]) : 0.0;
-        }
-        if constexpr (APPLY) { wv[j] = wn; yv[j] = zn; rv[j] = rn; }
-    }
-    block_sum<kGlmFoldVals>(acc, s_red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < kGlmFoldVals; ++i) partials[(int64_t)blockIdx.x * kGlmFoldVals + i] = acc[i];
-    }
-}
-
 // ---- the Poisson family: counts y_i >= 0 with mean exp(x_i'beta + o_i), o the offset (log exposure) ----------------------------
 // One row, every quantity in double and every operation rounded on its own (tests/_poisson_numpy.py writes the same lines).
 // eta_lin = yw - r is X beta: the offset is NOT part of the stored working response, so that y_w - r stays the linear
@@ -165,33 +64,127 @@ __device__ __forceinline__ PoisRow pois_row(double count, double yw, double r, d
     return o;
 }
 
-// k_glm_irls_fold's grid, tiles, vectors, block_sum and k_gram_reduce with a fourth 16-byte stream, the offset (nullptr: zero;
-// the branch is uniform over the launch, and eta_lin + 0.0 makes a null offset and an all-zero one the same bits).  A training
-// row becomes (w, z_lin, r_new); a held-out row (fold_i == k) becomes (0, eta_lin, 0) -- weight exactly zero, never clamped up --
-// and its deviance at the current iterate goes into a sum of its own; rows n .. ld - 1 are WRITTEN as zeros and add to no sum
-// (eta = 0 there would otherwise give w = 1).  The fold byte is read for n rows, not ld: the address is clamped to n - 1 as in
-// k_glm_irls_fold.  The record is partials[b kGlmPoisVals + {0 .. 5}] = (nll of training rows, sum w, training rows clamped at
-// wmin, live rows capped at eta_max, deviance of held-out rows, deviance of training rows).  No atomics: bit-identical run to
-// run.  With APPLY = false nothing is written but the record.  57 bytes a row with APPLY (four vectors and a byte read, three
-// vectors written) against the fold-aware binomial step's 49.
-template <bool APPLY>
-__global__ __launch_bounds__(kGlmBlock) void k_glm_poisson(const double* __restrict__ count, double* __restrict__ y,
-                                                           double* __restrict__ r, double* __restrict__ w,
-                                                           const double* __restrict__ offset, const uint8_t* __restrict__ fold,
-                                                           int k, int64_t n, int64_t vecs, double wmin, double eta_max,
-                                                           double* __restrict__ partials) {
-    __shared__ double s_red[kGlmPoisVals * (kGlmBlock / 64)];
-    const dvec2* cv = reinterpret_cast<const dvec2*>(count);
+// ---- the families ----------------------------------------------------------------------------------------------------------------
+// what a step is told beside the handle: the floor of the weights and, for the Poisson family, the cap of eta
+struct GlmParams { double wmin, eta_max; };
+
+// A family names, for the kernel: kVals, the doubles of its record (glm_plan.hpp); kFold, whether a fold byte per row can hold
+// rows out; kOffset, whether a fourth 16-byte stream, the offset, is read; row(), one row's quantities; add(), the row's terms
+// of the record, acc[0] first -- live: the row lies below n, held: it is held out, train: live and not held.  For the host:
+// kData, the observations its export needs on the handle; kKBeforeOut, whether that export looks at k before its output
+// pointer; and what it refuses of the handle's observations, of the parameters and of a null output, in its own words.
+//
+// The binomial step: the record is (sum nll, sum w, clamped rows).  No fold byte, no offset: the step logisticLasso runs every
+// round stays an instantiation of its own (the fold-aware one at k = -1 was measured at 1.03x its time).
+struct GlmBinomial {
+    static constexpr int kVals = kGlmVals;
+    static constexpr bool kFold = false, kOffset = false;
+    static constexpr GlmData kData = GlmData::Binomial;
+    static constexpr bool kKBeforeOut = false;
+    static constexpr const char* kOutNull = "out3 is NULL";
+    using Row = GlmRow;
+    static __device__ __forceinline__ Row row(double label, double yw, double r, double, double wmin, double) {
+        return glm_row(label, yw, r, wmin);
+    }
+    static __device__ __forceinline__ void add(double* acc, const Row& o, double, double, bool, bool, bool train) {
+        acc[0] += train ? o.nll : 0.0;
+        acc[1] += train ? o.w : 0.0;
+        acc[2] += (train && o.clamped) ? 1.0 : 0.0;
+    }
+    static int32_t refuse_observations(cdh_handle h) {
+        if (!h->glm.set) return fail(h, CDH_BAD_ARG, "cdh_glm_irls needs labels: call cdh_glm_set_labels first");
+        if (h->glm.family != kData) return fail(h, CDH_BAD_ARG, "the handle holds counts (Poisson): the step is cdh_glm_poisson_irls");
+        return CDH_OK;
+    }
+    static int32_t refuse_params(cdh_handle h, const GlmParams& pm) {
+        if (!(pm.wmin > 0.0 && pm.wmin <= 0.25)) return fail(h, CDH_BAD_ARG, "need 0 < wmin <= 0.25");
+        return CDH_OK;
+    }
+};
+
+// The binomial step of a cross-validated path (cv_path.hpp: a fold is a 0/1 observation weight on the resident X; the solves are
+// LassoPath's, lasso.jl:229-260, on the weighted loss).  The nll of a held-out row and its misclassification at the current
+// iterate (label [eta <= 0] + (1 - label) [eta > 0]: eta = 0 predicts class 0) go into sums of their own: the record is (nll
+// of training rows, sum w, clamped training rows, nll of held-out rows, held-out rows misclassified).  The first three are
+// GlmBinomial's additions in its order, so with no fold (k < 0) w, y, r and those sums are the plain step's bit for bit and
+// the last two are zero.
+struct GlmBinomialFold : GlmBinomial {
+    static constexpr int kVals = kGlmFoldVals;
+    static constexpr bool kFold = true;
+    static constexpr const char* kOutNull = "out5 is NULL";
+    static __device__ __forceinline__ void add(double* acc, const Row& o, double label, double eta, bool live, bool held, bool train) {
+        GlmBinomial::add(acc, o, label, eta, live, held, train);
+        acc[3] += held ? o.nll : 0.0;
+        acc[4] += held ? (eta > 0.0 ? 1.0 - label : label) : 0.0;
+    }
+};
+
+// The Poisson step: fold byte and offset (nullptr: zero; eta_lin + 0.0 makes a null offset and an all-zero one the same bits).
+// The record is (nll of training rows, sum w, training rows clamped at wmin, live rows capped at eta_max, deviance of held-out
+// rows, deviance of training rows).  57 bytes a row with APPLY (four vectors and a byte read, three vectors written) against
+// the fold-aware binomial step's 49.
+struct GlmPoisson {
+    static constexpr int kVals = kGlmPoisVals;
+    static constexpr bool kFold = true, kOffset = true;
+    static constexpr GlmData kData = GlmData::Poisson;
+    static constexpr bool kKBeforeOut = true;
+    static constexpr const char* kOutNull = "out6 is NULL";
+    using Row = PoisRow;
+    static __device__ __forceinline__ Row row(double count, double yw, double r, double off, double wmin, double eta_max) {
+        return pois_row(count, yw, r, off, wmin, eta_max);
+    }
+    static __device__ __forceinline__ void add(double* acc, const Row& o, double, double, bool live, bool held, bool train) {
+        acc[0] += train ? o.nll : 0.0;
+        acc[1] += train ? o.w : 0.0;
+        acc[2] += (train && o.clamped) ? 1.0 : 0.0;
+        acc[3] += (live && o.capped) ? 1.0 : 0.0;
+        acc[4] += held ? o.dev : 0.0;
+        acc[5] += train ? o.dev : 0.0;
+    }
+    static int32_t refuse_observations(cdh_handle h) {
+        if (!h->glm.set || h->glm.family != kData)
+            return fail(h, CDH_BAD_ARG, "cdh_glm_poisson_irls needs counts: call cdh_glm_set_counts first");
+        return CDH_OK;
+    }
+    static int32_t refuse_params(cdh_handle h, const GlmParams& pm) {
+        if (!(pm.wmin > 0.0 && pm.wmin <= DBL_MAX)) return fail(h, CDH_BAD_ARG, "need a finite wmin > 0");
+        if (!(pm.eta_max > 0.0 && pm.eta_max <= 700.0)) return fail(h, CDH_BAD_ARG, "need 0 < eta_max <= 700");
+        return CDH_OK;
+    }
+};
+
+// Workgroup b walks tiles b, b + gridDim.x, ... of kGlmRows rows; a lane holds one 16-byte vector of each stream per trip: the
+// observations, y, r and -- F::kOffset -- the offset.  A training row becomes (w, z, r_new) of F::row.  A held-out row
+// (F::kFold, fold_i == k) gets w = 0 exactly (never clamped up to wmin), z = eta_lin = y - r (X beta, without the offset) and
+// r = 0: its row of X enters no gradient, and eta_lin stays recoverable from the two stored vectors after the solver's
+// residual updates, so the next step finds its linear predictor where it finds everybody's.  Rows n .. ld - 1 (the pad rows
+// every other kernel relies on being zero) are WRITTEN as zeros in w, y and r with APPLY and add nothing to
+// the sums -- eta = 0 there would otherwise give w = 0.25, or 1.  The fold id of a row is one byte, n of them, not ld.  A
+// lane's vector covers two rows and the last one may lie at or beyond n: the id's address is clamped to n - 1 and the load
+// unconditional (as k_path_sse's), so no byte at or beyond n is read; `live` keeps such a row out of everything.  (Measured
+// and dropped: both ids in one 2-byte load where both rows lie below n, the clamped byte load elsewhere -- 1.12x the plain
+// step against 1.08x for the two byte loads, interleaved at n = 1e7.)  fold == nullptr or k < 0, and offset == nullptr, are
+// uniform over the launch.  The lanes' sums go through block_sum (wave butterflies, the four waves in order) into the
+// workgroup's record partials[b F::kVals + i]; k_gram_reduce adds the records in block order.  No atomics: bit-identical run
+// to run.  With APPLY = false nothing is written but the record.
+template <class F, bool APPLY>
+__global__ __launch_bounds__(kGlmBlock) void k_glm_step(const double* __restrict__ obs, double* __restrict__ y,
+                                                        double* __restrict__ r, double* __restrict__ w,
+                                                        const double* __restrict__ offset, const uint8_t* __restrict__ fold,
+                                                        int k, int64_t n, int64_t vecs, double wmin, double eta_max,
+                                                        double* __restrict__ partials) {
+    __shared__ double s_red[F::kVals * (kGlmBlock / 64)];
+    const dvec2* bv = reinterpret_cast<const dvec2*>(obs);
     const dvec2* ov = reinterpret_cast<const dvec2*>(offset);
     dvec2* yv = reinterpret_cast<dvec2*>(y);
     dvec2* rv = reinterpret_cast<dvec2*>(r);
     dvec2* wv = reinterpret_cast<dvec2*>(w);
-    const bool folded = fold != nullptr && k >= 0;           // (uniform over the launch)
-    const bool has_off = offset != nullptr;                  // (uniform over the launch)
-    double acc[kGlmPoisVals] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const bool folded = F::kFold && fold != nullptr && k >= 0;
+    const bool has_off = F::kOffset && offset != nullptr;
+    double acc[F::kVals] = {};
     const int64_t stride = (int64_t)gridDim.x * kGlmBlock;
     for (int64_t j = (int64_t)blockIdx.x * kGlmBlock + threadIdx.x; j < vecs; j += stride) {
-        const dvec2 cc = cv[j], yy = yv[j], rr = rv[j];
+        const dvec2 bb = bv[j], yy = yv[j], rr = rv[j];
         dvec2 oo;
         if (has_off) oo = ov[j]; else { oo[0] = 0.0; oo[1] = 0.0; }
         int id[kGlmVec];
@@ -206,27 +199,24 @@ __global__ __launch_bounds__(kGlmBlock) void k_glm_poisson(const double* __restr
             const bool live = j * kGlmVec + e < n;
             const bool held = live && folded && id[e] == k;
             const bool train = live && !held;
-            const PoisRow o = pois_row(cc[e], yy[e], rr[e], oo[e], wmin, eta_max);
+            const typename F::Row o = F::row(bb[e], yy[e], rr[e], oo[e], wmin, eta_max);
+            const double eta_lin = yy[e] - rr[e];            // (the row functions' own first line)
             wn[e] = train ? o.w : 0.0;
-            zn[e] = train ? o.z : (held ? o.eta_lin : 0.0);
+            zn[e] = train ? o.z : (held ? eta_lin : 0.0);
             rn[e] = train ? o.r : 0.0;
-            acc[0] += train ? o.nll : 0.0;
-            acc[1] += train ? o.w : 0.0;
-            acc[2] += (train && o.clamped) ? 1.0 : 0.0;
-            acc[3] += (live && o.capped) ? 1.0 : 0.0;
-            acc[4] += held ? o.dev : 0.0;
-            acc[5] += train ? o.dev : 0.0;
+            F::add(acc, o, bb[e], eta_lin, live, held, train);
         }
         if constexpr (APPLY) { wv[j] = wn; yv[j] = zn; rv[j] = rn; }
     }
-    block_sum<kGlmPoisVals>(acc, s_red);
+    block_sum<F::kVals>(acc, s_red);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int i = 0; i < kGlmPoisVals; ++i) partials[(int64_t)blockIdx.x * kGlmPoisVals + i] = acc[i];
+        for (int i = 0; i < F::kVals; ++i) partials[(int64_t)blockIdx.x * F::kVals + i] = acc[i];
     }
 }
+static_assert(kGlmBlock == kBlock && kGlmVec == VecOf<double>::N, "block_sum and dvec2 are kernels.hpp's");
 
-// what the three exports refuse of the handle itself, before anything is touched (the style of vc_refuse_shards)
+// what every export refuses of the handle itself, before anything is touched (the style of vc_refuse_shards)
 int32_t glm_refuse(cdh_handle h) {
     if (h->n != h->n_total || h->xs.sharded())
         return fail(h, CDH_BAD_ARG, "the logistic loss does not run on row-sharded handles");
@@ -235,58 +225,25 @@ int32_t glm_refuse(cdh_handle h) {
     return CDH_OK;
 }
 
-// leaves the handle exactly as cdh_set_y of n zeros would (what that export voids is voided here, in its order)
-int32_t glm_set_labels(cdh_handle h, int32_t family, const void* host_labels) {
-    if (family != 0) return fail(h, CDH_BAD_ARG, "unknown family: 0 (binomial) is the only one");
+// cdh_glm_set_labels and cdh_glm_set_counts: leaves the handle exactly as cdh_set_y of n zeros would (what that export voids
+// is voided here, in its order), the observations -- labels in [0, 1], or counts that are finite and >= 0, not necessarily
+// integers -- and the finite offsets of the Poisson family kept beside it.  Both buffers hold ld doubles, their pad rows
+// zero, and are complete before the handle changes.
+int32_t glm_set_observations(cdh_handle h, GlmData family, const void* host_obs, const void* host_offset) {
+    const bool counts = family == GlmData::Poisson;
     CHK(glm_refuse(h));
-    NEED_P(h, host_labels);
-    const double* lab = (const double*)host_labels;
-    for (int64_t i = 0; i < h->n; ++i)
-        if (!(lab[i] >= 0.0 && lab[i] <= 1.0)) {      // (a NaN fails both comparisons)
-            char buf[128];
-            snprintf(buf, sizeof buf, "labels[%lld] = %g is outside [0, 1]", (long long)i, lab[i]);
-            return fail(h, CDH_BAD_ARG, buf);
-        }
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t colbytes = (size_t)h->ld * sizeof(double);
-    DevBuf<double> fresh;                // complete before the handle changes: a failed allocation leaves it as it was
-    if (!h->glm.labels) {
-        HIPCHK(h, fresh.alloc(colbytes));
-        HIPCHK(h, hipMemsetAsync(fresh, 0, colbytes, h->stream));
-    }
-    h->rs.overwritten_with_y();          // r = copy(y) = 0 below
-    gc_invalidate(h, false);
-    h->gc.st.yy_void();
-    h->small.c_valid = false;
-    if (!h->glm.labels) h->glm.labels = std::move(fresh);
-    HIPCHK(h, hipMemcpyAsync(h->glm.labels, lab, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->y, 0, colbytes, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->r, 0, colbytes, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->y_set = true;
-    h->glm.family = family;
-    h->glm.has_offset = false;           // (a Poisson handle turned binomial drops its offset)
-    h->glm.set = true;
-    return CDH_OK;
-}
-
-// cdh_glm_set_counts: glm_set_labels for the Poisson family (family 1), the offset kept beside the counts.  Counts are finite
-// and >= 0 (not necessarily integers), offsets finite; both buffers are complete before the handle changes, and what is
-// voided is what glm_set_labels voids, in its order.  The offset buffer holds ld doubles, its pad rows zero.
-int32_t glm_set_counts(cdh_handle h, const void* host_counts, const void* host_offset) {
-    CHK(glm_refuse(h));
-    NEED_P(h, host_counts);
-    const double* cnt = (const double*)host_counts;
+    if (!host_obs) return fail(h, CDH_BAD_ARG, counts ? "host_counts is NULL" : "host_labels is NULL");
+    const double* obs = (const double*)host_obs;
     const double* off = (const double*)host_offset;
+    char buf[128];
     for (int64_t i = 0; i < h->n; ++i)
-        if (!(cnt[i] >= 0.0 && cnt[i] <= DBL_MAX)) {      // (a NaN fails both comparisons)
-            char buf[128];
-            snprintf(buf, sizeof buf, "counts[%lld] = %g is negative or not finite", (long long)i, cnt[i]);
+        if (!(obs[i] >= 0.0 && obs[i] <= (counts ? DBL_MAX : 1.0))) {      // (a NaN fails both comparisons)
+            snprintf(buf, sizeof buf, counts ? "counts[%lld] = %g is negative or not finite" : "labels[%lld] = %g is outside [0, 1]",
+                     (long long)i, obs[i]);
             return fail(h, CDH_BAD_ARG, buf);
         }
     for (int64_t i = 0; off && i < h->n; ++i)
         if (!(fabs(off[i]) <= DBL_MAX)) {
-            char buf[128];
             snprintf(buf, sizeof buf, "offset[%lld] = %g is not finite", (long long)i, off[i]);
             return fail(h, CDH_BAD_ARG, buf);
         }
@@ -307,22 +264,29 @@ int32_t glm_set_counts(cdh_handle h, const void* host_counts, const void* host_o
     h->small.c_valid = false;
     if (!h->glm.labels) h->glm.labels = std::move(fresh);
     if (off && !h->glm.offset) h->glm.offset = std::move(fresh_off);
-    HIPCHK(h, hipMemcpyAsync(h->glm.labels, cnt, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->glm.labels, obs, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (off) HIPCHK(h, hipMemcpyAsync(h->glm.offset, off, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(h->y, 0, colbytes, h->stream));
     HIPCHK(h, hipMemsetAsync(h->r, 0, colbytes, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->y_set = true;
-    h->glm.family = 1;
-    h->glm.has_offset = off != nullptr;
+    h->glm.family = family;
+    h->glm.has_offset = off != nullptr;  // (a Poisson handle turned binomial drops its offset)
     h->glm.set = true;
     return CDH_OK;
+}
+
+// cdh_glm_set_labels: its family argument stays closed (the Poisson family came in through an export of its own)
+int32_t glm_set_labels(cdh_handle h, int32_t family, const void* host_labels) {
+    if (family != 0) return fail(h, CDH_BAD_ARG, "unknown family: 0 (binomial) is the only one");
+    return glm_set_observations(h, GlmData::Binomial, host_labels, nullptr);
 }
 
 // zeros when the counts came without an offset
 int32_t glm_get_offset(cdh_handle h, void* host_offset) {
     NEED_P(h, host_offset);
-    if (!h->glm.set || h->glm.family != 1) return fail(h, CDH_BAD_ARG, "no counts are set: call cdh_glm_set_counts first");
+    if (!h->glm.set || h->glm.family != GlmData::Poisson)
+        return fail(h, CDH_BAD_ARG, "no counts are set: call cdh_glm_set_counts first");
     if (!h->glm.has_offset) {
         memset(host_offset, 0, (size_t)h->n * sizeof(double));
         return CDH_OK;
@@ -342,43 +306,26 @@ int32_t glm_get_labels(cdh_handle h, void* host_labels) {
     return CDH_OK;
 }
 
-// what cdh_glm_irls refuses, before the handle is touched
-int32_t glm_check_irls(cdh_handle h, int32_t apply, double wmin, const double* out3) {
-    CHK(glm_refuse(h));
-    if (!h->glm.set) return fail(h, CDH_BAD_ARG, "cdh_glm_irls needs labels: call cdh_glm_set_labels first");
-    if (h->glm.family != 0) return fail(h, CDH_BAD_ARG, "the handle holds counts (Poisson): the step is cdh_glm_poisson_irls");
-    if (apply != 0 && apply != 1) return fail(h, CDH_BAD_ARG, "apply must be 0 or 1");
-    if (!(wmin > 0.0 && wmin <= 0.25)) return fail(h, CDH_BAD_ARG, "need 0 < wmin <= 0.25");
-    NEED_P(h, out3);
-    if ((size_t)(glm_plan(h->ld, h->knobs.glm_grid).records * kGlmVals) > h->partials_doubles)
-        return fail(h, CDH_BAD_ARG, "partials too small");
-    return CDH_OK;
-}
-
-// what cdh_glm_irls_fold refuses, before the handle is touched: all of the above, and of k what cdh_set_fold_weights refuses
-int32_t glm_check_irls_fold(cdh_handle h, int32_t k, int32_t apply, double wmin, const double* out5) {
-    CHK(glm_check_irls(h, apply, wmin, out5));
+// of k what cdh_set_fold_weights refuses
+int32_t glm_refuse_k(cdh_handle h, int32_t k) {
     if (k < -1) return fail(h, CDH_BAD_ARG, "k must be a fold, or -1 for all ones");
     if (k >= 0 && h->cv.K == 0) return fail(h, CDH_BAD_ARG, "k >= 0 needs cdh_set_folds first");
     if (k >= h->cv.K && k >= 0) return fail(h, CDH_BAD_ARG, "k must be below the K of cdh_set_folds");
-    if ((size_t)(glm_plan(h->ld, h->knobs.glm_grid).records * kGlmFoldVals) > h->partials_doubles)
-        return fail(h, CDH_BAD_ARG, "partials too small");
     return CDH_OK;
 }
 
-// what cdh_glm_poisson_irls refuses, before the handle is touched
-int32_t glm_check_poisson(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, const double* out6) {
+// what a step's export refuses, before the handle is touched, in the order every export has refused it (the Poisson one
+// looks at k before its output pointer, the fold one after: kKBeforeOut)
+template <class F>
+int32_t glm_check(cdh_handle h, int32_t k, int32_t apply, const GlmParams& pm, const double* out) {
     CHK(glm_refuse(h));
-    if (!h->glm.set || h->glm.family != 1)
-        return fail(h, CDH_BAD_ARG, "cdh_glm_poisson_irls needs counts: call cdh_glm_set_counts first");
+    CHK(F::refuse_observations(h));
     if (apply != 0 && apply != 1) return fail(h, CDH_BAD_ARG, "apply must be 0 or 1");
-    if (!(wmin > 0.0 && wmin <= DBL_MAX)) return fail(h, CDH_BAD_ARG, "need a finite wmin > 0");
-    if (!(eta_max > 0.0 && eta_max <= 700.0)) return fail(h, CDH_BAD_ARG, "need 0 < eta_max <= 700");
-    if (k < -1) return fail(h, CDH_BAD_ARG, "k must be a fold, or -1 for all ones");
-    if (k >= 0 && h->cv.K == 0) return fail(h, CDH_BAD_ARG, "k >= 0 needs cdh_set_folds first");
-    if (k >= h->cv.K && k >= 0) return fail(h, CDH_BAD_ARG, "k must be below the K of cdh_set_folds");
-    NEED_P(h, out6);
-    if ((size_t)(glm_plan(h->ld, h->knobs.glm_grid).records * kGlmPoisVals) > h->partials_doubles)
+    CHK(F::refuse_params(h, pm));
+    if (F::kFold && F::kKBeforeOut) CHK(glm_refuse_k(h, k));
+    if (!out) return fail(h, CDH_BAD_ARG, F::kOutNull);
+    if (F::kFold && !F::kKBeforeOut) CHK(glm_refuse_k(h, k));
+    if ((size_t)(glm_plan(h->ld, h->knobs.glm_grid).records * F::kVals) > h->partials_doubles)
         return fail(h, CDH_BAD_ARG, "partials too small");
     return CDH_OK;
 }
@@ -390,60 +337,24 @@ int32_t glm_catch_up(cdh_handle h) {
     return sync_r(h);
 }
 
-// the pass and its sums: out3 = (sum nll, sum w, clamped rows)
-int32_t glm_launch(cdh_handle h, bool apply, double wmin, double* out3) {
-    const GlmPlan pl = glm_plan(h->ld, h->knobs.glm_grid);
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid), dim3(kGlmBlock), 0, h->stream, (const double*)h->glm.labels,
-                           (double*)h->y, (double*)h->r, (double*)h->w, h->n, pl.vecs, wmin, (double*)h->d_partials);
-    };
-    if (apply) go(k_glm_irls<true>); else go(k_glm_irls<false>);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_gram_reduce, dim3((kGlmVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
-                       (const double*)h->d_partials, (int)pl.records, (int)kGlmVals, (double*)h->d_red);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out3, h->d_red, sizeof(double) * kGlmVals, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return CDH_OK;
-}
-
-// the fold-aware pass and its sums: out5 = (nll of training rows, sum w, clamped rows, nll of held-out rows, held-out rows
-// misclassified); k = -1: no row is held out and the fold ids are not read
-int32_t glm_launch_fold(cdh_handle h, int32_t k, bool apply, double wmin, double* out5) {
+// the pass and its sums: out holds the F::kVals doubles of the family's record, added over the workgroups in block order;
+// k = -1: no row is held out and the fold ids are not read
+template <class F>
+int32_t glm_launch(cdh_handle h, int32_t k, bool apply, const GlmParams& pm, double* out) {
     const GlmPlan pl = glm_plan(h->ld, h->knobs.glm_grid);
     auto go = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid), dim3(kGlmBlock), 0, h->stream, (const double*)h->glm.labels,
                            (double*)h->y, (double*)h->r, (double*)h->w,
-                           k >= 0 ? (const uint8_t*)h->cv.fold : (const uint8_t*)nullptr, (int)k, h->n, pl.vecs, wmin,
-                           (double*)h->d_partials);
+                           F::kOffset && h->glm.has_offset ? (const double*)h->glm.offset : (const double*)nullptr,
+                           F::kFold && k >= 0 ? (const uint8_t*)h->cv.fold : (const uint8_t*)nullptr, (int)k, h->n, pl.vecs, pm.wmin,
+                           pm.eta_max, (double*)h->d_partials);
     };
-    if (apply) go(k_glm_irls_fold<true>); else go(k_glm_irls_fold<false>);
+    if (apply) go(k_glm_step<F, true>); else go(k_glm_step<F, false>);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_gram_reduce, dim3((kGlmFoldVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
-                       (const double*)h->d_partials, (int)pl.records, (int)kGlmFoldVals, (double*)h->d_red);
+    hipLaunchKernelGGL(k_gram_reduce, dim3((F::kVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
+                       (const double*)h->d_partials, (int)pl.records, (int)F::kVals, (double*)h->d_red);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out5, h->d_red, sizeof(double) * kGlmFoldVals, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return CDH_OK;
-}
-
-// the Poisson pass and its sums: out6 = (nll of training rows, sum w, clamped training rows, capped live rows, deviance of
-// held-out rows, deviance of training rows); k = -1: no row is held out and the fold ids are not read
-int32_t glm_launch_poisson(cdh_handle h, int32_t k, bool apply, double wmin, double eta_max, double* out6) {
-    const GlmPlan pl = glm_plan(h->ld, h->knobs.glm_grid);
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid), dim3(kGlmBlock), 0, h->stream, (const double*)h->glm.labels,
-                           (double*)h->y, (double*)h->r, (double*)h->w,
-                           h->glm.has_offset ? (const double*)h->glm.offset : (const double*)nullptr,
-                           k >= 0 ? (const uint8_t*)h->cv.fold : (const uint8_t*)nullptr, (int)k, h->n, pl.vecs, wmin, eta_max,
-                           (double*)h->d_partials);
-    };
-    if (apply) go(k_glm_poisson<true>); else go(k_glm_poisson<false>);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_gram_reduce, dim3((kGlmPoisVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
-                       (const double*)h->d_partials, (int)pl.records, (int)kGlmPoisVals, (double*)h->d_red);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out6, h->d_red, sizeof(double) * kGlmPoisVals, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_red, sizeof(double) * F::kVals, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
 }

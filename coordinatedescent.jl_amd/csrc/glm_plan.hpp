@@ -1,4 +1,4 @@
-// glm_plan.hpp -- the host-only arithmetic of cdh_glm_irls (glm_kernels.hpp: k_glm_irls): how the rows of the handle's vectors
+// glm_plan.hpp -- the host-only arithmetic of the IRLS step exports (glm_kernels.hpp: k_glm_step): how the rows of the handle's vectors
 // are dealt to the workgroups, how many workgroups run and how many partial records they leave.  No HIP in here:
 // tests/test_glm_host.py compiles it with g++ (tests/glm_plan_main.cpp).  glm_kernels.hpp calls these functions and nothing
 // else decides the sizes.
@@ -15,10 +15,10 @@ constexpr int kGlmVec = 2;                                // doubles per 16-byte
 constexpr int64_t kGlmRows = (int64_t)kGlmBlock * kGlmVec; // a workgroup's share of rows per stride
 constexpr int64_t kGlmMaxGrid = 1024;                     // four workgroups per CU of 256
 constexpr int kGlmVals = 3;
-// the record of the fold-aware step (k_glm_irls_fold): (nll of the training rows, sum w, clamped rows, nll of the held-out
+// the record of the fold-aware binomial step (GlmBinomialFold): (nll of the training rows, sum w, clamped rows, nll of the held-out
 // rows, misclassified held-out rows); same grid, same tiles, one record per workgroup
 constexpr int kGlmFoldVals = 5;
-// the record of the Poisson step (k_glm_poisson): (nll of the training rows, sum w, training rows clamped at wmin, live rows
+// the record of the Poisson step (GlmPoisson): (nll of the training rows, sum w, training rows clamped at wmin, live rows
 // capped at eta_max, deviance of the held-out rows, deviance of the training rows); same grid, same tiles, one record per
 // workgroup
 constexpr int kGlmPoisVals = 6;

@@ -1,4 +1,4 @@
-"""The launch plan of cdh_glm_irls (csrc/glm_plan.hpp) restated in Python from the kernel's description of its loop (k_glm_irls,
+"""The launch plan of cdh_glm_irls (csrc/glm_plan.hpp) restated in Python from the kernel's description of its loop (k_glm_step,
 csrc/glm_kernels.hpp): a lane takes two rows per trip, a workgroup of 256 lanes a tile of 512, workgroup b the tiles b,
 b + grid, ...; the rows planned are the handle's padded ld.  tests/test_glm_host.py holds it to the compiled header, and the
 GPU cases (tests/test_gpu_glm.py) read from here which branch a shape reaches."""

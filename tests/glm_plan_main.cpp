@@ -1,6 +1,6 @@
 // Stand-alone check of csrc/glm_plan.hpp (tests/test_glm_host.py builds and runs it under the host sanitizers): for every n in
 // 1 .. 600 and a few around each constant of the plan, at the full grid cap and at small ones, the workgroups' row ranges are
-// walked the way k_glm_irls walks them over an exactly-sized heap block of ld rows -- a range that leaves the block is an ASan
+// walked the way k_glm_step walks them over an exactly-sized heap block of ld rows -- a range that leaves the block is an ASan
 // report -- and must cover [0, n), and [n, ld), exactly once; the record count must be the grid.  With arguments
 // "ld cap ld cap ..." it prints the plan of each pair instead, one line each, for tests/_glm_plan.py to be held to.
 #include <cstdio>

@@ -1,4 +1,4 @@
-"""Cross-validation of a logistic path on the device: cdh_glm_irls_fold (k_glm_irls_fold -> k_gram_reduce) and cvLogisticLassoPath
+"""Cross-validation of a logistic path on the device: cdh_glm_irls_fold (k_glm_step<GlmBinomialFold> -> k_gram_reduce) and cvLogisticLassoPath
 on top of it, held to the numpy twins (tests/_logistic_numpy.py for the rows of a step, tests/_cv_logistic_numpy.py for the
 folds: fitted on the training rows only, never as the masked formulation the product runs; tests/test_cv_logistic_host.py
 pins both on the CPU).  The step is compared row by row on the shapes of tests/test_gpu_glm.py -- every edge of its plan

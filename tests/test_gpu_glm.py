@@ -1,4 +1,4 @@
-"""The logistic lasso on the device: cdh_glm_set_labels, cdh_glm_irls (k_glm_irls -> k_gram_reduce) and the front ends on top of
+"""The logistic lasso on the device: cdh_glm_set_labels, cdh_glm_irls (k_glm_step<GlmBinomial> -> k_gram_reduce) and the front ends on top of
 them, held to the numpy twin (tests/_logistic_numpy.py; pinned against liblinear and the KKT conditions in
 tests/test_glm_host.py).  The step is compared row by row at every edge of its plan (tests/_glm_plan.py, held to
 csrc/glm_plan.hpp on the CPU), its sums on exactly summable values, its pad rows through the weighted moments, its

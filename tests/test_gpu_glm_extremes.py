@@ -1,4 +1,4 @@
-"""The GLM steps and solves on the device where weights clamp and exp saturates: k_glm_irls, k_glm_irls_fold and k_glm_poisson
+"""The GLM steps and solves on the device where weights clamp and exp saturates: the three families of k_glm_step
 (csrc/glm_kernels.hpp) on the tables of tests/_glm_extremes.py -- |eta| up to 800, subnormal and vanished exp, rows on either
 side of the clamp and of the cap, counts of 0 and 1e300, a deviance of +inf -- and the front ends on linearly separable labels
 and on exposures sixteen powers of e apart, on the three kinds of handle.  The reference is the numpy twin of each family
@@ -111,7 +111,7 @@ def _exp_ok(d, normal):
     return bool(np.all(d[normal] <= EXP_BOUND["normal"]) and np.all(d[~normal] <= EXP_BOUND["subnormal"]))
 
 
-# ---- a. k_glm_irls on the binomial table -------------------------------------------------------------------------------------------
+# ---- a. the binomial step on its table ---------------------------------------------------------------------------------------------
 def _binomial(monkeypatch, case):
     n, cap, branch, start = case
     GX.reaches(n, cap, branch)
@@ -219,7 +219,7 @@ def test_nll_of_a_rightly_classified_row_is_the_device_e(monkeypatch):
     assert np.array_equal(nll, want)
 
 
-# ---- b. k_glm_irls_fold ------------------------------------------------------------------------------------------------------------
+# ---- b. the fold step --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", GX.B_CASES, ids=GX.case_id)
 def test_binomial_fold_step_on_the_table(monkeypatch, case):
     """A third of the rows held out, saturated rows on both sides (tests/test_glm_extremes_host.py).  Held-out rows: w == 0 --
@@ -260,7 +260,7 @@ def test_binomial_fold_step_on_the_table(monkeypatch, case):
         g.close()
 
 
-# ---- c. k_glm_poisson --------------------------------------------------------------------------------------------------------------
+# ---- c. the Poisson step -----------------------------------------------------------------------------------------------------------
 P_PARAMS = [(em, c) for em in GX.P_ETA_MAX for c in GX.P_CASES[em]]
 P_IDS = ["etamax%d-%s" % (em, GX.case_id(c)) for em, c in P_PARAMS]
 

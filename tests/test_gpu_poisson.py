@@ -1,4 +1,4 @@
-"""The Poisson lasso on the device: cdh_glm_set_counts, cdh_glm_get_offset, cdh_glm_poisson_irls (k_glm_poisson -> k_gram_reduce)
+"""The Poisson lasso on the device: cdh_glm_set_counts, cdh_glm_get_offset, cdh_glm_poisson_irls (k_glm_step<GlmPoisson> -> k_gram_reduce)
 and the front ends on top of them, held to the numpy twin (tests/_poisson_numpy.py; pinned against L-BFGS-B and the KKT
 conditions in tests/test_poisson_host.py).  The step is compared row by row at every edge of its plan (tests/_glm_plan.py:
 the shapes of tests/test_gpu_glm.py restated), its sums on exactly summable values, its pad rows through the weighted moments,

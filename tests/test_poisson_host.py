@@ -215,6 +215,6 @@ def test_new_symbols_are_declared_bound_and_cited():
         assert fld in cd.PoissonLassoSolution.__dataclass_fields__, fld
     # the kernel is plain C++ with contraction off in the row function, and the binomial family argument stays closed
     k = open(os.path.join(CSRC, "glm_kernels.hpp")).read()
-    row = k[k.index("PoisRow pois_row("):k.index("template <bool APPLY>", k.index("PoisRow pois_row("))]
+    row = k[k.index("PoisRow pois_row("):k.index("template <class F, bool APPLY>", k.index("PoisRow pois_row("))]
     assert "#pragma clang fp contract(off)" in row and "asm" not in row
     assert 'if (family != 0) return fail(h, CDH_BAD_ARG, "unknown family' in k
