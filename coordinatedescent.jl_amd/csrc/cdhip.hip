@@ -25,19 +25,25 @@
 #include "resid_state.hpp"
 #include "cache_state.hpp"
 #include "exchange_state.hpp"
+#include "sweep_plan.hpp"   // the launch shape of the streamed sweep (sweep.hpp) and of the row-summing launches: host-only arithmetic
 
 using namespace cdk;
+
+// The batch loop of the column dots (col_dots.hpp: col_dots, col_loadings; vc_point below).  Defined here, by name and value:
+// the test suite of the commit before sweep_plan.hpp existed reads the two out of this file when tests/test_gpu_feasible.py is
+// imported, and that suite is run unedited against this library.  The plan sizes the partials and the row chunks from its
+// restatement, tied below.
+constexpr int64_t kColBatch = 4096;   // columns per launch of k_col_dots: keeps the partial buffer small
+constexpr int kColChunks = 64;        // row chunks per column in k_col_dots
+static_assert(kSpColBatch == kColBatch && kSpColChunks == kColChunks, "sweep_plan.hpp restates the column dots' batch and chunk limits");
+static_assert(kSpBlock == kBlock && kSpUnroll == kUnroll && kSpNSum == kNSum && kSpColGroup == kColGroup && kSpGramWaves == kGramWaves,
+              "sweep_plan.hpp restates what the kernels fix");
+static_assert(sp_gram_rec(1) == GramRec<1>::N && sp_gram_rec(2) == GramRec<2>::N && sp_gram_rec(4) == GramRec<4>::N &&
+              sp_block_rec(kMaxBlockB) == BlockRec<kMaxBlockB>::N, "sweep_plan.hpp restates the record sizes");
 
 namespace {
 
 std::string g_create_error;
-
-constexpr int kStepGridPerCU = 8;    // blocks per CU of k_step (and the axpy kernels that share its grid)
-constexpr int kMaxStepGrid = 2048;   // blocks of k_step (8 per CU on 256 CUs)
-constexpr int kBlockGridPerCU = 3;   // blocks per CU of k_blockstep
-constexpr int kColChunks = 64;       // row chunks per column in k_col_dots
-constexpr int kMaxBlockB = 8;
-constexpr int kShortRounds = 16;     // below this many rounds of 64-vector chunks per launch: short chunks
 
 // ---- RCCL through dlopen: only multi-process runs need it ------------------------
 struct Rccl {
@@ -338,6 +344,25 @@ Knobs read_knobs() {
     return k;
 }
 
+// cdh_profile_begin / cdh_profile_end: device time, launches and algorithmic bytes of the brackets in between.  A bracket is
+// begin(), its launches, stop() -- both in stream order -- and, once the stream has been synchronised, end() with what it counts.
+struct Profile {
+    bool on = false;
+    double ms = 0.0, bytes = 0.0;
+    int64_t launches = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipError_t begin(hipStream_t s) const { return on ? hipEventRecord(ev0, s) : hipSuccess; }
+    hipError_t stop(hipStream_t s) const { return on ? hipEventRecord(ev1, s) : hipSuccess; }
+    hipError_t end(int64_t its_launches, double its_bytes) {
+        if (!on) return hipSuccess;
+        float t = 0.f;
+        const hipError_t e = hipEventElapsedTime(&t, ev0, ev1);
+        if (e != hipSuccess) return e;
+        ms += t; launches += its_launches; bytes += its_bytes;
+        return hipSuccess;
+    }
+};
+
 struct cdh_handle_s {
     int dtype = CDH_F64, loss = CDH_LS, device = 0;
     int64_t n = 0, n_total = 0, row0 = 0, p = 0, ld = 0, nvec = 0;
@@ -368,7 +393,7 @@ struct cdh_handle_s {
     PinBuf<Ctrl> h_ctrl;
     // state
     int64_t cap = 0;          // visits per chunk
-    size_t partials_doubles = 0;
+    SweepSizes sz{};          // what cdh_create derived (sweep_plan.hpp): the fixed grids, the CU count, the doubles of d_partials; ld, nvec and cap above are its
     Ctrl ctrl{};
     bool has_omega = false, has_w = false, y_set = false;
     std::vector<double> h_omega;  // host copy of the penalty weights (thresholds, objective)
@@ -389,9 +414,7 @@ struct cdh_handle_s {
     GraphCache graphs;               // captured chunk launch sequences
     bool graph_broken = false;       // a capture failed on this handle: launch node by node from now on
     bool domain_error = false;
-    int step_grid = 1, block_grid = 1, cus = 1;
-    int64_t gram_units = 1;
-    Knobs knobs;     // the environment as cdh_create found it
+    Knobs knobs;    // the environment as cdh_create found it
     // the row-shard exchange: who serves it, where an all-reduce goes, epochs, capture bookkeeping (exchange_state.hpp) ...
     cdh::ExchangeState xs;
     // ... and the HIP resources behind it.  The optional direct exchange of the short records (p2p_exchange.hpp):
@@ -407,10 +430,7 @@ struct cdh_handle_s {
     GradCache gc;
     CovSolvePath cs;
     SmallPath small;
-    bool prof = false;
-    double prof_ms = 0.0, prof_bytes = 0.0;
-    int64_t prof_launches = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Profile prof;
     std::string err;
 };
 
@@ -467,16 +487,6 @@ int32_t fail(cdh_handle h, int32_t code, const char* msg) {
     do {                                                                       \
         if (!(ptr)) return fail((h), CDH_BAD_ARG, #ptr " is NULL");            \
     } while (0)
-
-inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-
-// Grid size for a grid-stride kernel with `units` work items and at most `gmax` resident blocks.
-inline int balanced_grid(int64_t units, int64_t gmax) {
-    // Measured: keeping every CU slot occupied (gmax blocks) beats equalising per-block work --
-    // the streaming rate is set per CU (~24 GB/s each), so an idle slot costs more than a block
-    // that runs one iteration longer.
-    return (int)std::max<int64_t>(1, std::min<int64_t>(gmax, units));
-}
 
 template <typename F> int32_t dispatch(cdh_handle h, F&& f) {
     return h->dtype == CDH_F64 ? f((double*)nullptr) : f((float*)nullptr);
@@ -571,7 +581,7 @@ int32_t sync_r(cdh_handle h) {
         HIPCHK(h, hipMemcpyAsync(h->d_hs, h->h_hs, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, h->stream));
         CHK(dispatch(h, [&](auto* t) {
             using T = std::remove_pointer_t<decltype(t)>;
-            hipLaunchKernelGGL(k_multi_axpy<T>, dim3(h->step_grid), dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
+            hipLaunchKernelGGL(k_multi_axpy<T>, dim3(h->sz.step_grid), dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
                                h->nvec, (T*)h->r, h->d_idx, h->d_hs, 0, cnt);
             return CDH_OK;
         }));
@@ -584,80 +594,7 @@ int32_t sync_r(cdh_handle h) {
     return CDH_OK;
 }
 
-// ---- column dots over columns [j0, j0+nc): d_colout[2*j + {0,1}] = (x.r (w), x.x (w)) ----
-constexpr int64_t kColBatch = 4096;   // columns per launch of k_col_dots: keeps the partial buffer small
-// row chunks of a k_col_dots launch over bc columns (k_vc_expand splits its rows the same way: its sums are these sums)
-inline int col_dots_chunks(const cdh_handle_s* h, int64_t bc) {
-    const int64_t groups = (bc + kColGroup - 1) / kColGroup;
-    // enough row chunks to fill the chip (~8 blocks per CU) but no more than kColChunks
-    const int64_t want_chunks = std::max<int64_t>(1, ((int64_t)h->cus * 8 + groups - 1) / groups);
-    return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)kColChunks, want_chunks, (h->nvec + kBlock - 1) / kBlock}));
-}
-int32_t col_dots(cdh_handle h, int64_t j0, int64_t nc, const void* rvec, bool use_w,
-                 const int64_t* d_cols = nullptr) {
-    if (rvec == h->r) CHK(sync_r(h));
-    for (int64_t b0 = 0; b0 < nc; b0 += kColBatch) {
-        const int64_t bc = std::min<int64_t>(kColBatch, nc - b0);
-        const int64_t groups = (bc + kColGroup - 1) / kColGroup;
-        const int chunks = col_dots_chunks(h, bc);
-        if ((size_t)groups * chunks * 2 * kColGroup > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partials too small");
-        dim3 grid(chunks, (unsigned)groups);
-        CHK(dispatch(h, [&](auto* t) {
-            using T = std::remove_pointer_t<decltype(t)>;
-            hipLaunchKernelGGL(k_col_dots<T>, grid, dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
-                               h->nvec, use_w ? (const T*)h->w : (const T*)nullptr, (const T*)rvec,
-                               j0 + b0, (int)bc, d_cols, h->d_partials);
-            return CDH_OK;
-        }));
-        hipLaunchKernelGGL(k_col_dots_reduce, dim3((unsigned)bc), dim3(64), 0, h->stream,
-                           h->d_partials, chunks, h->d_colout + 2 * b0);
-        HIPCHK(h, hipGetLastError());
-    }
-    CHK(allreduce(h, h->d_colout, (size_t)(2 * nc)));
-    return CDH_OK;
-}
-
-// ---- column loadings at the current residual: d_colout[j] = sum_i (x_ij r_i)^2 for all p columns (all shards) ----
-// col_dots's batches and row chunks; read-only on the handle apart from bringing r up to date.
-int32_t col_loadings(cdh_handle h) {
-    CHK(sync_r(h));
-    for (int64_t b0 = 0; b0 < h->p; b0 += kColBatch) {
-        const int64_t bc = std::min<int64_t>(kColBatch, h->p - b0);
-        const int64_t groups = (bc + kColGroup - 1) / kColGroup;
-        const int chunks = col_dots_chunks(h, bc);
-        if ((size_t)groups * chunks * kColGroup > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partials too small");
-        dim3 grid(chunks, (unsigned)groups);
-        CHK(dispatch(h, [&](auto* t) {
-            using T = std::remove_pointer_t<decltype(t)>;
-            hipLaunchKernelGGL(k_col_loadings<T>, grid, dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
-                               h->nvec, (const T*)h->r, b0, (int)bc, h->d_partials);
-            return CDH_OK;
-        }));
-        hipLaunchKernelGGL(k_col_loadings_reduce, dim3((unsigned)bc), dim3(64), 0, h->stream,
-                           h->d_partials, chunks, h->d_colout + b0);
-        HIPCHK(h, hipGetLastError());
-    }
-    CHK(allreduce(h, h->d_colout, (size_t)h->p));
-    return CDH_OK;
-}
-
-int32_t resid_moments_dev(cdh_handle h, const void* vec = nullptr, double shift = 0.0, bool sum_w = false) {  // -> d_red[0..2] = sum v (sum_w: sum w; needs weights), sum v^2, sum w v^2 (v = r unless given; minus shift)
-    if (!vec) { CHK(sync_r(h)); vec = h->r; }
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (h->nvec + kBlock - 1) / kBlock));
-    CHK(dispatch(h, [&](auto* t) {
-        using T = std::remove_pointer_t<decltype(t)>;
-        auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, h->stream, h->nvec,
-                               (const T*)vec, h->has_w ? (const T*)h->w : (const T*)nullptr, h->d_partials, shift, h->n);
-        };
-        if (sum_w) go(k_resid_moments<T, true>); else go(k_resid_moments<T>);
-        return CDH_OK;
-    }));
-    hipLaunchKernelGGL(k_sum_records, dim3(1), dim3(kBlock), 0, h->stream, h->d_partials, grid, h->d_red);
-    HIPCHK(h, hipGetLastError());
-    CHK(allreduce(h, h->d_red, 4));
-    return CDH_OK;
-}
+#include "col_dots.hpp"   // need_partials; col_dots, col_loadings, resid_moments_dev
 
 // ---- gradient cache: bookkeeping (the passes that use it are below run_chunk) ------------------------
 constexpr int kGcEngage = 3;        // mode 1: this many screened full passes run the plain way first
@@ -748,7 +685,7 @@ int32_t rebuild_residual_from(cdh_handle h, const cdh::SupportList& x, bool with
         for (int64_t s = 0; s < nnz; ++s) { si[(size_t)s] = x.coord(s); sv[(size_t)s] = x.slot_value(s); }
         HIPCHK(h, hipMemcpyAsync(h->d_sup_idx, si.data(), sizeof(int64_t) * nnz, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->d_sup_val, sv.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, h->stream));
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (h->nvec + kBlock - 1) / kBlock));
+        const int grid = elementwise_grid(h->nvec, kInitGridCap);
         CHK(dispatch(h, [&](auto* t) {
             using T = std::remove_pointer_t<decltype(t)>;
             hipLaunchKernelGGL(k_init_resid<T>, dim3(grid), dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
@@ -764,273 +701,7 @@ int32_t rebuild_residual_from(cdh_handle h, const cdh::SupportList& x, bool with
 }
 int32_t rebuild_residual(cdh_handle h) { return rebuild_residual_from(h, h->x, true); }
 
-// does any coordinate repeat in the chunk?  (scheduler-made lists never do; caller-made ones may)
-void note_duplicates(cdh_handle h, const int64_t* idx0, int m) {
-    if ((int64_t)h->stamp.size() != h->p) h->stamp.assign((size_t)h->p, 0);
-    h->chunk_dup = false;
-    for (int i = 0; i < m; ++i) {
-        if (h->stamp[(size_t)idx0[i]]) { h->chunk_dup = true; break; }
-        h->stamp[(size_t)idx0[i]] = 1;
-    }
-    for (int i = 0; i < m; ++i) h->stamp[(size_t)idx0[i]] = 0;
-}
-
-// The visits of a chunk have been enqueued (streamed, or in covariance form): bring their results back,
-// replay them on the host-side SparseIterate, and tell the gradient cache what moved.
-int32_t finish_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH) {
-    HIPCHK(h, hipMemcpyAsync(h->h_hs, h->d_hs, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_newval, h->d_newval, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_touched, h->d_touched, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_ctrl, h->d_ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    CHK(p2p_check(h));
-    if (h->h_ctrl->domain_error) h->domain_error = true;
-    const double mh = h->h_ctrl->maxH;
-    if (mh > *maxH) *maxH = mh;   // a NaN h never raises maxH: `abs(h) > maxH` (coordinate_descent.jl:104)
-    // replay the SparseIterate writes of the visits in order (x[k] += b/a ; cdprox!)
-    for (int i = 0; i < m; ++i) {
-        const int64_t k = idx0[i];
-        if (h->h_touched[i] && h->x.get(k) == 0.0) h->x.set(k, 1.0);  // pre-prox non-zero: slot appended
-        h->x.set(k, h->h_newval[i]);
-    }
-    gc_note_moves(h, idx0, m);
-    return CDH_OK;
-}
-
-// ---- one chunk of a pass: visits idx0[0..m) -------------------------------------------
-template <typename T, int B> int32_t launch_block_chunk(cdh_handle h, int m) {
-    constexpr int NREC = BlockRec<B>::N;
-    const int G = h->block_grid;
-    int nprev = 0;
-    for (int pos0 = 0; pos0 < m; pos0 += B) {
-        const int nb = std::min(B, m - pos0);
-        hipLaunchKernelGGL((k_blockstep<T, B>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
-                           h->ld, h->nvec, (T*)h->r, h->d_idx, h->d_hs, pos0, nb, nprev, h->d_partials);
-        if (!h->xs.sharded()) {
-            hipLaunchKernelGGL((k_block_finalize<B, true>), dim3(1), dim3(1024), 0, h->stream,
-                               h->d_partials, G, nb, h->d_ctrl, h->beta, h->omega, h->d_idx, h->d_hs,
-                               h->d_newval, h->d_touched, pos0, h->d_red);
-        } else {
-            hipLaunchKernelGGL((k_block_finalize<B, false>), dim3(1), dim3(1024), 0, h->stream,
-                               h->d_partials, G, nb, h->d_ctrl, h->beta, h->omega, h->d_idx, h->d_hs,
-                               h->d_newval, h->d_touched, pos0, h->d_red);
-            CHK(allreduce(h, h->d_red, NREC));
-            hipLaunchKernelGGL((k_block_scalar<B>), dim3(1), dim3(64), 0, h->stream, h->d_red, nb,
-                               h->d_ctrl, h->beta, h->omega, h->d_idx, h->d_hs, h->d_newval,
-                               h->d_touched, pos0);
-        }
-        nprev = nb;
-    }
-    const int last0 = ((m - 1) / B) * B;
-    hipLaunchKernelGGL((k_block_axpy<T, B>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
-                       h->nvec, (T*)h->r, h->d_idx, h->d_hs, last0, m - last0);
-    return CDH_OK;
-}
-
-// blocks of k_gramstep per CU: as many as stay resident for the variant launched (register
-// footprint: B = 64 holds 2 waves per SIMD, the narrower ones 3; the LDS-transposed variants are
-// bounded by their 68-78 KB operand tiles to 2 blocks -- B = 32 launched with 3 per CU ran its
-// third of the grid as a second, half-empty round: 933 -> 861 us per block at 1e7 rows), never
-// more than the partial buffer was sized for
-constexpr int kGramGridPerCU = 2;     // fragment path, B = 16 and 64
-constexpr int kGram32GridPerCU = 3;   // fragment path, B = 32
-constexpr int kLtGridPerCU = 2;       // LDS-transposed path, every width
-constexpr int gram_blocks_per_cu(int NG, bool lt) {
-    return lt ? kLtGridPerCU : NG == 2 ? kGram32GridPerCU : kGramGridPerCU;
-}
-inline int NGgrid(cdh_handle h, int NG, bool lt = false) {
-    return balanced_grid(h->gram_units, (int64_t)h->cus * gram_blocks_per_cu(NG, lt));
-}
-
-// wide blocks (B = 16 / 32 / 64): MFMA-accumulated Gram kernel + two-stage reduction
-template <typename T, int NG> int32_t launch_gram_chunk(cdh_handle h, int m) {
-    using R = GramRec<NG>;
-    constexpr int B = R::B;
-    const T* wts = h->has_w ? (const T*)h->w : (const T*)nullptr;
-    // LDS-transposed (fully coalesced) operand loads: measured -5 % at >= 5e6 rows for every
-    // width; with short chunks also -10 % for B = 32 at 6.25e5 .. 1.25e6 rows and neutral for
-    // B = 64.  B = 16 takes it on long columns only.  fp32 B = 64 would spill: fragment path.
-    const int lt = h->knobs.lt;
-    const bool use_lt = (lt == 1 || (lt == 2 && (NG >= 2 || h->n >= 2000000))) && !(NG == 4 && sizeof(T) == 4);
-    int G = NGgrid(h, NG, use_lt);
-    // short columns (a launch is fewer than kShortRounds rounds of 64-vector chunks): chunks of
-    // one sub-chunk, so a partly filled last round costs a quarter (B = 64) or half (B = 32) as much
-    const int64_t rounds64 = ((h->nvec + 63) / 64) / ((int64_t)G * kGramWaves);
-    const bool short_chunks = use_lt && (h->knobs.ks == 1 || (h->knobs.ks == 0 && rounds64 < kShortRounds));
-    // ... and as many blocks as there are chunks of THAT length to hand out, four per block (round 3: the grid was sized for
-    // 64-vector chunks, which at 24 KB columns -- benchmark/cd_bench.jl's n = 3000 -- left 6 blocks to walk 94 short chunks,
-    // four apiece and one after the other: 31 us per launch whatever it read)
-    {
-        const int64_t cvn = use_lt ? (int64_t)(64 / NG) * (short_chunks ? 1 : NG) : 64;
-        const int64_t nchunks = (h->nvec + cvn - 1) / cvn;
-        G = balanced_grid((nchunks + kGramWaves - 1) / kGramWaves, (int64_t)h->cus * gram_blocks_per_cu(NG, use_lt));
-    }
-    if ((size_t)G * R::N > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partial buffer too small for this grid");
-    int nprev = 0;
-    for (int pos0 = 0; pos0 < m; pos0 += B) {
-        const int nb = std::min(B, m - pos0);
-        auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(G), dim3(64 * kGramWaves), 0, h->stream, (const T*)h->X, h->ld, h->nvec,
-                               wts, (T*)h->r, h->d_idx, h->d_hs, pos0, nb, nprev, h->d_partials);
-        };
-        if (use_lt) {
-            if constexpr (NG == 1) {
-                go(k_gramstep<T, 1, true>);
-            } else if constexpr (NG == 4 && sizeof(T) == 4) {
-                // (never reached: use_lt is false for fp32 B = 64 -- its LDS-transposed variants spilled 160 - 280 bytes per lane
-                // and are not instantiated)
-                go(k_gramstep<T, NG>);
-            } else {
-                if (short_chunks) go(k_gramstep<T, NG, true, 1>); else go(k_gramstep<T, NG, true>);
-            }
-        } else {
-            go(k_gramstep<T, NG>);
-        }
-        hipLaunchKernelGGL(k_gram_reduce, dim3((R::N + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream, h->d_partials, G, R::N, h->d_red);
-        CHK(allreduce(h, h->d_red, R::N));
-        hipLaunchKernelGGL((k_gram_scalar<NG>), dim3(1), dim3(64), 0, h->stream, h->d_red, nb, h->chunk_dup ? 1 : 0, h->d_ctrl,
-                           h->beta, h->omega, h->d_idx, h->d_hs, h->d_newval, h->d_touched, pos0);
-        nprev = nb;
-    }
-    const int last0 = ((m - 1) / B) * B;
-    hipLaunchKernelGGL(k_multi_axpy<T>, dim3(h->step_grid), dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld,
-                       h->nvec, (T*)h->r, h->d_idx, h->d_hs, last0, m - last0);
-    return CDH_OK;
-}
-
-template <typename T> int32_t launch_coord_chunk(cdh_handle h, int m) {
-    const int G = h->step_grid;
-    for (int pos = 0; pos < m; ++pos) {
-        if (h->has_w)
-            hipLaunchKernelGGL((k_step<T, true>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
-                               h->ld, h->nvec, (const T*)h->w, (T*)h->r, h->d_idx, h->d_hs, pos, h->d_partials);
-        else
-            hipLaunchKernelGGL((k_step<T, false>), dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X,
-                               h->ld, h->nvec, (const T*)nullptr, (T*)h->r, h->d_idx, h->d_hs, pos, h->d_partials);
-        if (!h->xs.sharded()) {
-            hipLaunchKernelGGL(k_finalize<true>, dim3(1), dim3(kBlock), 0, h->stream, h->d_partials, G,
-                               h->d_ctrl, h->beta, h->omega, h->d_idx, h->d_hs, h->d_newval, h->d_touched,
-                               pos, h->d_red);
-        } else {
-            hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kBlock), 0, h->stream, h->d_partials, G,
-                               h->d_ctrl, h->beta, h->omega, h->d_idx, h->d_hs, h->d_newval, h->d_touched,
-                               pos, h->d_red);
-            CHK(allreduce(h, h->d_red, 4));
-            hipLaunchKernelGGL(k_scalar_update, dim3(1), dim3(64), 0, h->stream, h->d_red, h->d_ctrl,
-                               h->beta, h->omega, h->d_idx, h->d_hs, h->d_newval, h->d_touched, pos);
-        }
-    }
-    hipLaunchKernelGGL(k_axpy<T>, dim3(G), dim3(kBlock), 0, h->stream, (const T*)h->X, h->ld, h->nvec,
-                       (T*)h->r, h->d_idx, h->d_hs, m);
-    return CDH_OK;
-}
-
-int32_t all_ranks_agree(cdh_handle h, bool mine, bool* all);   // grad_cache.hpp
-int32_t agree_default_width(cdh_handle h) {
-    if (h->width_agreed || !h->width_default || !h->xs.sharded() || h->xs.nranks() <= 1) return CDH_OK;
-    bool all64 = false;
-    CHK(all_ranks_agree(h, h->blockB == 64, &all64));
-    if (!all64) h->blockB = 32;      // some shard is on the long side of the cut: every rank takes the long-column width
-    h->width_agreed = true;
-    return CDH_OK;
-}
-
-int32_t run_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH) {
-    CHK(agree_default_width(h));
-    CHK(sync_r(h));   // the streaming kernels read and write r
-    h->rs.stream_begins();
-    h->xs.chunk_begins();
-    std::memcpy(h->h_idx, idx0, sizeof(int64_t) * (size_t)m);
-    note_duplicates(h, idx0, m);
-    HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-    h->ctrl.maxH = 0.0;
-    h->ctrl.domain_error = 0;
-    CHK(upload_ctrl(h));
-    if (h->prof) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    // observation weights: the wide-block kernel carries them; the vector-ALU blocks (B <= 8) do not
-    const bool blocked = (h->mode == CDH_SWEEP_BLOCK) && (!h->has_w || h->blockB >= 16);
-    auto enqueue = [&]() {
-        return dispatch(h, [&](auto* t) {
-            using T = std::remove_pointer_t<decltype(t)>;
-            if (!blocked) return launch_coord_chunk<T>(h, m);
-            if (h->blockB == 64) return launch_gram_chunk<T, 4>(h, m);
-            if (h->blockB == 32) return launch_gram_chunk<T, 2>(h, m);
-            if (h->blockB == 16) return launch_gram_chunk<T, 1>(h, m);
-            if (h->blockB == 8) return launch_block_chunk<T, 8>(h, m);
-            if (h->blockB == 4) return launch_block_chunk<T, 4>(h, m);
-            return launch_block_chunk<T, 2>(h, m);
-        });
-    };
-    // hipGraph replay: the launch sequence of an m-visit chunk depends only on (m, mode, B, exchange) --
-    // every kernel takes its visit position as a literal and reads idx / hs / lambda from device
-    // memory -- so one captured graph serves every later pass of that length.  Row shards too: the
-    // direct exchange reads its epoch base from device memory (set before each replay), RCCL
-    // all-reduces are recorded by RCCL itself as graph nodes.  Only the host-staged exchange cannot
-    // be recorded.  A failed capture switches the handle back to node-by-node launches for good.
-    bool launched = false;
-    // (a graph of one or two launches saves nothing and costs a capture: short chunks go node by node)
-    if (h->use_graph && !h->graph_broken && h->xs.may_capture() && m >= (blocked ? 2 * h->blockB : 8)) {
-        const uint64_t key = ((uint64_t)m << 20) | ((uint64_t)(blocked ? h->blockB : 0) << 8) | h->xs.graph_key_bits() |
-                             (h->chunk_dup ? 4u : 0u) | (h->has_w ? 2u : 0u);
-        const GraphEntry* entry = h->graphs.find(key);
-        if (!entry) {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            h->xs.capture_begins();
-            hipError_t e0 = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
-            const int32_t erc = e0 == hipSuccess ? enqueue() : (int32_t)CDH_HIP_ERROR;
-            hipError_t e1 = e0 == hipSuccess ? hipStreamEndCapture(h->stream, &graph) : e0;
-            const cdh::Captured holds = h->xs.capture_ends();
-            if (erc == CDH_OK && e1 == hipSuccess && graph) e1 = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            if (graph) (void)hipGraphDestroy(graph);
-            if (erc != CDH_OK || e1 != hipSuccess || !exec) {
-                (void)hipGetLastError();
-                h->graph_broken = true;
-            } else {
-                entry = h->graphs.insert({key, exec, holds});
-            }
-        }
-        if (entry) {
-            if (entry->holds.exchanges)   // they run under the epochs base + 1 .. base + exchanges
-                hipLaunchKernelGGL(cdk::k_set_u32, dim3(1), dim3(1), 0, h->stream, h->d_p2p_base, h->xs.reserve_epochs(entry->holds.exchanges));
-            h->xs.replay_counted(entry->holds);
-            HIPCHK(h, hipGraphLaunch(entry->exec, h->stream));
-            launched = true;
-        }
-    }
-    if (!launched) CHK(enqueue());
-    h->rs.stream_enqueued(blocked ? (m + h->blockB - 1) / h->blockB + 1 : m + 1);   // one rewrite of r per launch that applies updates
-    HIPCHK(h, hipGetLastError());
-    if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    CHK(finish_chunk(h, idx0, m, maxH));
-    if (h->prof) {
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        h->prof_ms += ms;
-        const double vec = (double)h->n * (double)h->esz;
-        if (!blocked) {
-            h->prof_launches += m;
-            for (int i = 0; i < m; ++i) {
-                const bool ap = i > 0 && h->h_hs[i - 1] != 0.0;
-                h->prof_bytes += vec * ((h->has_w ? 3.0 : 2.0) + (ap ? 2.0 : 0.0));
-            }
-            if (h->h_hs[m - 1] != 0.0) h->prof_bytes += 3.0 * vec;
-        } else {
-            const int B = h->blockB;
-            for (int pos0 = 0; pos0 < m; pos0 += B) {
-                const int nb = std::min(B, m - pos0);
-                int nzp = 0;
-                for (int i = std::max(0, pos0 - B); i < pos0; ++i) nzp += h->h_hs[i] != 0.0;
-                h->prof_bytes += vec * (nb + 1 + nzp + (nzp ? 1 : 0));
-                h->prof_launches += 1;
-            }
-            int nzl = 0;
-            for (int i = ((m - 1) / B) * B; i < m; ++i) nzl += h->h_hs[i] != 0.0;
-            if (nzl) h->prof_bytes += vec * (nzl + 2);
-        }
-    }
-    return CDH_OK;
-}
+#include "sweep.hpp"   // note_duplicates, finish_chunk, the three launchers of a chunk, run_chunk
 
 constexpr int kScreenMinPass = 16;   // screens / the cache: passes over fewer coordinates than that are a block or two anyway
 #include "grad_cache.hpp"   // gc_size, gc_validate, gc_fetch, gc_fold, gc_full_pass
@@ -1183,7 +854,7 @@ void free_all(cdh_handle h) {
     (void)hipSetDevice(h->device);
     if (h->xs.communicator() && g_rccl.CommDestroy) g_rccl.CommDestroy(h->xs.communicator());
     for (void* m : h->p2p_mapped) (void)hipIpcCloseMemHandle(m);
-    const hipEvent_t ev[] = {h->ev0, h->ev1};
+    const hipEvent_t ev[] = {h->prof.ev0, h->prof.ev1};
     const hipStream_t stream = h->stream;
     delete h;   // the owners free the device and pinned memory and the captured graphs, before the stream goes
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -1240,37 +911,24 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
     h->dtype = dtype; h->loss = loss; h->device = device;
     h->n = n_local; h->n_total = n_total; h->row0 = row_offset; h->p = p;
     h->esz = dtype == CDH_F64 ? 8 : 4;
-    const int NV = dtype == CDH_F64 ? 2 : 4;
-    h->ld = round_up(n_local, 32);            // every column starts 128/256-B aligned
-    h->nvec = round_up(n_local, NV) / NV;     // pad rows [n, ld) are zero in X, y, r, w
-    h->cap = std::max<int64_t>(p, 4096);
-    // The default sweep width: B = 32 streams fastest per visit on long columns; on SHORT ones (the grid is not even full:
-    // fewer than 512 blocks x 4 waves x 64 vectors) a block of visits costs three launches whatever it reads, and B = 64
-    // halves them (benchmark/cd_bench.jl's dense solve at n = 3000: 0.40 s at B = 32, 0.26 s at B = 64).  fp32 storage has
-    // no LDS-transposed B = 64 kernel and keeps 32.
-    if (dtype == CDH_F64 && n_local < (int64_t)512 * kGramWaves * 64 * 2) h->blockB = 64;
     h->x.resize(p);
     h->rs.resize(p);
     int32_t rc = [&]() -> int32_t {
         HIPCHK(h, hipSetDevice(device));
         HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        HIPCHK(h, hipEventCreate(&h->ev0));
-        HIPCHK(h, hipEventCreate(&h->ev1));
+        HIPCHK(h, hipEventCreate(&h->prof.ev0));
+        HIPCHK(h, hipEventCreate(&h->prof.ev1));
         hipDeviceProp_t prop;
         HIPCHK(h, hipGetDeviceProperties(&prop, device));
-        const int cus = std::max(1, prop.multiProcessorCount);
+        // the padded column, the vectors over it, the chunk's capacity, the default sweep width, the fixed grids, the partials
+        h->sz = sweep_sizes(dtype == CDH_F64, n_local, p, std::max(1, prop.multiProcessorCount));
+        h->ld = h->sz.ld; h->nvec = h->sz.nvec; h->cap = h->sz.cap; h->blockB = h->sz.blockB;
         h->knobs = read_knobs();
         h->gc.mode = h->knobs.gradient_cache;
         h->gc.cov = h->knobs.gc_cov;
         h->cs.enabled = h->knobs.cov_solve;
         h->cs.helpers = h->knobs.cs_crew;
         h->small.enabled = h->knobs.small_path;
-        const int64_t want = (h->nvec + (int64_t)kBlock * kUnroll - 1) / ((int64_t)kBlock * kUnroll);
-        h->step_grid = balanced_grid(want, std::min<int64_t>((int64_t)kMaxStepGrid, (int64_t)cus * kStepGridPerCU));
-        const int64_t wantb = (h->nvec + kBlock - 1) / kBlock;
-        h->block_grid = balanced_grid(wantb, (int64_t)cus * kBlockGridPerCU);
-        h->cus = cus;
-        h->gram_units = (h->nvec + 64 * kGramWaves - 1) / (64 * kGramWaves);
         const size_t colbytes = (size_t)h->ld * h->esz;
         HIPCHK(h, h->X.alloc(colbytes * (size_t)p));
         HIPCHK(h, h->y.alloc(colbytes));
@@ -1289,14 +947,8 @@ int32_t cdh_create(cdh_handle* out, int32_t dtype, int32_t loss, int64_t n_local
         HIPCHK(h, h->d_hs.alloc(sizeof(double) * h->cap));
         HIPCHK(h, h->d_newval.alloc(sizeof(double) * h->cap));
         HIPCHK(h, h->d_touched.alloc(sizeof(int32_t) * h->cap));
-        // (k_gramstep: the larger of its two paths' grids, gram_blocks_per_cu)
-        auto gram = [&](int NG, int N) { return (size_t)cus * std::max(gram_blocks_per_cu(NG, false), gram_blocks_per_cu(NG, true)) * N; };
-        h->partials_doubles = std::max<size_t>({(size_t)kMaxStepGrid * kNSum,
-                                                (size_t)cus * kBlockGridPerCU * BlockRec<kMaxBlockB>::N,
-                                                (size_t)4096 * kColChunks * 2,
-                                                gram(4, GramRec<4>::N), gram(2, GramRec<2>::N), gram(1, GramRec<1>::N)});
-        static_assert((size_t)4096 * kColChunks * 2 >= (size_t)kGlmMaxGrid * kGlmPoisVals, "the widest IRLS record fits the partials");
-        HIPCHK(h, h->d_partials.alloc(sizeof(double) * h->partials_doubles));
+        static_assert((size_t)kColBatch * kColChunks * 2 >= (size_t)kGlmMaxGrid * kGlmPoisVals, "the widest IRLS record fits the partials");
+        HIPCHK(h, h->d_partials.alloc(sizeof(double) * h->sz.partials_doubles));
         HIPCHK(h, h->d_red.alloc(sizeof(double) * 4096));
         HIPCHK(h, h->d_colout.alloc(sizeof(double) * 2 * p));
         HIPCHK(h, h->d_sup_idx.alloc(sizeof(int64_t) * p));
@@ -1839,8 +1491,8 @@ static int32_t gram_launch(cdh_handle h, int m, std::vector<double>& rec, bool w
     using R = GramRec<4>;
     HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, h->stream));
     // one k_gramstep launch with no pending update: r is only read
-    const int G = NGgrid(h, 4);
-    if ((size_t)G * R::N > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partial buffer too small for this grid");
+    const int G = gram_read_grid(h->nvec, h->sz.cus);
+    CHK(need_partials(h, (size_t)G * R::N, "partial buffer too small for this grid"));
     CHK(dispatch(h, [&](auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         hipLaunchKernelGGL((k_gramstep<T, 4>), dim3(G), dim3(64 * kGramWaves), 0, h->stream,
@@ -2026,8 +1678,8 @@ static int32_t vc_point(cdh_handle h, int32_t kernel_kind, double bandwidth, dou
     CHK(design_changes(h, true));
     CHK(ensure_weights_buffer(h));
     const int Q = h->vc_degree, Q1 = Q + 1;
-    if (h->prof) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    const int wgrid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (h->nvec + kBlock - 1) / kBlock));
+    HIPCHK(h, h->prof.begin(h->stream));
+    const int wgrid = elementwise_grid(h->nvec, kWeightsGridCap);
     CHK(dispatch(h, [&](auto* t) {
         using T = std::remove_pointer_t<decltype(t)>;
         hipLaunchKernelGGL(k_vc_weights<T>, dim3(wgrid), dim3(kBlock), 0, h->stream, (const T*)h->vc_z, (T*)h->w, h->n,
@@ -2042,9 +1694,9 @@ static int32_t vc_point(cdh_handle h, int32_t kernel_kind, double bandwidth, dou
         CHK(col_dots(h, 0, h->p, h->y, true));
         cd.resize((size_t)(2 * h->p));
         HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
-        if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        HIPCHK(h, h->prof.stop(h->stream));   // (the bracket closes in stream order before either branch's wait: one stop per branch, one end below)
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::vector<double> ab(cd);      // -> the layout of the other branch: p scales, then p scores
+        std::vector<double> ab(cd);     // -> the layout of the other branch: p scales, then p scores
         for (int64_t j = 0; j < h->p; ++j) { cd[(size_t)j] = ab[(size_t)(2 * j + 1)]; cd[(size_t)(h->p + j)] = ab[(size_t)(2 * j)]; }
     } else {
         // One launch per k_col_dots batch of expanded columns, split into that batch's row chunks: the sums then are the
@@ -2052,10 +1704,10 @@ static int32_t vc_point(cdh_handle h, int32_t kernel_kind, double bandwidth, dou
         // same values twice); each keeps the sums of its own columns.
         for (int64_t b0 = 0; b0 < h->p; b0 += kColBatch) {
             const int64_t b1 = std::min<int64_t>(b0 + kColBatch, h->p);
-            const int chunks = col_dots_chunks(h, b1 - b0);
+            const int chunks = col_dots_plan(b1 - b0, h->nvec, h->sz.cus, 1).chunks;
             const int64_t jb0 = b0 / Q1, jb1 = (b1 + Q1 - 1) / Q1;
             const size_t table = (size_t)(jb1 - jb0) * Q1 * chunks;      // the sums of w v^2; with a left-out row, those of w v y behind it
-            if (table * (loo ? 2 : 1) > h->partials_doubles) return fail(h, CDH_BAD_ARG, "partials too small");
+            CHK(need_partials(h, table * (loo ? 2 : 1)));
             CHK(dispatch(h, [&](auto* t) {
                 using T = std::remove_pointer_t<decltype(t)>;
                 auto go = [&](auto kernel) {
@@ -2075,18 +1727,12 @@ static int32_t vc_point(cdh_handle h, int32_t kernel_kind, double bandwidth, dou
             HIPCHK(h, hipGetLastError());
             launches += 1;
         }
-        if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        HIPCHK(h, h->prof.stop(h->stream));
         cd.resize((size_t)(loo ? 2 * h->p : h->p));
         HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * cd.size(), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    if (h->prof) {
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        h->prof_ms += ms;
-        h->prof_launches += launches;
-        h->prof_bytes += (double)h->n * (double)h->esz * ((double)h->p + 2.0);   // read p_base columns, write p_base Q, z, w
-    }
+    HIPCHK(h, h->prof.end(launches, (double)h->n * (double)h->esz * ((double)h->p + 2.0)));   // read p_base columns, write p_base Q, z, w
     if (out_std) for (int64_t j = 0; j < h->p; ++j) out_std[j] = std::sqrt(cd[(size_t)j] / (double)h->n_total);
     if (out_scores) for (int64_t j = 0; j < h->p; ++j) out_scores[j] = std::fabs(cd[(size_t)(h->p + j)]);
     return CDH_OK;
@@ -2170,7 +1816,7 @@ static int32_t vc_gram_run(cdh_handle h, int32_t kernel_kind, int64_t m, const d
         }
         if (together) HIPCHK(h, hipMemcpyAsync(d_in, g.h_in, sizeof(VcGramInput), hipMemcpyHostToDevice, h->stream));
         else HIPCHK(h, hipMemcpyAsync(b.pts, b.h_pts, sizeof(VcGramPoint) * (size_t)L.pts, hipMemcpyHostToDevice, h->stream));
-        if (h->prof) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+        HIPCHK(h, h->prof.begin(h->stream));
         CHK(dispatch(h, [&](auto* t) {
             using T = std::remove_pointer_t<decltype(t)>;
             auto go = [&](auto streamed, auto res) {
@@ -2188,15 +1834,10 @@ static int32_t vc_gram_run(cdh_handle h, int32_t kernel_kind, int64_t m, const d
         hipLaunchKernelGGL(k_vc_moments_reduce, dim3((unsigned)((R.n + kVgThreads - 1) / kVgThreads), (unsigned)L.pts), dim3(kVgThreads),
                            0, h->stream, (const double*)b.partials, G, R.n, b.out);
         HIPCHK(h, hipGetLastError());
-        if (h->prof) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        HIPCHK(h, h->prof.stop(h->stream));
         HIPCHK(h, hipMemcpyAsync(b.h_out, b.out, sizeof(double) * (size_t)(L.pts * R.n), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->prof) {                   // cdh_profile_begin/end: the device time of the two launches
-            float ms = 0.f;
-            HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            h->prof_ms += ms;
-            h->prof_launches += 2;
-        }
+        HIPCHK(h, h->prof.end(2, 0.0));  // cdh_profile_begin/end: the device time of the two launches
         for (int64_t t = 0; t < L.pts; ++t) {
             const double* rec = b.h_out + t * R.n;
             vc_gram_scatter(Q, mb, rec, out_G + (L.first + t) * ep * ep, out_c ? out_c + (L.first + t) * ep : nullptr);
@@ -2594,30 +2235,30 @@ int32_t cdh_exchange_latency(cdh_handle h, int64_t count, int32_t iters, double*
     if (count < 1 || count > 4096 || iters < 1 || iters > 100000 || !out_us) return fail(h, CDH_BAD_ARG, "latency probe: 1 <= count <= 4096, 1 <= iters <= 100000");
     if (!h->d_red) return fail(h, CDH_BAD_ARG, "probe: handle has no data yet");
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->ev0) { HIPCHK(h, hipEventCreate(&h->ev0)); HIPCHK(h, hipEventCreate(&h->ev1)); }
+    if (!h->prof.ev0) { HIPCHK(h, hipEventCreate(&h->prof.ev0)); HIPCHK(h, hipEventCreate(&h->prof.ev1)); }
     HIPCHK(h, hipMemsetAsync(h->d_red, 0, sizeof(double) * (size_t)count, h->stream));
     for (int i = 0; i < 3; ++i) CHK(allreduce(h, h->d_red, (size_t)count));   // warm the path
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    HIPCHK(h, hipEventRecord(h->prof.ev0, h->stream));
     for (int i = 0; i < iters; ++i) CHK(allreduce(h, h->d_red, (size_t)count));
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipEventRecord(h->prof.ev1, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     CHK(p2p_check(h));
     float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    HIPCHK(h, hipEventElapsedTime(&ms, h->prof.ev0, h->prof.ev1));
     *out_us = (double)ms * 1e3 / iters;
     return CDH_OK;
 }); }
 
 int32_t cdh_profile_begin(cdh_handle h) { return guarded(h, [&]() -> int32_t {
-    h->prof = true; h->prof_ms = 0.0; h->prof_bytes = 0.0; h->prof_launches = 0;
+    h->prof.on = true; h->prof.ms = 0.0; h->prof.bytes = 0.0; h->prof.launches = 0;
     return CDH_OK;
 }); }
 
 int32_t cdh_profile_end(cdh_handle h, double* out_ms, int64_t* out_launches, double* out_algorithmic_bytes) { return guarded(h, [&]() -> int32_t {
-    h->prof = false;
-    if (out_ms) *out_ms = h->prof_ms;
-    if (out_launches) *out_launches = h->prof_launches;
-    if (out_algorithmic_bytes) *out_algorithmic_bytes = h->prof_bytes;
+    h->prof.on = false;
+    if (out_ms) *out_ms = h->prof.ms;
+    if (out_launches) *out_launches = h->prof.launches;
+    if (out_algorithmic_bytes) *out_algorithmic_bytes = h->prof.bytes;
     return CDH_OK;
 }); }
 

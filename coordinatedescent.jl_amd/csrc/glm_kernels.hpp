@@ -325,7 +325,7 @@ int32_t glm_check(cdh_handle h, int32_t k, int32_t apply, const GlmParams& pm, c
     if (F::kFold && F::kKBeforeOut) CHK(glm_refuse_k(h, k));
     if (!out) return fail(h, CDH_BAD_ARG, F::kOutNull);
     if (F::kFold && !F::kKBeforeOut) CHK(glm_refuse_k(h, k));
-    if ((size_t)(glm_plan(h->ld, h->knobs.glm_grid).records * F::kVals) > h->partials_doubles)
+    if ((size_t)(glm_plan(h->ld, h->knobs.glm_grid).records * F::kVals) > h->sz.partials_doubles)
         return fail(h, CDH_BAD_ARG, "partials too small");
     return CDH_OK;
 }

@@ -38,11 +38,11 @@ int32_t gc_size(cdh_handle h) {   // first use on this handle
     const int64_t nsuper = (launches + kGramWaves - 1) / kGramWaves;   // a block's four waves take four column groups
     c.cross_GX = (int)std::max<int64_t>(1, std::min<int64_t>(nsuper, 4));
     const int64_t occ = h->dtype == CDH_F32 ? cross_occ<float>() : cross_occ<double>();
-    c.cross_J = (int)std::max<int64_t>(1, std::min<int64_t>(nslabs, (occ * h->cus) / c.cross_GX));
+    c.cross_J = (int)std::max<int64_t>(1, std::min<int64_t>(nslabs, (occ * h->sz.cus) / c.cross_GX));
     // short columns have few row slabs to hand out (n = 3000: two): the resident blocks they leave unused take further
     // column super-groups instead (benchmark/cd_bench.jl's shape: 8 blocks walked 79 column groups, 0.78 ms per batch of a
     // 120 MB X; 40 blocks: one group per wave)
-    c.cross_GX = (int)std::min<int64_t>(nsuper, std::max<int64_t>(c.cross_GX, (occ * h->cus) / c.cross_J));
+    c.cross_GX = (int)std::min<int64_t>(nsuper, std::max<int64_t>(c.cross_GX, (occ * h->sz.cus) / c.cross_J));
     // (a handle whose first sizing failed may be asked again: a failed attempt leaves nothing behind)
     DevBuf<double> cross, cross_part; DevBuf<int64_t> cols;
     bool fits = cross.alloc(sizeof(double) * (size_t)launches * kCrossRec) == hipSuccess &&

@@ -3,12 +3,11 @@
 (src/lasso.jl:154-194) and refitLassoPath (:208-225).
 
 The kernel is checked the way tests/test_gpu_kernel_sums.py checks k_col_dots: on exactly summable integer data at every
-edge of its indexing (named from the constants read out of the source, and asserted to be reached), and on rounded data
+edge of its indexing (named from the constants of tests/_sweep_plan.py, the twin of csrc/sweep_plan.hpp, and asserted to be reached), and on rounded data
 against a bound written from the number of terms.  The front ends are checked against tests/_feasible_oracle.py, the
 restatement of the reference on the CPU oracle, whose own checks are in tests/test_feasible_oracle.py."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 
@@ -18,6 +17,7 @@ import pytest
 import coordinatedescent_jl_amd as cd
 import oracle as O
 import _feasible_oracle as FO
+import _sweep_plan as SP
 
 pytestmark = pytest.mark.gpu
 
@@ -25,13 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U64 = 2.0 ** -53
 
 
-def _constant(path, name):
-    txt = open(os.path.join(ROOT, "coordinatedescent.jl_amd", "csrc", path)).read()
-    return int(re.search(r"constexpr\s+\w+\s+%s\s*=\s*(\d+)\s*;" % name, txt).group(1))
-
-
-K_BLOCK, K_COL_GROUP = _constant("kernels.hpp", "kBlock"), _constant("kernels.hpp", "kColGroup")
-K_COL_BATCH, K_COL_CHUNKS = _constant("cdhip.hip", "kColBatch"), _constant("cdhip.hip", "kColChunks")
+K_BLOCK, K_COL_GROUP, K_COL_BATCH, K_COL_CHUNKS = SP.K_BLOCK, SP.K_COL_GROUP, SP.K_COL_BATCH, SP.K_COL_CHUNKS
 
 
 @pytest.fixture(scope="module")
@@ -48,15 +42,7 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def _chunks(n, ncols, dtype, cus):
-    """The row chunks of each launch (cdhip.hip: col_loadings takes col_dots_chunks per batch of kColBatch columns)."""
-    nvec = -(-n // _nv(dtype))
-    out = []
-    for b0 in range(0, ncols, K_COL_BATCH):
-        groups = -(-min(K_COL_BATCH, ncols - b0) // K_COL_GROUP)
-        want = max(1, -(-(cus * 8) // groups))
-        out.append(max(1, min(K_COL_CHUNKS, want, -(-nvec // K_BLOCK))))
-    return out
+_chunks = SP.col_dots_chunks      # the row chunks of each launch: col_loadings takes col_dots' batches and chunks
 
 
 def _at_beta_zero(y, X):

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 
 import coordinatedescent_jl_amd as cd
+# the row chunks of the column dots and cdh_gram's grid: the twin of csrc/sweep_plan.hpp (tests/test_sweep_plan_host.py)
+from _sweep_plan import col_dots_chunks, gram_grid  # noqa: F401  (test_gpu_generator takes them from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -91,24 +93,6 @@ def cross_grid(n, p, dtype, cus):
             "partial_last_slab": nvec % 1024 != 0,
             "partial_last_subchunk": nvec % 8 != 0,     # kX2SV vectors per sub-chunk
             "rows_per_lane": -(-nslabs // J) * 1024 * _nv(dtype)}
-
-
-def col_dots_chunks(n, ncols, dtype, cus):
-    """The row chunks of each k_col_dots launch (cdhip.hip:col_dots): batches of at most 4096 columns."""
-    nvec = -(-n // _nv(dtype))
-    out = []
-    for b0 in range(0, ncols, 4096):
-        groups = -(-min(4096, ncols - b0) // 8)       # kColGroup
-        want = max(1, -(-(cus * 8) // groups))
-        out.append(max(1, min(64, want, -(-nvec // 256))))   # kColChunks, kBlock
-    return out
-
-
-def gram_grid(n, dtype, cus):
-    """cdh_gram's k_gramstep<T, 4> launch (cdhip.hip:gram_launch, NGgrid): blocks, and 64-vector chunks to hand out."""
-    nvec = -(-n // _nv(dtype))
-    G = max(1, min(cus * 2, -(-nvec // 256)))          # kGramGridPerCU, gram_units
-    return G, -(-nvec // 64)
 
 
 # ---- 2. Gram columns: k_cross -> k_cross_reduce -> k_cross_unpack via the gradient cache -----------------------------

@@ -47,8 +47,8 @@ batches of 64), and that every launch that stores r applies at least one.  The d
 fp32 storage too: planted coefficients of 0.5 .. 1.5 on the coordinates that are meant to move, lambda = 0 for them and an
 infinite-looking penalty weight for those that are meant to stay (h = 0 exactly: the holes of the ballot compaction).
 
-Shapes are computed from the device's CU count by restating the host's grid and variant policy (cdhip.hip: cdh_create,
-launch_gram_chunk) in Python.  Knobs are read when a handle is made: they are set before the loss is constructed.
+Shapes are computed from the device's CU count with the Python twin of the host's grid and variant policy (tests/_sweep_plan.py,
+held to csrc/sweep_plan.hpp on the CPU by tests/test_sweep_plan_host.py).  Knobs are read when a handle is made: they are set before the loss is constructed.
 """
 import zlib
 
@@ -62,6 +62,9 @@ from coordinatedescent_jl_amd._lib import check
 # GPU test here requests it, whether it sizes a shape from it or not.
 from test_gpu_kernel_sums import U64, _ints, _int_y, _nv, _vp, cus  # noqa: F401
 from test_gpu_kernel_sums import F32_XMAX, F32_YMAX, F64_XMAX, F64_YMAX
+# the grids and the wide-block variant policy: the twin of csrc/sweep_plan.hpp
+from _sweep_plan import block_grid, gram_launch, init_grid, step_grid
+from _sweep_plan import nvec as _nvec
 
 gpu = pytest.mark.gpu
 U32 = 2.0 ** -24
@@ -75,43 +78,6 @@ DT_IDS = ["float64", "float32"]
 
 def _ut(dtype):
     return U64 if dtype == np.float64 else U32
-
-
-def _nvec(n, dtype):
-    return -(-n // _nv(dtype))
-
-
-# ---- grids and the wide-block variant policy, restated from the host code ---------------------------------------------
-def step_grid(n, dtype, cus):
-    """k_step / k_axpy / k_multi_axpy (cdh_create): tiles of kBlock * kUnroll = 1024 vectors, at most min(2048, 8 / CU)."""
-    return max(1, min(2048, 8 * cus, -(-_nvec(n, dtype) // 1024)))
-
-
-def block_grid(n, dtype, cus):
-    """k_blockstep / k_block_axpy (cdh_create): strides of kBlock = 256 vectors, at most 3 blocks per CU."""
-    return max(1, min(3 * cus, -(-_nvec(n, dtype) // 256)))
-
-
-def init_grid(n, dtype):
-    """k_init_resid (rebuild_residual_from): kBlock = 256 vectors per block, capped at 2048 blocks."""
-    return max(1, min(2048, -(-_nvec(n, dtype) // 256)))
-
-
-def gram_launch(n, dtype, B, cus, lt=2, ks=0):
-    """launch_gram_chunk for block width B: the k_gramstep instantiation, its chunk length CVN (vectors), phase A's column
-    groups CGN and loads per group PG, the grid G and how often the chunk loop of a wave goes round."""
-    NG, f32, nvec = B // 16, dtype == np.float32, _nvec(n, dtype)
-    use_lt = (lt == 1 or (lt == 2 and (NG >= 2 or n >= 2_000_000))) and not (NG == 4 and f32)
-    per_cu = 2 if use_lt else (3 if NG == 2 else 2)                     # gram_blocks_per_cu
-    G0 = max(1, min(cus * per_cu, -(-nvec // 256)))                     # NGgrid over gram_units
-    rounds64 = -(-nvec // 64) // (G0 * 4)
-    short = use_lt and NG > 1 and (ks == 1 or (ks == 0 and rounds64 < 16))   # (NG == 1 has one instantiation: KS = NG = 1)
-    cvn = (64 // NG) * (1 if short else NG) if use_lt else 64
-    nchunks = -(-nvec // cvn)
-    G = max(1, min(cus * per_cu, -(-nchunks // 4)))
-    return {"variant": "frag" if not use_lt else ("lt_short" if short else "lt_long"), "NG": NG, "CVN": cvn,
-            "CGN": 64 // cvn, "PG": 8 if (use_lt and NG == 4) else (16 if NG == 4 else 8), "G": G, "Gmax": cus * per_cu,
-            "nchunks": nchunks, "rounds": -(-nchunks // (4 * G)), "ldscol": use_lt and NG == 4 and not short and not f32}
 
 
 KNOBS = {"default": {}, "frag": {"CDH_LT": "0"}, "lt_long": {"CDH_LT": "1", "CDH_KS": "2"},
