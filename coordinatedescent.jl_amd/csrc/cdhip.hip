@@ -26,6 +26,7 @@
 #include "cache_state.hpp"
 #include "exchange_state.hpp"
 #include "sweep_plan.hpp"   // the launch shape of the streamed sweep (sweep.hpp) and of the row-summing launches: host-only arithmetic
+#include "stats_plan.hpp"   // the launches of a Gram block (col_stats.hpp) and of a varying-coefficient point (vc_host.hpp): host-only arithmetic
 
 using namespace cdk;
 
@@ -40,6 +41,12 @@ static_assert(kSpBlock == kBlock && kSpUnroll == kUnroll && kSpNSum == kNSum && 
               "sweep_plan.hpp restates what the kernels fix");
 static_assert(sp_gram_rec(1) == GramRec<1>::N && sp_gram_rec(2) == GramRec<2>::N && sp_gram_rec(4) == GramRec<4>::N &&
               sp_block_rec(kMaxBlockB) == BlockRec<kMaxBlockB>::N, "sweep_plan.hpp restates the record sizes");
+constexpr bool gram_rec_restated() {
+    for (int s = 0; s < kGramLaunchCols; ++s)
+        for (int l = s; l < kGramLaunchCols; ++l) if (gs_g(s, l) != GramRec<4>::g(s, l)) return false;
+    return kGramLaunchCols == GramRec<4>::B && kGsOffC == GramRec<4>::OFF_C && kGsOffQ == GramRec<4>::OFF_Q && kGsRec == GramRec<4>::N;
+}
+static_assert(gram_rec_restated(), "stats_plan.hpp restates GramRec<4>");
 
 namespace {
 
@@ -733,7 +740,8 @@ int32_t screened_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double*
     }
     const int B = (h->mode == CDH_SWEEP_BLOCK) ? h->blockB : 1;
     GcThresholds T(h, 0.0);           // (no certificate: the dots are fresh)
-    std::vector<double> cd((size_t)(2 * kScreenMax));
+    std::vector<double> cd;
+    cd.reserve((size_t)(2 * kScreenMax));
     const int64_t scr_max = std::min<int64_t>({(int64_t)kScreenMax, h->p, h->cap});   // d_colout holds 2p values
     int64_t pos = 0, cool = 0, cool_len = kScreen, scr = std::min<int64_t>(kScreen, scr_max);
     while (pos < m) {
@@ -747,20 +755,21 @@ int32_t screened_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double*
         std::memcpy(h->h_idx, idx0 + pos, sizeof(int64_t) * (size_t)S);
         HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)S, hipMemcpyHostToDevice, h->stream));
         CHK(col_dots(h, 0, S, h->r, h->has_w, h->d_idx));   // X_k'W r, X_k'W X_k with observation weights
-        HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, h->stream));
+        CHK(queue_col_pairs(h, S, cd));
         if (h->loss == CDH_SQRT) {
             CHK(resid_moments_dev(h));
-            HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
+            CHK(queue_resid_sums(h));
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->loss == CDH_SQRT) T.rnorm = std::sqrt(h->h_red[1]);
+        if (h->loss == CDH_SQRT) T.rnorm = std::sqrt(resid_sums(h).sumsq);
+        const ColPairs xr(cd);
         int hit = S;
         for (int i = 0; i < S; ++i) {
             const int64_t k = idx0[pos + i];
             // a zero column (a == 0) goes to the exact path too: the reference turns it into NaN
-            if (h->x.get(k) != 0.0 || !(std::fabs(cd[(size_t)(2 * i)]) <= T.thr_of(k)) || !(cd[(size_t)(2 * i + 1)] > 0.0)) { hit = i; break; }
+            if (h->x.get(k) != 0.0 || !(std::fabs(xr.dot(i)) <= T.thr_of(k)) || !(xr.sq(i) > 0.0)) { hit = i; break; }
         }
-        for (int i = 0; i < hit; ++i) replay_settled(h, idx0[pos + i], cd[(size_t)(2 * i)] != 0.0);   // visits [pos, pos + hit) are settled
+        for (int i = 0; i < hit; ++i) replay_settled(h, idx0[pos + i], xr.dot(i) != 0.0);   // visits [pos, pos + hit) are settled
         pos += hit;
         if (hit < S) {
             const int mm = (int)std::min<int64_t>(std::max(B, 1), m - pos);
@@ -824,30 +833,9 @@ int32_t solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched, cd
     return CDH_OK;
 }
 
-int32_t lambda_max(cdh_handle h, double* out, std::vector<double>* dots = nullptr /* the (X_k'r, a_k) pairs, for a caller that can use them */) {
-    CHK(col_dots(h, 0, h->p, h->r, h->loss == CDH_WLS));
-    std::vector<double> cd_own;
-    std::vector<double>& cd = dots ? *dots : cd_own;
-    cd.resize((size_t)(2 * h->p));
-    HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
-    double denom = (double)h->n_total;
-    if (h->loss == CDH_SQRT) {
-        CHK(resid_moments_dev(h));
-        HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->rs.dots_taken(cd, h->loss == CDH_WLS);   // (col_dots has brought r up to date first)
-    if (h->loss == CDH_SQRT) denom = std::sqrt(h->h_red[1]);
-    const std::vector<double>& om = h->h_omega;
-    double lmax = 0.0;
-    for (int64_t k = 0; k < h->p; ++k) {
-        double t = std::fabs(-cd[(size_t)(2 * k)] / denom);
-        if (h->has_omega) t /= om[(size_t)k];
-        if (t > lmax) lmax = t;
-    }
-    *out = lmax;
-    return CDH_OK;
-}
+// _findLambdaMax (coordinate_descent.jl:118-149): col_stats.hpp, with the statistics it shares its read-backs with (declared
+// ahead, as rebuild_residual_from is: the cold start below calls it)
+int32_t lambda_max(cdh_handle h, double* out, std::vector<double>* dots = nullptr /* the (X_k'r, a_k) pairs, for a caller that can use them */);
 
 void free_all(cdh_handle h) {
     if (!h) return;
@@ -1201,31 +1189,8 @@ int32_t cdh_initialize(cdh_handle h, int64_t x_length, int64_t nnz, const int64_
     return rebuild_residual(h);
 }); }
 
-int32_t cdh_gradient(cdh_handle h, int64_t k1, double* out) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, out);
-    if (k1 < 1 || k1 > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(col_dots(h, k1 - 1, 1, h->r, h->loss == CDH_WLS));
-    HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_colout, sizeof(double) * 2, hipMemcpyDeviceToHost, h->stream));
-    double denom = (double)h->n_total;
-    double xr;
-    if (h->loss == CDH_SQRT) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        xr = h->h_red[0];
-        CHK(resid_moments_dev(h));
-        HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        denom = std::sqrt(h->h_red[1]);
-    } else {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        xr = h->h_red[0];
-    }
-    *out = -xr / denom;
-    return CDH_OK;
-}); }
-
 int32_t cdh_descend(cdh_handle h, int64_t k1, double* out_h) { return guarded(h, [&]() -> int32_t {
-    if (k1 < 1 || k1 > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
+    CHK(check_coordinate(h, k1));
     HIPCHK(h, hipSetDevice(h->device));
     const int64_t k0 = k1 - 1;
     double maxH = 0.0;
@@ -1250,10 +1215,8 @@ int32_t cdh_pass(cdh_handle h, int64_t m, const int64_t* idx1, double* out_maxH)
     if (m > 0) NEED_P(h, idx1);
     HIPCHK(h, hipSetDevice(h->device));
     std::vector<int64_t> idx0((size_t)m);
-    for (int64_t i = 0; i < m; ++i) {
-        if (idx1[i] < 1 || idx1[i] > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
-        idx0[(size_t)i] = idx1[i] - 1;
-    }
+    CHK(check_columns(h, idx1, m));
+    for (int64_t i = 0; i < m; ++i) idx0[(size_t)i] = idx1[i] - 1;
     double maxH = 0.0;
     h->gc.st.unprepared();
     if (m > 0) CHK(run_pass(h, idx0.data(), m, &maxH, h->screening >= 2));
@@ -1315,7 +1278,7 @@ int32_t cdh_coordinate_descent(cdh_handle h, const cdh_options* opt, cdh_stats* 
         double lmax = 0.0;
         const double denom = h->loss == CDH_SQRT ? std::sqrt(h->small.yy) : (double)h->n_total;
         for (int64_t k = 0; k < h->p; ++k) {
-            double t = std::fabs(-h->small.h_c[(size_t)(2 * k)] / denom);
+            double t = std::fabs(-ColPairs(h->small.h_c).dot(k) / denom);
             if (h->has_omega) t /= h->h_omega[(size_t)k];
             if (t > lmax) lmax = t;
         }
@@ -1394,27 +1357,6 @@ int32_t cdh_get_residual(cdh_handle h, void* out_n_local) { return guarded(h, [&
     return CDH_OK;
 }); }
 
-int32_t cdh_col_rms(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, out_p);
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(col_dots(h, 0, h->p, h->r, false));
-    std::vector<double> cd((size_t)(2 * h->p));
-    HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(cd[(size_t)(2 * j + 1)] / (double)h->n_total);
-    return CDH_OK;
-}); }
-
-int32_t cdh_loadings(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, out_p);
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(col_loadings(h));
-    HIPCHK(h, hipMemcpyAsync(out_p, h->d_colout, sizeof(double) * h->p, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(out_p[j] / (double)h->n_total);
-    return CDH_OK;
-}); }
-
 // ---- l1-penalised GLMs by IRLS (glm_kernels.hpp; no reference counterpart: a round's solve is the weighted lasso of
 // CDWeightedLSLoss, cd_differentiable_function.jl:118-194) ---------------------------------------------------------------------
 // The body of cdh_glm_irls, cdh_glm_irls_fold and cdh_glm_poisson_irls: stands in for cdh_get_residual, w and z on the host,
@@ -1473,142 +1415,6 @@ int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin
     return glm_step<GlmPoisson>(h, k, apply, GlmParams{wmin, eta_max}, out6);
 }); }
 
-int32_t cdh_xt_r(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, out_p);
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(col_dots(h, 0, h->p, h->r, false));
-    std::vector<double> cd((size_t)(2 * h->p));
-    HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t j = 0; j < h->p; ++j) out_p[j] = cd[(size_t)(2 * j)];
-    h->rs.dots_taken(std::move(cd), false);
-    return CDH_OK;
-}); }
-
-// one launch of the wide-block Gram kernel over up to 64 columns (0-based, in h->h_idx[0 .. m)): rec <- (G, c = X_S'r, q = r'r);
-// with `weighted`, G = X_S'WX_S and c = X_S'Wr (q stays r'r: the kernel weights its A operands only)
-static int32_t gram_launch(cdh_handle h, int m, std::vector<double>& rec, bool weighted) {
-    using R = GramRec<4>;
-    HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-    // one k_gramstep launch with no pending update: r is only read
-    const int G = gram_read_grid(h->nvec, h->sz.cus);
-    CHK(need_partials(h, (size_t)G * R::N, "partial buffer too small for this grid"));
-    CHK(dispatch(h, [&](auto* t) {
-        using T = std::remove_pointer_t<decltype(t)>;
-        hipLaunchKernelGGL((k_gramstep<T, 4>), dim3(G), dim3(64 * kGramWaves), 0, h->stream,
-                           (const T*)h->X, h->ld, h->nvec, weighted ? (const T*)h->w : (const T*)nullptr, (T*)h->r, h->d_idx,
-                           h->d_hs, 0, m, 0, h->d_partials);
-        return CDH_OK;
-    }));
-    hipLaunchKernelGGL(k_gram_reduce, dim3((R::N + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream, h->d_partials, G, R::N, h->d_red);
-    HIPCHK(h, hipGetLastError());
-    CHK(allreduce(h, h->d_red, R::N));
-    rec.resize((size_t)R::N);
-    HIPCHK(h, hipMemcpyAsync(rec.data(), h->d_red, sizeof(double) * R::N, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return CDH_OK;
-}
-constexpr int64_t kGramMaxCols = 4096;
-static int32_t gram_block(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q, bool weighted) {
-    if (m < 1 || m > kGramMaxCols) return fail(h, CDH_BAD_ARG, "need 1 <= m <= 4096 columns");
-    NEED_P(h, idx1);
-    NEED_P(h, out_G);
-    for (int64_t i = 0; i < m; ++i)
-        if (idx1[i] < 1 || idx1[i] > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(sync_r(h));
-    using R = GramRec<4>;
-    std::vector<double> rec;
-    if (m <= 64) {
-        for (int64_t i = 0; i < m; ++i) h->h_idx[i] = idx1[i] - 1;
-        CHK(gram_launch(h, (int)m, rec, weighted));
-        for (int64_t i = 0; i < m; ++i) {
-            for (int64_t j = 0; j < m; ++j) {
-                const int s = (int)std::min(i, j), l = (int)std::max(i, j);
-                out_G[i * m + j] = rec[(size_t)R::g(s, l)];
-            }
-            if (out_c) out_c[i] = rec[(size_t)(R::OFF_C + i)];
-        }
-        if (out_q) *out_q = rec[(size_t)R::OFF_Q];
-        return CDH_OK;
-    }
-    // More than one launch's worth (round 4; _findInitResiduals! takes any s, src/utils.jl:65-77): groups of 32 columns, one
-    // launch per PAIR of groups -- the 64 columns of a pair give the pair's two diagonal blocks and the block between them.
-    const int64_t ng = (m + 31) / 32;
-    for (int64_t a = 0; a < ng; ++a)
-        for (int64_t b = a + 1; b < ng; ++b) {
-            const int64_t a0 = 32 * a, a1 = std::min<int64_t>(a0 + 32, m), b0 = 32 * b, b1 = std::min<int64_t>(b0 + 32, m);
-            const int na = (int)(a1 - a0), nb = (int)(b1 - b0);
-            for (int i = 0; i < na; ++i) h->h_idx[i] = idx1[a0 + i] - 1;
-            for (int i = 0; i < nb; ++i) h->h_idx[na + i] = idx1[b0 + i] - 1;
-            CHK(gram_launch(h, na + nb, rec, weighted));
-            // column -> position inside the launch; every block and dot the launch holds is written (a diagonal block comes out
-            // of every pair its group is in, each time from the same sums over the same rows)
-            auto col_of = [&](int pos) { return pos < na ? a0 + pos : b0 + (pos - na); };
-            for (int pi = 0; pi < na + nb; ++pi) {
-                const int64_t i = col_of(pi);
-                for (int pj = 0; pj < na + nb; ++pj)
-                    out_G[i * m + col_of(pj)] = rec[(size_t)R::g(std::min(pi, pj), std::max(pi, pj))];
-                if (out_c) out_c[i] = rec[(size_t)(R::OFF_C + pi)];
-            }
-            if (out_q) *out_q = rec[(size_t)R::OFF_Q];
-        }
-    return CDH_OK;
-}
-
-int32_t cdh_gram(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) { return guarded(h, [&]() -> int32_t {
-    return gram_block(h, m, idx1, out_G, out_c, out_q, false);
-}); }
-
-// X_S'r (X_S'Wr for the weighted loss) for a list of columns: the refinement step of the screening init reads the normal
-// equations' residual off it (src/utils.jl:65-77 solves Xs \ y by QR; here: the Gram block plus refinement)
-int32_t cdh_xt_r_cols(cdh_handle h, int64_t m, const int64_t* idx1, double* out_m) { return guarded(h, [&]() -> int32_t {
-    if (m < 1 || m > h->cap) return fail(h, CDH_BAD_ARG, "need 1 <= m <= max(p, 4096) columns");
-    NEED_P(h, idx1);
-    NEED_P(h, out_m);
-    for (int64_t i = 0; i < m; ++i)
-        if (idx1[i] < 1 || idx1[i] > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
-    HIPCHK(h, hipSetDevice(h->device));
-    std::vector<double> cd(2 * (size_t)std::min<int64_t>(m, h->p));
-    for (int64_t o = 0; o < m; o += h->p) {          // d_colout holds 2p values
-        const int64_t mm = std::min<int64_t>(h->p, m - o);
-        for (int64_t i = 0; i < mm; ++i) h->h_idx[i] = idx1[o + i] - 1;
-        HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)mm, hipMemcpyHostToDevice, h->stream));
-        CHK(col_dots(h, 0, mm, h->r, h->loss == CDH_WLS, h->d_idx));
-        HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * (size_t)mm, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int64_t i = 0; i < mm; ++i) out_m[o + i] = cd[(size_t)(2 * i)];
-    }
-    return CDH_OK;
-}); }
-
-// X_S'WX_S, X_S'Wr, r'Wr: the weighted normal equations of the refit of locpolyl1 (varying_coefficient_lasso.jl:71-76) at the
-// current residual.  The Gram kernel weights G and c; r'Wr is the weighted moment of r.
-int32_t cdh_gram_weighted(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) { return guarded(h, [&]() -> int32_t {
-    if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "a weighted Gram block needs the CDH_WLS loss with its weights set");
-    CHK(gram_block(h, m, idx1, out_G, out_c, nullptr, true));
-    if (out_q) {
-        CHK(resid_moments_dev(h));
-        HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        *out_q = h->h_red[2];
-    }
-    return CDH_OK;
-}); }
-
-// _stdX!(out, w, X) (utils.jl:140-151): out_j = sqrt(sum_i w_i X_ij^2 / n_total)
-int32_t cdh_col_wrms(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, out_p);
-    if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "weighted column scales need the CDH_WLS loss with its weights set");
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(col_dots(h, 0, h->p, h->y, true));      // (the dots with y are not used; r may owe updates nobody needs here)
-    std::vector<double> cd((size_t)(2 * h->p));
-    HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t j = 0; j < h->p; ++j) out_p[j] = std::sqrt(cd[(size_t)(2 * j + 1)] / (double)h->n_total);
-    return CDH_OK;
-}); }
-
 // ---- cross-validation of a lasso path (cv_path.hpp; the solves are lasso.jl:229-260 on 0/1 weights, utils.jl:140-151) ------
 int32_t cdh_set_folds(cdh_handle h, const int32_t* fold_of_row, int32_t K, int64_t* out_count) { return guarded(h, [&]() -> int32_t {
     return cv_set_folds(h, fold_of_row, K, out_count);
@@ -1630,113 +1436,17 @@ int32_t cdh_path_sse(cdh_handle h, int32_t k, int64_t s, const int64_t* idx1, in
     return cv_path_sse(h, k, s, idx1, m, B, ldb, out_held, out_train);
 }); }
 
-// ---- varying-coefficient mode (varying_coefficient_lasso.jl:30-79) -------------------------------------------------
-static int32_t vc_refuse_shards(cdh_handle h) {
-    if (h->n != h->n_total || h->xs.sharded())
-        return fail(h, CDH_BAD_ARG, "varying-coefficient mode does not run on row-sharded handles");
-    return CDH_OK;
-}
+// ---- varying-coefficient mode (vc_host.hpp; varying_coefficient_lasso.jl:30-79) ----------------------------------------------
+}  // extern "C"
+namespace {
+#include "vc_host.hpp"   // vc_set_data, vc_point; the scratch, the launch body and the group planners of cdh_vc_gram and cdh_vc_gram_batch
+}  // namespace
+extern "C" {
 
 int32_t cdh_vc_set_data(cdh_handle h, int64_t p_base, int32_t degree, const void* host_X, int64_t ld,
                                     const void* host_z) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, host_X);
-    NEED_P(h, host_z);
-    if (degree < 0 || degree > 3) return fail(h, CDH_BAD_ARG, "the polynomial degree must be 0 .. 3");
-    CHK(vc_refuse_shards(h));
-    if (h->loss != CDH_WLS || p_base < 1 || h->p != p_base * (degree + 1) || ld < h->n)
-        return fail(h, CDH_DIM_MISMATCH, "need a CDH_WLS handle with p == p_base * (degree + 1) and ld >= n");
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t colbytes = (size_t)h->ld * h->esz;
-    DevBuf<void> z;                      // complete before the handle changes: a failed allocation leaves it as it was
-    if (!h->vc_z) {
-        HIPCHK(h, z.alloc(colbytes));
-        HIPCHK(h, hipMemsetAsync(z, 0, colbytes, h->stream));
-    }
-    CHK(design_changes(h, true));
-    if (!h->vc_z) h->vc_z = std::move(z);
-    h->vc_pbase = p_base; h->vc_degree = degree;
-    // base column j -> column j (degree + 1): one strided copy
-    HIPCHK(h, hipMemcpy2DAsync(h->X, colbytes * (size_t)(degree + 1), host_X, (size_t)ld * h->esz, (size_t)h->n * h->esz,
-                               (size_t)p_base, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->vc_z, host_z, (size_t)h->n * h->esz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return CDH_OK;
+    return vc_set_data(h, p_base, degree, host_X, ld, host_z);
 }); }
-
-// One point of the varying-coefficient design: weights, expansion, weighted column scales -- around z0 (row0 < 0), or around
-// the stored z[row0] with that row's weight zero and the screening scores |X_j'Wy| on top (the leave-one-out point).
-static int32_t vc_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, int64_t row0, double* out_std,
-                        double* out_scores) {
-    const bool loo = row0 >= 0;
-    if (h->vc_degree < 0) return fail(h, CDH_BAD_ARG, "a varying-coefficient point needs cdh_vc_set_data first");
-    if (kernel_kind != kVcGaussian && kernel_kind != kVcEpanechnikov) return fail(h, CDH_BAD_ARG, "unknown smoothing kernel");
-    if (!(bandwidth > 0.0) || !std::isfinite(bandwidth)) return fail(h, CDH_BAD_ARG, "the bandwidth must be positive");
-    if (!std::isfinite(z0)) return fail(h, CDH_BAD_ARG, "z0 must be finite");
-    CHK(vc_refuse_shards(h));
-    if (h->loss != CDH_WLS) return fail(h, CDH_BAD_ARG, "varying-coefficient mode needs the CDH_WLS loss");
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(design_changes(h, true));
-    CHK(ensure_weights_buffer(h));
-    const int Q = h->vc_degree, Q1 = Q + 1;
-    HIPCHK(h, h->prof.begin(h->stream));
-    const int wgrid = elementwise_grid(h->nvec, kWeightsGridCap);
-    CHK(dispatch(h, [&](auto* t) {
-        using T = std::remove_pointer_t<decltype(t)>;
-        hipLaunchKernelGGL(k_vc_weights<T>, dim3(wgrid), dim3(kBlock), 0, h->stream, (const T*)h->vc_z, (T*)h->w, h->n,
-                           h->nvec, (int)kernel_kind, bandwidth, z0, row0);
-        return CDH_OK;
-    }));
-    HIPCHK(h, hipGetLastError());
-    h->has_w = true;
-    int64_t launches = 1;
-    std::vector<double> cd;
-    if (Q == 0) {                        // nothing to expand: the weighted scales of the base columns (and their dots with y)
-        CHK(col_dots(h, 0, h->p, h->y, true));
-        cd.resize((size_t)(2 * h->p));
-        HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, h->prof.stop(h->stream));   // (the bracket closes in stream order before either branch's wait: one stop per branch, one end below)
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        std::vector<double> ab(cd);     // -> the layout of the other branch: p scales, then p scores
-        for (int64_t j = 0; j < h->p; ++j) { cd[(size_t)j] = ab[(size_t)(2 * j + 1)]; cd[(size_t)(h->p + j)] = ab[(size_t)(2 * j)]; }
-    } else {
-        // One launch per k_col_dots batch of expanded columns, split into that batch's row chunks: the sums then are the
-        // ones cdh_col_wrms takes.  A base column whose group straddles two batches is expanded by both launches (the
-        // same values twice); each keeps the sums of its own columns.
-        for (int64_t b0 = 0; b0 < h->p; b0 += kColBatch) {
-            const int64_t b1 = std::min<int64_t>(b0 + kColBatch, h->p);
-            const int chunks = col_dots_plan(b1 - b0, h->nvec, h->sz.cus, 1).chunks;
-            const int64_t jb0 = b0 / Q1, jb1 = (b1 + Q1 - 1) / Q1;
-            const size_t table = (size_t)(jb1 - jb0) * Q1 * chunks;      // the sums of w v^2; with a left-out row, those of w v y behind it
-            CHK(need_partials(h, table * (loo ? 2 : 1)));
-            CHK(dispatch(h, [&](auto* t) {
-                using T = std::remove_pointer_t<decltype(t)>;
-                auto go = [&](auto kernel) {
-                    hipLaunchKernelGGL(kernel, dim3((unsigned)chunks, (unsigned)(jb1 - jb0)), dim3(kBlock), 0, h->stream,
-                                       (T*)h->X, h->ld, h->nvec, (const T*)h->vc_z, (const T*)h->w, (T)z0, jb0, h->d_partials,
-                                       (const T*)h->y, row0);
-                };
-                if (loo) { if (Q == 1) go(k_vc_expand<T, 1, true>); else if (Q == 2) go(k_vc_expand<T, 2, true>); else go(k_vc_expand<T, 3, true>); }
-                else if (Q == 1) go(k_vc_expand<T, 1>); else if (Q == 2) go(k_vc_expand<T, 2>); else go(k_vc_expand<T, 3>);
-                return CDH_OK;
-            }));
-            hipLaunchKernelGGL(k_vc_reduce, dim3((unsigned)((jb1 - jb0) * Q1)), dim3(64), 0, h->stream, h->d_partials, chunks,
-                               jb0 * Q1, b0, b1, h->d_colout);
-            if (loo)
-                hipLaunchKernelGGL(k_vc_reduce, dim3((unsigned)((jb1 - jb0) * Q1)), dim3(64), 0, h->stream, h->d_partials + table,
-                                   chunks, jb0 * Q1, b0, b1, h->d_colout + h->p);
-            HIPCHK(h, hipGetLastError());
-            launches += 1;
-        }
-        HIPCHK(h, h->prof.stop(h->stream));
-        cd.resize((size_t)(loo ? 2 * h->p : h->p));
-        HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * cd.size(), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    HIPCHK(h, h->prof.end(launches, (double)h->n * (double)h->esz * ((double)h->p + 2.0)));   // read p_base columns, write p_base Q, z, w
-    if (out_std) for (int64_t j = 0; j < h->p; ++j) out_std[j] = std::sqrt(cd[(size_t)j] / (double)h->n_total);
-    if (out_scores) for (int64_t j = 0; j < h->p; ++j) out_scores[j] = std::fabs(cd[(size_t)(h->p + j)]);
-    return CDH_OK;
-}
 
 int32_t cdh_vc_set_point(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, double* out_std) { return guarded(h, [&]() -> int32_t {
     return vc_point(h, kernel_kind, bandwidth, z0, -1, out_std, nullptr);
@@ -1750,108 +1460,6 @@ int32_t cdh_vc_set_point_loo(cdh_handle h, int32_t kernel_kind, double bandwidth
     return vc_point(h, kernel_kind, bandwidth, 0.0, row0, out_std, out_scores);
 }); }
 
-// The weighted Gram matrix and right-hand side of the expanded design around one point, straight from the base design
-// (_expand_Xt_w_X!, _expand_Xt_w_Y!: varying_coefficient_lasso.jl:572-647): one pass over the listed base columns, z and y.
-// Reads the handle's data and writes only its own scratch: residual, cache, weights, expanded columns and iterate stay.
-// A batch of points per launch (the loops of locpoly on a grid, lvocv_locpoly and split_locpoly,
-// varying_coefficient_lasso.jl:217-235, 348-380, 383-409, over :572-647) is the same body over more points: point t of
-// cdh_vc_gram_batch is cdh_vc_gram at (bandwidth[t], z0[t], leave_out_row0[t]), bit for bit.
-static_assert(kVgbMaxPoints == CDH_VC_GRAM_MAX_POINTS && kVgMaxCols == CDH_VC_GRAM_MAX_COLS, "cdhip.h names the limits the headers derive");
-static int32_t vc_gram_scratch(cdh_handle h) {
-    VcGramScratch& g = h->vg;
-    if (g.ready) return CDH_OK;
-    VcGramScratch s;                     // complete before the handle changes
-    const size_t nrec = (size_t)vc_gram_rec(kVgMaxDegree, kVgMaxCols).n;
-    HIPCHK(h, s.partials.alloc(sizeof(double) * (size_t)kVgPartialDoubles));
-    HIPCHK(h, s.out.alloc(sizeof(double) * nrec));
-    HIPCHK(h, s.in.alloc(sizeof(VcGramInput)));
-    HIPCHK(h, s.e.alloc((size_t)h->ld * h->esz));
-    HIPCHK(h, s.h_out.alloc(sizeof(double) * nrec));
-    HIPCHK(h, s.h_in.alloc(sizeof(VcGramInput)));
-    s.ready = true;
-    g = std::move(s);
-    return CDH_OK;
-}
-static int32_t vc_gram_batch_scratch(cdh_handle h) {
-    VcGramBatchScratch& g = h->vgb;
-    if (g.ready) return CDH_OK;
-    VcGramBatchScratch s;                // complete before the handle changes
-    HIPCHK(h, s.partials.alloc(sizeof(double) * (size_t)kVgbPartialDoubles));
-    HIPCHK(h, s.out.alloc(sizeof(double) * (size_t)kVgbOutDoubles));
-    HIPCHK(h, s.pts.alloc(sizeof(VcGramPoint) * (size_t)kVgbMaxGroupPoints));
-    HIPCHK(h, s.h_out.alloc(sizeof(double) * (size_t)kVgbOutDoubles));
-    HIPCHK(h, s.h_pts.alloc(sizeof(VcGramPoint) * (size_t)kVgbMaxGroupPoints));
-    s.ready = true;
-    g = std::move(s);
-    return CDH_OK;
-}
-
-// The body of both exports, after their checks and their scratch: the points t < m in `ngroups` launch groups, each laid out
-// by group(h, m, mb, grp, &L) (CDH_OK, or the export's refusal), in the buffers b and the regime the export names.  Per call
-// the columns and e go to the device once; per group the points, k_vc_moments, k_vc_moments_reduce, one copy back, one
-// synchronise.  Where b's point is the one behind the columns (cdh_vc_gram), one copy takes columns and point `together`.
-struct VcGramGroup { int64_t first, pts, per, gy; };   // points first .. first + pts - 1 on a grid (G, gy), `per` a share (resident)
-typedef int32_t (*VcGramPlan)(cdh_handle h, int64_t m, int64_t mb, int64_t grp, VcGramGroup* L);
-static int32_t vc_gram_run(cdh_handle h, int32_t kernel_kind, int64_t m, const double* bandwidth, const double* z0,
-                           const int64_t* leave_out_row0, int32_t wpow, const void* host_e, int64_t mb, const int64_t* base_idx1,
-                           double* out_G, double* out_c, double* out_sum_w, const VcGramBufs& b, bool resident, int64_t ngroups,
-                           VcGramPlan group) {
-    VcGramScratch& g = h->vg;
-    VcGramInput* const d_in = g.in;
-    const int Q = h->vc_degree;
-    const int64_t n = h->n, Q1 = Q + 1, ep = mb * Q1;
-    const VcGramRec R = vc_gram_rec(Q, mb);
-    const int G = vc_gram_grid(n, Q, mb);
-    const bool together = b.h_pts == &g.h_in->pt;
-    for (int64_t i = 0; i < mb; ++i) g.h_in->cols[i] = (base_idx1[i] - 1) * Q1;      // base column j sits at column j (Q + 1)
-    if (!together)
-        HIPCHK(h, hipMemcpyAsync(d_in->cols, g.h_in->cols, sizeof(int64_t) * (size_t)mb, hipMemcpyHostToDevice, h->stream));
-    if (host_e) HIPCHK(h, hipMemcpyAsync(g.e, host_e, (size_t)n * h->esz, hipMemcpyHostToDevice, h->stream));   // once per call
-    for (int64_t grp = 0; grp < ngroups; ++grp) {
-        VcGramGroup L;
-        CHK(group(h, m, mb, grp, &L));
-        for (int64_t t = 0; t < L.pts; ++t) {
-            const int64_t lo = leave_out_row0 ? leave_out_row0[L.first + t] : -1;
-            b.h_pts[t] = VcGramPoint{lo >= 0 ? 0.0 : z0[L.first + t], bandwidth[L.first + t], lo};
-        }
-        if (together) HIPCHK(h, hipMemcpyAsync(d_in, g.h_in, sizeof(VcGramInput), hipMemcpyHostToDevice, h->stream));
-        else HIPCHK(h, hipMemcpyAsync(b.pts, b.h_pts, sizeof(VcGramPoint) * (size_t)L.pts, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, h->prof.begin(h->stream));
-        CHK(dispatch(h, [&](auto* t) {
-            using T = std::remove_pointer_t<decltype(t)>;
-            auto go = [&](auto streamed, auto res) {
-                hipLaunchKernelGGL(resident ? res : streamed, dim3((unsigned)G, (unsigned)L.gy), dim3(kVgThreads), 0, h->stream,
-                                   (const T*)h->X, h->ld, n, (const T*)h->vc_z, out_c ? (const T*)h->y : (const T*)nullptr,
-                                   host_e ? (const T*)g.e : (const T*)nullptr, (const int64_t*)d_in->cols, (int)mb, (int)kernel_kind,
-                                   (int)wpow, (const VcGramPoint*)b.pts, (int)L.pts, (int)L.per, b.partials);
-            };
-            if (Q == 0) go(k_vc_moments<T, 0, false>, k_vc_moments<T, 0, true>);
-            else if (Q == 1) go(k_vc_moments<T, 1, false>, k_vc_moments<T, 1, true>);
-            else if (Q == 2) go(k_vc_moments<T, 2, false>, k_vc_moments<T, 2, true>);
-            else go(k_vc_moments<T, 3, false>, k_vc_moments<T, 3, true>);
-            return CDH_OK;
-        }));
-        hipLaunchKernelGGL(k_vc_moments_reduce, dim3((unsigned)((R.n + kVgThreads - 1) / kVgThreads), (unsigned)L.pts), dim3(kVgThreads),
-                           0, h->stream, (const double*)b.partials, G, R.n, b.out);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, h->prof.stop(h->stream));
-        HIPCHK(h, hipMemcpyAsync(b.h_out, b.out, sizeof(double) * (size_t)(L.pts * R.n), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, h->prof.end(2, 0.0));  // cdh_profile_begin/end: the device time of the two launches
-        for (int64_t t = 0; t < L.pts; ++t) {
-            const double* rec = b.h_out + t * R.n;
-            vc_gram_scatter(Q, mb, rec, out_G + (L.first + t) * ep * ep, out_c ? out_c + (L.first + t) * ep : nullptr);
-            if (out_sum_w) out_sum_w[L.first + t] = rec[R.off_w];
-        }
-    }
-    return CDH_OK;
-}
-
-// One point: a batch of one in the small tier, always in the streamed regime (vc_gram_batch_types.hpp: vgb_resident)
-static int32_t vc_gram_one_group(cdh_handle, int64_t, int64_t, int64_t, VcGramGroup* L) {
-    *L = VcGramGroup{0, 1, 1, 1};
-    return CDH_OK;
-}
 int32_t cdh_vc_gram(cdh_handle h, int32_t kernel_kind, double bandwidth, double z0, int64_t leave_out_row0, int32_t wpow,
                     const void* host_e, int64_t mb, const int64_t* base_idx1, double* out_G, double* out_c,
                     double* out_sum_w) { return guarded(h, [&]() -> int32_t {
@@ -1870,16 +1478,6 @@ int32_t cdh_vc_gram(cdh_handle h, int32_t kernel_kind, double bandwidth, double 
                        VcGramBufs{g.partials, g.out, g.h_out, &g.in->pt, &g.h_in->pt}, false, 1, vc_gram_one_group);
 }); }
 
-// Many points: the plan of the call is vc_gram_batch_types.hpp's
-static int32_t vc_gram_batch_group(cdh_handle h, int64_t m, int64_t mb, int64_t grp, VcGramGroup* L) {
-    const int Q = h->vc_degree;
-    const int64_t n = h->n, pts = vgb_group_size(n, Q, mb, m, grp), gy = vgb_grid_y(n, Q, mb, pts);
-    *L = VcGramGroup{vgb_group_first(n, Q, mb, grp), pts, vgb_share_points(n, Q, mb, pts), gy};
-    if (pts < 1 || vgb_rec_offset(n, Q, mb, pts, 0) > kVgbPartialDoubles || pts * vc_gram_rec(Q, mb).n > kVgbOutDoubles ||
-        pts > kVgbMaxGroupPoints || gy < 1 || gy > 65535 || vgb_share_begin(n, Q, mb, pts, gy) != pts)
-        return fail(h, CDH_BAD_ARG, "cdh_vc_gram_batch: the plan of this call does not fit its scratch");
-    return CDH_OK;
-}
 int32_t cdh_vc_gram_batch(cdh_handle h, int32_t kernel_kind, int64_t m, const double* bandwidth, const double* z0,
                           const int64_t* leave_out_row0, int32_t wpow, const void* host_e, int64_t mb,
                           const int64_t* base_idx1, double* out_G, double* out_c, double* out_sum_w) { return guarded(h, [&]() -> int32_t {
@@ -1903,95 +1501,67 @@ int32_t cdh_vc_gram_batch(cdh_handle h, int32_t kernel_kind, int64_t m, const do
                        vgb_groups(h->n, h->vc_degree, mb, m), vc_gram_batch_group);
 }); }
 
-// _getSigma(w, r) (utils.jl:167-175): sum w, sum w r^2 at the current residual
-int32_t cdh_resid_wmoments(cdh_handle h, double* out_sum_w, double* out_sum_wr2) { return guarded(h, [&]() -> int32_t {
-    if (h->loss != CDH_WLS || !h->has_w) return fail(h, CDH_BAD_ARG, "weighted moments need the CDH_WLS loss with its weights set");
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(resid_moments_dev(h, nullptr, 0.0, true));
-    HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (out_sum_w) *out_sum_w = h->h_red[0];
-    if (out_sum_wr2) *out_sum_wr2 = h->h_red[2];
-    return CDH_OK;
+// ---- the read-only statistics (col_stats.hpp) -------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+#include "col_stats.hpp"   // the bodies of the exports below; gram_launch, gram_block; lambda_max
+}  // namespace
+extern "C" {
+
+int32_t cdh_gradient(cdh_handle h, int64_t k1, double* out) { return guarded(h, [&]() -> int32_t {
+    return gradient(h, k1, out);
 }); }
 
-// wX[i, S] (:132): out_m[k] = X[row0, idx1[k]] of the resident design, as doubles
+int32_t cdh_col_rms(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
+    return col_rms(h, out_p);
+}); }
+
+int32_t cdh_col_wrms(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
+    return col_wrms(h, out_p);
+}); }
+
+int32_t cdh_loadings(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
+    return loadings(h, out_p);
+}); }
+
+int32_t cdh_xt_r(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {
+    return xt_r(h, out_p);
+}); }
+
+int32_t cdh_xt_r_cols(cdh_handle h, int64_t m, const int64_t* idx1, double* out_m) { return guarded(h, [&]() -> int32_t {
+    return xt_r_cols(h, m, idx1, out_m);
+}); }
+
+int32_t cdh_gram(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) { return guarded(h, [&]() -> int32_t {
+    return gram_block(h, m, idx1, out_G, out_c, out_q, false);
+}); }
+
+int32_t cdh_gram_weighted(cdh_handle h, int64_t m, const int64_t* idx1, double* out_G, double* out_c, double* out_q) { return guarded(h, [&]() -> int32_t {
+    return gram_weighted(h, m, idx1, out_G, out_c, out_q);
+}); }
+
 int32_t cdh_get_X_row(cdh_handle h, int64_t row0, int64_t m, const int64_t* idx1, double* out_m) { return guarded(h, [&]() -> int32_t {
-    if (m < 1 || m > kGramMaxCols) return fail(h, CDH_BAD_ARG, "need 1 <= m <= 4096 columns");
-    NEED_P(h, idx1);
-    NEED_P(h, out_m);
-    if (row0 < 0 || row0 >= h->n) return fail(h, CDH_BAD_ARG, "row outside 0 .. n_local - 1");
-    for (int64_t i = 0; i < m; ++i)
-        if (idx1[i] < 1 || idx1[i] > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
-    HIPCHK(h, hipSetDevice(h->device));
-    for (int64_t o = 0; o < m; o += 2 * h->p) {          // d_colout holds 2p values
-        const int64_t mm = std::min<int64_t>(2 * h->p, m - o);
-        for (int64_t i = 0; i < mm; ++i) h->h_idx[i] = idx1[o + i] - 1;
-        HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)mm, hipMemcpyHostToDevice, h->stream));
-        CHK(dispatch(h, [&](auto* t) {
-            using T = std::remove_pointer_t<decltype(t)>;
-            hipLaunchKernelGGL(k_gather_row<T>, dim3((unsigned)((mm + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
-                               (const T*)h->X, h->ld, row0, h->d_idx, (int)mm, h->d_colout);
-            return CDH_OK;
-        }));
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(out_m + o, h->d_colout, sizeof(double) * (size_t)mm, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return CDH_OK;
+    return get_X_row(h, row0, m, idx1, out_m);
 }); }
 
-// std(f.r) as Statistics.std computes it (two passes: the mean, then the centred sum of squares; Bessel-corrected) --
-// lasso.jl:37,52,81,97,143 -- without the cancellation of the one-pass form when the mean is large against the spread
+int32_t cdh_resid_moments(cdh_handle h, double* out_sum, double* out_sumsq) { return guarded(h, [&]() -> int32_t {
+    return resid_moments(h, out_sum, out_sumsq);
+}); }
+
+int32_t cdh_resid_wmoments(cdh_handle h, double* out_sum_w, double* out_sum_wr2) { return guarded(h, [&]() -> int32_t {
+    return resid_wmoments(h, out_sum_w, out_sum_wr2);
+}); }
+
 int32_t cdh_resid_std(cdh_handle h, double* out_std, double* out_mean) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, out_std);
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(resid_moments_dev(h));
-    HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const double n = (double)h->n_total, mean = h->h_red[0] / n;
-    double ss = h->h_red[1], s1 = h->h_red[0];
-    if (mean != 0.0 && mean == mean) {
-        CHK(resid_moments_dev(h, nullptr, mean));
-        HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        s1 = h->h_red[0]; ss = h->h_red[1];         // of the centred values: s1 is rounding-sized
-    } else {
-        s1 = 0.0;
-    }
-    *out_std = std::sqrt(std::max(ss - s1 * s1 / n, 0.0) / (n - 1.0));
-    if (out_mean) *out_mean = mean;
-    return CDH_OK;
+    return resid_std(h, out_std, out_mean);
+}); }
+
+int32_t cdh_objective(cdh_handle h, double* out) { return guarded(h, [&]() -> int32_t {
+    return objective(h, out);
 }); }
 
 int32_t cdh_set_reuse_residual(cdh_handle h, int32_t on) { return guarded(h, [&]() -> int32_t {
     h->reuse_residual = on != 0;
-    return CDH_OK;
-}); }
-
-int32_t cdh_resid_moments(cdh_handle h, double* out_sum, double* out_sumsq) { return guarded(h, [&]() -> int32_t {
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(resid_moments_dev(h));
-    HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (out_sum) *out_sum = h->h_red[0];
-    if (out_sumsq) *out_sumsq = h->h_red[1];
-    return CDH_OK;
-}); }
-
-int32_t cdh_objective(cdh_handle h, double* out) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, out);
-    HIPCHK(h, hipSetDevice(h->device));
-    CHK(resid_moments_dev(h));
-    HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-    const std::vector<double>& om = h->h_omega;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    double pen = 0.0;
-    for (int64_t s = 0; s < h->x.nnz(); ++s)
-        pen += std::fabs(h->x.slot_value(s)) * (h->has_omega ? om[(size_t)h->x.coord(s)] : 1.0);
-    pen *= h->ctrl.lambda0;
-    const double ss = h->loss == CDH_WLS ? h->h_red[2] : h->h_red[1];
-    *out = (h->loss == CDH_SQRT ? std::sqrt(ss) : ss / (2.0 * (double)h->n_total)) + pen;
     return CDH_OK;
 }); }
 
@@ -2065,7 +1635,7 @@ int32_t cdh_cache_stats(cdh_handle h, int64_t* out10) { return guarded(h, [&]() 
 
 int32_t cdh_cache_gram_column(cdh_handle h, int64_t k1, double* out_p, double* out_eps) { return guarded(h, [&]() -> int32_t {
     NEED_P(h, out_p);
-    if (k1 < 1 || k1 > h->p) return fail(h, CDH_BAD_ARG, "coordinate out of range");
+    CHK(check_coordinate(h, k1));
     GradCache& c = h->gc;
     if (c.slot.empty() || c.slot[(size_t)(k1 - 1)] < 0 || (size_t)c.slot[(size_t)(k1 - 1)] >= c.G.size())
         return fail(h, CDH_BAD_ARG, "the gradient cache holds no Gram column for this coordinate");

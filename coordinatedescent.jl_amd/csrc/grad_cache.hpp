@@ -192,10 +192,10 @@ int32_t gc_cert_abs(cdh_handle h, double* out) {
     *out = 0.0;
     if (h->dtype != CDH_F32) return CDH_OK;
     if (!c.st.yy_current()) {
+        ResidSums s;
         CHK(resid_moments_dev(h, h->y));
-        HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        c.st.yy_summed(h->h_red[1]);
+        CHK(read_resid_sums(h, &s));
+        c.st.yy_summed(s.sumsq);
     }
     // ... plus (round 4) what the Gram entries themselves carry: k_cross takes fp32 storage on the fp32 matrix pipe, 256-row
     // partial sums in fp32 folded into fp64 tiles, so an entry is good to eps_G sqrt(a_i a_j) with eps_G ~ 2^-24 * 128 / sqrt(n)
@@ -223,10 +223,10 @@ bool cov_ok(cdh_handle h, const int64_t* idx0, int64_t m) {
 int32_t gc_ensure_q(cdh_handle h) {
     GradCache& c = h->gc;
     if (c.st.q_usable()) return CDH_OK;
+    ResidSums s;
     CHK(resid_moments_dev(h));
-    HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    c.st.q_summed(h->h_red[1]);
+    CHK(read_resid_sums(h, &s));
+    c.st.q_summed(s.sumsq);
     return CDH_OK;
 }
 // The carried r'r is only good to ~1e-16 of the value its recurrence started from (q <- q - 2 h b + h^2 a, block after block,
@@ -390,12 +390,11 @@ int32_t gc_validate(cdh_handle h, bool beta_known) {
         cd = h->rs.adopt_dots();
     } else {
         CHK(col_dots(h, 0, h->p, h->r, h->has_w));
-        cd.resize((size_t)(2 * h->p));
-        HIPCHK(h, hipMemcpyAsync(cd.data(), h->d_colout, sizeof(double) * 2 * h->p, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        CHK(read_col_pairs(h, h->p, cd));
         h->rs.dots_taken(cd, h->has_w);
     }
-    for (int64_t k = 0; k < h->p; ++k) { c.g[(size_t)k] = cd[(size_t)(2 * k)]; c.a[(size_t)k] = cd[(size_t)(2 * k + 1)]; }
+    const ColPairs pairs(cd);
+    for (int64_t k = 0; k < h->p; ++k) { c.g[(size_t)k] = pairs.dot(k); c.a[(size_t)k] = pairs.sq(k); }
     c.st.referenced(beta_known);
     c.n_validate += 1;
     return CDH_OK;
@@ -411,7 +410,8 @@ int32_t gc_adopt_dots(cdh_handle h, const std::vector<double>& cd) {
     if (c.mode == 0 || c.g.empty()) return CDH_OK;
     const bool beta_known = c.st.beta_known();
     gc_invalidate(h, false);
-    for (int64_t k = 0; k < h->p; ++k) { c.g[(size_t)k] = cd[(size_t)(2 * k)]; c.a[(size_t)k] = cd[(size_t)(2 * k + 1)]; }
+    const ColPairs pairs(cd);
+    for (int64_t k = 0; k < h->p; ++k) { c.g[(size_t)k] = pairs.dot(k); c.a[(size_t)k] = pairs.sq(k); }
     c.st.referenced(beta_known);
     return CDH_OK;
 }

@@ -530,13 +530,12 @@ int32_t small_prepare(cdh_handle h) {     // buffers, X'y and diag(G) of the cur
     if (!sp.c_valid) {                // c = X'y (X'Wy), a = diag(G), y'y: one dots pass over X with y in r's place, once per y
         CHK(col_dots(h, 0, h->p, h->y, h->has_w));
         HIPCHK(h, hipMemcpyAsync(sp.d_ca, h->d_colout, sizeof(double) * 2 * (size_t)h->p, hipMemcpyDeviceToDevice, h->stream));
-        sp.h_c.resize((size_t)(2 * h->p));
-        HIPCHK(h, hipMemcpyAsync(sp.h_c.data(), h->d_colout, sizeof(double) * 2 * (size_t)h->p, hipMemcpyDeviceToHost, h->stream));
+        CHK(queue_col_pairs(h, h->p, sp.h_c));
         CHK(resid_moments_dev(h, h->y));
         HIPCHK(h, hipMemcpyAsync(sp.d_ca + 2 * h->p, h->d_red + 1, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->h_red, h->d_red, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
+        CHK(queue_resid_sums(h));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        sp.yy = h->h_red[1];
+        sp.yy = resid_sums(h).sumsq;
         sp.c_valid = true;
     }
     if (sp.G_valid) return CDH_OK;

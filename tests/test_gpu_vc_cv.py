@@ -95,6 +95,43 @@ def test_scores_and_scales_are_exact_on_small_integer_data(dtype, n):
         f.close()
 
 
+@pytest.mark.parametrize("pb,degree", [(1366, 2), (2049, 1)])
+@pytest.mark.parametrize("n", [33, 5003])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_a_point_is_exact_across_the_column_batch_boundary(dtype, n, pb, degree):
+    """p = 4098 expanded columns: two k_vc_expand launches, over columns [0, 4096) and [4096, 4098).  At degree 2 the group
+    of the last base column, columns 4095 .. 4097, straddles the boundary: both launches expand it (the same values written
+    twice) and each keeps the sums of its own columns; at degree 1 the boundary falls between two groups.  n = 33 has pad
+    rows and one row chunk; at n = 5003 the two launches split their rows into different numbers of chunks.  The data of
+    test_scores_and_scales_are_exact_on_small_integer_data (z0 = 1/2 is a quarter too), so every sum equals numpy's to the
+    bit whatever the order: for set_point and for the leave-one-out point at the first and the last row, the expanded design
+    is the recurrence, the scales are the numpy sums and cdh_col_wrms of the state left behind, the scores the numpy sums."""
+    rng = np.random.default_rng(n + pb)
+    p = pb * (degree + 1)
+    assert p == 4098
+    X = np.asfortranarray(rng.integers(-127, 128, size=(n, pb)).astype(dtype))
+    z = (rng.integers(0, 5, size=n) / 4.0).astype(dtype)
+    y = rng.integers(-511, 512, size=n).astype(dtype)
+    kern = cd.EpanechnikovKernel(1.0)
+    f = cd.CDVaryingCoefficientLoss(y, X, z, degree)
+    for row in (None, 0, n - 1):
+        z0 = 0.5 if row is None else float(z[row])
+        std, scores = (f.set_point(kern, z0), None) if row is None else f.set_point_leave_out(kern, row)
+        d = z.astype(np.float64) - z0
+        w = np.where(np.abs(d) >= 1.0, 0.0, 0.75 * (1.0 - d * d))
+        if row is not None:
+            w[row] = 0.0
+        assert np.array_equal(f.w.astype(np.float64), w), row
+        eX = expand(X, z, z0, degree)
+        assert np.array_equal(f.X_cols(0, p), eX), row
+        eX = eX.astype(np.float64)
+        assert np.array_equal(std, np.sqrt((eX * eX * w[:, None]).sum(axis=0) / n)), row
+        assert np.array_equal(std, cd.stdX(f, weighted=True)), row
+        if row is not None:
+            assert np.array_equal(scores, np.abs((eX * (w * y.astype(np.float64))[:, None]).sum(axis=0))), row
+    f.close()
+
+
 # ---- 2. cdh_resid_wmoments --------------------------------------------------------------------------------------------
 def _wmoments(f):
     sw, swr2 = C.c_double(), C.c_double()
