@@ -27,6 +27,7 @@
 #include "exchange_state.hpp"
 #include "sweep_plan.hpp"   // the launch shape of the streamed sweep (sweep.hpp) and of the row-summing launches: host-only arithmetic
 #include "stats_plan.hpp"   // the launches of a Gram block (col_stats.hpp) and of a varying-coefficient point (vc_host.hpp): host-only arithmetic
+#include "solve_plan.hpp"   // the cold start's grid, the screen walk, the gates, where the pass loop stands (solve.hpp): host-only arithmetic
 
 using namespace cdk;
 
@@ -603,44 +604,7 @@ int32_t sync_r(cdh_handle h) {
 
 #include "col_dots.hpp"   // need_partials; col_dots, col_loadings, resid_moments_dev
 
-// ---- gradient cache: bookkeeping (the passes that use it are below run_chunk) ------------------------
-constexpr int kGcEngage = 3;        // mode 1: this many screened full passes run the plain way first
-constexpr int kGcBusy = 64;         // more inactive coordinates than this about to move: a plain pass is cheaper
-constexpr int kGcMaxFetch = 64;     // more uncached movers than this: re-reference instead of fetching their columns
-constexpr int kGcMaxSupport = 512;  // supports beyond this are not worth Gram columns
-constexpr size_t kGcMaxBytes = (size_t)1 << 30;
-constexpr int64_t kGcCovWindow = 2048;      // positions one covariance-form chunk of a full pass may span
-constexpr int64_t kGcRowsPerNnz = 400;   // rows the problem must have per non-zero for the HOST-side fold and re-check to pay ...
-constexpr int64_t kGcRowsPerNnzDev = 32; // ... and when the passes run on the device (round 3: g, the fold and the re-check never leave it)
-inline int64_t gc_rows_per_nnz(const cdh_handle_s* h) {
-    const GradCache& c = h->gc;
-    if (h->knobs.gc_rows_per_nnz > 0) return h->knobs.gc_rows_per_nnz;   // tests
-    return (c.cov && (c.d_scan || c.g.empty())) ? kGcRowsPerNnzDev : kGcRowsPerNnz;   // (before the first sizing: assume the device path)
-}
-
-// When the support has outgrown what the cache pays for.  Long columns: a support column costs 1/32 of a pass over X to fetch
-// and p doubles per move to apply, against the read of X a cached full pass saves -- the cache stands aside once n < 32 nnz
-// (400 nnz while the fold and the re-check ran on the host), and beyond kGcMaxSupport columns.  SHORT columns (a streamed
-// visit is launch-bound there: ~0.35 us as its share of a block of 64 whatever it reads, against ~0.13 us in covariance form,
-// and fetching a batch of columns is a pass over a small X) keep the cache whatever n / nnz is, up to kGcMaxSupportShort
-// columns: benchmark/cd_bench.jl's n = 3000, p = 5000 path down to 0.03 lambda_max (774 non-zeros) 0.204 -> 0.118 s with the
-// rule off below 512 columns, before the cap was raised.
-constexpr int kGcMaxSupportShort = 4096;
-constexpr size_t kGcShortColumnBytes = (size_t)1 << 20;
-inline bool gc_short_columns(const cdh_handle_s* h) {
-    return h->gc.cov && (h->gc.d_scan || h->gc.g.empty()) && (size_t)h->n * h->esz <= kGcShortColumnBytes;
-}
-inline bool gc_support_outgrown(const cdh_handle_s* h) {        // the rows-per-non-zero rule (modes 1 and 2)
-    if (h->gc.mode == 3 || gc_short_columns(h)) return false;
-    return h->x.nnz() * gc_rows_per_nnz(h) > h->n_total;
-}
-inline int64_t gc_max_support(const cdh_handle_s* h) { return gc_short_columns(h) ? kGcMaxSupportShort : kGcMaxSupport; }
-
-// every loss and both storage types (round 3); a weighted loss only once its weights are there (they are zero until
-// cdh_set_obs_weights: every a_k would be zero and nothing could be settled)
-inline bool gc_applicable(const cdh_handle_s* h) {
-    return h->gc.mode != 0 && (h->loss != CDH_WLS || h->has_w);
-}
+// ---- gradient cache: bookkeeping (its constants, its admission and its passes: grad_cache.hpp) ------------------------
 // g no longer describes r (y or the loss changed); with `columns` the Gram columns are gone too (X changed)
 void gc_invalidate(cdh_handle h, bool columns) {
     GradCache& c = h->gc;
@@ -710,7 +674,6 @@ int32_t rebuild_residual(cdh_handle h) { return rebuild_residual_from(h, h->x, t
 
 #include "sweep.hpp"   // note_duplicates, finish_chunk, the three launchers of a chunk, run_chunk
 
-constexpr int kScreenMinPass = 16;   // screens / the cache: passes over fewer coordinates than that are a block or two anyway
 #include "grad_cache.hpp"   // gc_size, gc_validate, gc_fetch, gc_fold, gc_full_pass
 #include "small_solve.hpp"  // small_applicable, small_prepare, small_solve
 #include "cov_solve.hpp"    // k_cov_solve, cov_solve: the pass loop of a cache-served solve on the device
@@ -718,124 +681,7 @@ constexpr int kScreenMinPass = 16;   // screens / the cache: passes over fewer c
 #include "cv_path.hpp"      // k_fold_weights, k_path_sse: the folds of a cross-validated path and its errors in one pass
 #include "glm_kernels.hpp"  // k_glm_step: the step between two IRLS rounds of a GLM family
 
-// _cdPass! (coordinate_descent.jl:94-110)
-// Screening of a FULL pass (exact, no reference counterpart).  A visit of a coordinate with
-// beta_k == 0 leaves everything unchanged unless |X_k'r| exceeds its threshold (LS: lambda n w_k,
-// cd_differentiable_function.jl:101-104 with x[k] == 0; SQRT: lambda w_k ||r||, :276), and as long
-// as nothing moves r does not change -- so one pass over S columns that only takes their dots
-// settles a whole run of such visits, and the Gram machinery is started at the first visit that
-// can move.  Same iterates as visiting one by one; a full pass over a sparse iterate then reads X
-// about once, at the plain streaming rate.  A 1e-9 relative margin sends borderline coordinates
-// through the exact path.  After a hit the next `cool` visits are not screened (doubling on
-// repeated hits), so a pass in which everything moves pays for a handful of screens only; a screen
-// that settles all of its columns doubles the next one (64 -> 1024 columns: one host round trip per
-// screen, so long quiet stretches run at the plain streaming rate of k_col_dots).
-constexpr int kScreen = 64, kScreenMax = 1024;
-
-int32_t screened_full_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH) {
-    {   // from the gradient cache when it is engaged: no read of X for the settled visits at all
-        bool handled = false;
-        CHK(gc_full_pass(h, idx0, m, maxH, &handled));
-        if (handled) return CDH_OK;
-    }
-    const int B = (h->mode == CDH_SWEEP_BLOCK) ? h->blockB : 1;
-    GcThresholds T(h, 0.0);           // (no certificate: the dots are fresh)
-    std::vector<double> cd;
-    cd.reserve((size_t)(2 * kScreenMax));
-    const int64_t scr_max = std::min<int64_t>({(int64_t)kScreenMax, h->p, h->cap});   // d_colout holds 2p values
-    int64_t pos = 0, cool = 0, cool_len = kScreen, scr = std::min<int64_t>(kScreen, scr_max);
-    while (pos < m) {
-        if (cool > 0) {   // unscreened stretch: whole Gram blocks
-            const int mm = (int)std::min<int64_t>({(int64_t)h->cap, m - pos, std::max<int64_t>(cool, B)});
-            CHK(run_chunk(h, idx0 + pos, mm, maxH));
-            pos += mm; cool -= mm;
-            continue;
-        }
-        const int S = (int)std::min<int64_t>(scr, m - pos);
-        std::memcpy(h->h_idx, idx0 + pos, sizeof(int64_t) * (size_t)S);
-        HIPCHK(h, hipMemcpyAsync(h->d_idx, h->h_idx, sizeof(int64_t) * (size_t)S, hipMemcpyHostToDevice, h->stream));
-        CHK(col_dots(h, 0, S, h->r, h->has_w, h->d_idx));   // X_k'W r, X_k'W X_k with observation weights
-        CHK(queue_col_pairs(h, S, cd));
-        if (h->loss == CDH_SQRT) {
-            CHK(resid_moments_dev(h));
-            CHK(queue_resid_sums(h));
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->loss == CDH_SQRT) T.rnorm = std::sqrt(resid_sums(h).sumsq);
-        const ColPairs xr(cd);
-        int hit = S;
-        for (int i = 0; i < S; ++i) {
-            const int64_t k = idx0[pos + i];
-            // a zero column (a == 0) goes to the exact path too: the reference turns it into NaN
-            if (h->x.get(k) != 0.0 || !(std::fabs(xr.dot(i)) <= T.thr_of(k)) || !(xr.sq(i) > 0.0)) { hit = i; break; }
-        }
-        for (int i = 0; i < hit; ++i) replay_settled(h, idx0[pos + i], xr.dot(i) != 0.0);   // visits [pos, pos + hit) are settled
-        pos += hit;
-        if (hit < S) {
-            const int mm = (int)std::min<int64_t>(std::max(B, 1), m - pos);
-            CHK(run_chunk(h, idx0 + pos, mm, maxH));
-            pos += mm;
-            cool = cool_len; cool_len = std::min<int64_t>(cool_len * 2, m);
-            scr = std::min<int64_t>(kScreen, scr_max);
-        } else {
-            cool_len = kScreen;
-            scr = std::min<int64_t>(scr * 2, scr_max);
-        }
-    }
-    return CDH_OK;
-}
-
-// _cdPass! (coordinate_descent.jl:94-110)
-int32_t run_pass(cdh_handle h, const int64_t* idx0, int64_t m, double* maxH, bool screen = false) {
-    *maxH = 0.0;
-    if (screen && h->screening && (h->loss != CDH_WLS || h->has_w) && m >= kScreenMinPass && h->x.nnz() * 4 <= h->p) {
-        CHK(screened_full_pass(h, idx0, m, maxH));
-    } else {
-        for (int64_t off = 0; off < m; off += h->cap) {
-            const int mm = (int)std::min<int64_t>(h->cap, m - off);
-            // an active pass while the gradient cache holds the support's Gram columns: no read of X at all
-            if (gc_ready_for_cov(h, idx0 + off, mm)) CHK(cov_chunk(h, idx0 + off, mm, maxH));
-            else CHK(run_chunk(h, idx0 + off, mm, maxH));
-        }
-    }
-    h->x.dropzeros();
-    return CDH_OK;
-}
-
-// _coordinateDescent! (coordinate_descent.jl:65-92)
-int32_t solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched, cdh_stats* st) {
-    bool prev_converged = false, converged = true;
-    std::vector<int64_t> visit;
-    st->converged = 0;
-    for (int64_t iter = 0; iter < o->maxIter;) {
-        // while the gradient cache can serve the passes, the loop itself runs on the device (cov_solve.hpp): one host round
-        // trip per solve; what comes back is where the state machine stands
-        {
-            int outcome = kCsNotNow;
-            CHK(cov_solve(h, o, sched, st, &prev_converged, &converged, &iter, &outcome));
-            if (outcome == kCsFinished) break;
-            if (outcome == kCsAgain) continue;
-        }
-        const bool full = converged;
-        sched.next_pass(h->x, full, visit);
-        double maxH = 0.0;
-        if (!visit.empty()) CHK(run_pass(h, visit.data(), (int64_t)visit.size(), &maxH, full));
-        else h->x.dropzeros();
-        h->gc.st.unprepared();
-        st->passes += 1; st->visits += (int64_t)visit.size(); st->maxH = maxH;
-        if (full) st->full_passes += 1;
-        prev_converged = converged;
-        converged = maxH < o->optTol;
-        ++iter;
-        if (prev_converged && converged) { st->converged = 1; break; }
-    }
-    st->domain_error = h->domain_error ? 1 : 0;
-    return CDH_OK;
-}
-
-// _findLambdaMax (coordinate_descent.jl:118-149): col_stats.hpp, with the statistics it shares its read-backs with (declared
-// ahead, as rebuild_residual_from is: the cold start below calls it)
-int32_t lambda_max(cdh_handle h, double* out, std::vector<double>* dots = nullptr /* the (X_k'r, a_k) pairs, for a caller that can use them */);
+#include "solve.hpp"       // screened_full_pass, run_pass, solve; the bodies of cdh_descend, cdh_pass, cdh_solve, cdh_coordinate_descent
 
 void free_all(cdh_handle h) {
     if (!h) return;
@@ -1190,17 +1036,7 @@ int32_t cdh_initialize(cdh_handle h, int64_t x_length, int64_t nnz, const int64_
 }); }
 
 int32_t cdh_descend(cdh_handle h, int64_t k1, double* out_h) { return guarded(h, [&]() -> int32_t {
-    CHK(check_coordinate(h, k1));
-    HIPCHK(h, hipSetDevice(h->device));
-    const int64_t k0 = k1 - 1;
-    double maxH = 0.0;
-    const int save_mode = h->mode;
-    h->mode = CDH_SWEEP_COORD;
-    int32_t rc = run_chunk(h, &k0, 1, &maxH);  // no dropzeros!: that is _cdPass!'s job
-    h->mode = save_mode;
-    if (rc != CDH_OK) return rc;
-    if (out_h) *out_h = h->h_hs[0];
-    return CDH_OK;
+    return descend(h, k1, out_h);
 }); }
 
 int32_t cdh_lambda_max(cdh_handle h, double* out) { return guarded(h, [&]() -> int32_t {
@@ -1210,127 +1046,15 @@ int32_t cdh_lambda_max(cdh_handle h, double* out) { return guarded(h, [&]() -> i
 }); }
 
 int32_t cdh_pass(cdh_handle h, int64_t m, const int64_t* idx1, double* out_maxH) { return guarded(h, [&]() -> int32_t {
-    if (m < 0) return fail(h, CDH_BAD_ARG, "m < 0");
-    CHK(exchange_alive(h));
-    if (m > 0) NEED_P(h, idx1);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::vector<int64_t> idx0((size_t)m);
-    CHK(check_columns(h, idx1, m));
-    for (int64_t i = 0; i < m; ++i) idx0[(size_t)i] = idx1[i] - 1;
-    double maxH = 0.0;
-    h->gc.st.unprepared();
-    if (m > 0) CHK(run_pass(h, idx0.data(), m, &maxH, h->screening >= 2));
-    else h->x.dropzeros();
-    if (out_maxH) *out_maxH = maxH;
-    return CDH_OK;
+    return pass(h, m, idx1, out_maxH);
 }); }
 
 int32_t cdh_solve(cdh_handle h, const cdh_options* opt, cdh_stats* out) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, opt);
-    CHK(exchange_alive(h));
-    HIPCHK(h, hipSetDevice(h->device));
-    cdh_stats st{};
-    if (small_applicable(h, opt)) {
-        CHK(small_prepare(h));
-        if (h->small.enabled) {     // (the preparation may find no room and switch the path off)
-            uint64_t rng = opt->seed;
-            const double lam = h->ctrl.lambda0;
-            int32_t rcs = small_solve(h, opt, &lam, 1, &rng, &st, false);
-            if (rcs != kSmallPrecisionLost) {
-                if (out) *out = st;
-                return rcs;
-            }
-            st = cdh_stats{};            // (r'r out of digits: the streamed kernels below take the call)
-        }
-    }
-    cdh::VisitScheduler sched(h->p, opt->randomize != 0, opt->seed);
-    const SmallRent rent(h, opt);
-    int32_t rc = solve(h, opt, sched, &st);
-    rent.pay(st);
-    if (out) *out = st;
-    return rc;
+    return solve_once(h, opt, out);
 }); }
 
 int32_t cdh_coordinate_descent(cdh_handle h, const cdh_options* opt, cdh_stats* out) { return guarded(h, [&]() -> int32_t {
-    NEED_P(h, opt);
-    CHK(exchange_alive(h));
-    HIPCHK(h, hipSetDevice(h->device));
-    cdh_stats st{};
-    cdh::VisitScheduler sched(h->p, opt->randomize != 0, opt->seed);
-    h->domain_error = false;
-    int32_t rc = CDH_OK;
-    bool small = small_applicable(h, opt, !opt->warmStart);   // a cold start is numSteps + 1 solves: it buys the Gram form outright
-    if (small) { CHK(small_prepare(h)); small = h->small.enabled; }
-    const SmallRent rent(h, opt);
-    uint64_t rng = opt->seed;       // the one-launch solve carries the scheduler's generator state itself
-    // ---- in one launch (small_solve.hpp) where the Gram form applies -- unless its r'r runs out of digits (kSmallPrecisionLost:
-    // nothing of the launch is used), in which case the streamed kernels below take the call ----
-    if (small && opt->warmStart) {
-        // initialize!(f, x) (:21) makes r = y - X x by definition: the one-launch solve derives its gradient from that
-        // identity (g = X'y - G x) and leaves the residual to be formed when somebody reads it
-        const double lam = h->ctrl.lambda0;
-        rc = small_solve(h, opt, &lam, 1, &rng, &st, true);
-    } else if (small) {
-        const double target = h->ctrl.lambda0;
-        h->x.clear();                                   // fill!(x, 0)           (:25)
-        HIPCHK(h, hipMemsetAsync(h->beta, 0, sizeof(double) * h->p, h->stream));
-        // _findLambdaMax (:29) at r = y: max_k |X_k'y| / n / omega_k (sqrt-lasso: / ||y||) -- from the cached X'y
-        double lmax = 0.0;
-        const double denom = h->loss == CDH_SQRT ? std::sqrt(h->small.yy) : (double)h->n_total;
-        for (int64_t k = 0; k < h->p; ++k) {
-            double t = std::fabs(-ColPairs(h->small.h_c).dot(k) / denom);
-            if (h->has_omega) t /= h->h_omega[(size_t)k];
-            if (t > lmax) lmax = t;
-        }
-        st.lambda_max = lmax;
-        const double l1 = std::log(lmax), l2 = std::log(target);
-        const double step = (l2 - l1) / (double)opt->numSteps;
-        if (step == 0.0 || step != step)
-            return fail(h, CDH_BAD_ARG, "cold start: the range log(lambda_max):step:log(lambda0) has a zero step");
-        std::vector<double> grid((size_t)opt->numSteps + 1);   // the numSteps + 1 solves of (:32-36) inside one launch
-        for (int64_t j = 0; j <= opt->numSteps; ++j) grid[(size_t)j] = std::exp((j == opt->numSteps) ? l2 : l1 + (double)j * step);
-        rc = small_solve(h, opt, grid.data(), (int)grid.size(), &rng, &st, true);
-    }
-    if (small && rc == kSmallPrecisionLost) { small = false; st = cdh_stats{}; rc = CDH_OK; }
-    if (small) {
-        // done above
-    } else if (opt->warmStart) {
-        // initialize!(f, x) (:21).  Optional shortcut for warm-started paths (LassoPath): the
-        // carried residual already equals y - X beta, so the rebuild only re-rounds it.
-        if (!(h->reuse_residual && h->rs.consistent())) CHK(rebuild_residual(h));
-        rc = solve(h, opt, sched, &st);
-    } else {
-        const double target = h->ctrl.lambda0;          // g itself is never mutated by the reference:
-        rc = [&]() -> int32_t {                         // whatever happens below, lambda0 is put back
-            h->x.clear();                               // fill!(x, 0)           (:25)
-            CHK(rebuild_residual(h));                   // initialize!(f, x)     (:26)
-            // 51 solves on the same X follow: the gradient cache (mode 1) need not wait for evidence
-            h->gc.full_seen = std::max<int64_t>(h->gc.full_seen, 1000);
-            double lmax = 0.0;
-            std::vector<double> dots;
-            CHK(lambda_max(h, &lmax, &dots));           // _findLambdaMax        (:29)
-            CHK(gc_adopt_dots(h, dots));                // ... whose pass over X is the cache's reference pass as well
-            st.lambda_max = lmax;
-            const double l1 = std::log(lmax), l2 = std::log(target);
-            const double step = (l2 - l1) / (double)opt->numSteps;
-            if (step == 0.0 || step != step)
-                return fail(h, CDH_BAD_ARG, "cold start: the range log(lambda_max):step:log(lambda0) has a zero step");
-            for (int64_t j = 0; j <= opt->numSteps; ++j) {  // (:32-36)
-                const double l = (j == opt->numSteps) ? l2 : l1 + (double)j * step;
-                h->ctrl.lambda0 = std::exp(l);
-                CHK(solve(h, opt, sched, &st));
-            }
-            return CDH_OK;
-        }();
-        h->ctrl.lambda0 = target;
-        if (rc == CDH_OK) {
-            CHK(upload_ctrl(h));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-        }
-    }
-    if (!small) rent.pay(st);
-    if (out) *out = st;
-    return rc;
+    return coordinate_descent(h, opt, out);
 }); }
 
 int32_t cdh_get_beta(cdh_handle h, double* out_p) { return guarded(h, [&]() -> int32_t {

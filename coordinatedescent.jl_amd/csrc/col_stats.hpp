@@ -247,14 +247,6 @@ int32_t lambda_max(cdh_handle h, double* out, std::vector<double>* dots /* the (
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->rs.dots_taken(cd, h->loss == CDH_WLS);   // (col_dots has brought r up to date first)
     if (h->loss == CDH_SQRT) denom = std::sqrt(resid_sums(h).sumsq);
-    const std::vector<double>& om = h->h_omega;
-    const ColPairs pairs(cd);
-    double lmax = 0.0;
-    for (int64_t k = 0; k < h->p; ++k) {
-        double t = std::fabs(-pairs.dot(k) / denom);
-        if (h->has_omega) t /= om[(size_t)k];
-        if (t > lmax) lmax = t;
-    }
-    *out = lmax;
+    *out = lambda_max_of(cd.data(), 2, h->p, denom, h->has_omega ? h->h_omega.data() : nullptr);   // the dots of the (X_k'r, a_k) pairs
     return CDH_OK;
 }

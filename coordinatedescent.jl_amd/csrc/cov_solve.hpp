@@ -1293,8 +1293,7 @@ int32_t cs_gate(cdh_handle h, const cdh_options* o, bool full, bool* go, double*
     if (o->randomize && h->p > kCsShuffleMaxP) return CDH_OK;
     double cert_abs = 0.0;
     if (full) {
-        // (the gate of run_pass: full passes over dense iterates are not screened at all)
-        if (!h->screening || h->x.nnz() * 4 > h->p) return CDH_OK;
+        if (!full_pass_screened(h, h->p)) return CDH_OK;               // the gate of run_pass, for the p visits of a full pass
         bool prepared = false;
         CHK(gc_prepare_full(h, &prepared, &cert_abs, false));       // the moves still pending on g go into the kernel with it
         c.st.prepared(prepared, cert_abs);                          // gc_full_pass, if it comes to that, does not prepare twice
@@ -1314,7 +1313,7 @@ int32_t cs_gate(cdh_handle h, const cdh_options* o, bool full, bool* go, double*
 }
 
 // What a launch leaves behind, taken over by the host: the iterate, the cache, the statistics.
-void cs_absorb(cdh_handle h, cdh::VisitScheduler& sched, cdh_stats* st, bool* prev_conv, bool* conv, int64_t* iter) {
+void cs_absorb(cdh_handle h, cdh::VisitScheduler& sched, cdh_stats* st, SolveProgress& at) {
     GradCache& c = h->gc;
     CovSolvePath& cp = h->cs;
     const CovSolveCtl& ctl = *cp.io.ctl;
@@ -1346,24 +1345,23 @@ void cs_absorb(cdh_handle h, cdh::VisitScheduler& sched, cdh_stats* st, bool* pr
     c.n_exact += ctl.cov_visits_full;
     if (ctl.domain_error) h->domain_error = true;
     sched.set_state(ctl.rng);
-    *prev_conv = ctl.prev_conv != 0; *conv = ctl.conv != 0; *iter += ctl.passes;
+    at.prev_converged = ctl.prev_conv != 0; at.converged = ctl.conv != 0; at.iter += ctl.passes;
     st->passes += ctl.passes; st->full_passes += ctl.full_passes; st->visits += ctl.visits;
     if (ctl.passes > 0) st->maxH = ctl.maxH;
 }
 
-// The passes of a solve from `*iter` on, on the device, as far as the gradient cache can serve them.
+// The passes of a solve from `at.iter` on, on the device, as far as the gradient cache can serve them.
 //   kCsFinished  the solve is over (converged, or maxIter passes done): statistics and the iterate are up to date
 //   kCsAgain     the kernel stopped for something the host has now supplied (Gram columns, a fresh g): call again
-//   kCsNotNow    the next pass runs the round-3 way (solve() below): the cache is not engaged, or the kernel undid a pass
-int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched, cdh_stats* st, bool* prev_conv, bool* conv,
-                  int64_t* iter, int* outcome) {
+//   kCsNotNow    the next pass runs the round-3 way (solve(), solve.hpp): the cache is not engaged, or the kernel undid a pass
+int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched, cdh_stats* st, SolveProgress& at, int* outcome) {
     GradCache& c = h->gc;
     CovSolvePath& cp = h->cs;
     *outcome = kCsNotNow;
     // ---- the gate ----
     bool go = false;
     double cert_abs = 0.0;
-    CHK(cs_gate(h, o, *conv, &go, &cert_abs));
+    CHK(cs_gate(h, o, at.converged, &go, &cert_abs));
     if (!go) return CDH_OK;
     // (from here on a "not now" hands the pass to the round-3 code, which expects the pending moves folded into g)
     auto not_now = [&]() -> int32_t { gc_fold(h); return CDH_OK; };
@@ -1373,10 +1371,9 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     // ---- the launch shape, once, for the LDS the launch will really have ----
     cs_probe_lds(cp);
     CsPlanIn in{};
-    in.p = h->p; in.nnz = h->x.nnz(); in.full = *conv; in.randomize = o->randomize != 0;
+    in.p = h->p; in.nnz = h->x.nnz(); in.full = at.converged; in.randomize = o->randomize != 0;
     in.lds_budget = cp.lds_budget; in.ucap_limit = h->knobs.cs_ucap; in.helpers = cp.helpers; in.big = cp.big;
-    in.support_limit = gc_max_support(h);
-    if (!(c.mode == 3 || gc_short_columns(h))) in.support_limit = std::min<int64_t>(in.support_limit, h->n_total / gc_rows_per_nnz(h));
+    in.support_limit = std::min<int64_t>(gc_max_support(h), gc_rows_limit(h));
     const CsPlan plan = cs_plan(in);
     if (!plan.run()) return not_now();
     CHK(cs_alloc(h));
@@ -1398,13 +1395,13 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
 
     CovSolveCtl& ctl = *cp.io.ctl;
     ctl.lambda0 = h->ctrl.lambda0; ctl.n_total = (double)h->n_total; ctl.optTol = o->optTol; ctl.cert_abs = cert_abs;
-    ctl.max_passes = o->maxIter - *iter;
+    ctl.max_passes = o->maxIter - at.iter;
     ctl.cov_budget = std::max<int64_t>(0, h->knobs.gc_refresh - c.st.cov_since_ref());
     ctl.loss = h->loss; ctl.has_omega = h->has_omega ? 1 : 0; ctl.randomize = o->randomize ? 1 : 0;
     ctl.nnz_limit = plan.nnz_limit; ctl.busy_limit = kGcBusy; ctl.inject_every = h->knobs.gc_inject_rollback; ctl.fold_limit = plan.fold_limit;
     ctl.tcap = plan.tcap; ctl.ncid = c.st.table_entries(); ctl.tepoch = cp.tepoch; ctl.full_cap = plan.full_cap; ctl.ucap_limit = in.ucap_limit;
     ctl.rng = sched.state(); ctl.q = c.st.q(); ctl.q_floor = h->loss == CDH_SQRT ? kGcQGuard * c.st.q_exact() : 0.0;
-    ctl.nnz = (int32_t)h->x.nnz(); ctl.prev_conv = *prev_conv ? 1 : 0; ctl.conv = *conv ? 1 : 0; ctl.inject_count = c.inject_count;
+    ctl.nnz = (int32_t)h->x.nnz(); ctl.prev_conv = at.prev_converged ? 1 : 0; ctl.conv = at.converged ? 1 : 0; ctl.inject_count = c.inject_count;
     ctl.status = -1; ctl.n_list = 0;
     const cdh::MoveLedger& moved = c.st.moved();
     ctl.n_moved = (int32_t)moved.size();        // in: the moves still pending on g (out: those pending when the kernel stops)
@@ -1419,7 +1416,7 @@ int32_t cov_solve(cdh_handle h, const cdh_options* o, cdh::VisitScheduler& sched
     HIPCHK(h, hipStreamSynchronize(h->stream));
     cp.n_launches += 1;
     if (ctl.status < 0) return fail(h, CDH_HIP_ERROR, "the device-resident solve returned no status");
-    cs_absorb(h, sched, st, prev_conv, conv, iter);
+    cs_absorb(h, sched, st, at);
 
     switch (ctl.status) {
     case kCsConverged: st->converged = 1; *outcome = kCsFinished; return CDH_OK;

@@ -1,12 +1,53 @@
 // grad_cache.hpp -- the gradient cache's passes: a section of cdhip.hip kept in its own file (included
 // once, inside cdhip.hip's anonymous namespace, after the handle, col_dots, allreduce and the grid helpers
-// it uses; run_chunk is defined further down in cdhip.hip).  The bookkeeping half (what invalidates the
-// cache, how moves are noted) stays next to the code that triggers it in cdhip.hip.
+// it uses; run_chunk is sweep.hpp's).  The bookkeeping half (what invalidates the cache, how moves are
+// noted) stays next to the code that triggers it in cdhip.hip; when the cache is admitted stands at the head.
 //
 // What it replaces: the n-sized reads of X that the reference's full passes spend on coordinates that do not
 // move (coordinate_descent.jl:94-110 over 1..p with descendCoordinate!'s dots, cd_differentiable_function.jl:
 // 94-99).  No reference counterpart; same iterates.  Design and measurements: DESIGN.md section 5a.
 #pragma once
+
+// ---- when the cache is admitted -------------------------------------------------------------------------------------------
+constexpr int kGcEngage = 3;        // mode 1: this many screened full passes run the plain way first
+constexpr int kGcBusy = 64;         // more inactive coordinates than this about to move: a plain pass is cheaper
+constexpr int kGcMaxFetch = 64;     // more uncached movers than this: re-reference instead of fetching their columns
+constexpr int kGcMaxSupport = 512;  // supports beyond this are not worth Gram columns
+constexpr size_t kGcMaxBytes = (size_t)1 << 30;
+constexpr int64_t kGcCovWindow = 2048;      // positions one covariance-form chunk of a full pass may span
+constexpr int64_t kGcRowsPerNnz = 400;   // rows the problem must have per non-zero for the HOST-side fold and re-check to pay ...
+constexpr int64_t kGcRowsPerNnzDev = 32; // ... and when the passes run on the device (round 3: g, the fold and the re-check never leave it)
+inline int64_t gc_rows_per_nnz(const cdh_handle_s* h) {
+    const GradCache& c = h->gc;
+    if (h->knobs.gc_rows_per_nnz > 0) return h->knobs.gc_rows_per_nnz;   // tests
+    return (c.cov && (c.d_scan || c.g.empty())) ? kGcRowsPerNnzDev : kGcRowsPerNnz;   // (before the first sizing: assume the device path)
+}
+
+// When the support has outgrown what the cache pays for.  Long columns: a support column costs 1/32 of a pass over X to fetch
+// and p doubles per move to apply, against the read of X a cached full pass saves -- the cache stands aside once n < 32 nnz
+// (400 nnz while the fold and the re-check ran on the host), and beyond kGcMaxSupport columns.  SHORT columns (a streamed
+// visit is launch-bound there: ~0.35 us as its share of a block of 64 whatever it reads, against ~0.13 us in covariance form,
+// and fetching a batch of columns is a pass over a small X) keep the cache whatever n / nnz is, up to kGcMaxSupportShort
+// columns: benchmark/cd_bench.jl's n = 3000, p = 5000 path down to 0.03 lambda_max (774 non-zeros) 0.204 -> 0.118 s with the
+// rule off below 512 columns, before the cap was raised.
+constexpr int kGcMaxSupportShort = 4096;
+constexpr size_t kGcShortColumnBytes = (size_t)1 << 20;
+inline bool gc_short_columns(const cdh_handle_s* h) {
+    return h->gc.cov && (h->gc.d_scan || h->gc.g.empty()) && (size_t)h->n * h->esz <= kGcShortColumnBytes;
+}
+inline int64_t gc_rows_limit(const cdh_handle_s* h) {            // the rows-per-non-zero rule (modes 1 and 2), as a support size
+    return rows_support_limit(h->n_total, gc_rows_per_nnz(h), h->gc.mode == 3 || gc_short_columns(h));
+}
+inline bool gc_support_outgrown(const cdh_handle_s* h) { return h->x.nnz() > gc_rows_limit(h); }
+inline int64_t gc_max_support(const cdh_handle_s* h) { return gc_short_columns(h) ? kGcMaxSupportShort : kGcMaxSupport; }
+
+// every loss and both storage types (round 3); a weighted loss only once its weights are there (they are zero until
+// cdh_set_obs_weights: every a_k would be zero and nothing could be settled)
+inline bool gc_applicable(const cdh_handle_s* h) { return h->gc.mode != 0 && weights_ready(h->loss == CDH_WLS, h->has_w); }
+// is a full pass of m visits screened (by the dots, or from the cache)?
+inline bool full_pass_screened(const cdh_handle_s* h, int64_t m) {
+    return screen_gate(h->screening, h->loss == CDH_WLS, h->has_w, m, h->x.nnz(), h->p);
+}
 
 void gc_fold(cdh_handle h);
 int32_t finish_chunk(cdh_handle h, const int64_t* idx0, int m, double* maxH);
@@ -767,7 +808,7 @@ int32_t gc_prepare_full(cdh_handle h, bool* go, double* cert_abs_out, bool fold 
     // paid that much in plain full passes on the same data: at most twice the cost of having known in advance
     const int64_t rent = std::max<int64_t>(kGcEngage, 1 + (3 * h->x.nnz()) / 64);
     if (!gc_applicable(h) || (c.mode == 1 && !c.st.valid() && c.full_seen <= rent)) return CDH_OK;
-    // the support has outgrown what the cache pays for (gc_support_outgrown, cdhip.hip: long columns only)
+    // the support has outgrown what the cache pays for (gc_support_outgrown: long columns only)
     if (gc_support_outgrown(h)) {
         if (c.st.valid()) gc_invalidate(h, false);
         return CDH_OK;

@@ -341,21 +341,13 @@ int32_t quad_coordinate_descent(cdh_quad q, const cdh_options* o, cdh_stats* out
         QCHK(hipGetLastError());
     } else {
         // fill!(x, 0); initialize!: g = b (:25-26); _findLambdaMax (:29) = max_k |b_k| / omega_k; the numSteps + 1 solves down the
-        // log grid (:32-36) inside the launch, the grid built as cdh_coordinate_descent builds it
+        // log grid (:32-36) inside the launch
         std::vector<double> grid(m * kQuadMaxLam, 0.0);
         for (size_t j = 0; j < m; ++j) {
             const double* om = q->has_omega ? q->h_omega.data() + (q->omega_shared ? 0 : j * p) : nullptr;
-            for (size_t k = 0; k < p; ++k) {
-                double t = std::fabs(q->h_B[j * p + k]);
-                if (om) t /= om[k];
-                if (t > lmax[j]) lmax[j] = t;
-            }
-            const double l1 = std::log(lmax[j]), l2 = std::log(q->h_lambda0[j]);
-            const double step = (l2 - l1) / (double)o->numSteps;
-            if (step == 0.0 || step != step)
+            lmax[j] = lambda_max_of(q->h_B.data() + j * p, 1, q->p, 1.0, om);
+            if (!cold_start_grid(lmax[j], q->h_lambda0[j], o->numSteps, grid.data() + j * kQuadMaxLam))
                 return quad_fail(CDH_BAD_ARG, "cold start: the range log(lambda_max):step:log(lambda0) of a problem has a zero step");
-            for (int64_t s = 0; s <= o->numSteps; ++s)
-                grid[j * kQuadMaxLam + (size_t)s] = std::exp((s == o->numSteps) ? l2 : l1 + (double)s * step);
         }
         QCHK(hipMemcpyAsync(q->grid, grid.data(), sizeof(double) * grid.size(), hipMemcpyHostToDevice, q->stream));
         QCHK(hipStreamSynchronize(q->stream));        // (grid is a local: the copy has read it before it goes)

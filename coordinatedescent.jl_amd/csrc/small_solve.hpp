@@ -452,7 +452,7 @@ inline double small_build_estimate(const cdh_handle_s* h) {
 }
 inline bool small_candidate(const cdh_handle_s* h, const cdh_options* o) {      // everything but the rent-or-buy decision
     return h->small.enabled && !h->xs.sharded() && h->p <= kSmallMaxP &&
-           h->gc.mode != 3 /* tests force the gradient cache's own path with mode 3 */ && (h->loss != CDH_WLS || h->has_w) &&
+           h->gc.mode != 3 /* tests force the gradient cache's own path with mode 3 */ && weights_ready(h->loss == CDH_WLS, h->has_w) &&
            o->numSteps + 1 <= kSmallMaxLam && o->numSteps >= 1;
 }
 inline bool small_applicable(const cdh_handle_s* h, const cdh_options* o, bool many_solves = false) {

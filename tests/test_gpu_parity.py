@@ -753,6 +753,118 @@ def test_screened_full_passes_match_oracle_and_unscreened(loss, rand):
     assert outs[0][2] == outs[1][2]                  # same number of passes with and without
 
 
+_SCREEN_EDGE = {}
+
+
+def _screen_edge_case(p, rand):
+    """n = 200 rows, non-zero columns at visit positions 0, 63, 64 and p - 1 where p has them; the oracle's two solves, once."""
+    if (p, rand) not in _SCREEN_EDGE:
+        rng = np.random.default_rng(300 + p)
+        planted = sorted({k for k in (0, 63, 64, p - 1) if k < p})
+        X = np.asfortranarray(rng.standard_normal((200, p)))
+        Y = X[:, planted] @ (4.0 * rng.choice([-1.0, 1.0], len(planted))) + 0.1 * rng.standard_normal(200)
+        o = dict(maxIter=2000, optTol=1e-12, randomize=rand, seed=11)
+        xo, fo = O.SparseIterate(p), O.CDLeastSquaresLoss(Y, X)
+        O.coordinateDescent_(xo, fo, O.ProxL1(0.5), O.CDOptions(**o))
+        first = xo.nzval2ind.tolist()
+        sto = O.coordinateDescent_(xo, fo, O.ProxL1(0.35), O.CDOptions(**o))
+        _SCREEN_EDGE[(p, rand)] = (X, Y, o, planted, first, xo.dense(), xo.nzval2ind.tolist(), sto["passes"], fo.r.copy())
+    return _SCREEN_EDGE[(p, rand)]
+
+
+@pytest.mark.parametrize("p", [15, 16, 64, 65, 193])
+@pytest.mark.parametrize("rand", [False, True], ids=["ordered", "random"])
+def test_screened_full_passes_at_the_walks_edges(p, rand):
+    """The screens of a full pass where their walk turns: a pass shorter than one screen, exactly one, one visit more, three
+    and a visit; movers at the first visit, at the last of the first screen, at the first of the second and at the last of the
+    pass.  Streamed solves (no one-launch solve), with the dots-only screens (cache 0) and from the gradient cache (mode 3);
+    p = 15 is below kScreenMinPass (nothing is screened: the cache never sees a pass), p = 16 is the first that is."""
+    X, Y, o, planted, first, beta_o, sup_o, passes_o, r_o = _screen_edge_case(p, rand)
+    assert sorted(k - 1 for k in first) == planted and sorted(k - 1 for k in sup_o) == planted and len(planted) * 4 <= p
+    for cache in (0, 3):
+        outs = []
+        for screen in (True, False):
+            f = cd.CDLeastSquaresLoss(Y, X)
+            f.set_onchip_solve(False)
+            f.set_gradient_cache(cache)
+            f.set_sweep_mode("block", 16)
+            f.set_screening(screen)
+            x = cd.SparseIterate(p)
+            cd.coordinateDescent_(x, f, cd.ProxL1(0.5), cd.CDOptions(**o))
+            # warm start from the solution at a larger lambda: first full pass over a sparse iterate
+            cd.coordinateDescent_(x, f, cd.ProxL1(0.35), cd.CDOptions(**o))
+            outs.append((x.dense(), x.nzval2ind.tolist(), f.last_stats["passes"], f.r))
+            assert f.onchip_stats()["solves"] == 0
+            if cache == 3:
+                assert (f.cache_stats()["passes"] > 0) == (screen and p >= 16), (p, screen, f.cache_stats())
+            f.close()
+        for beta, sup, passes, r in outs:
+            np.testing.assert_allclose(beta, beta_o, rtol=0, atol=BETA_TOL)
+            assert sup == sup_o                          # same support ORDER: same bookkeeping replayed
+            np.testing.assert_allclose(r, r_o, rtol=0, atol=1e-9)
+            assert passes == passes_o
+        assert outs[0][2] == outs[1][2]                  # same number of passes with and without
+
+
+def _raw_coordinate_descent(f, options):
+    """cdh_coordinate_descent at whatever penalty the handle holds (coordinateDescent_ would send one first)."""
+    o, st = options._c(), cd._lib.cdh_stats()
+    status = f._L.cdh_coordinate_descent(f._h, cd._lib.C.byref(o), cd._lib.C.byref(st))
+    return status, st
+
+
+@pytest.mark.parametrize("route", ["streamed", "one-launch"])
+def test_cold_start_down_to_lambda_max_itself_is_refused(route):
+    """log(lambda_max):step:log(lambda0) with lambda0 == lambda_max has a zero step (the reference's range throws): CDH_BAD_ARG
+    from the one-launch cold start and from the streamed one, with lambda_max taken from a first cold start of the same handle
+    (it comes out bit for bit the same).  The streamed route leaves the caller's lambda0 in place: a warm solve straight after
+    runs at it."""
+    rng, X, Y = _problem(77, 200, 40, 4, noise=0.5)
+    cold = dict(maxIter=500, optTol=1e-12, randomize=False, warmStart=False, numSteps=5)
+    f = cd.CDLeastSquaresLoss(Y, X)
+    f.set_onchip_solve(route == "one-launch")
+    if route == "one-launch":
+        f.set_gradient_cache(1)         # (mode 3 keeps the one-launch solve out: the cache's own passes are forced then)
+    x = cd.SparseIterate(40)
+    cd.coordinateDescent_(x, f, cd.ProxL1(0.05), cd.CDOptions(**cold))
+    lmax = f.last_stats["lambda_max"]
+    assert x.nnz > 0 and lmax > 0.05 and f.onchip_stats()["solves"] == (6 if route == "one-launch" else 0)     # numSteps + 1
+    with pytest.raises(cd.ArgumentError, match=r"cold start: the range log\(lambda_max\):step:log\(lambda0\) has a zero step"):
+        cd.coordinateDescent_(x, f, cd.ProxL1(lmax), cd.CDOptions(**cold))
+    f._set_penalty(cd.ProxL1(lmax))
+    status, st = _raw_coordinate_descent(f, cd.CDOptions(**cold))
+    assert status == cd._lib.CDH_BAD_ARG and b"has a zero step" in f._L.cdh_last_error(f._h)
+    assert st.lambda_max == (lmax if route == "streamed" else 0.0)      # (the streamed route reports what it refused; the same bits twice)
+    if route == "streamed":
+        # the handle's iterate is the zero the refused cold start left; the penalty is still the caller's lambda_max
+        warm = cd.CDOptions(maxIter=500, optTol=1e-12, randomize=False)
+        status, st = _raw_coordinate_descent(f, warm)
+        assert status == cd._lib.CDH_OK
+        f._pull(x)
+        f2, x2 = cd.CDLeastSquaresLoss(Y, X), cd.SparseIterate(40)
+        f2.set_onchip_solve(False)
+        cd.coordinateDescent_(x2, f2, cd.ProxL1(lmax), warm)
+        # at lambda_max the solution is zero but for the arg-max's rounding; at any smaller lambda0 it would not be
+        np.testing.assert_allclose(x.dense(), x2.dense(), rtol=0, atol=BETA_TOL)
+        assert st.passes == f2.last_stats["passes"] and st.converged == 1 and x.nnz <= 1 and np.max(np.abs(x.dense())) <= BETA_TOL
+        f2.close()
+    f.close()
+
+
+def test_quad_cold_start_down_to_lambda_max_itself_is_refused():
+    rng = np.random.default_rng(78)
+    M = rng.standard_normal((60, 12))
+    A, b = M.T @ M / 60.0, rng.standard_normal(12)
+    cold = dict(maxIter=500, optTol=1e-12, randomize=False, warmStart=False, numSteps=5)
+    f, x = cd.CDQuadraticLoss(A, b), cd.SparseIterate(12)
+    cd.coordinateDescent_(x, f, cd.ProxL1(0.05), cd.CDOptions(**cold))
+    lmax = f.last_stats["lambda_max"]
+    assert lmax == np.max(np.abs(b)) and x.nnz > 0
+    with pytest.raises(cd.ArgumentError, match=r"cold start: the range log\(lambda_max\):step:log\(lambda0\) of a problem has a zero step"):
+        cd.coordinateDescent_(x, f, cd.ProxL1(lmax), cd.CDOptions(**cold))
+    f.close()
+
+
 def test_zero_column_is_handled_like_the_oracle():
     """A zero column makes x[k] += b/a a 0/0 (the reference has no guard).  What
     ProximalBase's cdprox! then does with the NaN is not pinned by any reference test; oracle and
