@@ -22,6 +22,8 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   LogisticLassoSolution, LogisticLassoPathResult, cvLogisticLassoPath, CVLogisticLassoPathResult,
                   CDPoissonLoss, poissonLasso_, poissonLasso, poissonLambdaMax, PoissonLassoPath, PoissonLassoSolution,
                   PoissonLassoPathResult, cvPoissonLassoPath, CVPoissonLassoPathResult,
+                  CDCoxLoss, coxLasso_, coxLasso, coxLambdaMax, CoxLassoPath, CoxLassoSolution,
+                  CoxLassoPathResult, cvCoxLassoPath, CVCoxLassoPathResult,
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
                   get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
                   getSigma, findInitResiduals_,

@@ -631,6 +631,94 @@ class CDPoissonLoss(_GLMLoss):
         return self.irls_step(apply, irls.wmin, irls.etaMax, fold)
 
 
+def _survival(y, n=None):
+    """y = [time, status] (n x 2, glmnet's Surv matrix) -> (time, status) as contiguous float64 vectors, refused on the host
+    the way cdh_glm_set_survival would refuse them."""
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 2 or y.shape[1] != 2:
+        raise DimensionMismatch("y must be n x 2: [time, status]")
+    if n is not None and y.shape[0] != n:
+        raise DimensionMismatch("size(y, 1) != size(X, 1)")
+    time, status = np.ascontiguousarray(y[:, 0]), np.ascontiguousarray(y[:, 1])
+    if not np.all(np.isfinite(time)):
+        raise ArgumentError("time[%d] is not finite" % int(np.nonzero(~np.isfinite(time))[0][0]))
+    bad = (status != 0.0) & (status != 1.0)
+    if np.any(bad):
+        raise ArgumentError("status[%d] is neither 0 (censored) nor 1 (event)" % int(np.nonzero(bad)[0][0]))
+    if not np.any(status == 1.0):
+        raise ArgumentError("no row is an event: the partial likelihood is constant")
+    return time, status
+
+
+class CDCoxLoss(_GLMLoss):
+    """CDCoxLoss(y, X, offset=None): -(1/n) Σ δ_i (η_i - log S_i), η = Xβ + o, S_i = Σ_{t_j >= t_i} e^η_j -- the negative log
+    partial likelihood of the Cox model with Breslow ties (glmnet's family = "cox"); y is n x 2, [time, status], status 1 an
+    event and 0 censored; no reference counterpart.  Minimised by IRLS like its siblings CDLogisticLoss and CDPoissonLoss: a
+    round is the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the working response and
+    weights the handle's y and w hold from one irls_step to the next.  The step is not elementwise: the risk-set sums are
+    scans in time order, run on the device through the order cdh_glm_set_survival keeps; the rows stay in the caller's order.
+    There is no intercept (it cancels), and no strata, start-stop times, Efron ties or observation weights.  fp64 only, one
+    device."""
+
+    def __init__(self, y, X, offset=None, *, device=0):
+        self._time, status = _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
+        if offset is not None and not np.all(np.isfinite(np.asarray(offset, dtype=np.float64))):
+            raise ArgumentError("the offset is not finite")
+        super().__init__(status, X, offset, device=device)
+        del self._time
+
+    def _set_observations(self, status, off):
+        check(self._L.cdh_glm_set_survival(self._h, _vp(self._time), _vp(status), _vp(off)), self._h)
+
+    def _get_survival(self, which):
+        out = np.zeros(self.n)
+        args = (_vp(out), None) if which == 0 else (None, _vp(out))
+        check(self._L.cdh_glm_get_survival(self._h, *args), self._h)
+        return out
+
+    time = property(lambda self: self._get_survival(0), doc="The times, in the caller's row order.")
+    status = property(lambda self: self._get_survival(1), doc="The statuses: 1 an event, 0 censored.")
+    offset = CDPoissonLoss.offset
+
+    def _step(self, apply, wmin, eta_max, k):
+        out = np.zeros(5)
+        check(self._L.cdh_glm_cox_irls(self._h, int(k), 1 if apply else 0, float(wmin), float(eta_max),
+                                       out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        return out
+
+    @staticmethod
+    def _record(out, n):
+        return {"nll": float(out[0]) / n, "sum_w": float(out[1]), "clamped": int(out[2]), "capped": int(out[3]),
+                "events": int(out[4])}
+
+    def irls_step(self, apply=True, wmin=1e-5, eta_max=50.0, fold=None):
+        """One IRLS step at the iterate the handle holds (cdh_glm_cox_irls).  apply=True turns the handle's y, w and r into the
+        working response (without the offset), the working weights (e A - e² B, clamped below at wmin; η capped above at
+        eta_max) and their residual; apply=False only reads.  Returns {"nll": (1/n) Σ δ_i (log S_i - η_i), "sum_w": Σ w_i,
+        "clamped": rows whose weight was clamped (the rows before the first event always are), "capped": rows whose η was
+        capped, "events": Σ δ_i}, the sums over the training rows ("capped" over all rows).
+
+        fold=k (after set_folds): the rows of fold k are held out -- they leave the risk sets and the event sums, and get
+        w = 0, z = Xβ, r = 0."""
+        k = -1 if fold is None else int(fold)
+        if k < 0 and fold is not None:
+            raise ArgumentError("fold must be a fold id")
+        return self._record(self._step(apply, wmin, eta_max, k), self.n)
+
+    def _irls(self, apply, irls, fold):
+        """The step as the IRLS loop calls it.  Read-only with a fold it runs twice, with fold k held out and with nobody held
+        out, and adds "held_deviance" = -2 (ℓ_all - ℓ_train), glmnet's grouped partial-likelihood deviance of the held-out
+        rows (a sum), and "held_events", the events among them."""
+        if fold is None or apply:
+            return self.irls_step(apply, irls.wmin, irls.etaMax, fold)
+        train = self._step(False, irls.wmin, irls.etaMax, int(fold))
+        every = self._step(False, irls.wmin, irls.etaMax, -1)
+        res = self._record(train, self.n)
+        res["held_deviance"] = 2.0 * (float(every[0]) - float(train[0]))
+        res["held_events"] = int(every[4]) - int(train[4])
+        return res
+
+
 # --------------------------------------------------------------------------------------
 # Smoothing kernels (src/varying_coefficient_lasso.jl:3-21)
 # --------------------------------------------------------------------------------------
@@ -1666,6 +1754,59 @@ class CVPoissonLassoPathResult:
     fold_paths: list = None
 
 
+@dataclass
+class CoxLassoSolution:
+    """What coxLasso_ and coxLasso return.  nll is (1/n) Σ δ_i (log S_i - η_i) over the training rows at the final β and
+    events the events among them; capped counts the rows whose η the final step capped at etaMax; monotone is False if the
+    penalised objective F rose between two rounds by more than 1e-10 max(1, F) (there is no step halving: the rise is only
+    reported).  With fold=k: held_deviance = -2 (ℓ_all - ℓ_train) and held_events, the events among the held-out rows."""
+    x: SparseIterate
+    nll: float
+    rounds: int
+    converged: bool
+    monotone: bool
+    capped: int = 0
+    events: int = 0
+    penalty: ProxL1 = None
+    held_deviance: float = None
+    held_events: int = None
+
+
+@dataclass
+class CoxLassoPathResult(LassoPathResult):
+    """LassoPathResult with, per λ, the nll at the solution, the IRLS rounds taken and convergence (intercepts: None
+    throughout -- the Cox model has none)."""
+    nll: list = None
+    rounds: list = None
+    converged: list = None
+    intercepts: list = None
+
+
+@dataclass
+class CVCoxLassoPathResult:
+    """What cvCoxLassoPath returns.  Per fold k and λ_j, by the path fitted without the rows of fold k:
+    fold_deviance[k, j] = -2 (ℓ_all - ℓ_train) / (held-out events of fold k), ℓ the log partial likelihood of all rows and of
+    the training rows at that β; train_deviance[k, j] = -2 ℓ_train / (training events); rounds and converged of its IRLS
+    loop.  cvm, cvsd and the two selections (0-based positions in lambdapath) are taken from fold_deviance, the folds
+    weighted by their held-out events (fold_events)."""
+    lambdapath: np.ndarray
+    fold_sizes: np.ndarray
+    fold_deviance: np.ndarray
+    train_deviance: np.ndarray
+    rounds: np.ndarray
+    converged: np.ndarray
+    measure: str
+    cvm: np.ndarray
+    cvsd: np.ndarray
+    index_min: int
+    lambda_min: float
+    index_1se: int
+    lambda_1se: float
+    path: CoxLassoPathResult = None
+    fold_paths: list = None
+    fold_events: np.ndarray = None
+
+
 def _penalty_value(g, beta):
     return g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
 
@@ -1740,6 +1881,7 @@ class _GLMFamily:
     cv_result: type
     cv_measures: dict            # measure -> (sol, size_k) -> its value over the held-out rows; the first is fold_deviance
     cv_train: object             # (sol, n, n_k) -> train_deviance
+    cv_weight: object = None     # sol -> the fold's weight in cvm and cvsd (None: the fold's size)
 
 
 _LOGISTIC = _GLMFamily(
@@ -1760,6 +1902,16 @@ _POISSON = _GLMFamily(
     cv_result=CVPoissonLassoPathResult,
     cv_measures={"deviance": lambda sol, size: sol.held_deviance / size},
     cv_train=lambda sol, n, nk: sol.deviance / nk)
+
+_COX = _GLMFamily(
+    name="cox", loss=CDCoxLoss, start=None, observed=lambda f: (f.status, f.offset), start_before_upload=False,
+    solution=lambda x, last, rounds, converged, monotone, g: CoxLassoSolution(
+        x, last["nll"], rounds, converged, monotone, last["capped"], last["events"], g, last.get("held_deviance"),
+        last.get("held_events")),
+    path_result=CoxLassoPathResult, path_fields=("nll", "rounds", "converged"), cv_result=CVCoxLassoPathResult,
+    cv_measures={"deviance": lambda sol, size: sol.held_deviance / sol.held_events},
+    cv_train=lambda sol, n, nk: 2.0 * n * sol.nll / sol.events,
+    cv_weight=lambda sol: sol.held_events)
 
 
 def _glm_solve(fam, x, f, g, options, irls, fold):
@@ -1899,6 +2051,7 @@ def _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standa
     held, tdev = {name: np.zeros((K, m)) for name in fam.cv_measures}, np.zeros((K, m))
     rounds, conv = np.zeros((K, m), dtype=np.int64), np.zeros((K, m), dtype=bool)
     fold_paths = [] if keep_fold_paths else None
+    wts = sizes if fam.cv_weight is None else np.zeros(K)
     if fit_intercept and obs is None:
         obs, off = fam.observed(f)                       # (a loss that was passed in has no intercept: not reached in practice)
     # The path on all rows.  On the handle this call has just made it runs FIRST: the very calls the family's path makes on a
@@ -1930,6 +2083,8 @@ def _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standa
                     held[name][k, j] = value(sol, sizes[k])
                 tdev[k, j] = fam.cv_train(sol, n, nk)
                 rounds[k, j], conv[k, j] = sol.rounds, sol.converged
+                if fam.cv_weight is not None:
+                    wts[k] = fam.cv_weight(sol)
                 if keep_fold_paths:
                     _glm_keep(fam, res, sol, x, p, fit_intercept, nll=sol.nll * n / nk)
             if keep_fold_paths:
@@ -1939,7 +2094,7 @@ def _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standa
         if mode_before == 1:
             check(f._L.cdh_set_gradient_cache(f._h, 1), f._h)
         f.set_folds(None, 0)
-    cvm, cvsd, imin, i1se = _cv_select(lam, sizes, held[measure])
+    cvm, cvsd, imin, i1se = _cv_select(lam, wts, held[measure])
     if full_path and not owned:
         path = _glm_path_on(fam, f, lam, options, irls, np.inf, standardizeX, fit_intercept)
     dev, *others = held.values()
@@ -2084,6 +2239,87 @@ def cvPoissonLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=No
     as PoissonLassoPathResult (None unless keep_fold_paths)."""
     return _cv_glm_path(_POISSON, X, y, lambdapath, K, folds, options, irls, standardizeX, fit_intercept, seed, measure, offset,
                         full_path, keep_fold_paths)
+
+
+# ---- the Cox family, Breslow ties ------------------------------------------------------------------------------------------
+def coxLasso_(x, f, g, options=None, irls=None, fold=None):
+    """Minimise F(β) = -(1/n) Σ δ_i (η_i - log S_i) + λ0 Σ ω_j |β_j|, η = Xβ + o, over the CDCoxLoss f by IRLS, warm-started
+    from x (updated in place): logisticLasso_'s loop with f.irls_step of the Cox family (irls.wmin, irls.etaMax).  fold=k:
+    every step holds the rows of fold k out of the risk sets and the event sums, F is (1/n) Σ over the training rows, and the
+    solution carries held_deviance = -2 (ℓ_all - ℓ_train) and held_events at the final β."""
+    return _glm_solve(_COX, x, f, g, options, irls, fold)
+
+
+def coxLasso(X, y, lam, omega=None, options=None, irls=None, offset=None):
+    """ℓ1-penalised Cox regression with Breslow ties (glmnet's family = "cox"): the minimiser of
+    -(1/n) Σ δ_i (η_i - log S_i) + λ Σ ω_j |β_j|, η = Xβ + o, y = [time, status] (n x 2).  There is no intercept: it cancels
+    in the partial likelihood.  X may also be an existing CDCoxLoss (y and offset are then its own)."""
+    if not isinstance(X, CoordinateDifferentiableFunction):
+        _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
+    return _glm_lasso(_COX, X, y, lam, omega, options, irls, False, offset)
+
+
+def coxLambdaMax(f, omega=None):
+    """The smallest λ at which every coordinate of the Cox lasso is zero: max_j |X_j'(δ - eA)| / (n ω_j) at β = 0.
+    poissonLambdaMax's recipe: one applied irls_step at β = 0 leaves r = (δ - eA) / w, and the weighted gradient of the
+    handle (cdh_lambda_max: X_j'W r / n) is X_j'(δ - eA) / n whatever the clamp did to w.  The handle is left at β = 0, with
+    the penalty scales of the maximum."""
+    if not isinstance(f, CDCoxLoss):
+        raise TypeError("MethodError: coxLambdaMax takes a CDCoxLoss")
+    x = SparseIterate(f.p)
+    om = None if omega is None else np.asarray(omega, dtype=np.float64)[:f.p]
+    f._push(x, rebuild=True)
+    f._synced = None
+    f.irls_step(True, 1e-300)
+    f._set_penalty(ProxL1(1.0, om))
+    out = C.c_double()
+    check(f._L.cdh_lambda_max(f._h, C.byref(out)), f._h)
+    return out.value
+
+
+def CoxLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, offset=None):
+    """LassoPath's loop (src/lasso.jl:229-260) with coxLasso_ per λ: one handle, one x warm-started along λ,
+    ω = _stdX!(X) (cdh_col_rms) when standardising.  βpath[i] has length p."""
+    if not isinstance(X, CoordinateDifferentiableFunction):
+        _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
+    return _glm_path(_COX, X, y, lambdapath, options, irls, max_hat_s, standardizeX, False, offset)
+
+
+def cvCoxLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, seed=0, measure="deviance",
+                   offset=None, full_path=True, keep_fold_paths=False):
+    """K-fold cross-validation of CoxLassoPath(X, y, λpath, options, irls; standardizeX, offset) on the device (glmnet's
+    cv.glmnet(family = "cox", grouped = TRUE)); no reference counterpart.  X may also be an existing CDCoxLoss (y and offset
+    are then its own); the design is uploaded once.
+
+    cvLogisticLassoPath's structure: a fold is a 0/1 observation weight, and irls_step(fold=k) takes the held-out rows out
+    of the risk sets and the event sums and keeps them at w = 0, z = Xβ.  The Cox lasso on the n_k training rows of fold k
+    alone, at λ, has the iterates of that loop at λ·sqrt(n_k / n) with ω = _stdX!(w, X) of the 0/1 weights
+    (standardizeX=False: ω = 1 and λ·n_k / n): the loss is (1/n) Σ here and (1/n_k) Σ there.  The read-only steps that end
+    every solve give fold_deviance[k, j] = -2 (ℓ_all - ℓ_train) / (held-out events of fold k), the only measure; cvm and cvsd
+    weight the folds by those event counts.  A fold without a held-out event, or without a training event, is refused
+    before the upload.  Nothing n-sized moves after the upload.
+
+    folds: 0-based ids, one per row; otherwise np.random.default_rng(seed).permutation(n) % K.  There is no max_hat_s.  The
+    folds are dropped when the call returns or raises.  `path` is CoxLassoPath on all rows (None with full_path=False):
+    from a matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was
+    passed in it runs after them.  `fold_paths`: the K fold paths as CoxLassoPathResult (None unless keep_fold_paths)."""
+    if isinstance(X, CDCoxLoss):
+        status = X.status
+    elif isinstance(X, CoordinateDifferentiableFunction):
+        raise TypeError("MethodError: cvCoxLassoPath takes a matrix or a CDCoxLoss")
+    else:
+        _, status = _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
+    ids, sizes = _cv_fold_ids(len(status), K, folds, seed)
+    events = np.bincount(ids, weights=status, minlength=len(sizes)).astype(np.int64)
+    for k in range(len(sizes)):
+        if events[k] == 0:
+            raise ArgumentError("fold %d holds no event: its held-out deviance is undefined" % k)
+        if events[k] == events.sum():
+            raise ArgumentError("fold %d holds every event: its training rows have none" % k)
+    res = _cv_glm_path(_COX, X, y, lambdapath, K, folds, options, irls, standardizeX, False, seed, measure, offset,
+                       full_path, keep_fold_paths)
+    res.fold_events = events
+    return res
 
 
 # --------------------------------------------------------------------------------------

@@ -301,13 +301,21 @@ struct CvState {
 // The logistic loss (glm_kernels.hpp): the labels of the rows, resident from cdh_glm_set_labels on in a buffer of the handle's
 // own -- y holds the working response of the IRLS round, not the labels.  glm_plan.hpp: the grid and the rows of a workgroup.
 #include "glm_plan.hpp"
-enum class GlmData : int { Binomial = 0, Poisson = 1 };
+#include "cox_plan.hpp"   // the Cox step's tiles, runs and scratch layout; the time order and its tie groups: host-only arithmetic
+enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
+// The Cox group (cox_kernels.hpp; cox_layout): d -- the scans' scratch, the runs' sums and the times; i -- order and the tie
+// groups' bounds.  Allocated together by the first cdh_glm_set_survival, or not at all.
+struct CoxState {
+    DevBuf<double> d;
+    DevBuf<int32_t> i;
+};
 struct GlmState {
     DevBuf<double> labels;     // the labels, or the counts of the Poisson family
     DevBuf<double> offset;     // Poisson: ld doubles, pads zero; allocated by the first cdh_glm_set_counts that brings one
     GlmData family = GlmData::Binomial;   // what `labels` holds: cdh_glm_set_labels' labels or cdh_glm_set_counts' counts
     bool has_offset = false;   // the offset buffer holds this handle's offset (false: the step runs without one)
     bool set = false;
+    CoxState cox;              // GlmData::Cox: `labels` holds the status, `offset` the offset
 };
 
 struct Knobs {
@@ -322,6 +330,7 @@ struct Knobs {
     int cs_crew = 31;                // CDH_CS_CREW: its helper workgroups (0: none)
     int cs_ucap = 0;                 // CDH_CS_UCAP (tests): visit lists longer than this leave the loop's LDS block
     int64_t glm_grid = kGlmMaxGrid;  // CDH_GLM_GRID (tests): cap of k_glm_step's grid, so that a short vector gives a workgroup a second stride
+    int64_t cox_grid = kCoxMaxGrid;  // CDH_COX_GRID (tests): cap of the Cox step's grid, so that a few thousand rows give a workgroup several tiles
     bool small_path = true;          // CDH_SMALL_PATH: the one-launch solve
     int64_t small_max_bytes = -1;    // CDH_SMALL_MAX_BYTES: a fixed limit on n p sz instead of rent-or-buy (-1: none)
     int64_t small_always_bytes = (int64_t)kSmallAlwaysBytes;   // CDH_SMALL_ALWAYS_BYTES (tests: 0 makes every handle rent first)
@@ -344,6 +353,7 @@ Knobs read_knobs() {
     k.cs_crew = (int)std::max(0LL, std::min((long long)kCsCrewMax, num("CDH_CS_CREW", k.cs_crew)));
     k.cs_ucap = (int)std::max(0LL, num("CDH_CS_UCAP", 0));
     k.glm_grid = glm_grid_cap(num("CDH_GLM_GRID", k.glm_grid));
+    k.cox_grid = cox_grid_cap(num("CDH_COX_GRID", k.cox_grid));
     k.small_path = num("CDH_SMALL_PATH", 1) != 0;
     k.small_max_bytes = num("CDH_SMALL_MAX_BYTES", k.small_max_bytes);
     k.small_always_bytes = num("CDH_SMALL_ALWAYS_BYTES", k.small_always_bytes);
@@ -680,6 +690,7 @@ int32_t rebuild_residual(cdh_handle h) { return rebuild_residual_from(h, h->x, t
 #include "quad_solve.hpp"   // k_quad_solve, k_quad_init: a batch of CDQuadraticLoss problems, one workgroup each
 #include "cv_path.hpp"      // k_fold_weights, k_path_sse: the folds of a cross-validated path and its errors in one pass
 #include "glm_kernels.hpp"  // k_glm_step: the step between two IRLS rounds of a GLM family
+#include "cox_kernels.hpp"  // the Cox family's step: risk-set scans in time order, a chain of launches
 
 #include "solve.hpp"       // screened_full_pass, run_pass, solve; the bodies of cdh_descend, cdh_pass, cdh_solve, cdh_coordinate_descent
 
@@ -1083,8 +1094,9 @@ int32_t cdh_get_residual(cdh_handle h, void* out_n_local) { return guarded(h, [&
 
 // ---- l1-penalised GLMs by IRLS (glm_kernels.hpp; no reference counterpart: a round's solve is the weighted lasso of
 // CDWeightedLSLoss, cd_differentiable_function.jl:118-194) ---------------------------------------------------------------------
-// The body of cdh_glm_irls, cdh_glm_irls_fold and cdh_glm_poisson_irls: stands in for cdh_get_residual, w and z on the host,
-// cdh_set_y, cdh_set_obs_weights and cdh_initialize between two rounds.  F: the family (GlmBinomial, GlmBinomialFold, GlmPoisson).
+// The body of cdh_glm_irls, cdh_glm_irls_fold, cdh_glm_poisson_irls and cdh_glm_cox_irls: stands in for cdh_get_residual, w and z on the host,
+// cdh_set_y, cdh_set_obs_weights and cdh_initialize between two rounds.  F: the family (GlmBinomial, GlmBinomialFold, GlmPoisson,
+// and GlmCox of cox_kernels.hpp, whose glm_check and glm_launch are its own).
 extern "C++" template <class F>
 static int32_t glm_step(cdh_handle h, int32_t k, int32_t apply, const GlmParams& pm, double* out) {
     CHK(glm_check<F>(h, k, apply, pm, out));
@@ -1137,6 +1149,20 @@ int32_t cdh_glm_get_offset(cdh_handle h, void* host_offset) { return guarded(h, 
 
 int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double* out6) { return guarded(h, [&]() -> int32_t {
     return glm_step<GlmPoisson>(h, k, apply, GlmParams{wmin, eta_max}, out6);
+}); }
+
+// the Cox family of the same loop (cox_kernels.hpp): stands in for cdh_set_y of n zeros, the times sorted on the host, the
+// status and the offset kept where the other families keep their observations
+int32_t cdh_glm_set_survival(cdh_handle h, const void* host_time, const void* host_status, const void* host_offset) { return guarded(h, [&]() -> int32_t {
+    return cox_set_survival(h, host_time, host_status, host_offset);
+}); }
+
+int32_t cdh_glm_get_survival(cdh_handle h, void* host_time, void* host_status) { return guarded(h, [&]() -> int32_t {
+    return cox_get_survival(h, host_time, host_status);
+}); }
+
+int32_t cdh_glm_cox_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double* out5) { return guarded(h, [&]() -> int32_t {
+    return glm_step<GlmCox>(h, k, apply, GlmParams{wmin, eta_max}, out5);
 }); }
 
 // ---- cross-validation of a lasso path (cv_path.hpp; the solves are lasso.jl:229-260 on 0/1 weights, utils.jl:140-151) ------

@@ -1,0 +1,402 @@
+// cox_kernels.hpp -- the IRLS step of the l1-penalised Cox model with Breslow ties (no reference counterpart; a round's solve is
+// the weighted lasso of CDWeightedLSLoss, cd_differentiable_function.jl:118-194).  The first family whose step is not
+// elementwise: with e_i = exp(eta_i), S_i = sum of e over the rows at risk at t_i, A_i = sum of delta / S and B_i = sum of
+// delta / S^2 over the rows with t <= t_i, the working weight is w_i = e_i A_i - e_i^2 B_i and the gradient of the negative log
+// partial likelihood in eta is -(delta_i - e_i A_i) (Simon, Friedman, Hastie, Tibshirani 2011, eq. 9-10).  Included by cdhip.hip
+// inside its anonymous namespace, after glm_kernels.hpp, whose host body (glm_step), refusals and catch-up it shares; the
+// tiles, the runs of the workgroups and the scratch layout are cox_plan.hpp's.
+//
+// The design and the handle's vectors stay in the caller's row order.  cdh_glm_set_survival sorts the times on the host and
+// uploads `order` (sorted position -> row) with the bounds of every position's tie group (first, last: two int32 vectors); the
+// kernels gather through order, scan in sorted space and scatter w, z and r back.  The step is a chain of plain launches on
+// the handle's stream -- no workgroup waits for another, no atomics:
+//   k_cox_exp       e = exp(min(eta, eta_max)) and the training status in sorted order, the sum of e per run
+//   k_cox_offsets   the runs' sums into exclusive suffix offsets (one workgroup)
+//   k_cox_scan      T = suffix scan of e in place;  S of a position is T at its group's first position
+//   k_cox_hazard    h = delta / S, h2 = h / S in place of the status, their sums per run
+//   k_cox_offsets   the runs' sums into exclusive prefix offsets (one workgroup per scan)
+//   k_cox_scan      A, B = prefix scans of h, h2 in place, read at a group's last position
+//   k_cox_apply     w, z, r scattered to the rows, the record's partials;  k_gram_reduce adds them in block order
+// Every sum runs in a fixed order (cox_block_excl: __shfl_up over the 64 lanes, the four waves in order, the tiles of a run in
+// order, the runs in order), so the step is bit-identical run to run.
+
+// One position's share of the step, every quantity in double and every operation rounded on its own (tests/_cox_numpy.py
+// writes the same lines).  eta_lin = yw - r is X beta: the offset is NOT part of the stored working response.
+struct CoxEta { double eta_lin, ec, e; bool capped; };
+__device__ __forceinline__ CoxEta cox_eta(double yw, double r, double off, double eta_max) {
+#pragma clang fp contract(off)
+    CoxEta o;
+    o.eta_lin = yw - r;
+    const double eta = o.eta_lin + off;
+    o.capped = eta > eta_max;
+    o.ec = o.capped ? eta_max : eta;
+    o.e = exp(o.ec);
+    return o;
+}
+
+// A training row from its e, the scans read at its tie group's bounds and its status: eA = e A, w_raw = eA - e (e B) -- the
+// diagonal of the Hessian, which cancels to nothing where a row is most of its risk set -- clamped below at wmin;
+// d = delta - eA, r_new = d / w, z = eta_lin + r_new;  nll = delta (log S - eta), 0 where S = 0 (k_cox_hazard).  A row before the first event has A = B = 0:
+// w_raw = 0 is clamped and r_new = 0 exactly.
+struct CoxRow { double w, z, r, nll; bool clamped; };
+__device__ __forceinline__ CoxRow cox_row(const CoxEta& t, double S, double A, double B, double delta, double wmin) {
+#pragma clang fp contract(off)
+    CoxRow o;
+    const double eA = t.e * A;
+    const double eB = t.e * B;
+    const double w_raw = eA - t.e * eB;
+    o.clamped = !(w_raw >= wmin);
+    o.w = o.clamped ? wmin : w_raw;
+    const double d = delta - eA;
+    o.r = d / o.w;
+    o.z = t.eta_lin + o.r;
+    o.nll = (delta != 0.0 && S > 0.0) ? log(S) - t.ec : 0.0;
+    return o;
+}
+
+// The exclusive scan of one value per lane over the workgroup, in lane order, and the workgroup's total: Kogge-Stone over the
+// 64 lanes of a wave, the waves' totals added in wave order.  Two barriers: the first keeps the previous trip's readers of s_w
+// ahead of this trip's writers.
+__device__ __forceinline__ double cox_block_excl(double v, double* s_w /* [kCoxBlock / 64] */, double& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double t = __shfl_up(x, d, 64);
+        if (lane >= d) x = t + x;
+    }
+    double ex = __shfl_up(x, 1, 64);
+    if (lane == 0) ex = 0.0;
+    __syncthreads();
+    if (lane == 63) s_w[wv] = x;
+    __syncthreads();
+    double base = 0.0, all = 0.0;
+#pragma unroll
+    for (int i = 0; i < kCoxBlock / 64; ++i) {
+        if (i < wv) base += s_w[i];
+        all += s_w[i];
+    }
+    total = all;
+    return base + ex;
+}
+
+// is the row at sorted position s (row `row`) live, and held out of fold k?
+__device__ __forceinline__ bool cox_held(const uint8_t* __restrict__ fold, int k, int32_t row) {
+    return fold != nullptr && (int)fold[row] == k;
+}
+
+// e and the training status (delta of a live row that is not held out, else 0) in sorted order; sums[b]: the sum of e over
+// workgroup b's run.  A held-out row and a pad row contribute e = 0: they leave every risk set.  fold == nullptr: nobody is held.
+__global__ __launch_bounds__(kCoxBlock) void k_cox_exp(const int32_t* __restrict__ order, const double* __restrict__ status,
+                                                       const double* __restrict__ y, const double* __restrict__ r,
+                                                       const double* __restrict__ offset, const uint8_t* __restrict__ fold, int k,
+                                                       int64_t n, int64_t ld, int64_t tiles, double eta_max,
+                                                       double* __restrict__ eT, double* __restrict__ hA, double* __restrict__ sums) {
+    __shared__ double s_red[kCoxBlock / 64];
+    const int64_t t0 = cox_run_first(tiles, gridDim.x, blockIdx.x), t1 = cox_run_first(tiles, gridDim.x, blockIdx.x + 1);
+    double acc[1] = {0.0};
+    for (int64_t t = t0; t < t1; ++t) {
+        const int64_t s0 = t * kCoxTile + (int64_t)threadIdx.x * kCoxPer;
+        if (s0 >= ld) continue;
+#pragma unroll
+        for (int c = 0; c < kCoxPer; ++c) {
+            const int64_t s = s0 + c;
+            const int32_t row = order[s];
+            const bool train = s < n && !cox_held(fold, k, row);
+            const CoxEta o = cox_eta(y[row], r[row], offset ? offset[row] : 0.0, eta_max);
+            const double e = train ? o.e : 0.0;
+            eT[s] = e;
+            hA[s] = train ? status[row] : 0.0;
+            acc[0] += e;
+        }
+    }
+    block_sum<1>(acc, s_red);
+    if (threadIdx.x == 0) sums[blockIdx.x] = acc[0];
+}
+
+// The sums of `runs` runs into exclusive offsets, in place, one workgroup per scan (blockIdx.x picks the scan, kCoxMaxGrid doubles
+// apart): SUFFIX -- the sum of the later runs -- or prefix -- of the earlier ones.  A lane holds kCoxPer runs.
+template <bool SUFFIX>
+__global__ __launch_bounds__(kCoxBlock) void k_cox_offsets(double* __restrict__ sums, int runs) {
+    __shared__ double s_w[kCoxBlock / 64];
+    double* v = sums + (int64_t)blockIdx.x * kCoxMaxGrid;
+    const int q = SUFFIX ? kCoxBlock - 1 - (int)threadIdx.x : (int)threadIdx.x;     // the chunk this lane holds, in scan order
+    double x[kCoxPer], l[kCoxPer];
+#pragma unroll
+    for (int c = 0; c < kCoxPer; ++c) {
+        const int i = q * kCoxPer + c;
+        x[c] = i < runs ? v[i] : 0.0;
+    }
+    // l[c]: the sum of the lane's values that come before c in scan order
+    if (SUFFIX) { l[3] = 0.0; l[2] = x[3]; l[1] = l[2] + x[2]; l[0] = l[1] + x[1]; }
+    else        { l[0] = 0.0; l[1] = x[0]; l[2] = l[1] + x[1]; l[3] = l[2] + x[2]; }
+    const double mine = SUFFIX ? l[0] + x[0] : l[3] + x[3];
+    double total;
+    const double base = cox_block_excl(mine, s_w, total);
+#pragma unroll
+    for (int c = 0; c < kCoxPer; ++c) {
+        const int i = q * kCoxPer + c;
+        if (i < runs) v[i] = base + l[c];
+    }
+}
+static_assert(kCoxPer == 4, "k_cox_offsets and k_cox_scan write a lane's four partial sums out");
+
+// NV scans in place (buffers ld doubles apart from v, offsets kCoxMaxGrid apart from offs): inclusive SUFFIX scans -- v[s]
+// becomes the sum over the positions >= s -- or inclusive prefix scans.  Workgroup b walks its run backwards or forwards and
+// carries the sum of what it has passed, starting from its run's offset.
+template <int NV, bool SUFFIX>
+__global__ __launch_bounds__(kCoxBlock) void k_cox_scan(double* __restrict__ v, const double* __restrict__ offs, int64_t ld,
+                                                        int64_t tiles) {
+    __shared__ double s_w[NV][kCoxBlock / 64];
+    const int64_t t0 = cox_run_first(tiles, gridDim.x, blockIdx.x), t1 = cox_run_first(tiles, gridDim.x, blockIdx.x + 1);
+    const int q = SUFFIX ? kCoxBlock - 1 - (int)threadIdx.x : (int)threadIdx.x;
+    double carry[NV];
+#pragma unroll
+    for (int a = 0; a < NV; ++a) carry[a] = offs[(int64_t)a * kCoxMaxGrid + blockIdx.x];
+    for (int64_t i = 0; i < t1 - t0; ++i) {
+        const int64_t t = SUFFIX ? t1 - 1 - i : t0 + i;
+        const int64_t s0 = t * kCoxTile + (int64_t)q * kCoxPer;
+        const bool in = s0 < ld;
+#pragma unroll
+        for (int a = 0; a < NV; ++a) {
+            double* va = v + (int64_t)a * ld;
+            double x[kCoxPer], l[kCoxPer];
+#pragma unroll
+            for (int c = 0; c < kCoxPer; ++c) x[c] = in ? va[s0 + c] : 0.0;
+            // l[c]: the inclusive scan inside the lane
+            if (SUFFIX) { l[3] = x[3]; l[2] = l[3] + x[2]; l[1] = l[2] + x[1]; l[0] = l[1] + x[0]; }
+            else        { l[0] = x[0]; l[1] = l[0] + x[1]; l[2] = l[1] + x[2]; l[3] = l[2] + x[3]; }
+            double total;
+            const double base = carry[a] + cox_block_excl(SUFFIX ? l[0] : l[3], s_w[a], total);
+            if (in) {
+#pragma unroll
+                for (int c = 0; c < kCoxPer; ++c) va[s0 + c] = base + l[c];
+            }
+            carry[a] += total;
+        }
+    }
+}
+
+// h = delta / S and h2 = h / S over the status k_cox_exp left in hA, S = T at the group's first position; sums[b] and
+// sums[kCoxMaxGrid + b]: their sums over workgroup b's run.  A position without a training event has h = h2 = 0 whatever S
+// is (S = 0 behind the last training row).  eta is capped from above only: where exp underflows to 0 on every row of an
+// event's risk set (eta below -745) S is 0, and that event adds no hazard here and no term to the nll in k_cox_apply -- its
+// row gets eA = 0, the clamped weight and r = delta / wmin, all finite -- rather than an infinity.
+__global__ __launch_bounds__(kCoxBlock) void k_cox_hazard(const int32_t* __restrict__ first, const double* __restrict__ eT,
+                                                          double* __restrict__ hA, double* __restrict__ hB, int64_t ld, int64_t tiles,
+                                                          double* __restrict__ sums) {
+    __shared__ double s_red[2 * (kCoxBlock / 64)];
+    const int64_t t0 = cox_run_first(tiles, gridDim.x, blockIdx.x), t1 = cox_run_first(tiles, gridDim.x, blockIdx.x + 1);
+    double acc[2] = {0.0, 0.0};
+    for (int64_t t = t0; t < t1; ++t) {
+        const int64_t s0 = t * kCoxTile + (int64_t)threadIdx.x * kCoxPer;
+        if (s0 >= ld) continue;
+#pragma unroll
+        for (int c = 0; c < kCoxPer; ++c) {
+            const int64_t s = s0 + c;
+            const double delta = hA[s];
+            const double S = eT[first[s]];
+            const bool haz = delta != 0.0 && S > 0.0;
+            const double h = haz ? delta / S : 0.0;
+            const double h2 = haz ? h / S : 0.0;
+            hA[s] = h;
+            hB[s] = h2;
+            acc[0] += h;
+            acc[1] += h2;
+        }
+    }
+    block_sum<2>(acc, s_red);
+    if (threadIdx.x == 0) { sums[blockIdx.x] = acc[0]; sums[kCoxMaxGrid + blockIdx.x] = acc[1]; }
+}
+
+// The rows' share.  A training row becomes (w, z, r_new) of cox_row; a held-out row gets w = 0 exactly, z = eta_lin and r = 0,
+// the convention of k_glm_step; a pad row is WRITTEN as zeros with APPLY.  Every row is written by the one lane that read it
+// (order is a permutation).  The record: (sum of delta (log S - eta) over the training rows, sum w, training rows clamped at
+// wmin, live rows capped at eta_max, events among the training rows), partials[b kCoxVals + i].  With APPLY = false nothing is
+// written but the record.
+template <bool APPLY>
+__global__ __launch_bounds__(kCoxBlock) void k_cox_apply(const int32_t* __restrict__ order, const int32_t* __restrict__ first,
+                                                         const int32_t* __restrict__ last, const double* __restrict__ status,
+                                                         double* __restrict__ y, double* __restrict__ r, double* __restrict__ w,
+                                                         const double* __restrict__ offset, const uint8_t* __restrict__ fold, int k,
+                                                         int64_t n, int64_t ld, int64_t tiles, double wmin, double eta_max,
+                                                         const double* __restrict__ eT, const double* __restrict__ hA,
+                                                         const double* __restrict__ hB, double* __restrict__ partials) {
+    __shared__ double s_red[kCoxVals * (kCoxBlock / 64)];
+    const int64_t t0 = cox_run_first(tiles, gridDim.x, blockIdx.x), t1 = cox_run_first(tiles, gridDim.x, blockIdx.x + 1);
+    double acc[kCoxVals] = {};
+    for (int64_t t = t0; t < t1; ++t) {
+        const int64_t s0 = t * kCoxTile + (int64_t)threadIdx.x * kCoxPer;
+        if (s0 >= ld) continue;
+#pragma unroll
+        for (int c = 0; c < kCoxPer; ++c) {
+            const int64_t s = s0 + c;
+            const int32_t row = order[s];
+            const bool live = s < n;
+            const bool held = live && cox_held(fold, k, row);
+            const bool train = live && !held;
+            const CoxEta o = cox_eta(y[row], r[row], offset ? offset[row] : 0.0, eta_max);
+            const double delta = train ? status[row] : 0.0;
+            const CoxRow q = cox_row(o, eT[first[s]], hA[last[s]], hB[last[s]], delta, wmin);
+            if constexpr (APPLY) {
+                w[row] = train ? q.w : 0.0;
+                y[row] = train ? q.z : (held ? o.eta_lin : 0.0);
+                r[row] = train ? q.r : 0.0;
+            }
+            acc[0] += train ? q.nll : 0.0;
+            acc[1] += train ? q.w : 0.0;
+            acc[2] += (train && q.clamped) ? 1.0 : 0.0;
+            acc[3] += (live && o.capped) ? 1.0 : 0.0;
+            acc[4] += delta;
+        }
+    }
+    block_sum<kCoxVals>(acc, s_red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < kCoxVals; ++i) partials[(int64_t)blockIdx.x * kCoxVals + i] = acc[i];
+    }
+}
+static_assert(kCoxBlock == kBlock, "block_sum is kernels.hpp's");
+
+// ---- the host ------------------------------------------------------------------------------------------------------------------
+// cdh_glm_set_survival: leaves the handle exactly as cdh_set_y of n zeros would (what that export voids is voided here, in its
+// order), the status where the labels live, the offset where the Poisson family's lives, and the Cox group -- order, the tie
+// groups' bounds, the scans' scratch and the times -- allocated together and complete before the handle changes.
+int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_status, const void* host_offset) {
+    CHK(glm_refuse(h));
+    if (!host_time) return fail(h, CDH_BAD_ARG, "host_time is NULL");
+    if (!host_status) return fail(h, CDH_BAD_ARG, "host_status is NULL");
+    const double* tm = (const double*)host_time;
+    const double* st = (const double*)host_status;
+    const double* off = (const double*)host_offset;
+    char buf[128];
+    if (!cox_check(h->n, tm, st, off, buf, sizeof buf)) return fail(h, CDH_BAD_ARG, buf);
+    std::vector<int32_t> order, first, last;
+    cox_order(h->n, h->ld, tm, order, first, last);
+    HIPCHK(h, hipSetDevice(h->device));
+    const CoxLayout lay = cox_layout(h->ld);
+    const size_t colbytes = (size_t)h->ld * sizeof(double), idxbytes = (size_t)h->ld * sizeof(int32_t);
+    DevBuf<double> fresh, fresh_off, fresh_d;     // complete before the handle changes: a failed allocation leaves it as it was
+    DevBuf<int32_t> fresh_i;
+    if (!h->glm.labels) {
+        HIPCHK(h, fresh.alloc(colbytes));
+        HIPCHK(h, hipMemsetAsync(fresh, 0, colbytes, h->stream));
+    }
+    if (off && !h->glm.offset) {
+        HIPCHK(h, fresh_off.alloc(colbytes));
+        HIPCHK(h, hipMemsetAsync(fresh_off, 0, colbytes, h->stream));
+    }
+    if (!h->glm.cox.d) {
+        HIPCHK(h, fresh_d.alloc((size_t)lay.doubles * sizeof(double)));
+        HIPCHK(h, fresh_i.alloc((size_t)lay.ints * sizeof(int32_t)));
+        HIPCHK(h, hipMemsetAsync(fresh_d, 0, (size_t)lay.doubles * sizeof(double), h->stream));
+    }
+    h->rs.overwritten_with_y();          // r = copy(y) = 0 below
+    gc_invalidate(h, false);
+    h->gc.st.yy_void();
+    h->small.c_valid = false;
+    if (!h->glm.labels) h->glm.labels = std::move(fresh);
+    if (off && !h->glm.offset) h->glm.offset = std::move(fresh_off);
+    if (!h->glm.cox.d) { h->glm.cox.d = std::move(fresh_d); h->glm.cox.i = std::move(fresh_i); }
+    double* d = h->glm.cox.d;
+    int32_t* ii = h->glm.cox.i;
+    HIPCHK(h, hipMemcpyAsync(h->glm.labels, st, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (off) HIPCHK(h, hipMemcpyAsync(h->glm.offset, off, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d + lay.time, tm, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ii + lay.order, order.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ii + lay.first, first.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ii + lay.last, last.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->y, 0, colbytes, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->r, 0, colbytes, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (the host vectors above are pageable: the copies are done here)
+    h->y_set = true;
+    h->glm.family = GlmData::Cox;
+    h->glm.has_offset = off != nullptr;
+    h->glm.set = true;
+    return CDH_OK;
+}
+
+int32_t cox_get_survival(cdh_handle h, void* host_time, void* host_status) {
+    if (!host_time && !host_status) return fail(h, CDH_BAD_ARG, "host_time and host_status are both NULL");
+    if (!h->glm.set || h->glm.family != GlmData::Cox)
+        return fail(h, CDH_BAD_ARG, "no survival data are set: call cdh_glm_set_survival first");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)h->n * sizeof(double);
+    if (host_time)
+        HIPCHK(h, hipMemcpyAsync(host_time, (const double*)h->glm.cox.d + cox_layout(h->ld).time, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (host_status) HIPCHK(h, hipMemcpyAsync(host_status, h->glm.labels, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CDH_OK;
+}
+
+// The Cox family as glm_step sees it: what its export refuses, in cdh_glm_poisson_irls' order and words.
+struct GlmCox {
+    static constexpr int kVals = kCoxVals;
+    static constexpr bool kFold = true, kOffset = true;
+    static constexpr GlmData kData = GlmData::Cox;
+    static constexpr bool kKBeforeOut = true;
+    static constexpr const char* kOutNull = "out5 is NULL";
+    static int32_t refuse_observations(cdh_handle h) {
+        if (!h->glm.set || h->glm.family != kData)
+            return fail(h, CDH_BAD_ARG, "cdh_glm_cox_irls needs survival data: call cdh_glm_set_survival first");
+        return CDH_OK;
+    }
+    static int32_t refuse_params(cdh_handle h, const GlmParams& pm) { return GlmPoisson::refuse_params(h, pm); }
+};
+
+// glm_check with the Cox plan's records where the elementwise step's stand
+template <>
+int32_t glm_check<GlmCox>(cdh_handle h, int32_t k, int32_t apply, const GlmParams& pm, const double* out) {
+    CHK(glm_refuse(h));
+    CHK(GlmCox::refuse_observations(h));
+    if (apply != 0 && apply != 1) return fail(h, CDH_BAD_ARG, "apply must be 0 or 1");
+    CHK(GlmCox::refuse_params(h, pm));
+    CHK(glm_refuse_k(h, k));
+    if (!out) return fail(h, CDH_BAD_ARG, GlmCox::kOutNull);
+    if ((size_t)(cox_plan(h->ld, h->knobs.cox_grid).records * kCoxVals) > h->sz.partials_doubles)
+        return fail(h, CDH_BAD_ARG, "partials too small");
+    return CDH_OK;
+}
+
+// the chain and its record: out holds the kCoxVals doubles, added over the workgroups in block order; k = -1: no row is held
+// out and the fold ids are not read
+template <>
+int32_t glm_launch<GlmCox>(cdh_handle h, int32_t k, bool apply, const GlmParams& pm, double* out) {
+    const CoxPlan pl = cox_plan(h->ld, h->knobs.cox_grid);
+    const CoxLayout lay = cox_layout(h->ld);
+    double* d = h->glm.cox.d;
+    const int32_t* ii = h->glm.cox.i;
+    const int32_t *order = ii + lay.order, *first = ii + lay.first, *last = ii + lay.last;
+    double *eT = d + lay.eT, *hA = d + lay.hA, *hB = d + lay.hB, *sums = d + lay.sums, *sums_h = d + lay.sums + kCoxMaxGrid;
+    const double* status = h->glm.labels;
+    const double* off = h->glm.has_offset ? (const double*)h->glm.offset : (const double*)nullptr;
+    const uint8_t* fold = k >= 0 ? (const uint8_t*)h->cv.fold : (const uint8_t*)nullptr;
+    double *y = (double*)h->y, *r = (double*)h->r, *w = (double*)h->w;
+    const dim3 grid((unsigned)pl.grid), one(1), two(2), block(kCoxBlock);
+    hipLaunchKernelGGL(k_cox_exp, grid, block, 0, h->stream, order, status, (const double*)y, (const double*)r, off, fold, (int)k,
+                       h->n, h->ld, pl.tiles, pm.eta_max, eT, hA, sums);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_cox_offsets<true>, one, block, 0, h->stream, sums, (int)pl.grid);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL((k_cox_scan<1, true>), grid, block, 0, h->stream, eT, (const double*)sums, h->ld, pl.tiles);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_cox_hazard, grid, block, 0, h->stream, first, (const double*)eT, hA, hB, h->ld, pl.tiles, sums_h);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_cox_offsets<false>, two, block, 0, h->stream, sums_h, (int)pl.grid);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL((k_cox_scan<2, false>), grid, block, 0, h->stream, hA, (const double*)sums_h, h->ld, pl.tiles);
+    HIPCHK(h, hipGetLastError());
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, h->stream, order, first, last, status, y, r, w, off, fold, (int)k, h->n, h->ld,
+                           pl.tiles, pm.wmin, pm.eta_max, (const double*)eT, (const double*)hA, (const double*)hB,
+                           (double*)h->d_partials);
+    };
+    if (apply) go(k_cox_apply<true>); else go(k_cox_apply<false>);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_gram_reduce, dim3((kCoxVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
+                       (const double*)h->d_partials, (int)pl.records, (int)kCoxVals, (double*)h->d_red);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, h->d_red, sizeof(double) * kCoxVals, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CDH_OK;
+}

@@ -1,0 +1,109 @@
+// cox_plan.hpp -- the host-only arithmetic of the Cox step (cox_kernels.hpp: cdh_glm_set_survival, cdh_glm_cox_irls): the tile of
+// a scan, how the tiles are dealt to the workgroups, the layout of the step's scratch, and the time order with its tie groups
+// as cdh_glm_set_survival uploads them.  No HIP in here: tests/test_cox_plan_host.py compiles it with g++
+// (tests/cox_plan_main.cpp).  cox_kernels.hpp calls these functions and nothing else decides the sizes.
+//
+// The tie groups are kept as TWO int32 vectors, not as head flags: first[s] and last[s] are the first and the last sorted
+// position of the group that sorted position s belongs to.  The risk-set sum of a row is the suffix scan read at first[s], its
+// cumulative hazards the prefix scans read at last[s]: one gather each, and no scan over flags on the device.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <numeric>
+#include <vector>
+
+// ---- the kernels' shape ------------------------------------------------------------------------------------------------------
+// A lane holds kCoxPer consecutive sorted positions, a workgroup of kCoxBlock lanes a tile of kCoxTile positions.  The positions
+// planned are the padded ld of the handle (a multiple of 32, so a lane's positions lie wholly below ld or wholly beyond):
+// positions n .. ld - 1 stand for the pad rows n .. ld - 1, in place.  Workgroup b owns the CONTIGUOUS run of tiles
+// cox_run_first(b) .. cox_run_first(b + 1) - 1 and carries its running sum from tile to tile (forwards for a prefix scan,
+// backwards for a suffix scan); a launch of one workgroup turns the runs' sums into the runs' offsets between two scans.
+constexpr int kCoxBlock = 256;
+constexpr int kCoxPer = 4;
+constexpr int64_t kCoxTile = (int64_t)kCoxBlock * kCoxPer;
+constexpr int64_t kCoxMaxGrid = 1024;                     // the runs' sums are scanned by ONE workgroup: kCoxPer a lane
+constexpr int kCoxVals = 5;                               // the record: (nll, sum w, clamped, capped, events)
+static_assert(kCoxMaxGrid == kCoxTile, "k_cox_offsets scans the runs' sums as one tile");
+
+struct CoxPlan {
+    int64_t tiles;     // tiles of kCoxTile positions over ld (the last may be short)
+    int64_t grid;      // workgroups: min(tiles, cap), at least 1; every one owns at least one tile
+    int64_t records;   // partial records of the apply launch: one per workgroup
+    int64_t longest;   // tiles of the longest run
+};
+
+// cap: kCoxMaxGrid, or the smaller grid a test asks for (CDH_COX_GRID); values outside 1 .. kCoxMaxGrid mean kCoxMaxGrid
+constexpr int64_t cox_grid_cap(int64_t cap) { return (cap < 1 || cap > kCoxMaxGrid) ? kCoxMaxGrid : cap; }
+
+constexpr CoxPlan cox_plan(int64_t ld, int64_t cap = kCoxMaxGrid) {
+    const int64_t tiles = (ld + kCoxTile - 1) / kCoxTile;
+    const int64_t c = cox_grid_cap(cap);
+    int64_t grid = tiles < c ? tiles : c;
+    if (grid < 1) grid = 1;
+    return CoxPlan{tiles, grid, grid, (tiles + grid - 1) / grid};
+}
+
+// the first tile of workgroup b's run (b == grid: one past the last tile): the tiles split as evenly as integers allow,
+// tiles <= 2^21 and b <= 2^10, so the product stays far inside int64
+constexpr int64_t cox_run_first(int64_t tiles, int64_t grid, int64_t b) { return b * tiles / grid; }
+
+// ---- the scratch -------------------------------------------------------------------------------------------------------------
+// One buffer of doubles: e (then T, its suffix scan, in place), h (then A), h2 (then B) and the times, ld each, then the
+// runs' sums (then offsets) of the three scans, kCoxMaxGrid each.  One buffer of int32: order, first, last, ld each.
+struct CoxLayout {
+    int64_t eT, hA, hB, time, sums;   // offsets in doubles; sums + i kCoxMaxGrid: scan i's runs
+    int64_t doubles;
+    int64_t order, first, last;       // offsets in int32s
+    int64_t ints;
+};
+constexpr CoxLayout cox_layout(int64_t ld) {
+    return CoxLayout{0, ld, 2 * ld, 3 * ld, 4 * ld, 4 * ld + 3 * kCoxMaxGrid, 0, ld, 2 * ld, 3 * ld};
+}
+
+// ---- the time order and its tie groups ---------------------------------------------------------------------------------------
+// What cdh_glm_set_survival refuses of its data, the row named in msg (at least 128 chars): a time or an offset that is not
+// finite, a status other than 0 or 1, no event at all.  -> true when the data pass.
+inline bool cox_check(int64_t n, const double* time, const double* status, const double* offset, char* msg, size_t len) {
+    int64_t events = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!(fabs(time[i]) <= 1.7976931348623157e308)) {          // (a NaN fails the comparison)
+            snprintf(msg, len, "time[%lld] = %g is not finite", (long long)i, time[i]);
+            return false;
+        }
+        if (status[i] != 0.0 && status[i] != 1.0) {
+            snprintf(msg, len, "status[%lld] = %g is neither 0 (censored) nor 1 (event)", (long long)i, status[i]);
+            return false;
+        }
+        if (offset && !(fabs(offset[i]) <= 1.7976931348623157e308)) {
+            snprintf(msg, len, "offset[%lld] = %g is not finite", (long long)i, offset[i]);
+            return false;
+        }
+        events += status[i] == 1.0;
+    }
+    if (events == 0) {
+        snprintf(msg, len, "no row is an event: the partial likelihood is constant");
+        return false;
+    }
+    return true;
+}
+
+// order[s]: the row at sorted position s, by a stable ascending sort of the times (rows of equal time keep the caller's order);
+// first[s], last[s]: the bounds of s's tie group.  Positions n .. ld - 1 are the pad rows in place, each a group of its own.
+inline void cox_order(int64_t n, int64_t ld, const double* time, std::vector<int32_t>& order, std::vector<int32_t>& first,
+                      std::vector<int32_t>& last) {
+    order.resize((size_t)ld);
+    first.resize((size_t)ld);
+    last.resize((size_t)ld);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.begin() + n, [&](int32_t a, int32_t b) { return time[a] < time[b]; });
+    for (int64_t s = 0; s < n;) {
+        int64_t e = s + 1;
+        while (e < n && time[order[e]] == time[order[s]]) ++e;
+        for (int64_t q = s; q < e; ++q) { first[q] = (int32_t)s; last[q] = (int32_t)(e - 1); }
+        s = e;
+    }
+    for (int64_t s = n; s < ld; ++s) { first[s] = (int32_t)s; last[s] = (int32_t)s; }
+}

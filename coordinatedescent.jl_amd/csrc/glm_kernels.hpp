@@ -282,10 +282,10 @@ int32_t glm_set_labels(cdh_handle h, int32_t family, const void* host_labels) {
     return glm_set_observations(h, GlmData::Binomial, host_labels, nullptr);
 }
 
-// zeros when the counts came without an offset
+// zeros when the counts, or the survival data, came without an offset
 int32_t glm_get_offset(cdh_handle h, void* host_offset) {
     NEED_P(h, host_offset);
-    if (!h->glm.set || h->glm.family != GlmData::Poisson)
+    if (!h->glm.set || h->glm.family == GlmData::Binomial)      // (a Cox handle keeps its offset in the same buffer)
         return fail(h, CDH_BAD_ARG, "no counts are set: call cdh_glm_set_counts first");
     if (!h->glm.has_offset) {
         memset(host_offset, 0, (size_t)h->n * sizeof(double));

@@ -319,7 +319,8 @@ int32_t cdh_glm_irls_fold(cdh_handle h, int32_t k, int32_t apply, double wmin, d
  * makes it binomial again and drops the offset. */
 int32_t cdh_glm_set_counts(cdh_handle h, const void *host_counts, const void *host_offset_or_null);
 /* cdh_glm_get_offset (no reference counterpart; see cdh_glm_set_counts, cd_differentiable_function.jl:118-194): the n
- * offsets of a Poisson handle, zeros when none was given.  CDH_BAD_ARG without counts. */
+ * offsets of a Poisson handle, or of a Cox handle (cdh_glm_set_survival), zeros when none was given.  CDH_BAD_ARG on a handle
+ * that holds neither counts nor survival data -- a binomial handle included; the message names cdh_glm_set_counts either way. */
 int32_t cdh_glm_get_offset(cdh_handle h, void *host_offset);
 /* cdh_glm_poisson_irls (no reference counterpart; a round's solve is the weighted lasso of CDWeightedLSLoss,
  * cd_differentiable_function.jl:118-194): the step between two rounds at the iterate the handle holds, in one pass.
@@ -333,6 +334,44 @@ int32_t cdh_glm_get_offset(cdh_handle h, void *host_offset);
  * handle included); apply not in {0, 1}; wmin not finite or not > 0; eta_max outside (0, 700]; k < -1; k >= 0 without folds;
  * k >= K; out6 NULL. */
 int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double *out6);
+/* ---- l1-penalised Cox regression (Breslow ties, as glmnet's family = "cox"), by the same IRLS loop (no reference
+ * counterpart: a round's solve is the weighted lasso of CDWeightedLSLoss, cd_differentiable_function.jl:118-194) -----------
+ * Rows have a time t_i, a status delta_i (1: event, 0: censored) and optionally an offset o_i.  With eta = X beta + o and
+ * e_i = exp(min(eta_i, eta_max)):  S_i = sum of e_j over t_j >= t_i (the risk set; the same for every row of a tie group),
+ * A_i = sum of delta_k / S_k and B_i = sum of delta_k / S_k^2 over t_k <= t_i.
+ * F(beta) = -(1/n) sum_i delta_i (eta_i - log S_i) + lambda0 sum_j omega_j |beta_j|; there is no intercept (it cancels).
+ * Per row, in double, each operation rounded on its own: eA = e A; w_raw = eA - e (e B); clamped = w_raw < wmin,
+ * w = max(w_raw, wmin); d = delta - eA; r_new = d / w; z_lin = eta_lin + r_new (eta_lin = y_w - r = X beta WITHOUT the offset, as
+ * for the Poisson family).  Only w is clamped, so X'W r = X'(delta - eA), the negative gradient of the partial likelihood.
+ * S, A and B come from a segmented suffix scan and two segmented prefix scans in time order, a chain of launches on the
+ * handle's stream in which every sum has a fixed order.  Strata, start-stop times, Efron ties and observation weights are
+ * not offered. */
+/* cdh_glm_set_survival (no reference counterpart; the loss is that of cd_differentiable_function.jl:118-194 per round)
+ * stands in for cdh_set_y: it stores n statuses where cdh_glm_set_labels stores labels, n offsets (when not NULL) where
+ * cdh_glm_set_counts stores them, sorts the times on the host (stable, ascending) and keeps the order, the tie groups' bounds,
+ * the scans' scratch and the times in one group of buffers, allocated all-or-nothing before the handle changes; the design
+ * and the handle's vectors stay in the caller's row order.  Makes the handle a Cox handle and leaves it exactly as cdh_set_y
+ * of n zeros would.  CDH_BAD_ARG, the handle unchanged: what cdh_glm_set_labels refuses of the handle; a NULL time or
+ * status; a time or an offset that is not finite, a status other than 0 or 1 (the message names the row); no event at all.
+ * cdh_glm_irls, cdh_glm_irls_fold and cdh_glm_poisson_irls refuse a Cox handle; a later cdh_glm_set_labels or
+ * cdh_glm_set_counts makes it binomial or Poisson again.  cdh_glm_get_offset serves a Cox handle too. */
+int32_t cdh_glm_set_survival(cdh_handle h, const void *host_time, const void *host_status, const void *host_offset_or_null);
+/* cdh_glm_get_survival (no reference counterpart; see cdh_glm_set_survival, cd_differentiable_function.jl:118-194): the n
+ * times and the n statuses of a Cox handle, in the caller's row order; a NULL output is skipped.  CDH_BAD_ARG: both NULL; no
+ * survival data set. */
+int32_t cdh_glm_get_survival(cdh_handle h, void *host_time, void *host_status);
+/* cdh_glm_cox_irls (no reference counterpart; a round's solve is the weighted lasso of CDWeightedLSLoss,
+ * cd_differentiable_function.jl:118-194): the step between two rounds at the iterate the handle holds.
+ *   a training row becomes (w, y_w, r) = (w, z_lin, r_new); a row before the first event has w = wmin and r_new = 0 exactly;
+ *   a held-out row (fold id == k, after cdh_set_folds) leaves the risk sets and the event sums and becomes (0, eta_lin, 0);
+ *   rows n .. ld - 1 are written as zeros.
+ * k == -1: no row is held out and the fold ids are not read (the same bits whether or not folds are set).  out5 = {sum of
+ * delta_i (log S_i - eta_i) over the training rows, sum of w_i, training rows clamped at wmin, live rows capped at eta_max,
+ * events among the training rows}, each summed in a fixed order: bit-identical run to run.  The catch-up of r before the
+ * step, apply = 0 (read-only) and the state apply = 1 leaves are cdh_glm_irls'.  CDH_BAD_ARG, the handle unchanged: no
+ * survival data set; apply not in {0, 1}; wmin not finite or not > 0; eta_max outside (0, 700]; k < -1; k >= 0 without
+ * folds; k >= K; out5 NULL. */
+int32_t cdh_glm_cox_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double *out5);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects

@@ -557,6 +557,34 @@ function glm_poisson_irls!(X::HipMatrix{Float64}, k::Integer=-1; apply::Bool=tru
   (nll = out[1] / X.n, sum_w = out[2], clamped = Int(out[3]), capped = Int(out[4]), held_deviance = out[5], deviance = out[6])
 end
 
+# ---- l1-penalised Cox regression, Breslow ties, by the same loop (no reference counterpart) --------------------
+"the times, the statuses (1: event, 0: censored) and, optionally, the offsets of a Float64 design under the weighted loss; the working response is zeroed"
+function glm_set_survival!(X::HipMatrix{Float64}, time::Vector{Float64}, status::Vector{Float64}, offset::Union{Nothing,Vector{Float64}}=nothing)
+  length(time) == X.n && length(status) == X.n || throw(DimensionMismatch())
+  offset === nothing || length(offset) == X.n || throw(DimensionMismatch())
+  set_loss!(X, CDH_WLS)
+  check(X.handle, ccall((:cdh_glm_set_survival, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                        X.handle, time, status, offset === nothing ? C_NULL : pointer(offset)))
+  X.owner = nothing
+  X.synced = false
+  X
+end
+
+function glm_get_survival(X::HipMatrix{Float64})
+  time = Vector{Float64}(undef, X.n)
+  status = Vector{Float64}(undef, X.n)
+  check(X.handle, ccall((:cdh_glm_get_survival, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), X.handle, time, status))
+  (time, status)
+end
+
+"one Cox IRLS step at the iterate the handle holds, fold k (0-based, -1: none) held out; apply=false reads only"
+function glm_cox_irls!(X::HipMatrix{Float64}, k::Integer=-1; apply::Bool=true, wmin::Float64=1e-5, eta_max::Float64=50.0)
+  out = Vector{Float64}(undef, 5)
+  check(X.handle, ccall((:cdh_glm_cox_irls, libcdhip), Int32, (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Ptr{Float64}),
+                        X.handle, Int32(k), Int32(apply), wmin, eta_max, out))
+  (nll = out[1] / X.n, sum_w = out[2], clamped = Int(out[3]), capped = Int(out[4]), events = Int(out[5]))
+end
+
 # ---- locpolyl1 with the design expanded on the device (src/varying_coefficient_lasso.jl:30-79) ----------------
 # The reference rebuilds w, expandX and stdX on the host for every z0 (:63-65).  A HipVaryingDesign keeps the base
 # design and z in HBM; cdh_vc_set_point regenerates all three there, and the refit (:71-76) reads its weighted normal

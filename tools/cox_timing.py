@@ -1,0 +1,256 @@
+#!/usr/bin/env python3
+"""The Cox step against its yardsticks, and CoxLassoPath against the same loop composed on the host.  Prints ONE JSON line.
+
+Run without arguments it is a driver: every measurement below runs in a child process of its own under `timeout -k 10`, in
+order, and nothing runs after a child that failed or timed out (its status is in the line).  With --step NAME it is that child.
+
+  step_random, step_sorted   cdh_glm_cox_irls(apply = 1) -- and apply = 0 -- on an fp64 handle of N rows (default 2 000 000)
+      and one column, with an offset, times rounded to three decimals (tie groups of a few hundred rows), three rows in ten
+      censored; rows in random time order, or pre-sorted by time.  Against (i) a device-to-device copy of the bytes the chain
+      of launches moves, 228 a row: exp 52 (order, y, r, offset, status in; e and the status out), suffix scan 16, hazards
+      36 (status, first, S in; h, h2 out), prefix scans 32, apply 92 (order, first, last 12; y, r, offset, status 32; S, A, B
+      24 in; w, y, r 24 out) -- the copy reads and writes 114 N bytes; gathers and scatters through the order move whole 64-byte
+      sectors for 8 useful bytes when the rows are in random order, which the count does not include; and (ii) the same step
+      composed on the host: cdh_get_residual, the twin's formulas in numpy with the sort order cached (cumulative sums in
+      sorted order), cdh_set_y and cdh_set_obs_weights.  Interleaved call by call, REPS calls each per round, ROUNDS rounds;
+      reported are the rounds' minima, their minimum and spread.  Times are host clocks around calls that end in a stream
+      synchronise.
+  path   CoxLassoPath (default N2 = 2 000 000, P2 = 1000, M2 = 30 lambdas from 0.9 to 0.05 of lambda_max, with an offset, IRLS
+      optTol 1e-7) against the same warm-started loop composed from cdh_get_residual, numpy, cdh_set_y, cdh_set_obs_weights
+      and cdh_initialize per round, on one handle, PROUNDS rounds after a warm-up of each on the first three lambdas;
+      reported: wall times, the IRLS rounds of each, whether they agree at every lambda, the largest difference of the
+      coefficients.
+
+Environment: N, REPS, ROUNDS, N2, P2, M2, PROUNDS, STEP_TIMEOUT, PATH_TIMEOUT, OUT (a file that receives the line too)."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+env = lambda k, d: int(os.environ.get(k, d))  # noqa: E731
+STEPS = ("step_random", "step_sorted", "path")
+
+
+def driver():
+    res, ok = {}, True
+    for name in STEPS:
+        if not ok:
+            res[name] = {"skipped": "an earlier step failed"}
+            continue
+        limit = env("PATH_TIMEOUT", 600) if name == "path" else env("STEP_TIMEOUT", 180)
+        p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name],
+                           capture_output=True, text=True)
+        last = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        if p.returncode != 0 or not last:
+            res[name] = {"failed": p.returncode, "stderr_tail": p.stderr[-400:]}
+            ok = False
+        else:
+            res[name] = json.loads(last[-1])
+        print("cox_timing: %s %s" % (name, "done" if ok else "failed"), file=sys.stderr, flush=True)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if os.environ.get("OUT"):
+        os.makedirs(os.path.dirname(os.path.abspath(os.environ["OUT"])), exist_ok=True)
+        with open(os.environ["OUT"], "w") as fh:
+            fh.write(line + "\n")
+    return 0 if ok else 1
+
+
+if "--step" not in sys.argv:
+    sys.exit(driver())
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+sys.path.insert(0, ROOT)
+import coordinatedescent_jl_amd as cd  # noqa: E402
+
+step = sys.argv[sys.argv.index("--step") + 1]
+vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+PD = C.POINTER(C.c_double)
+WMIN, ETA_MAX = 1e-5, 50.0
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    out = fn()
+    return time.perf_counter() - t0, out
+
+
+class HostStep:
+    """The twin's step (tests/_cox_numpy.py: rows, the cumulative-sum form) with the sort order and the tie groups cached."""
+
+    def __init__(self, t, status, off):
+        n = len(t)
+        self.order = np.argsort(t, kind="stable")
+        ts = t[self.order]
+        head = np.r_[True, ts[1:] != ts[:-1]]
+        starts = np.nonzero(head)[0]
+        gid = np.cumsum(head) - 1
+        self.first, self.last = starts[gid], (np.r_[starts[1:], n] - 1)[gid]
+        self.ds, self.status, self.off = status[self.order], status, off
+        self.inv = np.empty(n, dtype=np.int64)
+        self.inv[self.order] = np.arange(n)
+
+    def __call__(self, eta_lin):
+        e = np.exp(np.minimum(eta_lin + self.off, ETA_MAX))
+        T = np.cumsum(e[self.order][::-1])[::-1]
+        Ss = T[self.first]
+        h = self.ds / Ss
+        A, B = np.cumsum(h)[self.last][self.inv], np.cumsum(h / Ss)[self.last][self.inv]
+        eA = e * A
+        w = np.maximum(eA - e * (e * B), WMIN)
+        return eta_lin + (self.status - eA) / w, w
+
+
+def survival(f, seed, presorted):
+    """Times ~ Exp(1) / exp(signal), rounded to three decimals; 30 % censored; an offset in (-0.5, 0.5)."""
+    n = f.n
+    rng = np.random.default_rng(seed)
+    sig = f.y
+    off = rng.uniform(-0.5, 0.5, n)
+    t = np.round(rng.exponential(1.0, n) / np.exp(0.5 * sig / np.std(sig) + off), 3)
+    if presorted:
+        t = np.sort(t)
+    status = (rng.random(n) >= 0.3).astype(np.float64)
+    cd.check(f._L.cdh_glm_set_survival(f._h, vp(t), vp(status), vp(off)), f._h)
+    return t, status, off
+
+
+def measure_step(presorted):
+    n, reps, rounds = env("N", 2_000_000), env("REPS", 5), env("ROUNDS", 3)
+    f, _ = cd.CDCoxLoss.generate(n, 1, seed=7, s=1, noise=1.0)
+    t, status, off = survival(f, 7, presorted)
+    x = cd.SparseIterate(1)
+    x[1] = 0.5
+    cd.initialize_(f, x)
+    L, h = f._L, f._h
+    out5, r = np.zeros(5), np.zeros(n)
+    host = HostStep(t, status, off)
+    z = f.y
+
+    def dev1():
+        cd.check(L.cdh_glm_cox_irls(h, -1, 1, WMIN, ETA_MAX, out5.ctypes.data_as(PD)), h)
+
+    def dev0():
+        cd.check(L.cdh_glm_cox_irls(h, -1, 0, WMIN, ETA_MAX, out5.ctypes.data_as(PD)), h)
+
+    def composed():
+        nonlocal z
+        cd.check(L.cdh_get_residual(h, vp(r)), h)
+        z, w = host(z - r)
+        cd.check(L.cdh_set_y(h, vp(z)), h)
+        cd.check(L.cdh_set_obs_weights(h, vp(w)), h)
+
+    src = torch.randn(114 * n // 8, dtype=torch.float64, device="cuda")
+    dst = torch.empty_like(src)
+
+    def copy():
+        dst.copy_(src)
+        torch.cuda.synchronize()
+
+    names, fns = ("cox_apply1", "cox_apply0", "copy_228_bytes_a_row"), (dev1, dev0, copy)
+    for fn in fns:
+        fn()
+    per = {k: [] for k in names}
+    for _ in range(rounds):
+        ts = [[] for _ in fns]
+        for _ in range(reps):
+            for tt, fn in zip(ts, fns):
+                tt.append(timed(fn)[0])
+        for k, tt in zip(names, ts):
+            per[k].append(min(tt))
+    # the composed step last: it replaces y and w from the host and leaves r for the next catch-up
+    comp = []
+    for _ in range(max(2, rounds)):
+        f._synced = None
+        cd.initialize_(f, x)
+        z = f.y
+        comp.append(timed(composed)[0])
+    res = {"n": n, "presorted": presorted, "tie_groups": int(len(np.unique(t))), "clamped": int(out5[2]), "events": int(out5[4]),
+           "bytes_a_row": 228}
+    for k, v in per.items():
+        res[k] = {"round_minima_ms": [1e3 * a for a in v], "min_ms": 1e3 * min(v), "spread_ms": 1e3 * (max(v) - min(v)),
+                  "TBps_of_228n": 228 * n / min(v) / 1e12}
+    res["host_composed_ms"] = [1e3 * a for a in comp]
+    res["cox_over_copy"] = min(per[names[0]]) / min(per[names[2]])
+    res["host_composed_over_cox"] = min(comp) / min(per[names[0]])
+    f.close()
+    return res
+
+
+def measure_path():
+    n, p, m, rounds = env("N2", 2_000_000), env("P2", 1000), env("M2", 30), env("PROUNDS", 2)
+    f, _ = cd.CDCoxLoss.generate(n, p, seed=11, s=10, noise=1.0)
+    t, status, off = survival(f, 11, False)
+    lmax = cd.coxLambdaMax(f)
+    lam = lmax * np.geomspace(0.9, 0.05, m)
+    opts = cd.CDOptions(maxIter=2000, optTol=1e-7, randomize=False)
+    irls = cd.IRLSOptions(maxIter=100)
+    host = HostStep(t, status, off)
+    L, h = f._L, f._h
+
+    def device_route(lams):
+        return cd.CoxLassoPath(f, None, lams, opts, irls, standardizeX=False)
+
+    def composed_route(lams):
+        x, betas, rounds_, r = cd.SparseIterate(p), [], [], np.zeros(n)
+        z = np.zeros(n)
+        cd.check(L.cdh_set_y(h, vp(z)), h)
+        f._synced = None
+        cd.initialize_(f, x)
+        mode = f.gradient_cache_mode()
+        if mode == 1:
+            f.set_gradient_cache(2)
+        try:
+            for lj in lams:
+                g_, beta, k = cd.ProxL1(lj), x.dense(), 0
+                for k in range(1, irls.maxIter + 1):
+                    cd.check(L.cdh_get_residual(h, vp(r)), h)
+                    z, w = host(z - r)
+                    cd.check(L.cdh_set_y(h, vp(z)), h)
+                    cd.check(L.cdh_set_obs_weights(h, vp(w)), h)
+                    f._synced = None
+                    cd.initialize_(f, x)
+                    cd.coordinateDescent_(x, f, g_, opts)
+                    beta, old = x.dense(), beta
+                    if np.max(np.abs(beta - old)) < irls.optTol:
+                        break
+                betas.append(beta)
+                rounds_.append(k)
+        finally:
+            if mode == 1:
+                f.set_gradient_cache(1)
+        return betas, rounds_
+
+    def reset():
+        cd.check(L.cdh_glm_set_survival(h, vp(t), vp(status), vp(off)), h)      # the Cox handle as it was made: y = r = 0
+        f._synced = None
+
+    device_route(lam[:3])
+    reset()
+    composed_route(lam[:3])
+    t_dev, t_com = [], []
+    for _ in range(rounds):
+        reset()
+        tt, path = timed(lambda: device_route(lam))
+        t_dev.append(tt)
+        reset()
+        tt, (betas, crounds) = timed(lambda: composed_route(lam))
+        t_com.append(tt)
+    diff = max(float(np.max(np.abs(b.dense() - c))) for b, c in zip(path.betapath, betas))
+    res = {"n": n, "p": p, "lambdas": m, "CoxLassoPath_s": t_dev, "composed_s": t_com,
+           "min_s": {"CoxLassoPath": min(t_dev), "composed": min(t_com)},
+           "composed_over_CoxLassoPath": min(t_com) / min(t_dev),
+           "irls_rounds": {"CoxLassoPath": int(sum(path.rounds)), "composed": int(sum(crounds))},
+           "same_rounds_per_lambda": list(path.rounds) == list(crounds), "all_converged": bool(all(path.converged)),
+           "nnz_last": int(path.betapath[-1].nnz), "max_abs_diff_beta": diff}
+    f.close()
+    return res
+
+
+out = measure_path() if step == "path" else measure_step(step == "step_sorted")
+print(json.dumps(out), flush=True)
