@@ -650,25 +650,80 @@ def _survival(y, n=None):
     return time, status
 
 
+def _strata_weights(strata, weights, n):
+    """strata -> contiguous int32 ids or None, weights -> float64 normalised to sum to n (v n / Σv) or None; refused on the
+    host: a wrong length, ids that are not integers or do not fit int32, a weight that is not finite or not > 0."""
+    if strata is not None:
+        a = np.asarray(strata)
+        if a.ndim != 1 or a.shape[0] != n:
+            raise DimensionMismatch("length(strata) != size(X, 1)")
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.number) or np.iscomplexobj(a):
+            raise ArgumentError("strata must be integers")
+        if not np.issubdtype(a.dtype, np.integer):
+            bad = ~(np.isfinite(a) & (a == np.floor(np.where(np.isfinite(a), a, 0.0))))
+            if np.any(bad):
+                raise ArgumentError("strata[%d] is not an integer" % int(np.nonzero(bad)[0][0]))
+        bad = (a < -2 ** 31) | (a > 2 ** 31 - 1)
+        if np.any(bad):
+            raise ArgumentError("strata[%d] does not fit int32" % int(np.nonzero(bad)[0][0]))
+        strata = np.ascontiguousarray(a, dtype=np.int32)
+    if weights is not None:
+        v = np.ascontiguousarray(weights, dtype=np.float64)
+        if v.ndim != 1 or v.shape[0] != n:
+            raise DimensionMismatch("length(weights) != size(X, 1)")
+        bad = ~(np.isfinite(v) & (v > 0.0))
+        if np.any(bad):
+            raise ArgumentError("weights[%d] is not finite and > 0" % int(np.nonzero(bad)[0][0]))
+        weights = v * n / v.sum()
+    return strata, weights
+
+
 class CDCoxLoss(_GLMLoss):
-    """CDCoxLoss(y, X, offset=None): -(1/n) Σ δ_i (η_i - log S_i), η = Xβ + o, S_i = Σ_{t_j >= t_i} e^η_j -- the negative log
+    """CDCoxLoss(y, X, offset=None; strata=None, weights=None): -(1/n) Σ δ_i (η_i - log S_i), η = Xβ + o, S_i = Σ_{t_j >= t_i} e^η_j -- the negative log
     partial likelihood of the Cox model with Breslow ties (glmnet's family = "cox"); y is n x 2, [time, status], status 1 an
     event and 0 censored; no reference counterpart.  Minimised by IRLS like its siblings CDLogisticLoss and CDPoissonLoss: a
     round is the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the working response and
     weights the handle's y and w hold from one irls_step to the next.  The step is not elementwise: the risk-set sums are
     scans in time order, run on the device through the order cdh_glm_set_survival keeps; the rows stay in the caller's order.
-    There is no intercept (it cancels), and no strata, start-stop times, Efron ties or observation weights.  fp64 only, one
-    device."""
+    There is no intercept (it cancels), and no start-stop times or Efron ties.
 
-    def __init__(self, y, X, offset=None, *, device=0):
+    strata (glmnet's stratifySurv): integer ids that fit int32; S_i, A_i and B_i then run over the rows of row i's stratum
+    only, by scans that restart at every stratum's boundary.  weights (glmnet's weights =): v_i > 0, normalised HERE to sum to
+    n (v n / Σv; the library stores what it is given), so that unit weights leave F as it was:
+    F = -(1/n) Σ v_i δ_i (η_i - log S_i) with S_i = Σ v_j e^η_j; the working weight is v e A - (v e)² B, so an integer weight
+    reproduces a replicated row's gradient and nll, not its diagonal.  The penalty scales of the paths stay the reference's
+    _stdX!, the root mean square over the rows present: they are NOT weighted by v.  fp64 only, one device."""
+
+    def __init__(self, y, X, offset=None, *, strata=None, weights=None, device=0):
         self._time, status = _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
         if offset is not None and not np.all(np.isfinite(np.asarray(offset, dtype=np.float64))):
             raise ArgumentError("the offset is not finite")
+        self._strata, self._weights = _strata_weights(strata, weights, len(status))
+        self._weighted = self._weights is not None
         super().__init__(status, X, offset, device=device)
-        del self._time
+        del self._time, self._strata, self._weights
 
     def _set_observations(self, status, off):
-        check(self._L.cdh_glm_set_survival(self._h, _vp(self._time), _vp(status), _vp(off)), self._h)
+        if self._strata is None and self._weights is None:
+            check(self._L.cdh_glm_set_survival(self._h, _vp(self._time), _vp(status), _vp(off)), self._h)
+        else:
+            check(self._L.cdh_glm_set_survival_strata(self._h, _vp(self._time), _vp(status), _vp(off), _vp(self._strata),
+                                                      _vp(self._weights)), self._h)
+
+    @property
+    def strata(self):
+        """The stratum ids (int32), in the caller's row order; zeros when none were given."""
+        out = np.zeros(self.n, dtype=np.int32)
+        check(self._L.cdh_glm_get_survival_strata(self._h, _vp(out), None), self._h)
+        return out
+
+    @property
+    def weights(self):
+        """The observation weights the handle holds (normalised to sum to n), in the caller's row order; ones when none
+        were given."""
+        out = np.zeros(self.n)
+        check(self._L.cdh_glm_get_survival_strata(self._h, None, _vp(out)), self._h)
+        return out
 
     def _get_survival(self, which):
         out = np.zeros(self.n)
@@ -686,17 +741,21 @@ class CDCoxLoss(_GLMLoss):
                                        out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
         return out
 
-    @staticmethod
-    def _record(out, n):
+    def _events(self, v):
+        """Σ v δ as the record reports it: an int on an unweighted loss, the float itself on a weighted one."""
+        return float(v) if getattr(self, "_weighted", False) else int(v)
+
+    def _record(self, out, n):
         return {"nll": float(out[0]) / n, "sum_w": float(out[1]), "clamped": int(out[2]), "capped": int(out[3]),
-                "events": int(out[4])}
+                "events": self._events(out[4])}
 
     def irls_step(self, apply=True, wmin=1e-5, eta_max=50.0, fold=None):
         """One IRLS step at the iterate the handle holds (cdh_glm_cox_irls).  apply=True turns the handle's y, w and r into the
         working response (without the offset), the working weights (e A - e² B, clamped below at wmin; η capped above at
         eta_max) and their residual; apply=False only reads.  Returns {"nll": (1/n) Σ δ_i (log S_i - η_i), "sum_w": Σ w_i,
         "clamped": rows whose weight was clamped (the rows before the first event always are), "capped": rows whose η was
-        capped, "events": Σ δ_i}, the sums over the training rows ("capped" over all rows).
+        capped, "events": Σ δ_i}, the sums over the training rows ("capped" over all rows).  With strata and weights S, A and B
+        are those of the row's stratum, e and δ are v e and v δ, and "events" is the float Σ v_i δ_i.
 
         fold=k (after set_folds): the rows of fold k are held out -- they leave the risk sets and the event sums, and get
         w = 0, z = Xβ, r = 0."""
@@ -715,7 +774,7 @@ class CDCoxLoss(_GLMLoss):
         every = self._step(False, irls.wmin, irls.etaMax, -1)
         res = self._record(train, self.n)
         res["held_deviance"] = 2.0 * (float(every[0]) - float(train[0]))
-        res["held_events"] = int(every[4]) - int(train[4])
+        res["held_events"] = self._events(every[4]) - self._events(train[4])
         return res
 
 
@@ -1757,7 +1816,7 @@ class CVPoissonLassoPathResult:
 @dataclass
 class CoxLassoSolution:
     """What coxLasso_ and coxLasso return.  nll is (1/n) Σ δ_i (log S_i - η_i) over the training rows at the final β and
-    events the events among them; capped counts the rows whose η the final step capped at etaMax; monotone is False if the
+    events the events among them (Σ v_i δ_i, a float, on a loss with observation weights; so is held_events); capped counts the rows whose η the final step capped at etaMax; monotone is False if the
     penalised objective F rose between two rounds by more than 1e-10 max(1, F) (there is no step halving: the rise is only
     reported).  With fold=k: held_deviance = -2 (ℓ_all - ℓ_train) and held_events, the events among the held-out rows."""
     x: SparseIterate
@@ -1922,20 +1981,24 @@ def _glm_solve(fam, x, f, g, options, irls, fold):
     return fam.solution(x, last, rounds, converged, monotone, g)
 
 
-def _glm_loss(fam, X, y, fit_intercept, offset):
-    """-> (f, owned): the family's loss over X (with a trailing column of ones when an intercept is fitted)."""
+def _glm_loss(fam, X, y, fit_intercept, offset, extra=None):
+    """-> (f, owned): the family's loss over X (with a trailing column of ones when an intercept is fitted).  extra: further
+    keywords of the loss (the Cox family's strata and weights), None where not given."""
+    extra = {k: v for k, v in (extra or {}).items() if v is not None}
     if isinstance(X, fam.loss):
         if fit_intercept:
             raise ArgumentError("fit_intercept appends a column of ones: pass the matrix, not a loss")
         if offset is not None:
             raise ArgumentError("the offset belongs to the loss: pass the matrix, or a loss made with it")
+        for name in extra:
+            raise ArgumentError("%s belongs to the loss: pass the matrix, or a loss made with it" % name)
         return X, False
     if isinstance(X, CoordinateDifferentiableFunction):
         raise TypeError("MethodError: takes a matrix or a %s" % fam.loss.__name__)
     X = np.asarray(X)
     if fit_intercept:
         X = np.asfortranarray(np.hstack([X, np.ones((X.shape[0], 1), dtype=X.dtype)]))
-    return (fam.loss(y, X) if offset is None else fam.loss(y, X, offset)), True
+    return (fam.loss(y, X, **extra) if offset is None else fam.loss(y, X, offset, **extra)), True
 
 
 def _glm_host_start(fam, y, offset):
@@ -1948,9 +2011,9 @@ def _glm_early_start(fam, X, y, fit_intercept, offset):
     return None
 
 
-def _glm_lasso(fam, X, y, lam, omega, options, irls, fit_intercept, offset=None):
+def _glm_lasso(fam, X, y, lam, omega, options, irls, fit_intercept, offset=None, extra=None):
     start = _glm_early_start(fam, X, y, fit_intercept, offset)
-    f, owned = _glm_loss(fam, X, y, fit_intercept, offset)
+    f, owned = _glm_loss(fam, X, y, fit_intercept, offset, extra)
     try:
         p = f.p - (1 if fit_intercept else 0)
         om = None if omega is None else np.asarray(omega, dtype=np.float64)
@@ -1967,9 +2030,9 @@ def _glm_lasso(fam, X, y, lam, omega, options, irls, fit_intercept, offset=None)
             f.close()
 
 
-def _glm_path(fam, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, offset=None):
+def _glm_path(fam, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, offset=None, extra=None):
     start = _glm_early_start(fam, X, y, fit_intercept, offset)
-    f, owned = _glm_loss(fam, X, y, fit_intercept, offset)
+    f, owned = _glm_loss(fam, X, y, fit_intercept, offset, extra)
     try:
         return _glm_path_on(fam, f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, start)
     finally:
@@ -2015,7 +2078,7 @@ def _glm_path_on(fam, f, lambdapath, options, irls, max_hat_s, standardizeX, fit
 
 
 def _cv_glm_path(fam, X, y, lambdapath, K, folds, options, irls, standardizeX, fit_intercept, seed, measure, offset,
-                 full_path, keep_fold_paths):
+                 full_path, keep_fold_paths, extra=None):
     front = "cv%sLassoPath" % fam.name.capitalize()
     if measure not in fam.cv_measures:
         raise ArgumentError("measure must be " + " or ".join('"%s"' % m for m in fam.cv_measures))
@@ -2033,7 +2096,7 @@ def _cv_glm_path(fam, X, y, lambdapath, K, folds, options, irls, standardizeX, f
         fam.start(obs, off)
         for k in range(len(sizes)):                     # before the upload: a fold whose start would be infinite
             fam.start(obs[ids != k], None if off is None else off[ids != k])
-    f, owned = _glm_loss(fam, X, y, fit_intercept, offset)
+    f, owned = _glm_loss(fam, X, y, fit_intercept, offset, extra)
     try:
         return _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, obs, off,
                                measure, full_path, keep_fold_paths)
@@ -2250,20 +2313,22 @@ def coxLasso_(x, f, g, options=None, irls=None, fold=None):
     return _glm_solve(_COX, x, f, g, options, irls, fold)
 
 
-def coxLasso(X, y, lam, omega=None, options=None, irls=None, offset=None):
+def coxLasso(X, y, lam, omega=None, options=None, irls=None, offset=None, strata=None, weights=None):
     """ℓ1-penalised Cox regression with Breslow ties (glmnet's family = "cox"): the minimiser of
     -(1/n) Σ δ_i (η_i - log S_i) + λ Σ ω_j |β_j|, η = Xβ + o, y = [time, status] (n x 2).  There is no intercept: it cancels
-    in the partial likelihood.  X may also be an existing CDCoxLoss (y and offset are then its own)."""
+    in the partial likelihood.  strata and weights: CDCoxLoss's (glmnet's stratifySurv and weights =; the weights are
+    normalised to sum to n).  X may also be an existing CDCoxLoss (y, offset, strata and weights are then its own)."""
     if not isinstance(X, CoordinateDifferentiableFunction):
         _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
-    return _glm_lasso(_COX, X, y, lam, omega, options, irls, False, offset)
+    return _glm_lasso(_COX, X, y, lam, omega, options, irls, False, offset, dict(strata=strata, weights=weights))
 
 
 def coxLambdaMax(f, omega=None):
     """The smallest λ at which every coordinate of the Cox lasso is zero: max_j |X_j'(δ - eA)| / (n ω_j) at β = 0.
     poissonLambdaMax's recipe: one applied irls_step at β = 0 leaves r = (δ - eA) / w, and the weighted gradient of the
-    handle (cdh_lambda_max: X_j'W r / n) is X_j'(δ - eA) / n whatever the clamp did to w.  The handle is left at β = 0, with
-    the penalty scales of the maximum."""
+    handle (cdh_lambda_max: X_j'W r / n) is X_j'(δ - eA) / n whatever the clamp did to w.  On a loss with strata and weights
+    the same step leaves X'W r = X'(vδ - v e A), A that of the row's stratum: the gradient of the weighted stratified partial
+    likelihood.  The handle is left at β = 0, with the penalty scales of the maximum."""
     if not isinstance(f, CDCoxLoss):
         raise TypeError("MethodError: coxLambdaMax takes a CDCoxLoss")
     x = SparseIterate(f.p)
@@ -2277,16 +2342,19 @@ def coxLambdaMax(f, omega=None):
     return out.value
 
 
-def CoxLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, offset=None):
+def CoxLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, offset=None, strata=None,
+                 weights=None):
     """LassoPath's loop (src/lasso.jl:229-260) with coxLasso_ per λ: one handle, one x warm-started along λ,
-    ω = _stdX!(X) (cdh_col_rms) when standardising.  βpath[i] has length p."""
+    ω = _stdX!(X) (cdh_col_rms) when standardising.  βpath[i] has length p.  strata and weights: CDCoxLoss's; the penalty
+    scales ω stay the root mean square over the rows present, not weighted by the observation weights."""
     if not isinstance(X, CoordinateDifferentiableFunction):
         _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
-    return _glm_path(_COX, X, y, lambdapath, options, irls, max_hat_s, standardizeX, False, offset)
+    return _glm_path(_COX, X, y, lambdapath, options, irls, max_hat_s, standardizeX, False, offset,
+                     dict(strata=strata, weights=weights))
 
 
 def cvCoxLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, seed=0, measure="deviance",
-                   offset=None, full_path=True, keep_fold_paths=False):
+                   offset=None, full_path=True, keep_fold_paths=False, strata=None, weights=None):
     """K-fold cross-validation of CoxLassoPath(X, y, λpath, options, irls; standardizeX, offset) on the device (glmnet's
     cv.glmnet(family = "cox", grouped = TRUE)); no reference counterpart.  X may also be an existing CDCoxLoss (y and offset
     are then its own); the design is uploaded once.
@@ -2299,25 +2367,35 @@ def cvCoxLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, 
     weight the folds by those event counts.  A fold without a held-out event, or without a training event, is refused
     before the upload.  Nothing n-sized moves after the upload.
 
+    strata and weights: CDCoxLoss's (refused, like offset, when a loss is passed in: they are then its own).  The folds keep
+    the λ scaling above and the unweighted penalty scales; "events" are then Σ v_i δ_i, floats: a fold is weighted by its
+    held-out Σ v δ (fold_events), and the refusals apply to those sums.
+
     folds: 0-based ids, one per row; otherwise np.random.default_rng(seed).permutation(n) % K.  There is no max_hat_s.  The
     folds are dropped when the call returns or raises.  `path` is CoxLassoPath on all rows (None with full_path=False):
     from a matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was
     passed in it runs after them.  `fold_paths`: the K fold paths as CoxLassoPathResult (None unless keep_fold_paths)."""
+    extra = dict(strata=strata, weights=weights)
     if isinstance(X, CDCoxLoss):
+        _glm_loss(_COX, X, y, False, offset, extra)               # (its refusals of what belongs to the loss)
         status = X.status
+        dv = status * X.weights if X._weighted else None
     elif isinstance(X, CoordinateDifferentiableFunction):
         raise TypeError("MethodError: cvCoxLassoPath takes a matrix or a CDCoxLoss")
     else:
         _, status = _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
+        _, v = _strata_weights(strata, weights, len(status))
+        dv = None if v is None else status * v
     ids, sizes = _cv_fold_ids(len(status), K, folds, seed)
-    events = np.bincount(ids, weights=status, minlength=len(sizes)).astype(np.int64)
-    for k in range(len(sizes)):
-        if events[k] == 0:
+    count = np.bincount(ids, weights=status, minlength=len(sizes)).astype(np.int64)
+    events = count if dv is None else np.bincount(ids, weights=dv, minlength=len(sizes))
+    for k in range(len(sizes)):                                   # (v > 0: Σ v δ is zero exactly where the count is)
+        if events[k] == 0 or count[k] == 0:
             raise ArgumentError("fold %d holds no event: its held-out deviance is undefined" % k)
-        if events[k] == events.sum():
+        if count[k] == count.sum():
             raise ArgumentError("fold %d holds every event: its training rows have none" % k)
     res = _cv_glm_path(_COX, X, y, lambdapath, K, folds, options, irls, standardizeX, False, seed, measure, offset,
-                       full_path, keep_fold_paths)
+                       full_path, keep_fold_paths, extra)
     res.fold_events = events
     return res
 

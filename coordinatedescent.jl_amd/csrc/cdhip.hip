@@ -304,10 +304,15 @@ struct CvState {
 #include "cox_plan.hpp"   // the Cox step's tiles, runs and scratch layout; the time order and its tie groups: host-only arithmetic
 enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
 // The Cox group (cox_kernels.hpp; cox_layout): d -- the scans' scratch, the runs' sums and the times; i -- order and the tie
-// groups' bounds.  Allocated together by the first cdh_glm_set_survival, or not at all.
+// groups' bounds.  Allocated together by the first cdh_glm_set_survival, or not at all.  sd, si -- the second pair, of a handle
+// with strata or observation weights: allocated together by the first cdh_glm_set_survival_strata that brings either, and in
+// use while `strata` is set (every other setter of observations clears it).
 struct CoxState {
     DevBuf<double> d;
     DevBuf<int32_t> i;
+    DevBuf<double> sd;
+    DevBuf<int32_t> si;
+    bool strata = false;
 };
 struct GlmState {
     DevBuf<double> labels;     // the labels, or the counts of the Poisson family
@@ -1159,6 +1164,15 @@ int32_t cdh_glm_set_survival(cdh_handle h, const void* host_time, const void* ho
 
 int32_t cdh_glm_get_survival(cdh_handle h, void* host_time, void* host_status) { return guarded(h, [&]() -> int32_t {
     return cox_get_survival(h, host_time, host_status);
+}); }
+
+// the same with strata (segments of the order, at which the scans restart) and observation weights; both NULL: the call above
+int32_t cdh_glm_set_survival_strata(cdh_handle h, const void* host_time, const void* host_status, const void* host_offset, const int32_t* host_strata, const void* host_weights) { return guarded(h, [&]() -> int32_t {
+    return cox_set_survival(h, host_time, host_status, host_offset, host_strata, host_weights);
+}); }
+
+int32_t cdh_glm_get_survival_strata(cdh_handle h, int32_t* host_strata, void* host_weights) { return guarded(h, [&]() -> int32_t {
+    return cox_get_survival_strata(h, host_strata, host_weights);
 }); }
 
 int32_t cdh_glm_cox_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double* out5) { return guarded(h, [&]() -> int32_t {

@@ -19,6 +19,17 @@
 //   k_cox_apply     w, z, r scattered to the rows, the record's partials;  k_gram_reduce adds them in block order
 // Every sum runs in a fixed order (cox_block_excl: __shfl_up over the 64 lanes, the four waves in order, the tiles of a run in
 // order, the runs in order), so the step is bit-identical run to run.
+//
+// Strata and observation weights (cdh_glm_set_survival_strata; glmnet's stratifySurv and weights =): a row has a weight v > 0
+// and a stratum id; ev = v e and dv = v delta take the places of e and delta, and S, A and B run over the rows of the row's own
+// stratum.  The order is then by (stratum, time), a stratum is a SEGMENT of sorted positions (sfirst, slast: its bounds, two more
+// int32 vectors), and the three scans are segmented: they restart at every head -- a stratum's last position for the suffix
+// scan, its first for the prefix scans -- by the operator (f1, v1) + (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2) carried through a
+// lane's four positions, cox_block_excl, the carry from tile to tile and the runs' offsets.  No sum ever crosses a boundary,
+// so the rounding error of a stratum's S, A and B is relative to ITS sums, whatever the other strata hold (a plain scan with a
+// subtraction at the boundary would carry n U of the later strata's sums into it).  Every kernel of the chain has the two
+// instantiations, chosen on the host (glm_launch<GlmCox>): a handle without strata and weights runs today's arithmetic, and
+// the additions a segmented scan does are the plain scan's in its order -- one stratum and unit weights give the same bits.
 
 // One position's share of the step, every quantity in double and every operation rounded on its own (tests/_cox_numpy.py
 // writes the same lines).  eta_lin = yw - r is X beta: the offset is NOT part of the stored working response.
@@ -57,26 +68,62 @@ __device__ __forceinline__ CoxRow cox_row(const CoxEta& t, double S, double A, d
 // The exclusive scan of one value per lane over the workgroup, in lane order, and the workgroup's total: Kogge-Stone over the
 // 64 lanes of a wave, the waves' totals added in wave order.  Two barriers: the first keeps the previous trip's readers of s_w
 // ahead of this trip's writers.
-__device__ __forceinline__ double cox_block_excl(double v, double* s_w /* [kCoxBlock / 64] */, double& total) {
+// SEG: the segmented scan of (value, head seen) pairs under (f1, v1) + (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2) -- a lane's
+// value is its sum since the last head it holds, f whether it holds one; the result is the sum since the last head among the
+// lanes before this one, f becomes whether there is one, tf whether the workgroup holds any.  The additions that do happen
+// are the plain scan's, in its order: without a head the bits are the same.  s_f: a flag word per wave.
+template <bool SEG>
+__device__ __forceinline__ double cox_block_excl(double v, double* s_w /* [kCoxBlock / 64] */, double& total, int& f,
+                                                 int* s_f /* [kCoxBlock / 64] */, int& tf) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double x = v;
+    int fl = f;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const double t = __shfl_up(x, d, 64);
-        if (lane >= d) x = t + x;
+        if constexpr (SEG) {
+            const int g = __shfl_up(fl, d, 64);
+            if (lane >= d) {
+                if (!fl) x = t + x;
+                fl |= g;
+            }
+        } else {
+            if (lane >= d) x = t + x;
+        }
     }
     double ex = __shfl_up(x, 1, 64);
     if (lane == 0) ex = 0.0;
+    int exf = 0;
+    if constexpr (SEG) {
+        exf = __shfl_up(fl, 1, 64);
+        if (lane == 0) exf = 0;
+    }
     __syncthreads();
-    if (lane == 63) s_w[wv] = x;
+    if (lane == 63) {
+        s_w[wv] = x;
+        if constexpr (SEG) s_f[wv] = fl;
+    }
     __syncthreads();
     double base = 0.0, all = 0.0;
+    int bf = 0, af = 0;
 #pragma unroll
     for (int i = 0; i < kCoxBlock / 64; ++i) {
-        if (i < wv) base += s_w[i];
-        all += s_w[i];
+        if constexpr (SEG) {
+            const int g = s_f[i];
+            if (i < wv) { base = g ? s_w[i] : base + s_w[i]; bf |= g; }
+            all = g ? s_w[i] : all + s_w[i];
+            af |= g;
+        } else {
+            if (i < wv) base += s_w[i];
+            all += s_w[i];
+        }
     }
     total = all;
+    if constexpr (SEG) {
+        tf = af;
+        f = exf | bf;
+        return exf ? ex : base + ex;
+    }
     return base + ex;
 }
 
@@ -87,13 +134,23 @@ __device__ __forceinline__ bool cox_held(const uint8_t* __restrict__ fold, int k
 
 // e and the training status (delta of a live row that is not held out, else 0) in sorted order; sums[b]: the sum of e over
 // workgroup b's run.  A held-out row and a pad row contribute e = 0: they leave every risk set.  fold == nullptr: nobody is held.
+// SW (strata and weights, cdh_glm_set_survival_strata): ev = v e and dv = v delta are stored, each product rounded on its own;
+// the run's record is (the sum since the last head in scan direction, head seen): the suffix scan's heads are the strata's
+// LAST positions, so the record's sum runs over the run's positions up to the end of the stratum its first position lies
+// in, and a head is seen when that stratum ends inside the run.
+template <bool SW>
 __global__ __launch_bounds__(kCoxBlock) void k_cox_exp(const int32_t* __restrict__ order, const double* __restrict__ status,
                                                        const double* __restrict__ y, const double* __restrict__ r,
                                                        const double* __restrict__ offset, const uint8_t* __restrict__ fold, int k,
                                                        int64_t n, int64_t ld, int64_t tiles, double eta_max,
-                                                       double* __restrict__ eT, double* __restrict__ hA, double* __restrict__ sums) {
+                                                       double* __restrict__ eT, double* __restrict__ hA, double* __restrict__ sums,
+                                                       const double* __restrict__ weight, const int32_t* __restrict__ slast,
+                                                       int32_t* __restrict__ heads) {
+#pragma clang fp contract(off)
     __shared__ double s_red[kCoxBlock / 64];
     const int64_t t0 = cox_run_first(tiles, gridDim.x, blockIdx.x), t1 = cox_run_first(tiles, gridDim.x, blockIdx.x + 1);
+    int64_t bound = ld;                       // SW: the last position of the stratum the run starts in
+    if constexpr (SW) bound = slast[t0 * kCoxTile];
     double acc[1] = {0.0};
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t s0 = t * kCoxTile + (int64_t)threadIdx.x * kCoxPer;
@@ -104,39 +161,78 @@ __global__ __launch_bounds__(kCoxBlock) void k_cox_exp(const int32_t* __restrict
             const int32_t row = order[s];
             const bool train = s < n && !cox_held(fold, k, row);
             const CoxEta o = cox_eta(y[row], r[row], offset ? offset[row] : 0.0, eta_max);
-            const double e = train ? o.e : 0.0;
-            eT[s] = e;
-            hA[s] = train ? status[row] : 0.0;
-            acc[0] += e;
+            if constexpr (SW) {
+                const double v = weight[row];
+                const double e = train ? v * o.e : 0.0;
+                eT[s] = e;
+                hA[s] = train ? v * status[row] : 0.0;
+                acc[0] += s <= bound ? e : 0.0;
+            } else {
+                const double e = train ? o.e : 0.0;
+                eT[s] = e;
+                hA[s] = train ? status[row] : 0.0;
+                acc[0] += e;
+            }
         }
     }
     block_sum<1>(acc, s_red);
-    if (threadIdx.x == 0) sums[blockIdx.x] = acc[0];
+    if (threadIdx.x == 0) {
+        sums[blockIdx.x] = acc[0];
+        if constexpr (SW) {
+            const int64_t end = t1 * kCoxTile < ld ? t1 * kCoxTile : ld;
+            heads[blockIdx.x] = bound < end ? 1 : 0;
+        }
+    }
 }
 
 // The sums of `runs` runs into exclusive offsets, in place, one workgroup per scan (blockIdx.x picks the scan, kCoxMaxGrid doubles
 // apart): SUFFIX -- the sum of the later runs -- or prefix -- of the earlier ones.  A lane holds kCoxPer runs.
-template <bool SUFFIX>
-__global__ __launch_bounds__(kCoxBlock) void k_cox_offsets(double* __restrict__ sums, int runs) {
+// SEG: the runs' records are (sum since the last head in scan direction, head seen: heads[i], one flag array for every scan of
+// the launch), and the offset of a run is the sum since the last head among the runs before it in scan direction.
+template <bool SUFFIX, bool SEG>
+__global__ __launch_bounds__(kCoxBlock) void k_cox_offsets(double* __restrict__ sums, int runs, const int32_t* __restrict__ heads) {
     __shared__ double s_w[kCoxBlock / 64];
+    __shared__ int s_f[kCoxBlock / 64];
     double* v = sums + (int64_t)blockIdx.x * kCoxMaxGrid;
     const int q = SUFFIX ? kCoxBlock - 1 - (int)threadIdx.x : (int)threadIdx.x;     // the chunk this lane holds, in scan order
     double x[kCoxPer], l[kCoxPer];
+    int hd[kCoxPer], fl[kCoxPer] = {0, 0, 0, 0};
 #pragma unroll
     for (int c = 0; c < kCoxPer; ++c) {
         const int i = q * kCoxPer + c;
         x[c] = i < runs ? v[i] : 0.0;
+        hd[c] = 0;
+        if constexpr (SEG) hd[c] = i < runs ? heads[i] : 0;
     }
-    // l[c]: the sum of the lane's values that come before c in scan order
-    if (SUFFIX) { l[3] = 0.0; l[2] = x[3]; l[1] = l[2] + x[2]; l[0] = l[1] + x[1]; }
-    else        { l[0] = 0.0; l[1] = x[0]; l[2] = l[1] + x[1]; l[3] = l[2] + x[2]; }
-    const double mine = SUFFIX ? l[0] + x[0] : l[3] + x[3];
+    // l[c]: the sum of the lane's values that come before c in scan order (SEG: since the last head among them, fl[c])
+    double mine;
+    int mf = 0;
+    if constexpr (SEG) {
+        if (SUFFIX) {
+            l[3] = 0.0;
+            l[2] = x[3];                            fl[2] = hd[3];
+            l[1] = hd[2] ? x[2] : l[2] + x[2];      fl[1] = fl[2] | hd[2];
+            l[0] = hd[1] ? x[1] : l[1] + x[1];      fl[0] = fl[1] | hd[1];
+            mine = hd[0] ? x[0] : l[0] + x[0];      mf = fl[0] | hd[0];
+        } else {
+            l[0] = 0.0;
+            l[1] = x[0];                            fl[1] = hd[0];
+            l[2] = hd[1] ? x[1] : l[1] + x[1];      fl[2] = fl[1] | hd[1];
+            l[3] = hd[2] ? x[2] : l[2] + x[2];      fl[3] = fl[2] | hd[2];
+            mine = hd[3] ? x[3] : l[3] + x[3];      mf = fl[3] | hd[3];
+        }
+    } else {
+        if (SUFFIX) { l[3] = 0.0; l[2] = x[3]; l[1] = l[2] + x[2]; l[0] = l[1] + x[1]; }
+        else        { l[0] = 0.0; l[1] = x[0]; l[2] = l[1] + x[1]; l[3] = l[2] + x[2]; }
+        mine = SUFFIX ? l[0] + x[0] : l[3] + x[3];
+    }
     double total;
-    const double base = cox_block_excl(mine, s_w, total);
+    int tf;
+    const double base = cox_block_excl<SEG>(mine, s_w, total, mf, s_f, tf);
 #pragma unroll
     for (int c = 0; c < kCoxPer; ++c) {
         const int i = q * kCoxPer + c;
-        if (i < runs) v[i] = base + l[c];
+        if (i < runs) v[i] = (SEG && fl[c]) ? l[c] : base + l[c];
     }
 }
 static_assert(kCoxPer == 4, "k_cox_offsets and k_cox_scan write a lane's four partial sums out");
@@ -144,10 +240,13 @@ static_assert(kCoxPer == 4, "k_cox_offsets and k_cox_scan write a lane's four pa
 // NV scans in place (buffers ld doubles apart from v, offsets kCoxMaxGrid apart from offs): inclusive SUFFIX scans -- v[s]
 // becomes the sum over the positions >= s -- or inclusive prefix scans.  Workgroup b walks its run backwards or forwards and
 // carries the sum of what it has passed, starting from its run's offset.
-template <int NV, bool SUFFIX>
+// SEG: the scans restart at every head -- bound[s] == s, bound the strata's last positions for the suffix scan and their first
+// for the prefix scans -- through the lane's four positions, the workgroup's scan and the carry from tile to tile.
+template <int NV, bool SUFFIX, bool SEG>
 __global__ __launch_bounds__(kCoxBlock) void k_cox_scan(double* __restrict__ v, const double* __restrict__ offs, int64_t ld,
-                                                        int64_t tiles) {
+                                                        int64_t tiles, const int32_t* __restrict__ bound) {
     __shared__ double s_w[NV][kCoxBlock / 64];
+    __shared__ int s_f[NV][kCoxBlock / 64];
     const int64_t t0 = cox_run_first(tiles, gridDim.x, blockIdx.x), t1 = cox_run_first(tiles, gridDim.x, blockIdx.x + 1);
     const int q = SUFFIX ? kCoxBlock - 1 - (int)threadIdx.x : (int)threadIdx.x;
     double carry[NV];
@@ -157,22 +256,46 @@ __global__ __launch_bounds__(kCoxBlock) void k_cox_scan(double* __restrict__ v, 
         const int64_t t = SUFFIX ? t1 - 1 - i : t0 + i;
         const int64_t s0 = t * kCoxTile + (int64_t)q * kCoxPer;
         const bool in = s0 < ld;
+        int hd[kCoxPer] = {0, 0, 0, 0};
+        if constexpr (SEG) {
+            if (in) {
+#pragma unroll
+                for (int c = 0; c < kCoxPer; ++c) hd[c] = (int64_t)bound[s0 + c] == s0 + c;
+            }
+        }
 #pragma unroll
         for (int a = 0; a < NV; ++a) {
             double* va = v + (int64_t)a * ld;
             double x[kCoxPer], l[kCoxPer];
+            int fl[kCoxPer] = {0, 0, 0, 0};
 #pragma unroll
             for (int c = 0; c < kCoxPer; ++c) x[c] = in ? va[s0 + c] : 0.0;
-            // l[c]: the inclusive scan inside the lane
-            if (SUFFIX) { l[3] = x[3]; l[2] = l[3] + x[2]; l[1] = l[2] + x[1]; l[0] = l[1] + x[0]; }
-            else        { l[0] = x[0]; l[1] = l[0] + x[1]; l[2] = l[1] + x[2]; l[3] = l[2] + x[3]; }
+            // l[c]: the inclusive scan inside the lane (SEG: since the last head at or before c in scan order, fl[c])
+            if constexpr (SEG) {
+                if (SUFFIX) {
+                    l[3] = x[3];                            fl[3] = hd[3];
+                    l[2] = hd[2] ? x[2] : l[3] + x[2];      fl[2] = fl[3] | hd[2];
+                    l[1] = hd[1] ? x[1] : l[2] + x[1];      fl[1] = fl[2] | hd[1];
+                    l[0] = hd[0] ? x[0] : l[1] + x[0];      fl[0] = fl[1] | hd[0];
+                } else {
+                    l[0] = x[0];                            fl[0] = hd[0];
+                    l[1] = hd[1] ? x[1] : l[0] + x[1];      fl[1] = fl[0] | hd[1];
+                    l[2] = hd[2] ? x[2] : l[1] + x[2];      fl[2] = fl[1] | hd[2];
+                    l[3] = hd[3] ? x[3] : l[2] + x[3];      fl[3] = fl[2] | hd[3];
+                }
+            } else {
+                if (SUFFIX) { l[3] = x[3]; l[2] = l[3] + x[2]; l[1] = l[2] + x[1]; l[0] = l[1] + x[0]; }
+                else        { l[0] = x[0]; l[1] = l[0] + x[1]; l[2] = l[1] + x[2]; l[3] = l[2] + x[3]; }
+            }
             double total;
-            const double base = carry[a] + cox_block_excl(SUFFIX ? l[0] : l[3], s_w[a], total);
+            int f = SUFFIX ? fl[0] : fl[3], tf = 0;
+            const double ex = cox_block_excl<SEG>(SUFFIX ? l[0] : l[3], s_w[a], total, f, s_f[a], tf);
+            const double base = (SEG && f) ? ex : carry[a] + ex;
             if (in) {
 #pragma unroll
-                for (int c = 0; c < kCoxPer; ++c) va[s0 + c] = base + l[c];
+                for (int c = 0; c < kCoxPer; ++c) va[s0 + c] = (SEG && fl[c]) ? l[c] : base + l[c];
             }
-            carry[a] += total;
+            carry[a] = (SEG && tf) ? total : carry[a] + total;
         }
     }
 }
@@ -182,11 +305,17 @@ __global__ __launch_bounds__(kCoxBlock) void k_cox_scan(double* __restrict__ v, 
 // is (S = 0 behind the last training row).  eta is capped from above only: where exp underflows to 0 on every row of an
 // event's risk set (eta below -745) S is 0, and that event adds no hazard here and no term to the nll in k_cox_apply -- its
 // row gets eA = 0, the clamped weight and r = delta / wmin, all finite -- rather than an infinity.
+// SEG: the prefix scans' heads are the strata's FIRST positions, so the run's records sum over its positions from the start of
+// the stratum its last position lies in, and a head is seen (heads[b]) when that stratum starts inside the run.
+template <bool SEG>
 __global__ __launch_bounds__(kCoxBlock) void k_cox_hazard(const int32_t* __restrict__ first, const double* __restrict__ eT,
                                                           double* __restrict__ hA, double* __restrict__ hB, int64_t ld, int64_t tiles,
-                                                          double* __restrict__ sums) {
+                                                          double* __restrict__ sums, const int32_t* __restrict__ sfirst,
+                                                          int32_t* __restrict__ heads) {
     __shared__ double s_red[2 * (kCoxBlock / 64)];
     const int64_t t0 = cox_run_first(tiles, gridDim.x, blockIdx.x), t1 = cox_run_first(tiles, gridDim.x, blockIdx.x + 1);
+    int64_t bound = 0;                        // SEG: the first position of the stratum the run ends in
+    if constexpr (SEG) bound = sfirst[(t1 * kCoxTile < ld ? t1 * kCoxTile : ld) - 1];
     double acc[2] = {0.0, 0.0};
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t s0 = t * kCoxTile + (int64_t)threadIdx.x * kCoxPer;
@@ -201,27 +330,40 @@ __global__ __launch_bounds__(kCoxBlock) void k_cox_hazard(const int32_t* __restr
             const double h2 = haz ? h / S : 0.0;
             hA[s] = h;
             hB[s] = h2;
-            acc[0] += h;
-            acc[1] += h2;
+            if constexpr (SEG) {
+                acc[0] += s >= bound ? h : 0.0;
+                acc[1] += s >= bound ? h2 : 0.0;
+            } else {
+                acc[0] += h;
+                acc[1] += h2;
+            }
         }
     }
     block_sum<2>(acc, s_red);
-    if (threadIdx.x == 0) { sums[blockIdx.x] = acc[0]; sums[kCoxMaxGrid + blockIdx.x] = acc[1]; }
+    if (threadIdx.x == 0) {
+        sums[blockIdx.x] = acc[0];
+        sums[kCoxMaxGrid + blockIdx.x] = acc[1];
+        if constexpr (SEG) heads[blockIdx.x] = bound >= t0 * kCoxTile ? 1 : 0;
+    }
 }
 
 // The rows' share.  A training row becomes (w, z, r_new) of cox_row; a held-out row gets w = 0 exactly, z = eta_lin and r = 0,
 // the convention of k_glm_step; a pad row is WRITTEN as zeros with APPLY.  Every row is written by the one lane that read it
 // (order is a permutation).  The record: (sum of delta (log S - eta) over the training rows, sum w, training rows clamped at
-// wmin, live rows capped at eta_max, events among the training rows), partials[b kCoxVals + i].  With APPLY = false nothing is
-// written but the record.
-template <bool APPLY>
+// wmin, live rows capped at eta_max, sum of dv over the training rows: the events among them, bit for bit, without weights),
+// partials[b kCoxVals + i].  With APPLY = false nothing is written but the record.
+// WT (observation weights v): cox_row's lines with ev = v e for e and dv = v delta for delta, every product rounded on its
+// own, and the nll term dv (log S - ec): w_raw = ev A - ev (ev B), d = dv - ev A.
+template <bool APPLY, bool WT>
 __global__ __launch_bounds__(kCoxBlock) void k_cox_apply(const int32_t* __restrict__ order, const int32_t* __restrict__ first,
                                                          const int32_t* __restrict__ last, const double* __restrict__ status,
                                                          double* __restrict__ y, double* __restrict__ r, double* __restrict__ w,
                                                          const double* __restrict__ offset, const uint8_t* __restrict__ fold, int k,
                                                          int64_t n, int64_t ld, int64_t tiles, double wmin, double eta_max,
                                                          const double* __restrict__ eT, const double* __restrict__ hA,
-                                                         const double* __restrict__ hB, double* __restrict__ partials) {
+                                                         const double* __restrict__ hB, double* __restrict__ partials,
+                                                         const double* __restrict__ weight) {
+#pragma clang fp contract(off)
     __shared__ double s_red[kCoxVals * (kCoxBlock / 64)];
     const int64_t t0 = cox_run_first(tiles, gridDim.x, blockIdx.x), t1 = cox_run_first(tiles, gridDim.x, blockIdx.x + 1);
     double acc[kCoxVals] = {};
@@ -235,9 +377,15 @@ __global__ __launch_bounds__(kCoxBlock) void k_cox_apply(const int32_t* __restri
             const bool live = s < n;
             const bool held = live && cox_held(fold, k, row);
             const bool train = live && !held;
-            const CoxEta o = cox_eta(y[row], r[row], offset ? offset[row] : 0.0, eta_max);
-            const double delta = train ? status[row] : 0.0;
-            const CoxRow q = cox_row(o, eT[first[s]], hA[last[s]], hB[last[s]], delta, wmin);
+            CoxEta o = cox_eta(y[row], r[row], offset ? offset[row] : 0.0, eta_max);
+            double delta = train ? status[row] : 0.0;
+            if constexpr (WT) {
+                const double v = weight[row];
+                o.e = v * o.e;
+                delta = v * delta;
+            }
+            CoxRow q = cox_row(o, eT[first[s]], hA[last[s]], hB[last[s]], delta, wmin);
+            if constexpr (WT) q.nll = delta * q.nll;
             if constexpr (APPLY) {
                 w[row] = train ? q.w : 0.0;
                 y[row] = train ? q.z : (held ? o.eta_lin : 0.0);
@@ -262,22 +410,30 @@ static_assert(kCoxBlock == kBlock, "block_sum is kernels.hpp's");
 // cdh_glm_set_survival: leaves the handle exactly as cdh_set_y of n zeros would (what that export voids is voided here, in its
 // order), the status where the labels live, the offset where the Poisson family's lives, and the Cox group -- order, the tie
 // groups' bounds, the scans' scratch and the times -- allocated together and complete before the handle changes.
-int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_status, const void* host_offset) {
+// cdh_glm_set_survival_strata is the same body: with strata or weights the order is by (stratum, time) and the second pair of
+// buffers (cox_layout: the strata's bounds, the ids, the runs' head flags; the weights as given, pads zero) is allocated with
+// the rest, all or nothing; an absent one of the two is stored as its default (stratum 0, weight 1).  Without both the calls,
+// the uploads and the handle are cdh_glm_set_survival's, and strata and weights set earlier are dropped.
+int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_status, const void* host_offset,
+                         const int32_t* host_strata = nullptr, const void* host_weights = nullptr) {
     CHK(glm_refuse(h));
     if (!host_time) return fail(h, CDH_BAD_ARG, "host_time is NULL");
     if (!host_status) return fail(h, CDH_BAD_ARG, "host_status is NULL");
     const double* tm = (const double*)host_time;
     const double* st = (const double*)host_status;
     const double* off = (const double*)host_offset;
+    const double* wt = (const double*)host_weights;
+    const bool sw = host_strata != nullptr || wt != nullptr;
     char buf[128];
-    if (!cox_check(h->n, tm, st, off, buf, sizeof buf)) return fail(h, CDH_BAD_ARG, buf);
-    std::vector<int32_t> order, first, last;
-    cox_order(h->n, h->ld, tm, order, first, last);
+    if (!cox_check(h->n, tm, st, off, buf, sizeof buf, wt)) return fail(h, CDH_BAD_ARG, buf);
+    std::vector<int32_t> order, first, last, sfirst, slast;
+    if (sw) cox_order_strata(h->n, h->ld, tm, host_strata, order, first, last, sfirst, slast);
+    else cox_order(h->n, h->ld, tm, order, first, last);
     HIPCHK(h, hipSetDevice(h->device));
     const CoxLayout lay = cox_layout(h->ld);
     const size_t colbytes = (size_t)h->ld * sizeof(double), idxbytes = (size_t)h->ld * sizeof(int32_t);
-    DevBuf<double> fresh, fresh_off, fresh_d;     // complete before the handle changes: a failed allocation leaves it as it was
-    DevBuf<int32_t> fresh_i;
+    DevBuf<double> fresh, fresh_off, fresh_d, fresh_sd;     // complete before the handle changes: a failed allocation leaves it as it was
+    DevBuf<int32_t> fresh_i, fresh_si;
     if (!h->glm.labels) {
         HIPCHK(h, fresh.alloc(colbytes));
         HIPCHK(h, hipMemsetAsync(fresh, 0, colbytes, h->stream));
@@ -291,6 +447,12 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
         HIPCHK(h, fresh_i.alloc((size_t)lay.ints * sizeof(int32_t)));
         HIPCHK(h, hipMemsetAsync(fresh_d, 0, (size_t)lay.doubles * sizeof(double), h->stream));
     }
+    if (sw && !h->glm.cox.sd) {
+        HIPCHK(h, fresh_sd.alloc((size_t)lay.strata_doubles * sizeof(double)));
+        HIPCHK(h, fresh_si.alloc((size_t)lay.strata_ints * sizeof(int32_t)));
+        HIPCHK(h, hipMemsetAsync(fresh_sd, 0, (size_t)lay.strata_doubles * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(fresh_si, 0, (size_t)lay.strata_ints * sizeof(int32_t), h->stream));
+    }
     h->rs.overwritten_with_y();          // r = copy(y) = 0 below
     gc_invalidate(h, false);
     h->gc.st.yy_void();
@@ -298,6 +460,7 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
     if (!h->glm.labels) h->glm.labels = std::move(fresh);
     if (off && !h->glm.offset) h->glm.offset = std::move(fresh_off);
     if (!h->glm.cox.d) { h->glm.cox.d = std::move(fresh_d); h->glm.cox.i = std::move(fresh_i); }
+    if (sw && !h->glm.cox.sd) { h->glm.cox.sd = std::move(fresh_sd); h->glm.cox.si = std::move(fresh_si); }
     double* d = h->glm.cox.d;
     int32_t* ii = h->glm.cox.i;
     HIPCHK(h, hipMemcpyAsync(h->glm.labels, st, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -306,12 +469,27 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
     HIPCHK(h, hipMemcpyAsync(ii + lay.order, order.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(ii + lay.first, first.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(ii + lay.last, last.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+    std::vector<int32_t> ids;            // (alive until the synchronise below)
+    std::vector<double> ones;
+    if (sw) {
+        double* sd = h->glm.cox.sd;
+        int32_t* si = h->glm.cox.si;
+        if (!host_strata) ids.assign((size_t)h->n, 0);
+        if (!wt) ones.assign((size_t)h->n, 1.0);
+        HIPCHK(h, hipMemcpyAsync(si + lay.sfirst, sfirst.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(si + lay.slast, slast.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(si + lay.strata, host_strata ? host_strata : ids.data(), (size_t)h->n * sizeof(int32_t),
+                                 hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(sd + lay.weight, wt ? wt : ones.data(), (size_t)h->n * sizeof(double), hipMemcpyHostToDevice,
+                                 h->stream));
+    }
     HIPCHK(h, hipMemsetAsync(h->y, 0, colbytes, h->stream));
     HIPCHK(h, hipMemsetAsync(h->r, 0, colbytes, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (the host vectors above are pageable: the copies are done here)
     h->y_set = true;
     h->glm.family = GlmData::Cox;
     h->glm.has_offset = off != nullptr;
+    h->glm.cox.strata = sw;
     h->glm.set = true;
     return CDH_OK;
 }
@@ -325,6 +503,29 @@ int32_t cox_get_survival(cdh_handle h, void* host_time, void* host_status) {
     if (host_time)
         HIPCHK(h, hipMemcpyAsync(host_time, (const double*)h->glm.cox.d + cox_layout(h->ld).time, bytes, hipMemcpyDeviceToHost, h->stream));
     if (host_status) HIPCHK(h, hipMemcpyAsync(host_status, h->glm.labels, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CDH_OK;
+}
+
+// cdh_glm_get_survival_strata: the stratum ids and the weights in the caller's row order; zeros and ones where the handle
+// holds none
+int32_t cox_get_survival_strata(cdh_handle h, int32_t* host_strata, void* host_weights) {
+    if (!host_strata && !host_weights) return fail(h, CDH_BAD_ARG, "host_strata and host_weights are both NULL");
+    if (!h->glm.set || h->glm.family != GlmData::Cox)
+        return fail(h, CDH_BAD_ARG, "no survival data are set: call cdh_glm_set_survival first");
+    if (!h->glm.cox.strata) {
+        if (host_strata) memset(host_strata, 0, (size_t)h->n * sizeof(int32_t));
+        if (host_weights) std::fill_n((double*)host_weights, (size_t)h->n, 1.0);
+        return CDH_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const CoxLayout lay = cox_layout(h->ld);
+    if (host_strata)
+        HIPCHK(h, hipMemcpyAsync(host_strata, (const int32_t*)h->glm.cox.si + lay.strata, (size_t)h->n * sizeof(int32_t),
+                                 hipMemcpyDeviceToHost, h->stream));
+    if (host_weights)
+        HIPCHK(h, hipMemcpyAsync(host_weights, (const double*)h->glm.cox.sd + lay.weight, (size_t)h->n * sizeof(double),
+                                 hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
 }
@@ -373,26 +574,38 @@ int32_t glm_launch<GlmCox>(cdh_handle h, int32_t k, bool apply, const GlmParams&
     const uint8_t* fold = k >= 0 ? (const uint8_t*)h->cv.fold : (const uint8_t*)nullptr;
     double *y = (double*)h->y, *r = (double*)h->r, *w = (double*)h->w;
     const dim3 grid((unsigned)pl.grid), one(1), two(2), block(kCoxBlock);
-    hipLaunchKernelGGL(k_cox_exp, grid, block, 0, h->stream, order, status, (const double*)y, (const double*)r, off, fold, (int)k,
-                       h->n, h->ld, pl.tiles, pm.eta_max, eT, hA, sums);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_cox_offsets<true>, one, block, 0, h->stream, sums, (int)pl.grid);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL((k_cox_scan<1, true>), grid, block, 0, h->stream, eT, (const double*)sums, h->ld, pl.tiles);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_cox_hazard, grid, block, 0, h->stream, first, (const double*)eT, hA, hB, h->ld, pl.tiles, sums_h);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_cox_offsets<false>, two, block, 0, h->stream, sums_h, (int)pl.grid);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL((k_cox_scan<2, false>), grid, block, 0, h->stream, hA, (const double*)sums_h, h->ld, pl.tiles);
-    HIPCHK(h, hipGetLastError());
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, h->stream, order, first, last, status, y, r, w, off, fold, (int)k, h->n, h->ld,
-                           pl.tiles, pm.wmin, pm.eta_max, (const double*)eT, (const double*)hA, (const double*)hB,
-                           (double*)h->d_partials);
+    // the instantiations are chosen here: a handle without strata and weights runs the plain scans and the unweighted rows
+    auto chain = [&](auto sw_tag) -> int32_t {
+        constexpr bool SW = decltype(sw_tag)::value;
+        const int32_t* si = SW ? (const int32_t*)h->glm.cox.si : (const int32_t*)nullptr;
+        const int32_t *sfirst = SW ? si + lay.sfirst : nullptr, *slast = SW ? si + lay.slast : nullptr;
+        int32_t* heads = SW ? (int32_t*)h->glm.cox.si + lay.heads : nullptr;
+        int32_t* heads_h = SW ? heads + kCoxMaxGrid : nullptr;
+        const double* weight = SW ? (const double*)h->glm.cox.sd + lay.weight : (const double*)nullptr;
+        hipLaunchKernelGGL(k_cox_exp<SW>, grid, block, 0, h->stream, order, status, (const double*)y, (const double*)r, off, fold,
+                           (int)k, h->n, h->ld, pl.tiles, pm.eta_max, eT, hA, sums, weight, slast, heads);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL((k_cox_offsets<true, SW>), one, block, 0, h->stream, sums, (int)pl.grid, (const int32_t*)heads);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL((k_cox_scan<1, true, SW>), grid, block, 0, h->stream, eT, (const double*)sums, h->ld, pl.tiles, slast);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(k_cox_hazard<SW>, grid, block, 0, h->stream, first, (const double*)eT, hA, hB, h->ld, pl.tiles, sums_h,
+                           sfirst, heads_h);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL((k_cox_offsets<false, SW>), two, block, 0, h->stream, sums_h, (int)pl.grid, (const int32_t*)heads_h);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL((k_cox_scan<2, false, SW>), grid, block, 0, h->stream, hA, (const double*)sums_h, h->ld, pl.tiles, sfirst);
+        HIPCHK(h, hipGetLastError());
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, h->stream, order, first, last, status, y, r, w, off, fold, (int)k, h->n, h->ld,
+                               pl.tiles, pm.wmin, pm.eta_max, (const double*)eT, (const double*)hA, (const double*)hB,
+                               (double*)h->d_partials, weight);
+        };
+        if (apply) go(k_cox_apply<true, SW>); else go(k_cox_apply<false, SW>);
+        HIPCHK(h, hipGetLastError());
+        return CDH_OK;
     };
-    if (apply) go(k_cox_apply<true>); else go(k_cox_apply<false>);
-    HIPCHK(h, hipGetLastError());
+    if (h->glm.cox.strata) CHK(chain(std::true_type{})); else CHK(chain(std::false_type{}));
     hipLaunchKernelGGL(k_gram_reduce, dim3((kCoxVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
                        (const double*)h->d_partials, (int)pl.records, (int)kCoxVals, (double*)h->d_red);
     HIPCHK(h, hipGetLastError());

@@ -1,7 +1,9 @@
 // cox_plan.hpp -- the host-only arithmetic of the Cox step (cox_kernels.hpp: cdh_glm_set_survival, cdh_glm_cox_irls): the tile of
 // a scan, how the tiles are dealt to the workgroups, the layout of the step's scratch, and the time order with its tie groups
-// as cdh_glm_set_survival uploads them.  No HIP in here: tests/test_cox_plan_host.py compiles it with g++
-// (tests/cox_plan_main.cpp).  cox_kernels.hpp calls these functions and nothing else decides the sizes.
+// as cdh_glm_set_survival uploads them -- and, for cdh_glm_set_survival_strata, the order by (stratum, time) with the bounds of
+// every position's stratum.  No HIP in here: tests/test_cox_plan_host.py and tests/test_cox_strata_plan_host.py compile it with
+// g++ (tests/cox_plan_main.cpp, tests/cox_strata_plan_main.cpp).  cox_kernels.hpp calls these functions and nothing else
+// decides the sizes.
 //
 // The tie groups are kept as TWO int32 vectors, not as head flags: first[s] and last[s] are the first and the last sorted
 // position of the group that sorted position s belongs to.  The risk-set sum of a row is the suffix scan read at first[s], its
@@ -53,20 +55,31 @@ constexpr int64_t cox_run_first(int64_t tiles, int64_t grid, int64_t b) { return
 // ---- the scratch -------------------------------------------------------------------------------------------------------------
 // One buffer of doubles: e (then T, its suffix scan, in place), h (then A), h2 (then B) and the times, ld each, then the
 // runs' sums (then offsets) of the three scans, kCoxMaxGrid each.  One buffer of int32: order, first, last, ld each.
+// A handle with strata or observation weights (cdh_glm_set_survival_strata) holds a SECOND pair of buffers, which a plain
+// handle never allocates: int32 -- sfirst and slast, the bounds of every position's stratum, the stratum ids in the caller's
+// row order (for the getter), ld each, then the head-seen flags of the runs, kCoxMaxGrid for the suffix scan and kCoxMaxGrid
+// for the two prefix scans; doubles -- the weights in the caller's row order, ld.
 struct CoxLayout {
     int64_t eT, hA, hB, time, sums;   // offsets in doubles; sums + i kCoxMaxGrid: scan i's runs
     int64_t doubles;
     int64_t order, first, last;       // offsets in int32s
     int64_t ints;
+    int64_t sfirst, slast, strata, heads;   // offsets in int32s of the second pair; heads + i kCoxMaxGrid: suffix (0), prefix (1)
+    int64_t strata_ints;
+    int64_t weight;                   // offset in doubles of the second pair
+    int64_t strata_doubles;
 };
 constexpr CoxLayout cox_layout(int64_t ld) {
-    return CoxLayout{0, ld, 2 * ld, 3 * ld, 4 * ld, 4 * ld + 3 * kCoxMaxGrid, 0, ld, 2 * ld, 3 * ld};
+    return CoxLayout{0, ld, 2 * ld, 3 * ld, 4 * ld, 4 * ld + 3 * kCoxMaxGrid, 0, ld, 2 * ld, 3 * ld,
+                     0, ld, 2 * ld, 3 * ld, 3 * ld + 2 * kCoxMaxGrid, 0, ld};
 }
 
 // ---- the time order and its tie groups ---------------------------------------------------------------------------------------
 // What cdh_glm_set_survival refuses of its data, the row named in msg (at least 128 chars): a time or an offset that is not
-// finite, a status other than 0 or 1, no event at all.  -> true when the data pass.
-inline bool cox_check(int64_t n, const double* time, const double* status, const double* offset, char* msg, size_t len) {
+// finite, a status other than 0 or 1, a weight (cdh_glm_set_survival_strata; NULL: none) that is not finite or not > 0, no
+// event at all.  -> true when the data pass.
+inline bool cox_check(int64_t n, const double* time, const double* status, const double* offset, char* msg, size_t len,
+                      const double* weights = nullptr) {
     int64_t events = 0;
     for (int64_t i = 0; i < n; ++i) {
         if (!(fabs(time[i]) <= 1.7976931348623157e308)) {          // (a NaN fails the comparison)
@@ -79,6 +92,10 @@ inline bool cox_check(int64_t n, const double* time, const double* status, const
         }
         if (offset && !(fabs(offset[i]) <= 1.7976931348623157e308)) {
             snprintf(msg, len, "offset[%lld] = %g is not finite", (long long)i, offset[i]);
+            return false;
+        }
+        if (weights && !(weights[i] > 0.0 && weights[i] <= 1.7976931348623157e308)) {
+            snprintf(msg, len, "weights[%lld] = %g is not finite and > 0", (long long)i, weights[i]);
             return false;
         }
         events += status[i] == 1.0;
@@ -106,4 +123,40 @@ inline void cox_order(int64_t n, int64_t ld, const double* time, std::vector<int
         s = e;
     }
     for (int64_t s = n; s < ld; ++s) { first[s] = (int32_t)s; last[s] = (int32_t)s; }
+}
+
+// The same order with strata: a stable ascending sort by (stratum id, time) -- the strata in ascending id order, the rows of a
+// stratum in time order, rows equal in both in the caller's order -- so that a stratum is a SEGMENT of sorted positions.
+// first[s], last[s]: the bounds of s's tie group (same stratum AND same time); sfirst[s], slast[s]: the bounds of s's stratum.
+// Positions n .. ld - 1 are the pad rows in place: each a tie group of its own, together ONE stratum (n .. ld - 1).
+// strata == nullptr: one stratum; order, first and last are then cox_order's, element for element.
+inline void cox_order_strata(int64_t n, int64_t ld, const double* time, const int32_t* strata, std::vector<int32_t>& order,
+                             std::vector<int32_t>& first, std::vector<int32_t>& last, std::vector<int32_t>& sfirst,
+                             std::vector<int32_t>& slast) {
+    order.resize((size_t)ld);
+    first.resize((size_t)ld);
+    last.resize((size_t)ld);
+    sfirst.resize((size_t)ld);
+    slast.resize((size_t)ld);
+    std::iota(order.begin(), order.end(), 0);
+    auto stratum = [&](int32_t row) { return strata ? strata[row] : 0; };
+    std::stable_sort(order.begin(), order.begin() + n, [&](int32_t a, int32_t b) {
+        return stratum(a) != stratum(b) ? stratum(a) < stratum(b) : time[a] < time[b];
+    });
+    for (int64_t s = 0; s < n;) {
+        int64_t se = s + 1;
+        while (se < n && stratum(order[se]) == stratum(order[s])) ++se;
+        for (int64_t g = s; g < se;) {
+            int64_t e = g + 1;
+            while (e < se && time[order[e]] == time[order[g]]) ++e;
+            for (int64_t q = g; q < e; ++q) { first[q] = (int32_t)g; last[q] = (int32_t)(e - 1); }
+            g = e;
+        }
+        for (int64_t q = s; q < se; ++q) { sfirst[q] = (int32_t)s; slast[q] = (int32_t)(se - 1); }
+        s = se;
+    }
+    for (int64_t s = n; s < ld; ++s) {
+        first[s] = (int32_t)s; last[s] = (int32_t)s;
+        sfirst[s] = (int32_t)n; slast[s] = (int32_t)(ld - 1);
+    }
 }

@@ -344,8 +344,13 @@ int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin
  * w = max(w_raw, wmin); d = delta - eA; r_new = d / w; z_lin = eta_lin + r_new (eta_lin = y_w - r = X beta WITHOUT the offset, as
  * for the Poisson family).  Only w is clamped, so X'W r = X'(delta - eA), the negative gradient of the partial likelihood.
  * S, A and B come from a segmented suffix scan and two segmented prefix scans in time order, a chain of launches on the
- * handle's stream in which every sum has a fixed order.  Strata, start-stop times, Efron ties and observation weights are
- * not offered. */
+ * handle's stream in which every sum has a fixed order.
+ * With strata and observation weights (cdh_glm_set_survival_strata): each row has a weight v_i > 0 and a stratum id g_i;
+ * ev = v e and dv = v delta take the places of e and delta, S_i runs over the rows of g_i with t_j >= t_i, A_i and B_i over the
+ * rows of g_i with t_k <= t_i: ev = v e; evA = ev A; w_raw = evA - ev (ev B); d = dv - evA; the nll term is dv (log S - eta).
+ * The rows are ordered by (stratum, time) and the three scans restart at every stratum's boundary (segmented scans, the
+ * rounding error of a sum relative to its own stratum's sum).  The diagonal is v e A - (v e)^2 B: an integer weight
+ * reproduces a replicated row's gradient and nll, not its diagonal.  Start-stop times and Efron ties are not offered. */
 /* cdh_glm_set_survival (no reference counterpart; the loss is that of cd_differentiable_function.jl:118-194 per round)
  * stands in for cdh_set_y: it stores n statuses where cdh_glm_set_labels stores labels, n offsets (when not NULL) where
  * cdh_glm_set_counts stores them, sorts the times on the host (stable, ascending) and keeps the order, the tie groups' bounds,
@@ -360,6 +365,22 @@ int32_t cdh_glm_set_survival(cdh_handle h, const void *host_time, const void *ho
  * times and the n statuses of a Cox handle, in the caller's row order; a NULL output is skipped.  CDH_BAD_ARG: both NULL; no
  * survival data set. */
 int32_t cdh_glm_get_survival(cdh_handle h, void *host_time, void *host_status);
+/* cdh_glm_set_survival_strata (no reference counterpart; see cdh_glm_set_survival, cd_differentiable_function.jl:118-194):
+ * cdh_glm_set_survival with n int32 stratum ids and n weights, either of which may be NULL (one stratum; unit weights).
+ * With both NULL it IS cdh_glm_set_survival, call for call and bit for bit.  Otherwise the order is a stable ascending sort
+ * by (stratum id, time) -- every int32 is a valid id -- and the bounds of every position's stratum, the ids and the weights
+ * live in a second group of buffers, allocated all-or-nothing with the rest before the handle changes.  The weights are stored
+ * as given: the library does not normalise them.  CDH_BAD_ARG, the handle unchanged: what cdh_glm_set_survival refuses; a
+ * weight that is not finite or not > 0 (the message names the row).  cdh_glm_set_survival, cdh_glm_set_labels and
+ * cdh_glm_set_counts drop the strata and the weights. */
+int32_t cdh_glm_set_survival_strata(cdh_handle h, const void *host_time, const void *host_status,
+                                    const void *host_offset_or_null, const int32_t *host_strata_or_null,
+                                    const void *host_weights_or_null);
+/* cdh_glm_get_survival_strata (no reference counterpart; see cdh_glm_set_survival_strata,
+ * cd_differentiable_function.jl:118-194): the n stratum ids and the n weights of a Cox handle, in the caller's row order --
+ * zeros where it holds no strata, ones where it holds no weights; a NULL output is skipped.  CDH_BAD_ARG: both NULL; no
+ * survival data set. */
+int32_t cdh_glm_get_survival_strata(cdh_handle h, int32_t *host_strata, void *host_weights);
 /* cdh_glm_cox_irls (no reference counterpart; a round's solve is the weighted lasso of CDWeightedLSLoss,
  * cd_differentiable_function.jl:118-194): the step between two rounds at the iterate the handle holds.
  *   a training row becomes (w, y_w, r) = (w, z_lin, r_new); a row before the first event has w = wmin and r_new = 0 exactly;
@@ -367,7 +388,9 @@ int32_t cdh_glm_get_survival(cdh_handle h, void *host_time, void *host_status);
  *   rows n .. ld - 1 are written as zeros.
  * k == -1: no row is held out and the fold ids are not read (the same bits whether or not folds are set).  out5 = {sum of
  * delta_i (log S_i - eta_i) over the training rows, sum of w_i, training rows clamped at wmin, live rows capped at eta_max,
- * events among the training rows}, each summed in a fixed order: bit-identical run to run.  The catch-up of r before the
+ * sum of dv_i = v_i delta_i over the training rows: the events among them, bit for bit, on a handle without weights}, each
+ * summed in a fixed order: bit-identical run to run; on a handle with strata and weights the first sum is that of
+ * dv_i (log S_i - eta_i).  The catch-up of r before the
  * step, apply = 0 (read-only) and the state apply = 1 leaves are cdh_glm_irls'.  CDH_BAD_ARG, the handle unchanged: no
  * survival data set; apply not in {0, 1}; wmin not finite or not > 0; eta_max outside (0, 700]; k < -1; k >= 0 without
  * folds; k >= K; out5 NULL. */

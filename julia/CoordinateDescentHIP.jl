@@ -577,12 +577,36 @@ function glm_get_survival(X::HipMatrix{Float64})
   (time, status)
 end
 
+"glm_set_survival! with stratum ids (Int32; nothing: one stratum) and observation weights (stored as given; nothing: ones); with neither it is glm_set_survival!"
+function glm_set_survival_strata!(X::HipMatrix{Float64}, time::Vector{Float64}, status::Vector{Float64}, offset::Union{Nothing,Vector{Float64}}=nothing;
+                                  strata::Union{Nothing,Vector{Int32}}=nothing, weights::Union{Nothing,Vector{Float64}}=nothing)
+  length(time) == X.n && length(status) == X.n || throw(DimensionMismatch())
+  for v in (offset, strata, weights)
+    v === nothing || length(v) == X.n || throw(DimensionMismatch())
+  end
+  set_loss!(X, CDH_WLS)
+  check(X.handle, ccall((:cdh_glm_set_survival_strata, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cvoid}),
+                        X.handle, time, status, offset === nothing ? C_NULL : pointer(offset),
+                        strata === nothing ? C_NULL : pointer(strata), weights === nothing ? C_NULL : pointer(weights)))
+  X.owner = nothing
+  X.synced = false
+  X
+end
+
+"the stratum ids (zeros without strata) and the observation weights (ones without weights) of a Cox handle, in the caller's row order"
+function glm_get_survival_strata(X::HipMatrix{Float64})
+  strata = Vector{Int32}(undef, X.n)
+  weights = Vector{Float64}(undef, X.n)
+  check(X.handle, ccall((:cdh_glm_get_survival_strata, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Cvoid}), X.handle, strata, weights))
+  (strata, weights)
+end
+
 "one Cox IRLS step at the iterate the handle holds, fold k (0-based, -1: none) held out; apply=false reads only"
 function glm_cox_irls!(X::HipMatrix{Float64}, k::Integer=-1; apply::Bool=true, wmin::Float64=1e-5, eta_max::Float64=50.0)
   out = Vector{Float64}(undef, 5)
   check(X.handle, ccall((:cdh_glm_cox_irls, libcdhip), Int32, (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Ptr{Float64}),
                         X.handle, Int32(k), Int32(apply), wmin, eta_max, out))
-  (nll = out[1] / X.n, sum_w = out[2], clamped = Int(out[3]), capped = Int(out[4]), events = Int(out[5]))
+  (nll = out[1] / X.n, sum_w = out[2], clamped = Int(out[3]), capped = Int(out[4]), events = isinteger(out[5]) ? Int(out[5]) : out[5])   # the sum of v delta: the event count, an Int, without weights
 end
 
 # ---- locpolyl1 with the design expanded on the device (src/varying_coefficient_lasso.jl:30-79) ----------------

@@ -21,7 +21,13 @@ order, and nothing runs after a child that failed or timed out (its status is in
       reported: wall times, the IRLS rounds of each, whether they agree at every lambda, the largest difference of the
       coefficients.
 
-Environment: N, REPS, ROUNDS, N2, P2, M2, PROUNDS, STEP_TIMEOUT, PATH_TIMEOUT, OUT (a file that receives the line too)."""
+STRATA=S (default 0: everything above, unchanged) runs the same three measurements with S strata (ids uniform over the rows) and
+observation weights uniform in [0.25, 4], normalised to sum to n, through cdh_glm_set_survival_strata: "pre-sorted" is then by
+(stratum, time), the host's step takes its cumulative sums per stratum, and the copy moves 252 bytes a row -- the weight is
+gathered in the exp and the apply launch (16) and one int32 stratum bound is read in each of the two scan launches (8).  The
+line gains the keys "strata" and "weighted" in every measurement.
+
+Environment: N, REPS, ROUNDS, N2, P2, M2, PROUNDS, STEP_TIMEOUT, PATH_TIMEOUT, STRATA, OUT (a file that receives the line too)."""
 import ctypes as C
 import json
 import os
@@ -72,6 +78,8 @@ step = sys.argv[sys.argv.index("--step") + 1]
 vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
 PD = C.POINTER(C.c_double)
 WMIN, ETA_MAX = 1e-5, 50.0
+STRATA = env("STRATA", 0)
+BYTES = 252 if STRATA else 228
 
 
 def timed(fn):
@@ -81,55 +89,92 @@ def timed(fn):
 
 
 class HostStep:
-    """The twin's step (tests/_cox_numpy.py: rows, the cumulative-sum form) with the sort order and the tie groups cached."""
+    """The twin's step (tests/_cox_numpy.py: rows, the cumulative-sum form) with the sort order and the tie groups cached.
+    With strata g and weights v (tests/_cox_strata_numpy.py) the order is by (stratum, time) and a cumulative sum restarts
+    at a stratum's boundary: the sum over all positions less its value just outside the stratum."""
 
-    def __init__(self, t, status, off):
+    def __init__(self, t, status, off, g=None, v=None):
         n = len(t)
-        self.order = np.argsort(t, kind="stable")
+        self.order = np.argsort(t, kind="stable") if g is None else np.lexsort((t, g))
         ts = t[self.order]
         head = np.r_[True, ts[1:] != ts[:-1]]
+        self.sfirst = self.slast = None
+        if g is not None:
+            gs = g[self.order]
+            shead = np.r_[True, gs[1:] != gs[:-1]]
+            head |= shead
+            sstarts = np.nonzero(shead)[0]
+            sid = np.cumsum(shead) - 1
+            self.sfirst, self.slast = sstarts[sid], (np.r_[sstarts[1:], n] - 1)[sid]
         starts = np.nonzero(head)[0]
         gid = np.cumsum(head) - 1
         self.first, self.last = starts[gid], (np.r_[starts[1:], n] - 1)[gid]
-        self.ds, self.status, self.off = status[self.order], status, off
+        self.v = np.ones(n) if v is None else v
+        self.dv = self.v * status
+        self.ds, self.off = self.dv[self.order], off
         self.inv = np.empty(n, dtype=np.int64)
         self.inv[self.order] = np.arange(n)
 
+    def _suffix(self, a):
+        T = np.cumsum(a[::-1])[::-1]
+        return T if self.slast is None else T - np.r_[T[1:], 0.0][self.slast]
+
+    def _prefix(self, a):
+        c = np.cumsum(a)
+        return c if self.sfirst is None else c - np.r_[0.0, c[:-1]][self.sfirst]
+
     def __call__(self, eta_lin):
-        e = np.exp(np.minimum(eta_lin + self.off, ETA_MAX))
-        T = np.cumsum(e[self.order][::-1])[::-1]
-        Ss = T[self.first]
+        e = self.v * np.exp(np.minimum(eta_lin + self.off, ETA_MAX))
+        Ss = self._suffix(e[self.order])[self.first]
         h = self.ds / Ss
-        A, B = np.cumsum(h)[self.last][self.inv], np.cumsum(h / Ss)[self.last][self.inv]
+        A, B = self._prefix(h)[self.last][self.inv], self._prefix(h / Ss)[self.last][self.inv]
         eA = e * A
         w = np.maximum(eA - e * (e * B), WMIN)
-        return eta_lin + (self.status - eA) / w, w
+        return eta_lin + (self.dv - eA) / w, w
 
 
 def survival(f, seed, presorted):
-    """Times ~ Exp(1) / exp(signal), rounded to three decimals; 30 % censored; an offset in (-0.5, 0.5)."""
+    """Times ~ Exp(1) / exp(signal), rounded to three decimals; 30 % censored; an offset in (-0.5, 0.5).  With STRATA: ids
+    uniform over the rows and weights uniform in [0.25, 4], normalised to sum to n.  -> (t, status, off, strata, weights)."""
     n = f.n
     rng = np.random.default_rng(seed)
     sig = f.y
     off = rng.uniform(-0.5, 0.5, n)
     t = np.round(rng.exponential(1.0, n) / np.exp(0.5 * sig / np.std(sig) + off), 3)
-    if presorted:
-        t = np.sort(t)
     status = (rng.random(n) >= 0.3).astype(np.float64)
-    cd.check(f._L.cdh_glm_set_survival(f._h, vp(t), vp(status), vp(off)), f._h)
-    return t, status, off
+    if not STRATA:
+        if presorted:
+            t = np.sort(t)
+        cd.check(f._L.cdh_glm_set_survival(f._h, vp(t), vp(status), vp(off)), f._h)
+        return t, status, off, None, None
+    g = rng.integers(0, STRATA, n).astype(np.int32)
+    v = rng.uniform(0.25, 4.0, n)
+    v = v * n / v.sum()
+    if presorted:
+        o = np.lexsort((t, g))
+        t, g = np.ascontiguousarray(t[o]), np.ascontiguousarray(g[o])
+    set_survival(f, t, status, off, g, v)
+    f._weighted = True
+    return t, status, off, g, v
+
+
+def set_survival(f, t, status, off, g, v):
+    if g is None:
+        cd.check(f._L.cdh_glm_set_survival(f._h, vp(t), vp(status), vp(off)), f._h)
+    else:
+        cd.check(f._L.cdh_glm_set_survival_strata(f._h, vp(t), vp(status), vp(off), vp(g), vp(v)), f._h)
 
 
 def measure_step(presorted):
     n, reps, rounds = env("N", 2_000_000), env("REPS", 5), env("ROUNDS", 3)
     f, _ = cd.CDCoxLoss.generate(n, 1, seed=7, s=1, noise=1.0)
-    t, status, off = survival(f, 7, presorted)
+    t, status, off, g, v = survival(f, 7, presorted)
     x = cd.SparseIterate(1)
     x[1] = 0.5
     cd.initialize_(f, x)
     L, h = f._L, f._h
     out5, r = np.zeros(5), np.zeros(n)
-    host = HostStep(t, status, off)
+    host = HostStep(t, status, off, g, v)
     z = f.y
 
     def dev1():
@@ -145,14 +190,14 @@ def measure_step(presorted):
         cd.check(L.cdh_set_y(h, vp(z)), h)
         cd.check(L.cdh_set_obs_weights(h, vp(w)), h)
 
-    src = torch.randn(114 * n // 8, dtype=torch.float64, device="cuda")
+    src = torch.randn(BYTES // 2 * n // 8, dtype=torch.float64, device="cuda")
     dst = torch.empty_like(src)
 
     def copy():
         dst.copy_(src)
         torch.cuda.synchronize()
 
-    names, fns = ("cox_apply1", "cox_apply0", "copy_228_bytes_a_row"), (dev1, dev0, copy)
+    names, fns = ("cox_apply1", "cox_apply0", "copy_%d_bytes_a_row" % BYTES), (dev1, dev0, copy)
     for fn in fns:
         fn()
     per = {k: [] for k in names}
@@ -170,11 +215,11 @@ def measure_step(presorted):
         cd.initialize_(f, x)
         z = f.y
         comp.append(timed(composed)[0])
-    res = {"n": n, "presorted": presorted, "tie_groups": int(len(np.unique(t))), "clamped": int(out5[2]), "events": int(out5[4]),
-           "bytes_a_row": 228}
+    res = {"n": n, "presorted": presorted, "tie_groups": int(len(np.unique(t))), "clamped": int(out5[2]),
+           "events": float(out5[4]) if STRATA else int(out5[4]), "bytes_a_row": BYTES, "strata": STRATA, "weighted": bool(STRATA)}
     for k, v in per.items():
         res[k] = {"round_minima_ms": [1e3 * a for a in v], "min_ms": 1e3 * min(v), "spread_ms": 1e3 * (max(v) - min(v)),
-                  "TBps_of_228n": 228 * n / min(v) / 1e12}
+                  "TBps_of_%dn" % BYTES: BYTES * n / min(v) / 1e12}
     res["host_composed_ms"] = [1e3 * a for a in comp]
     res["cox_over_copy"] = min(per[names[0]]) / min(per[names[2]])
     res["host_composed_over_cox"] = min(comp) / min(per[names[0]])
@@ -185,12 +230,12 @@ def measure_step(presorted):
 def measure_path():
     n, p, m, rounds = env("N2", 2_000_000), env("P2", 1000), env("M2", 30), env("PROUNDS", 2)
     f, _ = cd.CDCoxLoss.generate(n, p, seed=11, s=10, noise=1.0)
-    t, status, off = survival(f, 11, False)
+    t, status, off, g, v = survival(f, 11, False)
     lmax = cd.coxLambdaMax(f)
     lam = lmax * np.geomspace(0.9, 0.05, m)
     opts = cd.CDOptions(maxIter=2000, optTol=1e-7, randomize=False)
     irls = cd.IRLSOptions(maxIter=100)
-    host = HostStep(t, status, off)
+    host = HostStep(t, status, off, g, v)
     L, h = f._L, f._h
 
     def device_route(lams):
@@ -227,7 +272,7 @@ def measure_path():
         return betas, rounds_
 
     def reset():
-        cd.check(L.cdh_glm_set_survival(h, vp(t), vp(status), vp(off)), h)      # the Cox handle as it was made: y = r = 0
+        set_survival(f, t, status, off, g, v)                   # the Cox handle as it was made: y = r = 0
         f._synced = None
 
     device_route(lam[:3])
@@ -242,7 +287,7 @@ def measure_path():
         tt, (betas, crounds) = timed(lambda: composed_route(lam))
         t_com.append(tt)
     diff = max(float(np.max(np.abs(b.dense() - c))) for b, c in zip(path.betapath, betas))
-    res = {"n": n, "p": p, "lambdas": m, "CoxLassoPath_s": t_dev, "composed_s": t_com,
+    res = {"n": n, "p": p, "lambdas": m, "strata": STRATA, "weighted": bool(STRATA), "CoxLassoPath_s": t_dev, "composed_s": t_com,
            "min_s": {"CoxLassoPath": min(t_dev), "composed": min(t_com)},
            "composed_over_CoxLassoPath": min(t_com) / min(t_dev),
            "irls_rounds": {"CoxLassoPath": int(sum(path.rounds)), "composed": int(sum(crounds))},
