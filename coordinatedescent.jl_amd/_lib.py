@@ -130,6 +130,8 @@ def lib():
         "cdh_glm_get_survival": [vp, vp, vp],
         "cdh_glm_set_survival_strata": [vp, vp, vp, vp, vp, vp],
         "cdh_glm_get_survival_strata": [vp, vp, vp],
+        "cdh_glm_set_survival_interval": [vp, vp, vp, vp, vp, vp, vp],
+        "cdh_glm_get_survival_start": [vp, vp],
         "cdh_glm_cox_irls": [vp, i32, i32, f64, f64, P(f64)],
         "cdh_generate": [vp, C.c_uint64, i64, f64, vp],
         "cdh_set_penalty": [vp, f64, vp, i64],

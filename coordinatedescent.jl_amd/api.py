@@ -631,15 +631,20 @@ class CDPoissonLoss(_GLMLoss):
         return self.irls_step(apply, irls.wmin, irls.etaMax, fold)
 
 
-def _survival(y, n=None):
-    """y = [time, status] (n x 2, glmnet's Surv matrix) -> (time, status) as contiguous float64 vectors, refused on the host
-    the way cdh_glm_set_survival would refuse them."""
+def _survival3(y, n=None):
+    """y = [time, status] (n x 2, glmnet's Surv matrix) or [start, stop, status] (n x 3, Surv(start, stop, status)) ->
+    (start or None, time, status) as contiguous float64 vectors, time the stop time; refused on the host the way
+    cdh_glm_set_survival and cdh_glm_set_survival_interval would refuse them.  One refusal is worded for this layer: a
+    three-column y whose first column is not below its second is not an interval matrix at all -- what a [time, status, ...]
+    matrix with a column too many looks like -- so it is a DimensionMismatch, as every other y that is not a Surv matrix is;
+    the message names the row and the two values."""
     y = np.asarray(y, dtype=np.float64)
-    if y.ndim != 2 or y.shape[1] != 2:
-        raise DimensionMismatch("y must be n x 2: [time, status]")
+    if y.ndim != 2 or y.shape[1] not in (2, 3):
+        raise DimensionMismatch("y must be n x 2: [time, status], or n x 3: [start, stop, status]")
     if n is not None and y.shape[0] != n:
         raise DimensionMismatch("size(y, 1) != size(X, 1)")
-    time, status = np.ascontiguousarray(y[:, 0]), np.ascontiguousarray(y[:, 1])
+    start = np.ascontiguousarray(y[:, 0]) if y.shape[1] == 3 else None
+    time, status = np.ascontiguousarray(y[:, -2]), np.ascontiguousarray(y[:, -1])
     if not np.all(np.isfinite(time)):
         raise ArgumentError("time[%d] is not finite" % int(np.nonzero(~np.isfinite(time))[0][0]))
     bad = (status != 0.0) & (status != 1.0)
@@ -647,7 +652,20 @@ def _survival(y, n=None):
         raise ArgumentError("status[%d] is neither 0 (censored) nor 1 (event)" % int(np.nonzero(bad)[0][0]))
     if not np.any(status == 1.0):
         raise ArgumentError("no row is an event: the partial likelihood is constant")
-    return time, status
+    if start is not None:
+        if not np.all(np.isfinite(start)):
+            raise ArgumentError("start[%d] is not finite" % int(np.nonzero(~np.isfinite(start))[0][0]))
+        bad = ~(start < time)
+        if np.any(bad):
+            i = int(np.nonzero(bad)[0][0])
+            raise DimensionMismatch("y is n x 3 but not [start, stop, status]: start[%d] = %g is not below stop[%d] = %g"
+                                    % (i, start[i], i, time[i]))
+    return start, time, status
+
+
+def _survival(y, n=None):
+    """_survival3 without the start times: (time, status)."""
+    return _survival3(y, n)[1:]
 
 
 def _strata_weights(strata, weights, n):
@@ -685,7 +703,17 @@ class CDCoxLoss(_GLMLoss):
     round is the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the working response and
     weights the handle's y and w hold from one irls_step to the next.  The step is not elementwise: the risk-set sums are
     scans in time order, run on the device through the order cdh_glm_set_survival keeps; the rows stay in the caller's order.
-    There is no intercept (it cancels), and no start-stop times or Efron ties.
+    There is no intercept (it cancels), and no Efron ties.
+
+    Start-stop times (glmnet's Surv(start, stop, status)): y is n x 3, [start, stop, status], and row i is at risk at t iff
+    start_i < t <= stop_i -- time-varying covariates (a subject is several rows), delayed entry, recurrent events.  A row
+    whose start equals an event time is not at risk at it; one whose stop equals it is.  S(t) is then a DIFFERENCE, the sum
+    over stop_j >= t less the sum over start_j >= t (a second order by (stratum, start), a second scan), and A_i = P(stop_i) -
+    P(start_i) with P(u) = Σ_{event times t <= u} δ / S(t), B likewise.  The subtraction is inherent -- glmnet and
+    survival::coxph subtract too: the error of S is relative to the two sums of the row's stratum, about n U (T + T2), not to
+    S, and that of A and B to P(stop) + P(start); an event whose computed S is not > 0 is skipped, a working weight driven
+    negative is clamped at wmin.  The handle then always runs the segmented, weighted arithmetic.  The library does not know
+    subjects: in cross-validation the rows of one subject should share a fold -- pass folds=.
 
     strata (glmnet's stratifySurv): integer ids that fit int32; S_i, A_i and B_i then run over the rows of row i's stratum
     only, by scans that restart at every stratum's boundary.  weights (glmnet's weights =): v_i > 0, normalised HERE to sum to
@@ -695,16 +723,20 @@ class CDCoxLoss(_GLMLoss):
     _stdX!, the root mean square over the rows present: they are NOT weighted by v.  fp64 only, one device."""
 
     def __init__(self, y, X, offset=None, *, strata=None, weights=None, device=0):
-        self._time, status = _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
+        self._start, self._time, status = _survival3(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
         if offset is not None and not np.all(np.isfinite(np.asarray(offset, dtype=np.float64))):
             raise ArgumentError("the offset is not finite")
         self._strata, self._weights = _strata_weights(strata, weights, len(status))
         self._weighted = self._weights is not None
+        self._interval = self._start is not None
         super().__init__(status, X, offset, device=device)
-        del self._time, self._strata, self._weights
+        del self._start, self._time, self._strata, self._weights
 
     def _set_observations(self, status, off):
-        if self._strata is None and self._weights is None:
+        if self._start is not None:
+            check(self._L.cdh_glm_set_survival_interval(self._h, _vp(self._start), _vp(self._time), _vp(status), _vp(off),
+                                                        _vp(self._strata), _vp(self._weights)), self._h)
+        elif self._strata is None and self._weights is None:
             check(self._L.cdh_glm_set_survival(self._h, _vp(self._time), _vp(status), _vp(off)), self._h)
         else:
             check(self._L.cdh_glm_set_survival_strata(self._h, _vp(self._time), _vp(status), _vp(off), _vp(self._strata),
@@ -731,7 +763,16 @@ class CDCoxLoss(_GLMLoss):
         check(self._L.cdh_glm_get_survival(self._h, *args), self._h)
         return out
 
-    time = property(lambda self: self._get_survival(0), doc="The times, in the caller's row order.")
+    @property
+    def start(self):
+        """The start times, in the caller's row order; None when y had two columns (every row at risk from -inf)."""
+        if not getattr(self, "_interval", False):
+            return None
+        out = np.zeros(self.n)
+        check(self._L.cdh_glm_get_survival_start(self._h, _vp(out)), self._h)
+        return out
+
+    time = property(lambda self: self._get_survival(0), doc="The times (the stop times of start-stop data), in the caller's row order.")
     status = property(lambda self: self._get_survival(1), doc="The statuses: 1 an event, 0 censored.")
     offset = CDPoissonLoss.offset
 
@@ -2316,7 +2357,8 @@ def coxLasso_(x, f, g, options=None, irls=None, fold=None):
 def coxLasso(X, y, lam, omega=None, options=None, irls=None, offset=None, strata=None, weights=None):
     """ℓ1-penalised Cox regression with Breslow ties (glmnet's family = "cox"): the minimiser of
     -(1/n) Σ δ_i (η_i - log S_i) + λ Σ ω_j |β_j|, η = Xβ + o, y = [time, status] (n x 2).  There is no intercept: it cancels
-    in the partial likelihood.  strata and weights: CDCoxLoss's (glmnet's stratifySurv and weights =; the weights are
+    in the partial likelihood.  y = [start, stop, status] (n x 3): start-stop times, row i at risk over (start_i, stop_i]
+    (CDCoxLoss).  strata and weights: CDCoxLoss's (glmnet's stratifySurv and weights =; the weights are
     normalised to sum to n).  X may also be an existing CDCoxLoss (y, offset, strata and weights are then its own)."""
     if not isinstance(X, CoordinateDifferentiableFunction):
         _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
@@ -2345,7 +2387,8 @@ def coxLambdaMax(f, omega=None):
 def CoxLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, offset=None, strata=None,
                  weights=None):
     """LassoPath's loop (src/lasso.jl:229-260) with coxLasso_ per λ: one handle, one x warm-started along λ,
-    ω = _stdX!(X) (cdh_col_rms) when standardising.  βpath[i] has length p.  strata and weights: CDCoxLoss's; the penalty
+    ω = _stdX!(X) (cdh_col_rms) when standardising.  βpath[i] has length p.  y may be n x 3, [start, stop, status]
+    (CDCoxLoss).  strata and weights: CDCoxLoss's; the penalty
     scales ω stay the root mean square over the rows present, not weighted by the observation weights."""
     if not isinstance(X, CoordinateDifferentiableFunction):
         _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
@@ -2370,6 +2413,10 @@ def cvCoxLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, 
     strata and weights: CDCoxLoss's (refused, like offset, when a loss is passed in: they are then its own).  The folds keep
     the λ scaling above and the unweighted penalty scales; "events" are then Σ v_i δ_i, floats: a fold is weighted by its
     held-out Σ v δ (fold_events), and the refusals apply to those sums.
+
+    Start-stop times (y n x 3, or a CDCoxLoss made with them): a subject may be several rows, and the library does not know
+    subjects -- the rows of one subject should share a fold, so pass folds= with one id per subject repeated over its rows;
+    the random folds split rows.
 
     folds: 0-based ids, one per row; otherwise np.random.default_rng(seed).permutation(n) % K.  There is no max_hat_s.  The
     folds are dropped when the call returns or raises.  `path` is CoxLassoPath on all rows (None with full_path=False):

@@ -306,13 +306,18 @@ enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
 // The Cox group (cox_kernels.hpp; cox_layout): d -- the scans' scratch, the runs' sums and the times; i -- order and the tie
 // groups' bounds.  Allocated together by the first cdh_glm_set_survival, or not at all.  sd, si -- the second pair, of a handle
 // with strata or observation weights: allocated together by the first cdh_glm_set_survival_strata that brings either, and in
-// use while `strata` is set (every other setter of observations clears it).
+// use while `strata` is set (every other setter of observations clears it).  vd, vi -- the third pair, of a handle with start
+// times: allocated together by the first cdh_glm_set_survival_interval that brings them, and in use while `interval` is set
+// (then `strata` is set too; every setter without start times clears it).
 struct CoxState {
     DevBuf<double> d;
     DevBuf<int32_t> i;
     DevBuf<double> sd;
     DevBuf<int32_t> si;
+    DevBuf<double> vd;
+    DevBuf<int32_t> vi;
     bool strata = false;
+    bool interval = false;
 };
 struct GlmState {
     DevBuf<double> labels;     // the labels, or the counts of the Poisson family
@@ -1171,6 +1176,14 @@ int32_t cdh_glm_set_survival_strata(cdh_handle h, const void* host_time, const v
     return cox_set_survival(h, host_time, host_status, host_offset, host_strata, host_weights);
 }); }
 
+int32_t cdh_glm_set_survival_interval(cdh_handle h, const void* host_start, const void* host_stop, const void* host_status, const void* host_offset, const int32_t* host_strata, const void* host_weights) { return guarded(h, [&]() -> int32_t {
+    return cox_set_survival(h, host_stop, host_status, host_offset, host_strata, host_weights, host_start);
+}); }
+
+int32_t cdh_glm_get_survival_start(cdh_handle h, void* host_start) { return guarded(h, [&]() -> int32_t {
+    return cox_get_survival_start(h, host_start);
+}); }
+
 int32_t cdh_glm_get_survival_strata(cdh_handle h, int32_t* host_strata, void* host_weights) { return guarded(h, [&]() -> int32_t {
     return cox_get_survival_strata(h, host_strata, host_weights);
 }); }
@@ -1759,3 +1772,8 @@ int32_t cdh_quad_coordinate_descent(cdh_quad q, const cdh_options* opt, cdh_stat
 }); }
 
 }  // extern "C"
+
+// the start-stop chain of the Cox step, LAST: its kernels are emitted behind every other kernel (the reason is in the file)
+namespace {
+#include "cox_interval.hpp"
+}  // namespace

@@ -30,6 +30,22 @@
 // subtraction at the boundary would carry n U of the later strata's sums into it).  Every kernel of the chain has the two
 // instantiations, chosen on the host (glm_launch<GlmCox>): a handle without strata and weights runs today's arithmetic, and
 // the additions a segmented scan does are the plain scan's in its order -- one stratum and unit weights give the same bits.
+//
+// Start-stop times (cdh_glm_set_survival_interval; glmnet's Surv(start, stop, status)): row i is at risk at t iff
+// start_i < t <= stop_i, inside its stratum.  The order above is by (stratum, stop); a SECOND order by (stratum, start) holds
+// every stratum in the same positions, ev is gathered into it (k_cox_gather: the same bits in both orders) and suffix-scanned
+// there, segmented, into T2.  Two static int32 lookups made on the host (cox_order_interval) finish the sums:
+//   S = T[first[s]] - T2[lo[s]]           the rows whose stop is >= the time less those whose start is too (lo = -1: none)
+//   A = hA[last[s]] - hA[enter[s]]        the hazard over the event times in (start, stop]; B likewise (enter = -1: from the start)
+// No scatter-add and no atomic: every sum keeps its fixed order.  The subtractions are inherent -- glmnet and survival::coxph
+// subtract too -- and they stay inside the row's stratum: the error of S is relative to T + T2, about n U (T + T2), not to S,
+// and that of A and B to P(stop) + P(start).  An event whose computed S is not > 0 is skipped (k_cox_hazard's convention), a
+// w_raw driven negative is clamped (cox_row's !(w_raw >= wmin)).  An interval handle always runs the segmented, weighted
+// arithmetic (absent strata and weights are stored as their defaults): one chain more, chosen on the host, and the plain and
+// the strata instantiations are untouched.  With every lookup -1 the chain gives the strata chain's bits.
+//   k_cox_exp<true>  k_cox_gather  k_cox_offsets x2  k_cox_scan (T)  k_cox_scan (T2)  k_cox_hazard_iv  k_cox_offsets
+//   k_cox_scan (A, B)  k_cox_apply_iv  k_gram_reduce
+// The three kernels of its own and its launcher live in cox_interval.hpp, which cdhip.hip includes LAST (the reason is there).
 
 // One position's share of the step, every quantity in double and every operation rounded on its own (tests/_cox_numpy.py
 // writes the same lines).  eta_lin = yw - r is X beta: the offset is NOT part of the stored working response.
@@ -414,8 +430,13 @@ static_assert(kCoxBlock == kBlock, "block_sum is kernels.hpp's");
 // buffers (cox_layout: the strata's bounds, the ids, the runs' head flags; the weights as given, pads zero) is allocated with
 // the rest, all or nothing; an absent one of the two is stored as its default (stratum 0, weight 1).  Without both the calls,
 // the uploads and the handle are cdh_glm_set_survival's, and strata and weights set earlier are dropped.
+// cdh_glm_set_survival_interval is the same body again: with start times host_time are the stop times, the handle always holds
+// the second pair (absent strata and weights as their defaults) and the THIRD (cox_layout: the start order, the two lookups,
+// the second suffix scan's scratch, the starts as given), allocated with the rest, all or nothing.  Without start times it is
+// cdh_glm_set_survival_strata call for call, and every setter without them drops start times set earlier.
 int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_status, const void* host_offset,
-                         const int32_t* host_strata = nullptr, const void* host_weights = nullptr) {
+                         const int32_t* host_strata = nullptr, const void* host_weights = nullptr,
+                         const void* host_start = nullptr) {
     CHK(glm_refuse(h));
     if (!host_time) return fail(h, CDH_BAD_ARG, "host_time is NULL");
     if (!host_status) return fail(h, CDH_BAD_ARG, "host_status is NULL");
@@ -423,17 +444,21 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
     const double* st = (const double*)host_status;
     const double* off = (const double*)host_offset;
     const double* wt = (const double*)host_weights;
-    const bool sw = host_strata != nullptr || wt != nullptr;
-    char buf[128];
+    const double* sta = (const double*)host_start;
+    const bool iv = sta != nullptr;
+    const bool sw = host_strata != nullptr || wt != nullptr || iv;
+    char buf[160];
     if (!cox_check(h->n, tm, st, off, buf, sizeof buf, wt)) return fail(h, CDH_BAD_ARG, buf);
-    std::vector<int32_t> order, first, last, sfirst, slast;
-    if (sw) cox_order_strata(h->n, h->ld, tm, host_strata, order, first, last, sfirst, slast);
+    if (iv && !cox_check_interval(h->n, sta, tm, buf, sizeof buf)) return fail(h, CDH_BAD_ARG, buf);
+    std::vector<int32_t> order, first, last, sfirst, slast, order2, pos2, lo, enter;
+    if (iv) cox_order_interval(h->n, h->ld, sta, tm, host_strata, order, first, last, sfirst, slast, order2, pos2, lo, enter);
+    else if (sw) cox_order_strata(h->n, h->ld, tm, host_strata, order, first, last, sfirst, slast);
     else cox_order(h->n, h->ld, tm, order, first, last);
     HIPCHK(h, hipSetDevice(h->device));
     const CoxLayout lay = cox_layout(h->ld);
     const size_t colbytes = (size_t)h->ld * sizeof(double), idxbytes = (size_t)h->ld * sizeof(int32_t);
-    DevBuf<double> fresh, fresh_off, fresh_d, fresh_sd;     // complete before the handle changes: a failed allocation leaves it as it was
-    DevBuf<int32_t> fresh_i, fresh_si;
+    DevBuf<double> fresh, fresh_off, fresh_d, fresh_sd, fresh_vd;     // complete before the handle changes: a failed allocation leaves it as it was
+    DevBuf<int32_t> fresh_i, fresh_si, fresh_vi;
     if (!h->glm.labels) {
         HIPCHK(h, fresh.alloc(colbytes));
         HIPCHK(h, hipMemsetAsync(fresh, 0, colbytes, h->stream));
@@ -453,6 +478,12 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
         HIPCHK(h, hipMemsetAsync(fresh_sd, 0, (size_t)lay.strata_doubles * sizeof(double), h->stream));
         HIPCHK(h, hipMemsetAsync(fresh_si, 0, (size_t)lay.strata_ints * sizeof(int32_t), h->stream));
     }
+    if (iv && !h->glm.cox.vd) {
+        HIPCHK(h, fresh_vd.alloc((size_t)lay.interval_doubles * sizeof(double)));
+        HIPCHK(h, fresh_vi.alloc((size_t)lay.interval_ints * sizeof(int32_t)));
+        HIPCHK(h, hipMemsetAsync(fresh_vd, 0, (size_t)lay.interval_doubles * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(fresh_vi, 0, (size_t)lay.interval_ints * sizeof(int32_t), h->stream));
+    }
     h->rs.overwritten_with_y();          // r = copy(y) = 0 below
     gc_invalidate(h, false);
     h->gc.st.yy_void();
@@ -461,6 +492,7 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
     if (off && !h->glm.offset) h->glm.offset = std::move(fresh_off);
     if (!h->glm.cox.d) { h->glm.cox.d = std::move(fresh_d); h->glm.cox.i = std::move(fresh_i); }
     if (sw && !h->glm.cox.sd) { h->glm.cox.sd = std::move(fresh_sd); h->glm.cox.si = std::move(fresh_si); }
+    if (iv && !h->glm.cox.vd) { h->glm.cox.vd = std::move(fresh_vd); h->glm.cox.vi = std::move(fresh_vi); }
     double* d = h->glm.cox.d;
     int32_t* ii = h->glm.cox.i;
     HIPCHK(h, hipMemcpyAsync(h->glm.labels, st, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -483,6 +515,14 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
         HIPCHK(h, hipMemcpyAsync(sd + lay.weight, wt ? wt : ones.data(), (size_t)h->n * sizeof(double), hipMemcpyHostToDevice,
                                  h->stream));
     }
+    if (iv) {
+        double* vd = h->glm.cox.vd;
+        int32_t* vi = h->glm.cox.vi;
+        HIPCHK(h, hipMemcpyAsync(vi + lay.pos2, pos2.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(vi + lay.lo, lo.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(vi + lay.enter, enter.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(vd + lay.start, sta, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
     HIPCHK(h, hipMemsetAsync(h->y, 0, colbytes, h->stream));
     HIPCHK(h, hipMemsetAsync(h->r, 0, colbytes, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (the host vectors above are pageable: the copies are done here)
@@ -490,6 +530,7 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
     h->glm.family = GlmData::Cox;
     h->glm.has_offset = off != nullptr;
     h->glm.cox.strata = sw;
+    h->glm.cox.interval = iv;
     h->glm.set = true;
     return CDH_OK;
 }
@@ -503,6 +544,18 @@ int32_t cox_get_survival(cdh_handle h, void* host_time, void* host_status) {
     if (host_time)
         HIPCHK(h, hipMemcpyAsync(host_time, (const double*)h->glm.cox.d + cox_layout(h->ld).time, bytes, hipMemcpyDeviceToHost, h->stream));
     if (host_status) HIPCHK(h, hipMemcpyAsync(host_status, h->glm.labels, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CDH_OK;
+}
+
+// cdh_glm_get_survival_start: the start times in the caller's row order; refused when the handle holds none
+int32_t cox_get_survival_start(cdh_handle h, void* host_start) {
+    NEED_P(h, host_start);
+    if (!h->glm.set || h->glm.family != GlmData::Cox || !h->glm.cox.interval)
+        return fail(h, CDH_BAD_ARG, "no start times are set: call cdh_glm_set_survival_interval with host_start first");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(host_start, (const double*)h->glm.cox.vd + cox_layout(h->ld).start, (size_t)h->n * sizeof(double),
+                             hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
 }
@@ -559,6 +612,9 @@ int32_t glm_check<GlmCox>(cdh_handle h, int32_t k, int32_t apply, const GlmParam
     return CDH_OK;
 }
 
+// the chain of a handle with start times, up to the partials (cox_interval.hpp, at the end of cdhip.hip)
+int32_t cox_launch_interval(cdh_handle h, int32_t k, bool apply, const GlmParams& pm);
+
 // the chain and its record: out holds the kCoxVals doubles, added over the workgroups in block order; k = -1: no row is held
 // out and the fold ids are not read
 template <>
@@ -605,7 +661,8 @@ int32_t glm_launch<GlmCox>(cdh_handle h, int32_t k, bool apply, const GlmParams&
         HIPCHK(h, hipGetLastError());
         return CDH_OK;
     };
-    if (h->glm.cox.strata) CHK(chain(std::true_type{})); else CHK(chain(std::false_type{}));
+    if (h->glm.cox.interval) CHK(cox_launch_interval(h, k, apply, pm));      // cox_interval.hpp
+    else if (h->glm.cox.strata) CHK(chain(std::true_type{})); else CHK(chain(std::false_type{}));
     hipLaunchKernelGGL(k_gram_reduce, dim3((kCoxVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
                        (const double*)h->d_partials, (int)pl.records, (int)kCoxVals, (double*)h->d_red);
     HIPCHK(h, hipGetLastError());

@@ -1,8 +1,10 @@
 // cox_plan.hpp -- the host-only arithmetic of the Cox step (cox_kernels.hpp: cdh_glm_set_survival, cdh_glm_cox_irls): the tile of
 // a scan, how the tiles are dealt to the workgroups, the layout of the step's scratch, and the time order with its tie groups
 // as cdh_glm_set_survival uploads them -- and, for cdh_glm_set_survival_strata, the order by (stratum, time) with the bounds of
-// every position's stratum.  No HIP in here: tests/test_cox_plan_host.py and tests/test_cox_strata_plan_host.py compile it with
-// g++ (tests/cox_plan_main.cpp, tests/cox_strata_plan_main.cpp).  cox_kernels.hpp calls these functions and nothing else
+// every position's stratum; for cdh_glm_set_survival_interval, the second order by (stratum, start) and the two static lookups
+// that turn the scans into the sums over (start, stop].  No HIP in here: tests/test_cox_plan_host.py,
+// tests/test_cox_strata_plan_host.py and tests/test_cox_interval_plan_host.py compile it with g++ (tests/cox_plan_main.cpp,
+// tests/cox_strata_plan_main.cpp, tests/cox_interval_plan_main.cpp).  cox_kernels.hpp calls these functions and nothing else
 // decides the sizes.
 //
 // The tie groups are kept as TWO int32 vectors, not as head flags: first[s] and last[s] are the first and the last sorted
@@ -59,6 +61,10 @@ constexpr int64_t cox_run_first(int64_t tiles, int64_t grid, int64_t b) { return
 // handle never allocates: int32 -- sfirst and slast, the bounds of every position's stratum, the stratum ids in the caller's
 // row order (for the getter), ld each, then the head-seen flags of the runs, kCoxMaxGrid for the suffix scan and kCoxMaxGrid
 // for the two prefix scans; doubles -- the weights in the caller's row order, ld.
+// A handle with start times (cdh_glm_set_survival_interval) holds the second pair AND a THIRD: int32 -- pos2 (the start order,
+// as positions of the stop order), lo and enter (cox_order_interval), ld each, then the head-seen flags of the second suffix
+// scan's runs, kCoxMaxGrid; doubles -- the start times in the caller's row order, T2 (ev in start order, then its suffix scan
+// in place), ld each, then that scan's runs' sums, kCoxMaxGrid.
 struct CoxLayout {
     int64_t eT, hA, hB, time, sums;   // offsets in doubles; sums + i kCoxMaxGrid: scan i's runs
     int64_t doubles;
@@ -68,10 +74,15 @@ struct CoxLayout {
     int64_t strata_ints;
     int64_t weight;                   // offset in doubles of the second pair
     int64_t strata_doubles;
+    int64_t pos2, lo, enter, heads2;  // offsets in int32s of the third pair
+    int64_t interval_ints;
+    int64_t start, T2, sums2;         // offsets in doubles of the third pair
+    int64_t interval_doubles;
 };
 constexpr CoxLayout cox_layout(int64_t ld) {
     return CoxLayout{0, ld, 2 * ld, 3 * ld, 4 * ld, 4 * ld + 3 * kCoxMaxGrid, 0, ld, 2 * ld, 3 * ld,
-                     0, ld, 2 * ld, 3 * ld, 3 * ld + 2 * kCoxMaxGrid, 0, ld};
+                     0, ld, 2 * ld, 3 * ld, 3 * ld + 2 * kCoxMaxGrid, 0, ld,
+                     0, ld, 2 * ld, 3 * ld, 3 * ld + kCoxMaxGrid, 0, ld, 2 * ld, 2 * ld + kCoxMaxGrid};
 }
 
 // ---- the time order and its tie groups ---------------------------------------------------------------------------------------
@@ -158,5 +169,68 @@ inline void cox_order_strata(int64_t n, int64_t ld, const double* time, const in
     for (int64_t s = n; s < ld; ++s) {
         first[s] = (int32_t)s; last[s] = (int32_t)s;
         sfirst[s] = (int32_t)n; slast[s] = (int32_t)(ld - 1);
+    }
+}
+
+// ---- start-stop times: the second order and the two lookups --------------------------------------------------------------------
+// What cdh_glm_set_survival_interval refuses of its start times, after cox_check has passed the stop times: a start that is not
+// finite, and an interval (start, stop] that is empty, start >= stop; the row named in msg.  -> true when they pass.
+inline bool cox_check_interval(int64_t n, const double* start, const double* stop, char* msg, size_t len) {
+    for (int64_t i = 0; i < n; ++i) {
+        if (!(fabs(start[i]) <= 1.7976931348623157e308)) {
+            snprintf(msg, len, "start[%lld] = %g is not finite", (long long)i, start[i]);
+            return false;
+        }
+        if (!(start[i] < stop[i])) {
+            snprintf(msg, len, "start[%lld] = %g is not below stop[%lld] = %g", (long long)i, start[i], (long long)i, stop[i]);
+            return false;
+        }
+    }
+    return true;
+}
+
+// Row i is at risk at t iff start_i < t <= stop_i.  order, first, last, sfirst and slast are cox_order_strata's on the stop
+// times, element for element.  order2[s]: the row at position s of the SECOND order, a stable ascending sort by (stratum,
+// start); a stratum occupies the same positions in both orders, so sfirst and slast bound it in either.  pos2[s]: the position
+// of that row in the stop order (order[pos2[s]] == order2[s]): what the device gathers ev through, so that ev is the same bits
+// in both orders.  Two lookups, both inside the stratum of stop-order position s:
+//   lo[s]     the first start-order position whose start is >= the stop time of position s; -1 if none.  The suffix scan of ev in
+//             start order read there is the sum over the rows that have NOT YET entered at that time: a row whose start equals
+//             an event time is not at risk at it.
+//   enter[s]  the last stop-order position whose stop time is <= the start of row order[s]; -1 if none.  The prefix scans of
+//             the hazard read there are the sums over the event times the row was not yet at risk at.
+// Pad positions n .. ld - 1 stay in place in both orders, with lo = enter = -1.
+inline void cox_order_interval(int64_t n, int64_t ld, const double* start, const double* stop, const int32_t* strata,
+                               std::vector<int32_t>& order, std::vector<int32_t>& first, std::vector<int32_t>& last,
+                               std::vector<int32_t>& sfirst, std::vector<int32_t>& slast, std::vector<int32_t>& order2,
+                               std::vector<int32_t>& pos2, std::vector<int32_t>& lo, std::vector<int32_t>& enter) {
+    cox_order_strata(n, ld, stop, strata, order, first, last, sfirst, slast);
+    order2.resize((size_t)ld);
+    pos2.resize((size_t)ld);
+    lo.assign((size_t)ld, -1);
+    enter.assign((size_t)ld, -1);
+    std::iota(order2.begin(), order2.end(), 0);
+    auto stratum = [&](int32_t row) { return strata ? strata[row] : 0; };
+    std::stable_sort(order2.begin(), order2.begin() + n, [&](int32_t a, int32_t b) {
+        return stratum(a) != stratum(b) ? stratum(a) < stratum(b) : start[a] < start[b];
+    });
+    std::vector<int32_t> where((size_t)ld);                       // row -> its position in the stop order
+    for (int64_t s = 0; s < ld; ++s) where[(size_t)order[s]] = (int32_t)s;
+    for (int64_t s = 0; s < ld; ++s) pos2[s] = where[(size_t)order2[s]];
+    for (int64_t s = 0; s < n; ++s) {
+        const int64_t a = sfirst[s], b = slast[s];
+        const double t = stop[order[s]], u = start[order[s]];
+        int64_t l = a, r = b + 1;                                 // the first position of a .. b in start order with start >= t
+        while (l < r) {
+            const int64_t m = l + (r - l) / 2;
+            if (start[order2[m]] >= t) r = m; else l = m + 1;
+        }
+        lo[s] = l <= b ? (int32_t)l : -1;
+        l = a, r = b + 1;                                         // the first position of a .. b in stop order with stop > u
+        while (l < r) {
+            const int64_t m = l + (r - l) / 2;
+            if (stop[order[m]] > u) r = m; else l = m + 1;
+        }
+        enter[s] = l > a ? (int32_t)(l - 1) : -1;
     }
 }

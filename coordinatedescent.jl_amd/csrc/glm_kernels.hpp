@@ -272,7 +272,8 @@ int32_t glm_set_observations(cdh_handle h, GlmData family, const void* host_obs,
     h->y_set = true;
     h->glm.family = family;
     h->glm.has_offset = off != nullptr;  // (a Poisson handle turned binomial drops its offset)
-    h->glm.cox.strata = false;           // (and a Cox handle its strata and observation weights)
+    h->glm.cox.strata = false;           // (and a Cox handle its strata and observation weights,
+    h->glm.cox.interval = false;         //  and its start times)
     h->glm.set = true;
     return CDH_OK;
 }

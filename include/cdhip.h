@@ -350,7 +350,14 @@ int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin
  * rows of g_i with t_k <= t_i: ev = v e; evA = ev A; w_raw = evA - ev (ev B); d = dv - evA; the nll term is dv (log S - eta).
  * The rows are ordered by (stratum, time) and the three scans restart at every stratum's boundary (segmented scans, the
  * rounding error of a sum relative to its own stratum's sum).  The diagonal is v e A - (v e)^2 B: an integer weight
- * reproduces a replicated row's gradient and nll, not its diagonal.  Start-stop times and Efron ties are not offered. */
+ * reproduces a replicated row's gradient and nll, not its diagonal.
+ * With start-stop times (cdh_glm_set_survival_interval; glmnet's Surv(start, stop, status)): row i is at risk at t iff
+ * start_i < t <= stop_i, inside its stratum.  S(t) = sum of ev_j over stop_j >= t LESS the sum over start_j >= t -- a second
+ * order by (stratum, start) with a second segmented suffix scan, read through a static lookup; A_i = P(stop_i) - P(start_i) with
+ * P(u) the sum of dv / S(t) over the event times t <= u, B_i the same with dv / S^2 -- the prefix scans read at two positions.
+ * The subtractions are inherent (glmnet and survival::coxph subtract too): the error of S is relative to the two sums of its
+ * stratum, about n U (T + T2), not to S, and that of A and B to P(stop) + P(start); nothing crosses a stratum's boundary.  An
+ * event whose computed S is not > 0 is skipped, a w_raw driven negative is clamped at wmin.  Efron ties are not offered. */
 /* cdh_glm_set_survival (no reference counterpart; the loss is that of cd_differentiable_function.jl:118-194 per round)
  * stands in for cdh_set_y: it stores n statuses where cdh_glm_set_labels stores labels, n offsets (when not NULL) where
  * cdh_glm_set_counts stores them, sorts the times on the host (stable, ascending) and keeps the order, the tie groups' bounds,
@@ -376,6 +383,22 @@ int32_t cdh_glm_get_survival(cdh_handle h, void *host_time, void *host_status);
 int32_t cdh_glm_set_survival_strata(cdh_handle h, const void *host_time, const void *host_status,
                                     const void *host_offset_or_null, const int32_t *host_strata_or_null,
                                     const void *host_weights_or_null);
+/* cdh_glm_set_survival_interval (no reference counterpart; see cdh_glm_set_survival, cd_differentiable_function.jl:118-194):
+ * cdh_glm_set_survival_strata with n start times: row i is at risk over (start_i, stop_i].  With host_start NULL it IS
+ * cdh_glm_set_survival_strata, call for call and bit for bit.  Otherwise the handle always runs the segmented and weighted
+ * arithmetic (absent strata and weights are stored as one stratum and unit weights), and the start order -- a stable ascending
+ * sort by (stratum id, start) -- the two lookups, the second scan's scratch and the starts live in a third group of buffers,
+ * allocated all-or-nothing with the rest before the handle changes.  A row whose start equals an event time is not at risk
+ * at it; a row whose stop equals it is.  CDH_BAD_ARG, the handle unchanged: what cdh_glm_set_survival_strata refuses (of the
+ * stop times what it refuses of the times); a start that is not finite; start >= stop (the message names the row).
+ * cdh_glm_set_survival, cdh_glm_set_survival_strata, cdh_glm_set_labels and cdh_glm_set_counts drop the start times. */
+int32_t cdh_glm_set_survival_interval(cdh_handle h, const void *host_start_or_null, const void *host_stop,
+                                      const void *host_status, const void *host_offset_or_null,
+                                      const int32_t *host_strata_or_null, const void *host_weights_or_null);
+/* cdh_glm_get_survival_start (no reference counterpart; see cdh_glm_set_survival_interval,
+ * cd_differentiable_function.jl:118-194): the n start times of a Cox handle, in the caller's row order; the stop times are
+ * cdh_glm_get_survival's "time".  CDH_BAD_ARG: host_start NULL; the handle holds no start times. */
+int32_t cdh_glm_get_survival_start(cdh_handle h, void *host_start);
 /* cdh_glm_get_survival_strata (no reference counterpart; see cdh_glm_set_survival_strata,
  * cd_differentiable_function.jl:118-194): the n stratum ids and the n weights of a Cox handle, in the caller's row order --
  * zeros where it holds no strata, ones where it holds no weights; a NULL output is skipped.  CDH_BAD_ARG: both NULL; no

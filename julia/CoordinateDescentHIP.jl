@@ -601,6 +601,30 @@ function glm_get_survival_strata(X::HipMatrix{Float64})
   (strata, weights)
 end
 
+"glm_set_survival_strata! with start times: row i is at risk over (start[i], stop[i]]; start === nothing: it is glm_set_survival_strata!"
+function glm_set_survival_interval!(X::HipMatrix{Float64}, start::Union{Nothing,Vector{Float64}}, stop::Vector{Float64}, status::Vector{Float64},
+                                    offset::Union{Nothing,Vector{Float64}}=nothing;
+                                    strata::Union{Nothing,Vector{Int32}}=nothing, weights::Union{Nothing,Vector{Float64}}=nothing)
+  length(stop) == X.n && length(status) == X.n || throw(DimensionMismatch())
+  for v in (start, offset, strata, weights)
+    v === nothing || length(v) == X.n || throw(DimensionMismatch())
+  end
+  set_loss!(X, CDH_WLS)
+  check(X.handle, ccall((:cdh_glm_set_survival_interval, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cvoid}),
+                        X.handle, start === nothing ? C_NULL : pointer(start), stop, status, offset === nothing ? C_NULL : pointer(offset),
+                        strata === nothing ? C_NULL : pointer(strata), weights === nothing ? C_NULL : pointer(weights)))
+  X.owner = nothing
+  X.synced = false
+  X
+end
+
+"the start times of a Cox handle set by glm_set_survival_interval!, in the caller's row order"
+function glm_get_survival_start(X::HipMatrix{Float64})
+  start = Vector{Float64}(undef, X.n)
+  check(X.handle, ccall((:cdh_glm_get_survival_start, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), X.handle, start))
+  start
+end
+
 "one Cox IRLS step at the iterate the handle holds, fold k (0-based, -1: none) held out; apply=false reads only"
 function glm_cox_irls!(X::HipMatrix{Float64}, k::Integer=-1; apply::Bool=true, wmin::Float64=1e-5, eta_max::Float64=50.0)
   out = Vector{Float64}(undef, 5)

@@ -27,7 +27,16 @@ observation weights uniform in [0.25, 4], normalised to sum to n, through cdh_gl
 gathered in the exp and the apply launch (16) and one int32 stratum bound is read in each of the two scan launches (8).  The
 line gains the keys "strata" and "weighted" in every measurement.
 
-Environment: N, REPS, ROUNDS, N2, P2, M2, PROUNDS, STEP_TIMEOUT, PATH_TIMEOUT, STRATA, OUT (a file that receives the line too)."""
+INTERVAL=1 (default 0) adds start times -- start = time x U(0, 0.9) floored to three decimals, 0 for three rows in ten; the times
+are then at least 0.001 -- through cdh_glm_set_survival_interval, with STRATA's strata and weights or, with STRATA=0, one
+stratum and unit weights (the interval handle runs the segmented, weighted chain either way).  The host's step keeps the second
+order and the two lookups cached.  The copy moves 336 bytes a row, the strata step's 252 and 84 more: the gather of ev into the
+start order 20 (pos2 4, ev in 8, T2 out 8), T2's suffix scan 20 (16 and the stratum bound 4), the hazards 12 (lo 4, T2 8), the
+apply launch 32 (lo and enter 8, T2 8, the hazards' prefix sums at the entry 16).  Of these pos2 and enter are gathers in random
+order whatever the rows' order; lo is monotone inside a stratum.  The line gains the key "interval".
+
+Environment: N, REPS, ROUNDS, N2, P2, M2, PROUNDS, STEP_TIMEOUT, PATH_TIMEOUT, STRATA, INTERVAL, OUT (a file that receives the
+line too)."""
 import ctypes as C
 import json
 import os
@@ -79,7 +88,8 @@ vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
 PD = C.POINTER(C.c_double)
 WMIN, ETA_MAX = 1e-5, 50.0
 STRATA = env("STRATA", 0)
-BYTES = 252 if STRATA else 228
+INTERVAL = env("INTERVAL", 0)
+BYTES = 336 if INTERVAL else (252 if STRATA else 228)
 
 
 def timed(fn):
@@ -91,10 +101,13 @@ def timed(fn):
 class HostStep:
     """The twin's step (tests/_cox_numpy.py: rows, the cumulative-sum form) with the sort order and the tie groups cached.
     With strata g and weights v (tests/_cox_strata_numpy.py) the order is by (stratum, time) and a cumulative sum restarts
-    at a stratum's boundary: the sum over all positions less its value just outside the stratum."""
+    at a stratum's boundary: the sum over all positions less its value just outside the stratum.  With start times
+    (tests/_cox_interval_numpy.py) a second order by (stratum, start) and the two lookups lo and enter are cached too."""
 
-    def __init__(self, t, status, off, g=None, v=None):
+    def __init__(self, t, status, off, g=None, v=None, start=None):
         n = len(t)
+        if start is not None and g is None:
+            g = np.zeros(n, dtype=np.int32)
         self.order = np.argsort(t, kind="stable") if g is None else np.lexsort((t, g))
         ts = t[self.order]
         head = np.r_[True, ts[1:] != ts[:-1]]
@@ -114,6 +127,18 @@ class HostStep:
         self.ds, self.off = self.dv[self.order], off
         self.inv = np.empty(n, dtype=np.int64)
         self.inv[self.order] = np.arange(n)
+        self.order2 = None
+        if start is not None:
+            self.order2 = np.lexsort((start, g))
+            self.lo, self.enter = np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64)
+            s2, u = start[self.order2], start[self.order]
+            for a, b in zip(sstarts.tolist(), (np.r_[sstarts[1:], n] - 1).tolist()):
+                lo = np.searchsorted(s2[a:b + 1], ts[a:b + 1], side="left")
+                self.lo[a:b + 1] = np.where(lo <= b - a, a + lo, -1)
+                en = np.searchsorted(ts[a:b + 1], u[a:b + 1], side="right") - 1
+                self.enter[a:b + 1] = np.where(en >= 0, a + en, -1)
+            self.has_lo, self.has_enter = self.lo >= 0, self.enter >= 0
+            self.lo, self.enter = np.maximum(self.lo, 0), np.maximum(self.enter, 0)
 
     def _suffix(self, a):
         T = np.cumsum(a[::-1])[::-1]
@@ -126,8 +151,14 @@ class HostStep:
     def __call__(self, eta_lin):
         e = self.v * np.exp(np.minimum(eta_lin + self.off, ETA_MAX))
         Ss = self._suffix(e[self.order])[self.first]
+        if self.order2 is not None:
+            Ss = Ss - np.where(self.has_lo, self._suffix(e[self.order2])[self.lo], 0.0)
         h = self.ds / Ss
-        A, B = self._prefix(h)[self.last][self.inv], self._prefix(h / Ss)[self.last][self.inv]
+        cA, cB = self._prefix(h), self._prefix(h / Ss)
+        A, B = cA[self.last], cB[self.last]
+        if self.order2 is not None:
+            A, B = A - np.where(self.has_enter, cA[self.enter], 0.0), B - np.where(self.has_enter, cB[self.enter], 0.0)
+        A, B = A[self.inv], B[self.inv]
         eA = e * A
         w = np.maximum(eA - e * (e * B), WMIN)
         return eta_lin + (self.dv - eA) / w, w
@@ -135,31 +166,46 @@ class HostStep:
 
 def survival(f, seed, presorted):
     """Times ~ Exp(1) / exp(signal), rounded to three decimals; 30 % censored; an offset in (-0.5, 0.5).  With STRATA: ids
-    uniform over the rows and weights uniform in [0.25, 4], normalised to sum to n.  -> (t, status, off, strata, weights)."""
+    uniform over the rows and weights uniform in [0.25, 4], normalised to sum to n.  With INTERVAL: start times (the module's
+    docstring).  -> (t, status, off, strata, weights, start)."""
     n = f.n
     rng = np.random.default_rng(seed)
     sig = f.y
     off = rng.uniform(-0.5, 0.5, n)
     t = np.round(rng.exponential(1.0, n) / np.exp(0.5 * sig / np.std(sig) + off), 3)
     status = (rng.random(n) >= 0.3).astype(np.float64)
+    if INTERVAL:
+        t = np.maximum(t, 0.001)
+
+    def starts(t):
+        if not INTERVAL:
+            return None
+        r2 = np.random.default_rng(seed + 1000)
+        return np.where(r2.random(n) < 0.3, 0.0, np.floor(t * r2.uniform(0.0, 0.9, n) * 1000.0) / 1000.0)
+
     if not STRATA:
         if presorted:
             t = np.sort(t)
-        cd.check(f._L.cdh_glm_set_survival(f._h, vp(t), vp(status), vp(off)), f._h)
-        return t, status, off, None, None
+        start = starts(t)
+        set_survival(f, t, status, off, None, None, start)
+        return t, status, off, None, None, start
     g = rng.integers(0, STRATA, n).astype(np.int32)
     v = rng.uniform(0.25, 4.0, n)
     v = v * n / v.sum()
     if presorted:
         o = np.lexsort((t, g))
         t, g = np.ascontiguousarray(t[o]), np.ascontiguousarray(g[o])
-    set_survival(f, t, status, off, g, v)
+    start = starts(t)
+    set_survival(f, t, status, off, g, v, start)
     f._weighted = True
-    return t, status, off, g, v
+    return t, status, off, g, v, start
 
 
-def set_survival(f, t, status, off, g, v):
-    if g is None:
+def set_survival(f, t, status, off, g, v, start=None):
+    if start is not None:
+        cd.check(f._L.cdh_glm_set_survival_interval(f._h, vp(start), vp(t), vp(status), vp(off), None if g is None else vp(g),
+                                                    None if v is None else vp(v)), f._h)
+    elif g is None:
         cd.check(f._L.cdh_glm_set_survival(f._h, vp(t), vp(status), vp(off)), f._h)
     else:
         cd.check(f._L.cdh_glm_set_survival_strata(f._h, vp(t), vp(status), vp(off), vp(g), vp(v)), f._h)
@@ -168,13 +214,13 @@ def set_survival(f, t, status, off, g, v):
 def measure_step(presorted):
     n, reps, rounds = env("N", 2_000_000), env("REPS", 5), env("ROUNDS", 3)
     f, _ = cd.CDCoxLoss.generate(n, 1, seed=7, s=1, noise=1.0)
-    t, status, off, g, v = survival(f, 7, presorted)
+    t, status, off, g, v, start = survival(f, 7, presorted)
     x = cd.SparseIterate(1)
     x[1] = 0.5
     cd.initialize_(f, x)
     L, h = f._L, f._h
     out5, r = np.zeros(5), np.zeros(n)
-    host = HostStep(t, status, off, g, v)
+    host = HostStep(t, status, off, g, v, start)
     z = f.y
 
     def dev1():
@@ -216,7 +262,7 @@ def measure_step(presorted):
         z = f.y
         comp.append(timed(composed)[0])
     res = {"n": n, "presorted": presorted, "tie_groups": int(len(np.unique(t))), "clamped": int(out5[2]),
-           "events": float(out5[4]) if STRATA else int(out5[4]), "bytes_a_row": BYTES, "strata": STRATA, "weighted": bool(STRATA)}
+           "events": float(out5[4]) if STRATA else int(out5[4]), "bytes_a_row": BYTES, "strata": STRATA, "weighted": bool(STRATA), "interval": INTERVAL}
     for k, v in per.items():
         res[k] = {"round_minima_ms": [1e3 * a for a in v], "min_ms": 1e3 * min(v), "spread_ms": 1e3 * (max(v) - min(v)),
                   "TBps_of_%dn" % BYTES: BYTES * n / min(v) / 1e12}
@@ -230,12 +276,12 @@ def measure_step(presorted):
 def measure_path():
     n, p, m, rounds = env("N2", 2_000_000), env("P2", 1000), env("M2", 30), env("PROUNDS", 2)
     f, _ = cd.CDCoxLoss.generate(n, p, seed=11, s=10, noise=1.0)
-    t, status, off, g, v = survival(f, 11, False)
+    t, status, off, g, v, start = survival(f, 11, False)
     lmax = cd.coxLambdaMax(f)
     lam = lmax * np.geomspace(0.9, 0.05, m)
     opts = cd.CDOptions(maxIter=2000, optTol=1e-7, randomize=False)
     irls = cd.IRLSOptions(maxIter=100)
-    host = HostStep(t, status, off, g, v)
+    host = HostStep(t, status, off, g, v, start)
     L, h = f._L, f._h
 
     def device_route(lams):
@@ -272,7 +318,7 @@ def measure_path():
         return betas, rounds_
 
     def reset():
-        set_survival(f, t, status, off, g, v)                   # the Cox handle as it was made: y = r = 0
+        set_survival(f, t, status, off, g, v, start)            # the Cox handle as it was made: y = r = 0
         f._synced = None
 
     device_route(lam[:3])
@@ -287,7 +333,7 @@ def measure_path():
         tt, (betas, crounds) = timed(lambda: composed_route(lam))
         t_com.append(tt)
     diff = max(float(np.max(np.abs(b.dense() - c))) for b, c in zip(path.betapath, betas))
-    res = {"n": n, "p": p, "lambdas": m, "strata": STRATA, "weighted": bool(STRATA), "CoxLassoPath_s": t_dev, "composed_s": t_com,
+    res = {"n": n, "p": p, "lambdas": m, "strata": STRATA, "weighted": bool(STRATA), "interval": INTERVAL, "CoxLassoPath_s": t_dev, "composed_s": t_com,
            "min_s": {"CoxLassoPath": min(t_dev), "composed": min(t_com)},
            "composed_over_CoxLassoPath": min(t_com) / min(t_dev),
            "irls_rounds": {"CoxLassoPath": int(sum(path.rounds)), "composed": int(sum(crounds))},
