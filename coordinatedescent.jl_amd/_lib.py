@@ -126,6 +126,8 @@ def lib():
         "cdh_glm_set_counts": [vp, vp, vp],
         "cdh_glm_get_offset": [vp, vp],
         "cdh_glm_poisson_irls": [vp, i32, i32, f64, f64, P(f64)],
+        "cdh_glm_set_weights": [vp, vp],
+        "cdh_glm_get_weights": [vp, vp],
         "cdh_glm_set_survival": [vp, vp, vp, vp],
         "cdh_glm_get_survival": [vp, vp, vp],
         "cdh_glm_set_survival_strata": [vp, vp, vp, vp, vp, vp],

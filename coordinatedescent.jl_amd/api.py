@@ -516,8 +516,9 @@ class _GLMLoss(CDWeightedLSLoss):
     the handle's own beside the working response, and the objective read off a read-only step.  A family adds
     _set_observations (its export), irls_step with its own arguments, and _irls: that step as the IRLS loop calls it."""
     _objective_step = {}                 # the arguments of objective's read-only irls_step
+    _has_weights = False                 # observation weights are set on the handle (cdh_glm_set_weights)
 
-    def __init__(self, y, X, offset=None, *, device=0):
+    def __init__(self, y, X, offset=None, *, weights=None, device=0):
         X = np.asarray(X)
         obs = np.ascontiguousarray(y, dtype=np.float64)
         off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64)
@@ -528,12 +529,26 @@ class _GLMLoss(CDWeightedLSLoss):
         if off is not None and off.shape != obs.shape:
             raise DimensionMismatch("length(offset) != size(X, 1)")
         n, p = X.shape
+        v = _strata_weights(None, weights, n)[1]
         self._create(X.dtype, n, p, device, None, 0)
         step = max(1, (64 << 20) // max(1, n * X.itemsize))
         for j0 in range(0, p, step):
             blk = np.asfortranarray(X[:, j0:j0 + step])
             check(self._L.cdh_set_X_cols(self._h, j0, blk.shape[1], _vp(blk), n), self._h)
         self._set_observations(obs, off)
+        if v is not None:
+            check(self._L.cdh_glm_set_weights(self._h, _vp(v)), self._h)
+            self._has_weights = True
+
+    def _get_weights(self):
+        """The observation weights the handle holds (normalised to sum to n); ones when none were given."""
+        out = np.zeros(self.n)
+        check(self._L.cdh_glm_get_weights(self._h, _vp(out)), self._h)
+        return out
+
+    def _prior(self):
+        """The observation weights of a loss made with them, None otherwise (no call is made then)."""
+        return self._get_weights() if self._has_weights else None
 
     def _observations(self):
         out = np.zeros(self.n)
@@ -551,19 +566,26 @@ class _GLMLoss(CDWeightedLSLoss):
 
 
 class CDLogisticLoss(_GLMLoss):
-    """CDLogisticLoss(y, X): (1/n) Σ [log(1 + e^η_i) - y_i η_i], η = Xβ, labels y_i in [0, 1]; no reference counterpart.
+    """CDLogisticLoss(y, X; weights=None): (1/n) Σ [log(1 + e^η_i) - y_i η_i], η = Xβ, labels y_i in [0, 1]; no reference counterpart.
     Minimised by IRLS: a round is the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the
     working response z and weights w, which the handle's y and w hold from one irls_step to the next; the labels live in a
-    buffer of their own (cdh_glm_set_labels).  fp64 only, one device."""
+    buffer of their own (cdh_glm_set_labels).  fp64 only, one device.
+
+    weights (glmnet's weights =): v_i finite and > 0 -- case or survey weights, class re-balancing, the trials of a
+    proportion label -- normalised HERE to sum to n (v n / Σv; the library stores what it is given), so that unit weights
+    leave F as it was: F = (1/n) Σ v_i [log(1 + e^η_i) - y_i η_i].  A row's step is the unweighted one and its stored working
+    weight v_i w_i (cdh_glm_set_weights): an integer weight reproduces a replicated row.  The penalty scales of the paths
+    stay the reference's _stdX!, the root mean square over the rows present: they are NOT weighted by v."""
     _objective_step = {"wmin": 0.25}     # (the sum of nll does not depend on wmin)
 
-    def __init__(self, y, X, *, device=0):
-        super().__init__(y, X, device=device)
+    def __init__(self, y, X, *, weights=None, device=0):
+        super().__init__(y, X, weights=weights, device=device)
 
     def _set_observations(self, labels, _):
         check(self._L.cdh_glm_set_labels(self._h, 0, _vp(labels)), self._h)
 
     labels = property(_GLMLoss._observations)
+    weights = property(_GLMLoss._get_weights)
 
     def irls_step(self, apply=True, wmin=1e-5, fold=None):
         """One IRLS step at the iterate the handle holds (cdh_glm_irls).  apply=True turns the handle's y, w and r into the
@@ -572,7 +594,10 @@ class CDLogisticLoss(_GLMLoss):
 
         fold=k (cdh_glm_irls_fold, after set_folds): the rows of fold k are held out -- w = 0, z = η, r = 0 -- and the three
         sums run over the other rows; the dict gains "held_nll" = Σ nll_i and "held_miss" = Σ y_i [η_i <= 0] + (1 - y_i) [η_i > 0]
-        over the held-out rows (sums, not means).  "nll" stays (1/n) Σ over the training rows: the handle's objective."""
+        over the held-out rows (sums, not means).  "nll" stays (1/n) Σ over the training rows: the handle's objective.
+
+        On a loss with weights every sum but "clamped" is weighted by v: "nll" = (1/n) Σ v_i nll_i, "sum_w" = Σ v_i w_i,
+        "held_nll" = Σ v_i nll_i and "held_miss" = Σ v_i miss_i."""
         po = C.POINTER(C.c_double)
         if fold is None:
             out = np.zeros(3)
@@ -588,16 +613,24 @@ class CDLogisticLoss(_GLMLoss):
 
 
 class CDPoissonLoss(_GLMLoss):
-    """CDPoissonLoss(y, X, offset=None): (1/n) Σ [μ_i - y_i η_i], η = Xβ + o, μ = e^η, counts y_i >= 0 and offsets o_i (log
+    """CDPoissonLoss(y, X, offset=None; weights=None): (1/n) Σ [μ_i - y_i η_i], η = Xβ + o, μ = e^η, counts y_i >= 0 and offsets o_i (log
     exposure); no reference counterpart.  Minimised by IRLS like CDLogisticLoss (a sibling, not a subclass of it): a round is
     the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the working response and weights
     the handle's y and w hold from one irls_step to the next.  The counts and the offset live in buffers of their own
-    (cdh_glm_set_counts), and the stored working response leaves the offset out: f.y - f.r is Xβ.  fp64 only, one device."""
+    (cdh_glm_set_counts), and the stored working response leaves the offset out: f.y - f.r is Xβ.  fp64 only, one device.
+
+    weights (glmnet's weights =): v_i finite and > 0 (frequency or survey weights), normalised HERE to sum to n (v n / Σv; the
+    library stores what it is given): F = (1/n) Σ v_i [μ_i - y_i η_i].  A row's step is the unweighted one and its stored
+    working weight v_i w_i (cdh_glm_set_weights).  The penalty scales of the paths are NOT weighted by v."""
+
+    def __init__(self, y, X, offset=None, *, weights=None, device=0):
+        super().__init__(y, X, offset, weights=weights, device=device)
 
     def _set_observations(self, counts, off):
         check(self._L.cdh_glm_set_counts(self._h, _vp(counts), _vp(off)), self._h)
 
     counts = property(_GLMLoss._observations)
+    weights = property(_GLMLoss._get_weights)
 
     @property
     def offset(self):
@@ -614,7 +647,10 @@ class CDPoissonLoss(_GLMLoss):
         ("capped" over all rows).
 
         fold=k (after set_folds): the rows of fold k are held out -- w = 0, z = Xβ, r = 0 -- and the dict gains
-        "held_deviance" = Σ dev_i over them (a sum, not a mean)."""
+        "held_deviance" = Σ dev_i over them (a sum, not a mean).
+
+        On a loss with weights "nll", "sum_w", "deviance" and "held_deviance" are weighted by v ((1/n) Σ v_i nll_i, Σ v_i w_i,
+        Σ v_i dev_i); "clamped" and "capped" stay row counts."""
         out = np.zeros(6)
         k = -1 if fold is None else int(fold)
         if k < 0 and fold is not None:
@@ -1944,19 +1980,23 @@ def _irls_rounds(x, f, g, options, irls, fold):
     return last, rounds, converged, monotone
 
 
-def _logit_start(labels):
-    ybar = float(np.mean(labels))
+def _logit_start(labels, weights=None):
+    """The intercept of the null model: logit(ȳ), ȳ = Σvy / Σv with observation weights."""
+    ybar = float(np.mean(labels)) if weights is None else float(np.sum(weights * labels) / np.sum(weights))
     if not 0.0 < ybar < 1.0:
         raise ArgumentError("fit_intercept needs labels of both kinds: the null model's intercept is infinite")
     return float(np.log(ybar / (1.0 - ybar)))
 
 
-def _poisson_start(counts, offset=None):
-    """The intercept of the null model: log(Σy / Σ e^o)."""
-    total = float(np.sum(counts))
+def _poisson_start(counts, offset=None, weights=None):
+    """The intercept of the null model: log(Σy / Σ e^o), log(Σvy / Σ v e^o) with observation weights."""
+    total = float(np.sum(counts)) if weights is None else float(np.sum(weights * counts))
     if not total > 0.0:
         raise ArgumentError("fit_intercept needs a positive count: the null model's intercept is -infinity")
-    expo = float(len(counts)) if offset is None else float(np.sum(np.exp(offset)))
+    if weights is None:
+        expo = float(len(counts)) if offset is None else float(np.sum(np.exp(offset)))
+    else:
+        expo = float(np.sum(weights)) if offset is None else float(np.sum(weights * np.exp(offset)))
     return float(np.log(total / expo))
 
 
@@ -1971,8 +2011,9 @@ def _split_intercept(x, p):
 class _GLMFamily:
     name: str                    # "logistic", "poisson": the front ends' names (logisticLasso_, cvLogisticLassoPath, ...)
     loss: type
-    start: object                # (observations, offset or None) -> the null model's intercept, or the family's refusal
-    observed: object             # f -> (observations, offset or None), fetched from the loss
+    start: object                # (observations, offset or None, weights or None) -> the null model's intercept, or the
+                                 # family's refusal
+    observed: object             # f -> (observations, offset or None, weights or None), fetched from the loss
     start_before_upload: bool    # a matrix's front ends refuse an infinite start before the upload (the Poisson ones), or
                                  # find it on the way: after the upload, a path from the labels the handle returns
     solution: object             # (x, the last read-only step's dict, rounds, converged, monotone, g) -> the Solution
@@ -1980,13 +2021,14 @@ class _GLMFamily:
     path_fields: tuple           # the Solution's fields a path keeps per λ, between betapath and intercepts
     cv_result: type
     cv_measures: dict            # measure -> (sol, size_k) -> its value over the held-out rows; the first is fold_deviance
-    cv_train: object             # (sol, n, n_k) -> train_deviance
+                                 # (size_k: the held-out rows, or their Σ v on a loss with observation weights)
+    cv_train: object             # (sol, n, n_k) -> train_deviance (n_k: the training rows, or their Σ v)
     cv_weight: object = None     # sol -> the fold's weight in cvm and cvsd (None: the fold's size)
 
 
 _LOGISTIC = _GLMFamily(
-    name="logistic", loss=CDLogisticLoss, start=lambda labels, offset=None: _logit_start(labels),
-    observed=lambda f: (f.labels, None), start_before_upload=False,
+    name="logistic", loss=CDLogisticLoss, start=lambda labels, offset=None, weights=None: _logit_start(labels, weights),
+    observed=lambda f: (f.labels, None, f._prior()), start_before_upload=False,
     solution=lambda x, last, rounds, converged, monotone, g: LogisticLassoSolution(
         x, last["nll"], rounds, converged, monotone, None, g, last.get("held_nll"), last.get("held_miss")),
     path_result=LogisticLassoPathResult, path_fields=("nll", "rounds", "converged"), cv_result=CVLogisticLassoPathResult,
@@ -1995,7 +2037,7 @@ _LOGISTIC = _GLMFamily(
 
 _POISSON = _GLMFamily(
     name="poisson", loss=CDPoissonLoss, start=_poisson_start,
-    observed=lambda f: (f.counts, f.offset), start_before_upload=True,
+    observed=lambda f: (f.counts, f.offset, f._prior()), start_before_upload=True,
     solution=lambda x, last, rounds, converged, monotone, g: PoissonLassoSolution(
         x, last["nll"], last["deviance"], rounds, converged, monotone, last["capped"], None, g, last.get("held_deviance")),
     path_result=PoissonLassoPathResult, path_fields=("nll", "deviance", "rounds", "converged"),
@@ -2004,7 +2046,7 @@ _POISSON = _GLMFamily(
     cv_train=lambda sol, n, nk: sol.deviance / nk)
 
 _COX = _GLMFamily(
-    name="cox", loss=CDCoxLoss, start=None, observed=lambda f: (f.status, f.offset), start_before_upload=False,
+    name="cox", loss=CDCoxLoss, start=None, observed=lambda f: (f.status, f.offset, None), start_before_upload=False,
     solution=lambda x, last, rounds, converged, monotone, g: CoxLassoSolution(
         x, last["nll"], rounds, converged, monotone, last["capped"], last["events"], g, last.get("held_deviance"),
         last.get("held_events")),
@@ -2042,18 +2084,28 @@ def _glm_loss(fam, X, y, fit_intercept, offset, extra=None):
     return (fam.loss(y, X, **extra) if offset is None else fam.loss(y, X, offset, **extra)), True
 
 
-def _glm_host_start(fam, y, offset):
-    return fam.start(np.asarray(y, dtype=np.float64), None if offset is None else np.asarray(offset, dtype=np.float64))
+def _glm_host_start(fam, y, offset, weights=None):
+    return fam.start(np.asarray(y, dtype=np.float64), None if offset is None else np.asarray(offset, dtype=np.float64), weights)
 
 
-def _glm_early_start(fam, X, y, fit_intercept, offset):
+def _glm_host_weights(X, fit_intercept, extra):
+    """The observation weights a matrix's front end was given, checked and normalised as the loss will store them -- what
+    an intercept's start is computed from; None without an intercept, without weights, or with a loss (which refuses them)."""
+    v = (extra or {}).get("weights")
+    if v is None or not fit_intercept or isinstance(X, CoordinateDifferentiableFunction):
+        return None
+    return _strata_weights(None, v, np.shape(X)[0])[1]
+
+
+def _glm_early_start(fam, X, y, fit_intercept, offset, weights=None):
     if fit_intercept and fam.start_before_upload and not isinstance(X, CoordinateDifferentiableFunction):
-        return _glm_host_start(fam, y, offset)
+        return _glm_host_start(fam, y, offset, weights)
     return None
 
 
 def _glm_lasso(fam, X, y, lam, omega, options, irls, fit_intercept, offset=None, extra=None):
-    start = _glm_early_start(fam, X, y, fit_intercept, offset)
+    v = _glm_host_weights(X, fit_intercept, extra)
+    start = _glm_early_start(fam, X, y, fit_intercept, offset, v)
     f, owned = _glm_loss(fam, X, y, fit_intercept, offset, extra)
     try:
         p = f.p - (1 if fit_intercept else 0)
@@ -2061,7 +2113,7 @@ def _glm_lasso(fam, X, y, lam, omega, options, irls, fit_intercept, offset=None,
         x = SparseIterate(f.p)
         if fit_intercept:
             om = np.r_[np.ones(p) if om is None else om, 0.0]
-            x[p + 1] = _glm_host_start(fam, y, offset) if start is None else start
+            x[p + 1] = _glm_host_start(fam, y, offset, v) if start is None else start
         sol = _glm_solve(fam, x, f, ProxL1(lam, om), options, irls, None)
         if fit_intercept:
             sol.x, sol.intercept = _split_intercept(x, p)
@@ -2072,7 +2124,7 @@ def _glm_lasso(fam, X, y, lam, omega, options, irls, fit_intercept, offset=None,
 
 
 def _glm_path(fam, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, offset=None, extra=None):
-    start = _glm_early_start(fam, X, y, fit_intercept, offset)
+    start = _glm_early_start(fam, X, y, fit_intercept, offset, _glm_host_weights(X, fit_intercept, extra))
     f, owned = _glm_loss(fam, X, y, fit_intercept, offset, extra)
     try:
         return _glm_path_on(fam, f, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, start)
@@ -2130,13 +2182,14 @@ def _cv_glm_path(fam, X, y, lambdapath, K, folds, options, irls, standardizeX, f
         raise ArgumentError("lambdapath is empty")
     n = X.n if isinstance(X, _HipLoss) else np.shape(X)[0]
     ids, sizes = _cv_fold_ids(int(n), K, folds, seed)
-    obs = off = None
+    obs = off = v = None
     if fit_intercept and not isinstance(X, _HipLoss):
         obs = np.ascontiguousarray(y, dtype=np.float64)
         off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64)
-        fam.start(obs, off)
+        v = _glm_host_weights(X, fit_intercept, extra)
+        fam.start(obs, off, v)
         for k in range(len(sizes)):                     # before the upload: a fold whose start would be infinite
-            fam.start(obs[ids != k], None if off is None else off[ids != k])
+            fam.start(obs[ids != k], None if off is None else off[ids != k], None if v is None else v[ids != k])
     f, owned = _glm_loss(fam, X, y, fit_intercept, offset, extra)
     try:
         return _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, obs, off,
@@ -2155,9 +2208,15 @@ def _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standa
     held, tdev = {name: np.zeros((K, m)) for name in fam.cv_measures}, np.zeros((K, m))
     rounds, conv = np.zeros((K, m), dtype=np.int64), np.zeros((K, m), dtype=bool)
     fold_paths = [] if keep_fold_paths else None
-    wts = sizes if fam.cv_weight is None else np.zeros(K)
+    # Observation weights v (the binomial and the Poisson family; they sum to n): fold k's problem is the weighted path on its
+    # training rows with their weights renormalised to sum to n_k, F_k = (1/V_k) Σ_train v nll + λ Σ ω|β|, V_k = Σ_train v;
+    # the handle minimises (1/n) Σ_train v nll + λ' Σ ω|β|, so λ' = λ V_k / n, and the held-out sums divide by Σ_held v.
+    # Without weights V_k = n_k and Σ_held v = size_k: today's numbers.
+    v = f._prior()
+    held_v = sizes if v is None else np.bincount(ids, weights=v, minlength=K)
+    wts = held_v if fam.cv_weight is None else np.zeros(K)
     if fit_intercept and obs is None:
-        obs, off = fam.observed(f)                       # (a loss that was passed in has no intercept: not reached in practice)
+        obs, off, _ = fam.observed(f)                    # (a loss that was passed in has no intercept: not reached in practice)
     # The path on all rows.  On the handle this call has just made it runs FIRST: the very calls the family's path makes on a
     # fresh handle, so the same bits (after the folds an intercept's start η = b0 would be read as y - (y - b0) off the working
     # response they left, and the handle's cache policy has a history).  A loss that was passed in gets it LAST, and comes
@@ -2165,7 +2224,7 @@ def _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standa
     path = None
     if full_path and owned:
         path = _glm_path_on(fam, f, lam, options, irls, np.inf, standardizeX, fit_intercept,
-                            fam.start(obs, off) if fit_intercept else None)
+                            fam.start(obs, off, v) if fit_intercept else None)
     mode_before = f.gradient_cache_mode()                # a path is many solves on one X, as in _solve_path: 1 -> 2 for its duration
     try:
         f.set_folds(ids, K)
@@ -2176,21 +2235,24 @@ def _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standa
             nk = n - sizes[k]
             sx = stdX(f, weighted=True) if standardizeX else np.ones(f.p)     # while w still holds the 0/1 weights
             scale = np.sqrt(nk / n) if standardizeX else nk / n
+            vk = nk if v is None else float(np.sum(v[ids != k]))              # V_k
+            if v is not None:
+                scale = (vk / n) / np.sqrt(nk / n) if standardizeX else vk / n
             x = SparseIterate(f.p)
             if fit_intercept:
                 sx[p] = 0.0
-                x[p + 1] = fam.start(obs[ids != k], None if off is None else off[ids != k])
+                x[p + 1] = fam.start(obs[ids != k], None if off is None else off[ids != k], None if v is None else v[ids != k])
             res = fam.path_result(list(lam), [], *[[] for _ in fam.path_fields], [])
             for j in range(m):
                 sol = _glm_solve(fam, x, f, ProxL1(lam[j] * scale, sx), options, irls, k)
                 for name, value in fam.cv_measures.items():
-                    held[name][k, j] = value(sol, sizes[k])
-                tdev[k, j] = fam.cv_train(sol, n, nk)
+                    held[name][k, j] = value(sol, held_v[k])
+                tdev[k, j] = fam.cv_train(sol, n, vk)
                 rounds[k, j], conv[k, j] = sol.rounds, sol.converged
                 if fam.cv_weight is not None:
                     wts[k] = fam.cv_weight(sol)
                 if keep_fold_paths:
-                    _glm_keep(fam, res, sol, x, p, fit_intercept, nll=sol.nll * n / nk)
+                    _glm_keep(fam, res, sol, x, p, fit_intercept, nll=sol.nll * n / vk)
             if keep_fold_paths:
                 fold_paths.append(res)
     finally:
@@ -2219,23 +2281,31 @@ def logisticLasso_(x, f, g, options=None, irls=None, fold=None):
     return _glm_solve(_LOGISTIC, x, f, g, options, irls, fold)
 
 
-def logisticLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=False):
+def logisticLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=False, *, weights=None):
     """ℓ1-penalised logistic regression (glmnet's family = "binomial"): the minimiser of
     (1/n) Σ [log(1 + e^η_i) - y_i η_i] + λ Σ ω_j |β_j|, η = Xβ (+ b with fit_intercept: a column of ones appended as
     coordinate p + 1 with ω = 0, started at log(ȳ / (1 - ȳ)) and returned apart from x, which has length p).  X may also be
-    an existing CDLogisticLoss (y is then ignored; no intercept)."""
-    return _glm_lasso(_LOGISTIC, X, y, lam, omega, options, irls, fit_intercept)
+    an existing CDLogisticLoss (y is then ignored; no intercept).  weights: CDLogisticLoss's observation weights (glmnet's weights =; normalised to
+    sum to n): F = (1/n) Σ v_i nll_i, the penalty scales not weighted by v; refused when a loss is passed in (they are then its own).  With
+    weights the intercept starts at logit(Σvy / Σv)."""
+    return _glm_lasso(_LOGISTIC, X, y, lam, omega, options, irls, fit_intercept, None, dict(weights=weights))
 
 
 def logisticLambdaMax(f, omega=None, fit_intercept=False):
     """The smallest λ at which every penalised coordinate of the logistic lasso is zero: max_j |X_j'(y - p̂)| / (n ω_j) at the
     null model (β = 0; with fit_intercept the last column of f is the column of ones, its coordinate log(ȳ / (1 - ȳ)) and
     left out of the maximum).  One irls_step at the null model and one cdh_xt_r: the step leaves r = (y - p̂) / w, and at
-    the null model every row has the same weight w̄ = Σw / n, so X'(y - p̂) = w̄ X'r.  The handle is left at the null model."""
+    the null model every row has the same weight w̄ = Σw / n, so X'(y - p̂) = w̄ X'r.  The handle is left at the null model.
+
+    On a loss with observation weights the maximum is that of |X_j'(v∘(y - p̂))| / (n ω_j), the intercept logit(Σvy / Σv), and
+    the route poissonLambdaMax's: the stored null weights v_i w̄ differ by row, so the shortcut does not hold -- one applied
+    step and cdh_lambda_max (X_j'W r / n), which leaves the handle with the penalty scales of the maximum."""
     if not isinstance(f, CDLogisticLoss):
         raise TypeError("MethodError: logisticLambdaMax takes a CDLogisticLoss")
     p = f.p - (1 if fit_intercept else 0)
     x = SparseIterate(f.p)
+    if f._has_weights:
+        return _lambda_max_by_step(f, x, p, omega, fit_intercept and _logit_start(f.labels, f.weights), 1e-12)
     if fit_intercept:
         x[p + 1] = _logit_start(f.labels)
     f._push(x, rebuild=True)
@@ -2249,14 +2319,33 @@ def logisticLambdaMax(f, omega=None, fit_intercept=False):
     return float(t.max())
 
 
-def LogisticLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, fit_intercept=False):
+def _lambda_max_by_step(f, x, p, omega, start, wmin):
+    """max_j |X_j'W r| / (n ω_j) after one applied step at the null model (start: the intercept's coordinate, or False): the
+    body of poissonLambdaMax, and of logisticLambdaMax on a loss with observation weights."""
+    om = None if omega is None else np.asarray(omega, dtype=np.float64)[:p]
+    if start is not False:
+        x[p + 1] = start
+        om = np.r_[np.ones(p) if om is None else om, np.inf]        # (|g| / inf = 0: the intercept is out of the maximum)
+    f._push(x, rebuild=True)
+    f._synced = None
+    f.irls_step(True, wmin)
+    f._set_penalty(ProxL1(1.0, om))
+    out = C.c_double()
+    check(f._L.cdh_lambda_max(f._h, C.byref(out)), f._h)
+    return out.value
+
+
+def LogisticLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, fit_intercept=False, *,
+                      weights=None):
     """LassoPath's loop (src/lasso.jl:229-260) with logisticLasso_ per λ: one handle, one x warm-started along λ,
-    ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p."""
-    return _glm_path(_LOGISTIC, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept)
+    ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p.  weights: CDLogisticLoss's observation weights (glmnet's weights =; normalised to
+    sum to n): F = (1/n) Σ v_i nll_i, the penalty scales not weighted by v; refused when a loss is passed in (they are then its own)."""
+    return _glm_path(_LOGISTIC, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, None,
+                     dict(weights=weights))
 
 
 def cvLogisticLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, fit_intercept=False,
-                        seed=0, measure="deviance", full_path=True, keep_fold_paths=False):
+                        seed=0, measure="deviance", full_path=True, keep_fold_paths=False, *, weights=None):
     """K-fold cross-validation of LogisticLassoPath(X, y, λpath, options, irls; standardizeX, fit_intercept) on the device
     (glmnet's cv.glmnet(family = "binomial")); no reference counterpart.  X may also be an existing CDLogisticLoss (y is then
     ignored; no intercept); the design is uploaded once.
@@ -2272,9 +2361,15 @@ def cvLogisticLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=N
     different λ.  With fit_intercept every fold starts at the logit of its own training rows' mean label.  The folds are
     dropped when the call returns or raises.  `path` is LogisticLassoPath on all rows (None with full_path=False): from a
     matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was passed
-    in it runs after them, so that the loss comes back with the weights of all rows.  `fold_paths`: the K fold paths as LogisticLassoPathResult (None unless keep_fold_paths)."""
+    in it runs after them, so that the loss comes back with the weights of all rows.  `fold_paths`: the K fold paths as LogisticLassoPathResult (None unless keep_fold_paths).
+
+    weights (or a loss made with them): fold k's problem is the weighted path on its training rows with their weights
+    renormalised to sum to n_k.  With V_k = Σ v over the training rows, λ is scaled by (V_k / n) / sqrt(n_k / n)
+    (standardizeX=False: V_k / n) -- today's factors when v ≡ 1 -- and ω stays _stdX!(w, X) of the 0/1 weights, not weighted
+    by v.  The held-out measures divide by Σ v over the held-out rows, which is also the fold's weight in cvm and cvsd;
+    train_deviance divides by V_k; fold_sizes stay row counts."""
     return _cv_glm_path(_LOGISTIC, X, y, lambdapath, K, folds, options, irls, standardizeX, fit_intercept, seed, measure, None,
-                        full_path, keep_fold_paths)
+                        full_path, keep_fold_paths, dict(weights=weights))
 
 
 # ---- the Poisson family with an offset ----------------------------------------------------------------------------------------
@@ -2286,12 +2381,14 @@ def poissonLasso_(x, f, g, options=None, irls=None, fold=None):
     return _glm_solve(_POISSON, x, f, g, options, irls, fold)
 
 
-def poissonLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=False, offset=None):
+def poissonLasso(X, y, lam, omega=None, options=None, irls=None, fit_intercept=False, offset=None, *, weights=None):
     """ℓ1-penalised Poisson regression (glmnet's family = "poisson" with offset): the minimiser of
     (1/n) Σ [μ_i - y_i η_i] + λ Σ ω_j |β_j|, η = Xβ + o (+ b with fit_intercept: a column of ones appended as coordinate
     p + 1 with ω = 0, started at log(Σy / Σ e^o) and returned apart from x, which has length p).  X may also be an existing
-    CDPoissonLoss (y and offset are then its own; no intercept)."""
-    return _glm_lasso(_POISSON, X, y, lam, omega, options, irls, fit_intercept, offset)
+    CDPoissonLoss (y and offset are then its own; no intercept).  weights: CDPoissonLoss's observation weights (glmnet's weights =; normalised to
+    sum to n): F = (1/n) Σ v_i nll_i, the penalty scales not weighted by v; refused when a loss is passed in (they are then its own).  With
+    weights the intercept starts at log(Σvy / Σ v e^o)."""
+    return _glm_lasso(_POISSON, X, y, lam, omega, options, irls, fit_intercept, offset, dict(weights=weights))
 
 
 def poissonLambdaMax(f, omega=None, fit_intercept=False):
@@ -2300,33 +2397,26 @@ def poissonLambdaMax(f, omega=None, fit_intercept=False):
     log(Σy / Σ e^o) and left out of the maximum).  One applied irls_step at the null model leaves r = (y - μ) / w, and the
     weighted gradient of the handle (cdh_lambda_max: X_j'W r / n) is X_j'(y - μ) / n -- with an offset the null weights differ
     by row, so the binomial's w̄ X'r does not hold here.  Nothing n-sized crosses the host beyond the counts and the offset of
-    an intercept's start.  The handle is left at the null model, with the penalty scales of the maximum."""
+    an intercept's start.  The handle is left at the null model, with the penalty scales of the maximum.  On a loss with
+    observation weights the same step leaves X'W r = X'(v∘(y - μ)), and the intercept is log(Σvy / Σ v e^o)."""
     if not isinstance(f, CDPoissonLoss):
         raise TypeError("MethodError: poissonLambdaMax takes a CDPoissonLoss")
     p = f.p - (1 if fit_intercept else 0)
-    x = SparseIterate(f.p)
-    om = None if omega is None else np.asarray(omega, dtype=np.float64)[:p]
-    if fit_intercept:
-        x[p + 1] = _poisson_start(f.counts, f.offset)
-        om = np.r_[np.ones(p) if om is None else om, np.inf]        # (|g| / inf = 0: the intercept is out of the maximum)
-    f._push(x, rebuild=True)
-    f._synced = None
-    f.irls_step(True, 1e-300)
-    f._set_penalty(ProxL1(1.0, om))
-    out = C.c_double()
-    check(f._L.cdh_lambda_max(f._h, C.byref(out)), f._h)
-    return out.value
+    return _lambda_max_by_step(f, SparseIterate(f.p), p, omega,
+                               fit_intercept and _poisson_start(f.counts, f.offset, f._prior()), 1e-300)
 
 
 def PoissonLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, fit_intercept=False,
-                     offset=None):
+                     offset=None, *, weights=None):
     """LassoPath's loop (src/lasso.jl:229-260) with poissonLasso_ per λ: one handle, one x warm-started along λ,
-    ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p."""
-    return _glm_path(_POISSON, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, offset)
+    ω = _stdX!(X) (cdh_col_rms) when standardising, the intercept -- if any -- unpenalised.  βpath[i] has length p.  weights: CDPoissonLoss's observation weights (glmnet's weights =; normalised to
+    sum to n): F = (1/n) Σ v_i nll_i, the penalty scales not weighted by v; refused when a loss is passed in (they are then its own)."""
+    return _glm_path(_POISSON, X, y, lambdapath, options, irls, max_hat_s, standardizeX, fit_intercept, offset,
+                     dict(weights=weights))
 
 
 def cvPoissonLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, fit_intercept=False,
-                       seed=0, measure="deviance", offset=None, full_path=True, keep_fold_paths=False):
+                       seed=0, measure="deviance", offset=None, full_path=True, keep_fold_paths=False, *, weights=None):
     """K-fold cross-validation of PoissonLassoPath(X, y, λpath, options, irls; standardizeX, fit_intercept, offset) on the
     device (glmnet's cv.glmnet(family = "poisson", offset = ...)); no reference counterpart.  X may also be an existing
     CDPoissonLoss (y and offset are then its own; no intercept); the design is uploaded once.
@@ -2340,9 +2430,15 @@ def cvPoissonLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=No
     folds are dropped when the call returns or raises.  `path` is PoissonLassoPath on all rows (None with full_path=False):
     from a matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was
     passed in it runs after them, so that the loss comes back with the weights of all rows.  `fold_paths`: the K fold paths
-    as PoissonLassoPathResult (None unless keep_fold_paths)."""
+    as PoissonLassoPathResult (None unless keep_fold_paths).
+
+    weights (CDPoissonLoss's; or a loss made with them): fold k's problem is the weighted path on its training rows with their weights
+    renormalised to sum to n_k.  With V_k = Σ v over the training rows, λ is scaled by (V_k / n) / sqrt(n_k / n)
+    (standardizeX=False: V_k / n) -- today's factors when v ≡ 1 -- and ω stays _stdX!(w, X) of the 0/1 weights, not weighted
+    by v.  The held-out measures divide by Σ v over the held-out rows, which is also the fold's weight in cvm and cvsd;
+    train_deviance divides by V_k; fold_sizes stay row counts."""
     return _cv_glm_path(_POISSON, X, y, lambdapath, K, folds, options, irls, standardizeX, fit_intercept, seed, measure, offset,
-                        full_path, keep_fold_paths)
+                        full_path, keep_fold_paths, dict(weights=weights))
 
 
 # ---- the Cox family, Breslow ties ------------------------------------------------------------------------------------------

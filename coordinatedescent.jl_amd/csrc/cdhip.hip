@@ -324,6 +324,9 @@ struct GlmState {
     DevBuf<double> offset;     // Poisson: ld doubles, pads zero; allocated by the first cdh_glm_set_counts that brings one
     GlmData family = GlmData::Binomial;   // what `labels` holds: cdh_glm_set_labels' labels or cdh_glm_set_counts' counts
     bool has_offset = false;   // the offset buffer holds this handle's offset (false: the step runs without one)
+    DevBuf<double> prior;      // binomial and Poisson: the observation weights v, ld doubles, pads zero; allocated by the
+                               // first cdh_glm_set_weights that brings them, in use while `weighted` is set
+    bool weighted = false;     // the step runs its weighted instantiation (every setter of observations clears it)
     bool set = false;
     CoxState cox;              // GlmData::Cox: `labels` holds the status, `offset` the offset
 };
@@ -1106,6 +1109,7 @@ int32_t cdh_get_residual(cdh_handle h, void* out_n_local) { return guarded(h, [&
 // CDWeightedLSLoss, cd_differentiable_function.jl:118-194) ---------------------------------------------------------------------
 // The body of cdh_glm_irls, cdh_glm_irls_fold, cdh_glm_poisson_irls and cdh_glm_cox_irls: stands in for cdh_get_residual, w and z on the host,
 // cdh_set_y, cdh_set_obs_weights and cdh_initialize between two rounds.  F: the family (GlmBinomial, GlmBinomialFold, GlmPoisson,
+// GlmBinomialFoldW and GlmPoissonW where the handle holds observation weights -- chosen by the exports, on the host --
 // and GlmCox of cox_kernels.hpp, whose glm_check and glm_launch are its own).
 extern "C++" template <class F>
 static int32_t glm_step(cdh_handle h, int32_t k, int32_t apply, const GlmParams& pm, double* out) {
@@ -1139,12 +1143,20 @@ int32_t cdh_glm_get_labels(cdh_handle h, void* host_labels) { return guarded(h, 
 
 // the step between two rounds (glm_step), the binomial family
 int32_t cdh_glm_irls(cdh_handle h, int32_t apply, double wmin, double* out3) { return guarded(h, [&]() -> int32_t {
-    return glm_step<GlmBinomial>(h, -1, apply, GlmParams{wmin, 0.0}, out3);
+    const GlmParams pm{wmin, 0.0};
+    if (!h->glm.weighted) return glm_step<GlmBinomial>(h, -1, apply, pm, out3);
+    // with weights: the fold-aware weighted step at k = -1, behind this export's own refusals; the first three sums are its record
+    CHK(glm_check<GlmBinomial>(h, -1, apply, pm, out3));
+    double out5[kGlmFoldVals];
+    CHK(glm_step<GlmBinomialFoldW>(h, -1, apply, pm, out5));
+    std::copy(out5, out5 + kGlmVals, out3);
+    return CDH_OK;
 }); }
 
 // the same step inside a fold of a cross-validated path (cv_path.hpp; the solves are LassoPath's, lasso.jl:229-260, on the
 // weighted loss): held-out rows keep weight zero through every round, and their deviance and class error come out of the pass
 int32_t cdh_glm_irls_fold(cdh_handle h, int32_t k, int32_t apply, double wmin, double* out5) { return guarded(h, [&]() -> int32_t {
+    if (h->glm.weighted) return glm_step<GlmBinomialFoldW>(h, k, apply, GlmParams{wmin, 0.0}, out5);
     return glm_step<GlmBinomialFold>(h, k, apply, GlmParams{wmin, 0.0}, out5);
 }); }
 
@@ -1158,7 +1170,18 @@ int32_t cdh_glm_get_offset(cdh_handle h, void* host_offset) { return guarded(h, 
 }); }
 
 int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double* out6) { return guarded(h, [&]() -> int32_t {
+    if (h->glm.weighted) return glm_step<GlmPoissonW>(h, k, apply, GlmParams{wmin, eta_max}, out6);
     return glm_step<GlmPoisson>(h, k, apply, GlmParams{wmin, eta_max}, out6);
+}); }
+
+// observation weights of the binomial and the Poisson family: stands in for the v in cdh_set_obs_weights of v w, composed on
+// the host every round
+int32_t cdh_glm_set_weights(cdh_handle h, const void* host_weights) { return guarded(h, [&]() -> int32_t {
+    return glm_set_weights(h, host_weights, [&]() -> int32_t { return design_changes(h, false); });
+}); }
+
+int32_t cdh_glm_get_weights(cdh_handle h, void* host_weights) { return guarded(h, [&]() -> int32_t {
+    return glm_get_weights(h, host_weights);
 }); }
 
 // the Cox family of the same loop (cox_kernels.hpp): stands in for cdh_set_y of n zeros, the times sorted on the host, the

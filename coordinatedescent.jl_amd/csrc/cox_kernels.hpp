@@ -531,6 +531,7 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
     h->glm.has_offset = off != nullptr;
     h->glm.cox.strata = sw;
     h->glm.cox.interval = iv;
+    h->glm.weighted = false;             // (the weights of cdh_glm_set_weights go with the labels or counts they came with)
     h->glm.set = true;
     return CDH_OK;
 }

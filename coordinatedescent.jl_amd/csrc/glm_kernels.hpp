@@ -3,8 +3,8 @@
 // residual stands for, the working weights, the working response and the new residual in one pass over the rows, with the
 // sums a caller needs of it.  Included by cdhip.hip inside its anonymous namespace, after the handle; the grid and the rows of
 // a workgroup are glm_plan.hpp's.  One kernel (k_glm_step) and one host body (glm_step) serve every family; a family -- the
-// binomial, the binomial inside a fold, the Poisson with an offset -- is a struct that names its row function, its record
-// and what its export refuses.
+// binomial, the binomial inside a fold, the Poisson with an offset, and the last two with observation weights -- is a struct
+// that names its row function, its record and what its export refuses.
 
 // One row, every quantity in double and every operation rounded on its own (no contraction into FMAs: tests/_logistic_numpy.py
 // writes the same lines).  eta = yw - r;  a = |eta|, e = exp(-a);  p = 1 / (1 + e) or e / (1 + e) by the sign of eta and
@@ -69,8 +69,10 @@ __device__ __forceinline__ PoisRow pois_row(double count, double yw, double r, d
 struct GlmParams { double wmin, eta_max; };
 
 // A family names, for the kernel: kVals, the doubles of its record (glm_plan.hpp); kFold, whether a fold byte per row can hold
-// rows out; kOffset, whether a fourth 16-byte stream, the offset, is read; row(), one row's quantities; add(), the row's terms
-// of the record, acc[0] first -- live: the row lies below n, held: it is held out, train: live and not held.  For the host:
+// rows out; kOffset, whether a fourth 16-byte stream, the offset, is read; kWeights, whether one more 16-byte stream, the
+// observation weights v, is read -- o.w is then v times the family's clamped weight when add() sees it; row(), one row's
+// quantities; add(), the row's terms of the record, acc[0] first -- v: the row's observation weight (1 without kWeights),
+// live: the row lies below n, held: it is held out, train: live and not held.  For the host:
 // kData, the observations its export needs on the handle; kKBeforeOut, whether that export looks at k before its output
 // pointer; and what it refuses of the handle's observations, of the parameters and of a null output, in its own words.
 //
@@ -78,7 +80,7 @@ struct GlmParams { double wmin, eta_max; };
 // round stays an instantiation of its own (the fold-aware one at k = -1 was measured at 1.03x its time).
 struct GlmBinomial {
     static constexpr int kVals = kGlmVals;
-    static constexpr bool kFold = false, kOffset = false;
+    static constexpr bool kFold = false, kOffset = false, kWeights = false;
     static constexpr GlmData kData = GlmData::Binomial;
     static constexpr bool kKBeforeOut = false;
     static constexpr const char* kOutNull = "out3 is NULL";
@@ -86,7 +88,7 @@ struct GlmBinomial {
     static __device__ __forceinline__ Row row(double label, double yw, double r, double, double wmin, double) {
         return glm_row(label, yw, r, wmin);
     }
-    static __device__ __forceinline__ void add(double* acc, const Row& o, double, double, bool, bool, bool train) {
+    static __device__ __forceinline__ void add(double* acc, const Row& o, double, double, double, bool, bool, bool train) {
         acc[0] += train ? o.nll : 0.0;
         acc[1] += train ? o.w : 0.0;
         acc[2] += (train && o.clamped) ? 1.0 : 0.0;
@@ -112,10 +114,30 @@ struct GlmBinomialFold : GlmBinomial {
     static constexpr int kVals = kGlmFoldVals;
     static constexpr bool kFold = true;
     static constexpr const char* kOutNull = "out5 is NULL";
-    static __device__ __forceinline__ void add(double* acc, const Row& o, double label, double eta, bool live, bool held, bool train) {
-        GlmBinomial::add(acc, o, label, eta, live, held, train);
+    static __device__ __forceinline__ void add(double* acc, const Row& o, double label, double eta, double v, bool live, bool held,
+                                               bool train) {
+        GlmBinomial::add(acc, o, label, eta, v, live, held, train);
         acc[3] += held ? o.nll : 0.0;
         acc[4] += held ? (eta > 0.0 ? 1.0 - label : label) : 0.0;
+    }
+};
+
+// The binomial step of a handle with observation weights (cdh_glm_set_weights): GlmBinomialFold's record with every sum but
+// the count of clamped rows weighted by v -- (sum v nll and sum w = sum v w_fam of the training rows, clamped training rows,
+// sum v nll and sum v miss of the held-out rows), each product rounded on its own.  It serves cdh_glm_irls too (k = -1, the
+// first three sums returned): with weights there is no fold-free instantiation.
+struct GlmBinomialFoldW : GlmBinomialFold {
+    static constexpr bool kWeights = true;
+    static __device__ __forceinline__ void add(double* acc, const Row& o, double label, double eta, double v, bool, bool held,
+                                               bool train) {
+#pragma clang fp contract(off)
+        const double vn = v * o.nll;
+        const double vm = v * (eta > 0.0 ? 1.0 - label : label);
+        acc[0] += train ? vn : 0.0;
+        acc[1] += train ? o.w : 0.0;
+        acc[2] += (train && o.clamped) ? 1.0 : 0.0;
+        acc[3] += held ? vn : 0.0;
+        acc[4] += held ? vm : 0.0;
     }
 };
 
@@ -125,7 +147,7 @@ struct GlmBinomialFold : GlmBinomial {
 // the fold-aware binomial step's 49.
 struct GlmPoisson {
     static constexpr int kVals = kGlmPoisVals;
-    static constexpr bool kFold = true, kOffset = true;
+    static constexpr bool kFold = true, kOffset = true, kWeights = false;
     static constexpr GlmData kData = GlmData::Poisson;
     static constexpr bool kKBeforeOut = true;
     static constexpr const char* kOutNull = "out6 is NULL";
@@ -133,7 +155,7 @@ struct GlmPoisson {
     static __device__ __forceinline__ Row row(double count, double yw, double r, double off, double wmin, double eta_max) {
         return pois_row(count, yw, r, off, wmin, eta_max);
     }
-    static __device__ __forceinline__ void add(double* acc, const Row& o, double, double, bool live, bool held, bool train) {
+    static __device__ __forceinline__ void add(double* acc, const Row& o, double, double, double, bool live, bool held, bool train) {
         acc[0] += train ? o.nll : 0.0;
         acc[1] += train ? o.w : 0.0;
         acc[2] += (train && o.clamped) ? 1.0 : 0.0;
@@ -153,6 +175,31 @@ struct GlmPoisson {
     }
 };
 
+// The Poisson step of a handle with observation weights: GlmPoisson's record with the nll, sum w = sum v w_fam and both
+// deviances weighted by v, each product rounded on its own; clamped and capped stay row counts.  65 bytes a row with APPLY
+// (five vectors and a byte read, three vectors written) against GlmPoisson's 57.
+struct GlmPoissonW : GlmPoisson {
+    static constexpr bool kWeights = true;
+    static __device__ __forceinline__ void add(double* acc, const Row& o, double, double, double v, bool live, bool held, bool train) {
+#pragma clang fp contract(off)
+        const double vn = v * o.nll;
+        const double vd = v * o.dev;
+        acc[0] += train ? vn : 0.0;
+        acc[1] += train ? o.w : 0.0;
+        acc[2] += (train && o.clamped) ? 1.0 : 0.0;
+        acc[3] += (live && o.capped) ? 1.0 : 0.0;
+        acc[4] += held ? vd : 0.0;
+        acc[5] += train ? vd : 0.0;
+    }
+};
+
+// w = v w_fam of a row with an observation weight: one rounded multiplication, after r_new = d / w_fam -- so r and z are the
+// unweighted step's bits and X'W r = X'(v (y - mu)) whatever the clamp did to w_fam
+__device__ __forceinline__ double glm_prior_times(double v, double w_fam) {
+#pragma clang fp contract(off)
+    return v * w_fam;
+}
+
 // Workgroup b walks tiles b, b + gridDim.x, ... of kGlmRows rows; a lane holds one 16-byte vector of each stream per trip: the
 // observations, y, r and -- F::kOffset -- the offset.  A training row becomes (w, z, r_new) of F::row.  A held-out row
 // (F::kFold, fold_i == k) gets w = 0 exactly (never clamped up to wmin), z = eta_lin = y - r (X beta, without the offset) and
@@ -164,14 +211,15 @@ struct GlmPoisson {
 // unconditional (as k_path_sse's), so no byte at or beyond n is read; `live` keeps such a row out of everything.  (Measured
 // and dropped: both ids in one 2-byte load where both rows lie below n, the clamped byte load elsewhere -- 1.12x the plain
 // step against 1.08x for the two byte loads, interleaved at n = 1e7.)  fold == nullptr or k < 0, and offset == nullptr, are
-// uniform over the launch.  The lanes' sums go through block_sum (wave butterflies, the four waves in order) into the
+// uniform over the launch.  F::kWeights: `prior` holds ld observation weights, its pad rows zero, so its vector is loaded
+// like the observations'; without kWeights the pointer is not looked at.  The lanes' sums go through block_sum (wave butterflies, the four waves in order) into the
 // workgroup's record partials[b F::kVals + i]; k_gram_reduce adds the records in block order.  No atomics: bit-identical run
 // to run.  With APPLY = false nothing is written but the record.
 template <class F, bool APPLY>
 __global__ __launch_bounds__(kGlmBlock) void k_glm_step(const double* __restrict__ obs, double* __restrict__ y,
                                                         double* __restrict__ r, double* __restrict__ w,
-                                                        const double* __restrict__ offset, const uint8_t* __restrict__ fold,
-                                                        int k, int64_t n, int64_t vecs, double wmin, double eta_max,
+                                                        const double* __restrict__ offset, const double* __restrict__ prior,
+                                                        const uint8_t* __restrict__ fold, int k, int64_t n, int64_t vecs, double wmin, double eta_max,
                                                         double* __restrict__ partials) {
     __shared__ double s_red[F::kVals * (kGlmBlock / 64)];
     const dvec2* bv = reinterpret_cast<const dvec2*>(obs);
@@ -187,6 +235,8 @@ __global__ __launch_bounds__(kGlmBlock) void k_glm_step(const double* __restrict
         const dvec2 bb = bv[j], yy = yv[j], rr = rv[j];
         dvec2 oo;
         if (has_off) oo = ov[j]; else { oo[0] = 0.0; oo[1] = 0.0; }
+        dvec2 vv;
+        if constexpr (F::kWeights) vv = reinterpret_cast<const dvec2*>(prior)[j]; else { vv[0] = 1.0; vv[1] = 1.0; }
         int id[kGlmVec];
 #pragma unroll
         for (int e = 0; e < kGlmVec; ++e) {
@@ -199,12 +249,13 @@ __global__ __launch_bounds__(kGlmBlock) void k_glm_step(const double* __restrict
             const bool live = j * kGlmVec + e < n;
             const bool held = live && folded && id[e] == k;
             const bool train = live && !held;
-            const typename F::Row o = F::row(bb[e], yy[e], rr[e], oo[e], wmin, eta_max);
+            typename F::Row o = F::row(bb[e], yy[e], rr[e], oo[e], wmin, eta_max);
+            if constexpr (F::kWeights) o.w = glm_prior_times(vv[e], o.w);
             const double eta_lin = yy[e] - rr[e];            // (the row functions' own first line)
             wn[e] = train ? o.w : 0.0;
             zn[e] = train ? o.z : (held ? eta_lin : 0.0);
             rn[e] = train ? o.r : 0.0;
-            F::add(acc, o, bb[e], eta_lin, live, held, train);
+            F::add(acc, o, bb[e], eta_lin, vv[e], live, held, train);
         }
         if constexpr (APPLY) { wv[j] = wn; yv[j] = zn; rv[j] = rn; }
     }
@@ -274,6 +325,7 @@ int32_t glm_set_observations(cdh_handle h, GlmData family, const void* host_obs,
     h->glm.has_offset = off != nullptr;  // (a Poisson handle turned binomial drops its offset)
     h->glm.cox.strata = false;           // (and a Cox handle its strata and observation weights,
     h->glm.cox.interval = false;         //  and its start times)
+    h->glm.weighted = false;             // (and every handle the weights of cdh_glm_set_weights)
     h->glm.set = true;
     return CDH_OK;
 }
@@ -304,6 +356,61 @@ int32_t glm_get_labels(cdh_handle h, void* host_labels) {
     if (!h->glm.set) return fail(h, CDH_BAD_ARG, "no labels are set: call cdh_glm_set_labels first");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(host_labels, h->glm.labels, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CDH_OK;
+}
+
+// cdh_glm_set_weights: the observation weights v of a binomial or a Poisson handle, stored as given in a buffer of ld doubles
+// whose pad rows are zero, complete before the handle changes; nullptr drops them.  voids(): what cdh_set_obs_weights voids,
+// through its own call (the loss of every later round changes); y, r and beta stay.
+template <class Voids>
+int32_t glm_set_weights(cdh_handle h, const void* host_weights, Voids&& voids) {
+    CHK(glm_refuse(h));
+    if (!h->glm.set) return fail(h, CDH_BAD_ARG, "cdh_glm_set_weights needs labels or counts: call cdh_glm_set_labels or cdh_glm_set_counts first");
+    if (h->glm.family == GlmData::Cox)
+        return fail(h, CDH_BAD_ARG, "the handle holds survival data (Cox): its weights come through cdh_glm_set_survival_strata");
+    const double* v = (const double*)host_weights;
+    if (v) {
+        const int64_t bad = glm_first_bad_weight(v, h->n);
+        if (bad < h->n) {
+            char buf[128];
+            snprintf(buf, sizeof buf, "weights[%lld] = %g is not finite and > 0", (long long)bad, v[bad]);
+            return fail(h, CDH_BAD_ARG, buf);
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t colbytes = (size_t)h->ld * sizeof(double);
+    DevBuf<double> fresh;                // complete before the handle changes: a failed allocation leaves it as it was
+    if (v && !h->glm.prior) {
+        HIPCHK(h, fresh.alloc(colbytes));
+        HIPCHK(h, hipMemsetAsync(fresh, 0, colbytes, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    CHK(voids());
+    if (!v) {
+        h->glm.weighted = false;
+        return CDH_OK;
+    }
+    if (!h->glm.prior) h->glm.prior = std::move(fresh);
+    h->glm.weighted = false;             // (a failed copy leaves a handle without weights, not one with half of them)
+    HIPCHK(h, hipMemcpyAsync(h->glm.prior, v, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->glm.weighted = true;
+    return CDH_OK;
+}
+
+// ones when the handle holds none
+int32_t glm_get_weights(cdh_handle h, void* host_weights) {
+    NEED_P(h, host_weights);
+    if (!h->glm.set) return fail(h, CDH_BAD_ARG, "no labels or counts are set: call cdh_glm_set_labels or cdh_glm_set_counts first");
+    if (h->glm.family == GlmData::Cox)
+        return fail(h, CDH_BAD_ARG, "the handle holds survival data (Cox): its weights are cdh_glm_get_survival_strata's");
+    if (!h->glm.weighted) {
+        std::fill_n((double*)host_weights, (size_t)h->n, 1.0);
+        return CDH_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(host_weights, h->glm.prior, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CDH_OK;
 }
@@ -348,6 +455,7 @@ int32_t glm_launch(cdh_handle h, int32_t k, bool apply, const GlmParams& pm, dou
         hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid), dim3(kGlmBlock), 0, h->stream, (const double*)h->glm.labels,
                            (double*)h->y, (double*)h->r, (double*)h->w,
                            F::kOffset && h->glm.has_offset ? (const double*)h->glm.offset : (const double*)nullptr,
+                           F::kWeights ? (const double*)h->glm.prior : (const double*)nullptr,
                            F::kFold && k >= 0 ? (const uint8_t*)h->cv.fold : (const uint8_t*)nullptr, (int)k, h->n, pl.vecs, pm.wmin,
                            pm.eta_max, (double*)h->d_partials);
     };

@@ -3,6 +3,7 @@
 // tests/test_glm_host.py compiles it with g++ (tests/glm_plan_main.cpp).  glm_kernels.hpp calls these functions and nothing
 // else decides the sizes.
 #pragma once
+#include <float.h>
 #include <stdint.h>
 
 // ---- the kernel's shape ------------------------------------------------------------------------------------------------------
@@ -51,4 +52,13 @@ constexpr int64_t glm_rows_first(const GlmPlan& pl, int64_t ld, int64_t b, int64
 constexpr int64_t glm_rows_end(const GlmPlan& pl, int64_t ld, int64_t b, int64_t t) {
     const int64_t r = (b + t * pl.grid + 1) * kGlmRows;
     return r < ld ? r : ld;
+}
+
+// ---- observation weights -------------------------------------------------------------------------------------------------------
+// what cdh_glm_set_weights refuses: the index of the first weight that is not finite or not > 0 (a NaN fails both comparisons;
+// a denormal is a weight like any other), or n when there is none
+inline int64_t glm_first_bad_weight(const double* v, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(v[i] > 0.0 && v[i] <= DBL_MAX)) return i;
+    return n;
 }

@@ -334,6 +334,29 @@ int32_t cdh_glm_get_offset(cdh_handle h, void *host_offset);
  * handle included); apply not in {0, 1}; wmin not finite or not > 0; eta_max outside (0, 700]; k < -1; k >= 0 without folds;
  * k >= K; out6 NULL. */
 int32_t cdh_glm_poisson_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double *out6);
+/* ---- observation weights of the binomial and the Poisson family (glmnet's weights =; no reference counterpart: a round's
+ * solve is the weighted lasso of CDWeightedLSLoss, cd_differentiable_function.jl:118-194) ---------------------------------
+ * F(beta) = (1/n) sum_i v_i nll_i + lambda0 sum_j omega_j |beta_j|, nll_i the family's own and v_i finite and > 0.  A
+ * training row's step is the unweighted one -- r_new and z are its bits -- and the stored working weight is
+ * w_i = v_i w_i^fam, w_i^fam the family's weight already clamped at wmin, one rounded multiplication: X'W r =
+ * X'(v (y - mu)) whatever the clamp did.  Held-out rows stay (0, eta_lin, 0), rows n .. ld - 1 zeros.  The records keep
+ * their layouts: the nll, sum w, the held-out nll and both deviances become sums weighted by v (sum v_i nll_i, sum w_i,
+ * ...), the held-out misclassification sum v_i miss_i; the clamped and capped rows stay counts.  The three step exports
+ * run the weighted instantiation while the handle holds weights; their signatures and what they refuse do not change, and
+ * cdh_glm_irls returns the first three sums of the fold-aware weighted step at k = -1. */
+/* cdh_glm_set_weights (no reference counterpart; see above, cd_differentiable_function.jl:118-194) stands in for the v in
+ * cdh_set_obs_weights(v w), composed on the host every round: it stores n weights AS GIVEN (the library does not normalise
+ * them; the front ends pass weights that sum to n) in a buffer of ld doubles the handle owns (pads zero, allocated
+ * all-or-nothing before the handle changes).  NULL drops the weights: the steps are the unweighted ones again, bit for bit.
+ * It voids what cdh_set_obs_weights voids and leaves y, r and beta alone.  CDH_BAD_ARG, the handle unchanged: what
+ * cdh_glm_set_labels refuses of the handle; a handle without labels or counts; a Cox handle (its weights come through
+ * cdh_glm_set_survival_strata); a weight that is not finite or not > 0 (the message names the row).  cdh_glm_set_labels,
+ * cdh_glm_set_counts and the three cdh_glm_set_survival* drop the weights. */
+int32_t cdh_glm_set_weights(cdh_handle h, const void *host_weights_or_null);
+/* cdh_glm_get_weights (no reference counterpart; see cdh_glm_set_weights, cd_differentiable_function.jl:118-194): the n
+ * weights the handle holds, ones when none are set.  CDH_BAD_ARG: host_weights NULL; a handle without labels or counts; a
+ * Cox handle (cdh_glm_get_survival_strata returns its weights). */
+int32_t cdh_glm_get_weights(cdh_handle h, void *host_weights);
 /* ---- l1-penalised Cox regression (Breslow ties, as glmnet's family = "cox"), by the same IRLS loop (no reference
  * counterpart: a round's solve is the weighted lasso of CDWeightedLSLoss, cd_differentiable_function.jl:118-194) -----------
  * Rows have a time t_i, a status delta_i (1: event, 0: censored) and optionally an offset o_i.  With eta = X beta + o and

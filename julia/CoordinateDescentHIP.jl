@@ -557,6 +557,21 @@ function glm_poisson_irls!(X::HipMatrix{Float64}, k::Integer=-1; apply::Bool=tru
   (nll = out[1] / X.n, sum_w = out[2], clamped = Int(out[3]), capped = Int(out[4]), held_deviance = out[5], deviance = out[6])
 end
 
+"observation weights (finite, > 0; stored as given) of a design that holds labels or counts; nothing drops them. y, r and the iterate stay"
+function glm_set_weights!(X::HipMatrix{Float64}, weights::Union{Nothing,Vector{Float64}})
+  weights === nothing || length(weights) == X.n || throw(DimensionMismatch())
+  check(X.handle, ccall((:cdh_glm_set_weights, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}),
+                        X.handle, weights === nothing ? C_NULL : pointer(weights)))
+  X
+end
+
+"the observation weights of a design that holds labels or counts; ones when none are set"
+function glm_get_weights(X::HipMatrix{Float64})
+  out = Vector{Float64}(undef, X.n)
+  check(X.handle, ccall((:cdh_glm_get_weights, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), X.handle, out))
+  out
+end
+
 # ---- l1-penalised Cox regression, Breslow ties, by the same loop (no reference counterpart) --------------------
 "the times, the statuses (1: event, 0: censored) and, optionally, the offsets of a Float64 design under the weighted loss; the working response is zeroed"
 function glm_set_survival!(X::HipMatrix{Float64}, time::Vector{Float64}, status::Vector{Float64}, offset::Union{Nothing,Vector{Float64}}=nothing)

@@ -19,7 +19,15 @@ the library had before it.
      ROUNDS rounds after a warm-up of each; reported: wall times, their minima and spread, the IRLS rounds of each (they must
      be equal), the n-sized host transfers per round of each, and the largest difference of the coefficients.
 
-Writes the report to OUT (default profiles/poisson_shape.txt).  Environment: N, REPS, ROUNDS, N2, P2, M2, OUT."""
+WEIGHTS=1: the same with observation weights (log-uniform over [0.25, 4], normalised to sum to n; cdh_glm_set_weights).
+ (a) gains the Poisson step on a handle of the same shape WITH weights: the same kernel with one more 16-byte stream, 65
+     bytes a row against 57.  THE EXPECTATION, stated before the run: both stream, so the weighted step takes the
+     unweighted one's time x 65 / 57 (= 1.140); met when the measured ratio is within the spread of the rounds' minima (as a
+     share of the minimum) above that, missed otherwise.
+ (b) becomes PoissonLassoPath on the loss with weights against the composed loop with v w for w.
+The report is then APPENDED to OUT (default profiles/glm_weights_timing.txt, which tools/logistic_shape.py shares).
+
+Writes the report to OUT (default profiles/poisson_shape.txt).  Environment: N, REPS, ROUNDS, N2, P2, M2, OUT, WEIGHTS."""
 import ctypes as C
 import json
 import os
@@ -36,8 +44,11 @@ import coordinatedescent_jl_amd as cd  # noqa: E402
 env = lambda k, d: int(os.environ.get(k, d))  # noqa: E731
 n, reps, rounds = env("N", 10_000_000), env("REPS", 5), env("ROUNDS", 3)
 n2, p2, m2 = env("N2", 2_000_000), env("P2", 1000), env("M2", 30)
-out_path = os.environ.get("OUT", os.path.join(ROOT, "profiles", "poisson_shape.txt"))
+weighted = env("WEIGHTS", 0) == 1
+out_path = os.environ.get("OUT", os.path.join(ROOT, "profiles", "glm_weights_timing.txt" if weighted else "poisson_shape.txt"))
 lines = [f"device: {torch.cuda.get_device_name(0)}, HIP {torch.version.hip}; float64"]
+if weighted:
+    lines.insert(0, "== tools/poisson_shape.py WEIGHTS=1 ==")
 print(lines[0], flush=True)
 vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
 PD = C.POINTER(C.c_double)
@@ -62,6 +73,15 @@ def poisson(n_, p_, seed, s):
     return f, counts, o
 
 
+def set_weights(f, seed):
+    """Log-uniform weights over [0.25, 4], normalised to sum to n, on a loss made by generate (what weights= does)."""
+    v = np.exp(np.random.default_rng(100 + seed).uniform(np.log(0.25), np.log(4.0), f.n))
+    v *= f.n / v.sum()
+    cd.check(f._L.cdh_glm_set_weights(f._h, vp(v)), f._h)
+    f._has_weights = True
+    return v
+
+
 # ---- (a) the step against the copy of its bytes and against the binomial step --------------------------------------------
 f, _, _ = poisson(n, 1, 7, 1)
 g, _ = cd.CDLogisticLoss.generate(n, 1, seed=7, s=1, noise=1.0)
@@ -70,7 +90,11 @@ cd.check(g._L.cdh_glm_set_labels(g._h, 0, vp(labels)), g._h)
 ids = (np.arange(n) % K).astype(np.int32)
 x = cd.SparseIterate(1)
 x[1] = 2.0
-for h in (f, g):
+fw = None
+if weighted:
+    fw, _, _ = poisson(n, 1, 7, 1)
+    set_weights(fw, 7)
+for h in (f, g) + ((fw,) if weighted else ()):
     h.set_folds(ids, K)
     cd.initialize_(h, x)                                                       # eta_lin = 2 X_1: spread over about +-8
 out6, out5 = np.zeros(6), np.zeros(5)
@@ -92,6 +116,13 @@ def copy57():
 pois1(), pois0(), binom1(), copy57()                                           # warm-up of all four
 names = ("cdh_glm_poisson_irls_apply1", "cdh_glm_poisson_irls_apply0", "cdh_glm_irls_fold_apply1", "copy_57_bytes_a_row")
 fns = (pois1, pois0, binom1, copy57)
+if weighted:
+    out6w = np.zeros(6)
+    wpois1 = lambda: cd.check(fw._L.cdh_glm_poisson_irls(fw._h, 0, 1, WMIN, ETA_MAX, out6w.ctypes.data_as(PD)), fw._h)  # noqa: E731
+    wpois0 = lambda: cd.check(fw._L.cdh_glm_poisson_irls(fw._h, 0, 0, WMIN, ETA_MAX, out6w.ctypes.data_as(PD)), fw._h)  # noqa: E731
+    wpois1(), wpois0()
+    names += ("weighted_poisson_irls_apply1", "weighted_poisson_irls_apply0")
+    fns += (wpois1, wpois0)
 per_round = {k: [] for k in names}
 for _ in range(rounds):
     ts = [[] for _ in fns]
@@ -104,6 +135,9 @@ f.close()
 g.close()
 del src, dst
 moved = {names[0]: 57 * n, names[1]: 33 * n, names[2]: 49 * n, names[3]: copied}
+if weighted:
+    fw.close()
+    moved.update({names[4]: 65 * n, names[5]: 41 * n})
 res = {"n": n, "bytes_a_row": {"poisson_apply1": 57, "poisson_apply0": 33, "binomial_fold_apply1": 49, "copy": copied / n},
        "clamped_rows": int(out6[2]), "capped_rows": int(out6[3])}
 for k, v in per_round.items():
@@ -115,11 +149,18 @@ res["poisson_over_copy"] = min(per_round[names[0]]) / min(per_round[names[3]])
 res["poisson_over_binomial_fold"] = ratio
 res["expected_poisson_over_binomial_fold"] = 57 / 49
 res["expectation"] = "met" if ratio <= 57 / 49 * (1.0 + slack) else "missed"
+if weighted:
+    wratio = min(per_round[names[4]]) / min(per_round[names[0]])
+    wslack = max((max(v) - min(v)) / min(v) for v in (per_round[names[0]], per_round[names[4]]))
+    res["weighted_over_unweighted"] = wratio
+    res["expected_weighted_over_unweighted"] = 65 / 57
+    res["weighted_expectation"] = "met" if wratio <= 65 / 57 * (1.0 + wslack) else "missed"
 lines.append(json.dumps(res))
 print(lines[-1], flush=True)
 
 # ---- (b) the front end against the composed loop ------------------------------------------------------------------------
 f, counts, o = poisson(n2, p2, 11, 10)
+v_obs = set_weights(f, 11) if weighted else 1.0
 lmax = cd.poissonLambdaMax(f)
 lam = lmax * np.geomspace(0.9, 0.05, m2)
 opts = cd.CDOptions(maxIter=2000, optTol=1e-7, randomize=False)
@@ -152,6 +193,7 @@ def composed_route():
                 mu = np.exp(np.minimum(eta_lin + o, irls.etaMax))
                 w = np.maximum(mu, irls.wmin)
                 z = eta_lin + (counts - mu) / w
+                w = v_obs * w if weighted else w
                 cd.check(L.cdh_set_y(h, vp(z)), h)
                 cd.check(L.cdh_set_obs_weights(h, vp(w)), h)
                 f._synced = None
@@ -177,7 +219,7 @@ for _ in range(rounds):
     t_com.append(t)
 f.close()
 diff = max(float(np.max(np.abs(b.dense() - c))) for b, c in zip(path.betapath, betas))
-res = {"n": n2, "p": p2, "lambdas": m2, "PoissonLassoPath_s": t_dev, "composed_s": t_com,
+res = {"n": n2, "p": p2, "lambdas": m2, "weights": weighted, "PoissonLassoPath_s": t_dev, "composed_s": t_com,
        "min_s": {"PoissonLassoPath": min(t_dev), "composed": min(t_com)},
        "spread_s": {"PoissonLassoPath": max(t_dev) - min(t_dev), "composed": max(t_com) - min(t_com)},
        "composed_over_PoissonLassoPath": min(t_com) / min(t_dev),
@@ -189,6 +231,6 @@ lines.append(json.dumps(res))
 print(lines[-1], flush=True)
 
 os.makedirs(os.path.dirname(out_path), exist_ok=True)
-with open(out_path, "w") as fh:
+with open(out_path, "a" if weighted else "w") as fh:
     fh.write("\n".join(lines) + "\n")
 print(f"wrote {out_path}")
