@@ -732,6 +732,21 @@ def _strata_weights(strata, weights, n):
     return strata, weights
 
 
+_COX_TIES = ("breslow", "efron")             # cdh_glm_set_cox_ties' 0 and 1
+
+
+def _cox_ties(ties, X=None, y=None):
+    """What the Cox front ends refuse of their ties keyword before the device: an unknown rule, and Efron together with
+    start-stop times (a matrix with a three-column y, or a loss made with them).  -> ties."""
+    if not isinstance(ties, str) or ties not in _COX_TIES:
+        raise ArgumentError('ties must be "breslow" or "efron", not %r' % (ties,))
+    interval = getattr(X, "_interval", False) if isinstance(X, CoordinateDifferentiableFunction) else \
+        (y is not None and np.ndim(y) == 2 and np.shape(y)[1] == 3)
+    if ties == "efron" and interval:
+        raise ArgumentError("Efron ties are not offered with start-stop times (y n x 3)")
+    return ties
+
+
 class CDCoxLoss(_GLMLoss):
     """CDCoxLoss(y, X, offset=None; strata=None, weights=None): -(1/n) Σ δ_i (η_i - log S_i), η = Xβ + o, S_i = Σ_{t_j >= t_i} e^η_j -- the negative log
     partial likelihood of the Cox model with Breslow ties (glmnet's family = "cox"); y is n x 2, [time, status], status 1 an
@@ -739,7 +754,14 @@ class CDCoxLoss(_GLMLoss):
     round is the weighted lasso of CDWeightedLSLoss (src/cd_differentiable_function.jl:118-194) on the working response and
     weights the handle's y and w hold from one irls_step to the next.  The step is not elementwise: the risk-set sums are
     scans in time order, run on the device through the order cdh_glm_set_survival keeps; the rows stay in the caller's order.
-    There is no intercept (it cancels), and no Efron ties.
+    There is no intercept (it cancels).
+
+    Ties: Breslow unless set_ties("efron") is called -- Efron's rule, survival::coxph's default, for right-censored data (not
+    yet with start-stop times).  Among the training rows of a tie group with d events, D = Σ v e and m = (Σ v δ) / d over them,
+    the l-th event's denominator is S - (l/d) D: F = -(1/n) Σ_g [Σ_events v δ η - m Σ_l log(S - (l/d) D)], and A_i, B_i sum
+    m c / den and m c² / den² with c = 1 - l/d inside an event's own group and 1 elsewhere.  The weights follow coxph's
+    convention (every event of a group enters with the group's mean event weight).  The group sums are scans that restart at
+    the groups' bounds, on the device: constant work per row whatever the groups' sizes.
 
     Start-stop times (glmnet's Surv(start, stop, status)): y is n x 3, [start, stop, status], and row i is at risk at t iff
     start_i < t <= stop_i -- time-varying covariates (a subject is several rows), delayed entry, recurrent events.  A row
@@ -777,6 +799,24 @@ class CDCoxLoss(_GLMLoss):
         else:
             check(self._L.cdh_glm_set_survival_strata(self._h, _vp(self._time), _vp(status), _vp(off), _vp(self._strata),
                                                       _vp(self._weights)), self._h)
+
+    def set_ties(self, ties):
+        """The tie rule of the step's sums (cdh_glm_set_cox_ties): "breslow" (the default) or "efron", survival::coxph's default.
+        Efron is refused on a loss with start-stop times.  The handle's y, w and r are not touched: the next irls_step runs
+        under the new rule."""
+        _cox_ties(ties)
+        if ties == "efron" and getattr(self, "_interval", False):
+            raise ArgumentError("Efron ties are not offered with start-stop times (y n x 3)")
+        check(self._L.cdh_glm_set_cox_ties(self._h, _COX_TIES.index(ties)), self._h)
+
+    @property
+    def ties(self):
+        """The tie rule the handle holds: "breslow" or "efron"."""
+        if getattr(self, "_h", None) is None:
+            return "breslow"
+        out = C.c_int32()
+        check(self._L.cdh_glm_get_cox_ties(self._h, C.byref(out)), self._h)
+        return _COX_TIES[out.value]
 
     @property
     def strata(self):
@@ -2066,8 +2106,11 @@ def _glm_solve(fam, x, f, g, options, irls, fold):
 
 def _glm_loss(fam, X, y, fit_intercept, offset, extra=None):
     """-> (f, owned): the family's loss over X (with a trailing column of ones when an intercept is fitted).  extra: further
-    keywords of the loss (the Cox family's strata and weights), None where not given."""
+    keywords of the loss (the Cox family's strata and weights), None where not given; "ties" among them is the Cox family's
+    tie rule, which is not a keyword of the loss: it is set on the loss right after it is built, and on a loss that was passed in
+    it must be the loss's own."""
     extra = {k: v for k, v in (extra or {}).items() if v is not None}
+    ties = extra.pop("ties", None)
     if isinstance(X, fam.loss):
         if fit_intercept:
             raise ArgumentError("fit_intercept appends a column of ones: pass the matrix, not a loss")
@@ -2075,13 +2118,23 @@ def _glm_loss(fam, X, y, fit_intercept, offset, extra=None):
             raise ArgumentError("the offset belongs to the loss: pass the matrix, or a loss made with it")
         for name in extra:
             raise ArgumentError("%s belongs to the loss: pass the matrix, or a loss made with it" % name)
+        if ties is not None and ties != X.ties:
+            raise ArgumentError('ties="%s" disagrees with the loss, whose rule is "%s": the tie rule belongs to the loss '
+                                "(set_ties)" % (ties, X.ties))
         return X, False
     if isinstance(X, CoordinateDifferentiableFunction):
         raise TypeError("MethodError: takes a matrix or a %s" % fam.loss.__name__)
     X = np.asarray(X)
     if fit_intercept:
         X = np.asfortranarray(np.hstack([X, np.ones((X.shape[0], 1), dtype=X.dtype)]))
-    return (fam.loss(y, X, **extra) if offset is None else fam.loss(y, X, offset, **extra)), True
+    f = fam.loss(y, X, **extra) if offset is None else fam.loss(y, X, offset, **extra)
+    if ties is not None:
+        try:
+            f.set_ties(ties)
+        except Exception:
+            f.close()
+            raise
+    return f, True
 
 
 def _glm_host_start(fam, y, offset, weights=None):
@@ -2450,15 +2503,18 @@ def coxLasso_(x, f, g, options=None, irls=None, fold=None):
     return _glm_solve(_COX, x, f, g, options, irls, fold)
 
 
-def coxLasso(X, y, lam, omega=None, options=None, irls=None, offset=None, strata=None, weights=None):
+def coxLasso(X, y, lam, omega=None, options=None, irls=None, offset=None, strata=None, weights=None, ties="breslow"):
     """ℓ1-penalised Cox regression with Breslow ties (glmnet's family = "cox"): the minimiser of
     -(1/n) Σ δ_i (η_i - log S_i) + λ Σ ω_j |β_j|, η = Xβ + o, y = [time, status] (n x 2).  There is no intercept: it cancels
     in the partial likelihood.  y = [start, stop, status] (n x 3): start-stop times, row i at risk over (start_i, stop_i]
     (CDCoxLoss).  strata and weights: CDCoxLoss's (glmnet's stratifySurv and weights =; the weights are
-    normalised to sum to n).  X may also be an existing CDCoxLoss (y, offset, strata and weights are then its own)."""
+    normalised to sum to n).  ties: "breslow" or "efron" (CDCoxLoss.set_ties; survival::coxph's default is "efron"), refused
+    with start-stop times.  X may also be an existing CDCoxLoss (y, offset, strata and weights are then its own, and ties must
+    name the loss's own rule)."""
+    _cox_ties(ties, X, y)
     if not isinstance(X, CoordinateDifferentiableFunction):
         _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
-    return _glm_lasso(_COX, X, y, lam, omega, options, irls, False, offset, dict(strata=strata, weights=weights))
+    return _glm_lasso(_COX, X, y, lam, omega, options, irls, False, offset, dict(strata=strata, weights=weights, ties=ties))
 
 
 def coxLambdaMax(f, omega=None):
@@ -2481,19 +2537,20 @@ def coxLambdaMax(f, omega=None):
 
 
 def CoxLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, offset=None, strata=None,
-                 weights=None):
+                 weights=None, ties="breslow"):
     """LassoPath's loop (src/lasso.jl:229-260) with coxLasso_ per λ: one handle, one x warm-started along λ,
     ω = _stdX!(X) (cdh_col_rms) when standardising.  βpath[i] has length p.  y may be n x 3, [start, stop, status]
     (CDCoxLoss).  strata and weights: CDCoxLoss's; the penalty
-    scales ω stay the root mean square over the rows present, not weighted by the observation weights."""
+    scales ω stay the root mean square over the rows present, not weighted by the observation weights.  ties: coxLasso's."""
+    _cox_ties(ties, X, y)
     if not isinstance(X, CoordinateDifferentiableFunction):
         _survival(y, np.shape(X)[0] if np.ndim(X) == 2 else None)
     return _glm_path(_COX, X, y, lambdapath, options, irls, max_hat_s, standardizeX, False, offset,
-                     dict(strata=strata, weights=weights))
+                     dict(strata=strata, weights=weights, ties=ties))
 
 
 def cvCoxLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, standardizeX=True, seed=0, measure="deviance",
-                   offset=None, full_path=True, keep_fold_paths=False, strata=None, weights=None):
+                   offset=None, full_path=True, keep_fold_paths=False, strata=None, weights=None, ties="breslow"):
     """K-fold cross-validation of CoxLassoPath(X, y, λpath, options, irls; standardizeX, offset) on the device (glmnet's
     cv.glmnet(family = "cox", grouped = TRUE)); no reference counterpart.  X may also be an existing CDCoxLoss (y and offset
     are then its own); the design is uploaded once.
@@ -2517,8 +2574,12 @@ def cvCoxLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, 
     folds: 0-based ids, one per row; otherwise np.random.default_rng(seed).permutation(n) % K.  There is no max_hat_s.  The
     folds are dropped when the call returns or raises.  `path` is CoxLassoPath on all rows (None with full_path=False):
     from a matrix it runs before the folds, on the fresh handle, and is that call's result bit for bit; on a loss that was
-    passed in it runs after them.  `fold_paths`: the K fold paths as CoxLassoPathResult (None unless keep_fold_paths)."""
-    extra = dict(strata=strata, weights=weights)
+    passed in it runs after them.  `fold_paths`: the K fold paths as CoxLassoPathResult (None unless keep_fold_paths).
+
+    ties: coxLasso's.  With "efron" a fold's tie groups count their TRAINING rows only (d, D and m), the held-out deviance is
+    2 (ℓ_all - ℓ_train) of Efron's likelihood, and the λ scaling of the folds is the same: all three follow from the step."""
+    _cox_ties(ties, X, y)
+    extra = dict(strata=strata, weights=weights, ties=ties)
     if isinstance(X, CDCoxLoss):
         _glm_loss(_COX, X, y, False, offset, extra)               # (its refusals of what belongs to the loss)
         status = X.status

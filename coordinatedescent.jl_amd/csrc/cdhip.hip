@@ -302,13 +302,17 @@ struct CvState {
 // own -- y holds the working response of the IRLS round, not the labels.  glm_plan.hpp: the grid and the rows of a workgroup.
 #include "glm_plan.hpp"
 #include "cox_plan.hpp"   // the Cox step's tiles, runs and scratch layout; the time order and its tie groups: host-only arithmetic
+#include "cox_efron.hpp"  // the three launches of the Efron chain that the second translation unit (cox_efron.hip) defines
 enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
 // The Cox group (cox_kernels.hpp; cox_layout): d -- the scans' scratch, the runs' sums and the times; i -- order and the tie
 // groups' bounds.  Allocated together by the first cdh_glm_set_survival, or not at all.  sd, si -- the second pair, of a handle
 // with strata or observation weights: allocated together by the first cdh_glm_set_survival_strata that brings either, and in
 // use while `strata` is set (every other setter of observations clears it).  vd, vi -- the third pair, of a handle with start
 // times: allocated together by the first cdh_glm_set_survival_interval that brings them, and in use while `interval` is set
-// (then `strata` is set too; every setter without start times clears it).
+// (then `strata` is set too; every setter without start times clears it).  ed, ei -- the Efron pair (cox_efron_layout), of a
+// handle set to Efron ties: allocated together by the first cdh_glm_set_cox_ties that asks for them, and in use while `efron`
+// is set (then `strata` is set too: the Efron chain is segmented and weighted; a setter with start times, the label and the
+// count setters clear it).
 struct CoxState {
     DevBuf<double> d;
     DevBuf<int32_t> i;
@@ -316,8 +320,11 @@ struct CoxState {
     DevBuf<int32_t> si;
     DevBuf<double> vd;
     DevBuf<int32_t> vi;
+    DevBuf<double> ed;
+    DevBuf<int32_t> ei;
     bool strata = false;
     bool interval = false;
+    bool efron = false;
 };
 struct GlmState {
     DevBuf<double> labels;     // the labels, or the counts of the Poisson family
@@ -1215,6 +1222,14 @@ int32_t cdh_glm_cox_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, do
     return glm_step<GlmCox>(h, k, apply, GlmParams{wmin, eta_max}, out5);
 }); }
 
+int32_t cdh_glm_set_cox_ties(cdh_handle h, int32_t ties) { return guarded(h, [&]() -> int32_t {
+    return cox_set_ties(h, ties);
+}); }
+
+int32_t cdh_glm_get_cox_ties(cdh_handle h, int32_t* ties) { return guarded(h, [&]() -> int32_t {
+    return cox_get_ties(h, ties);
+}); }
+
 // ---- cross-validation of a lasso path (cv_path.hpp; the solves are lasso.jl:229-260 on 0/1 weights, utils.jl:140-151) ------
 int32_t cdh_set_folds(cdh_handle h, const int32_t* fold_of_row, int32_t K, int64_t* out_count) { return guarded(h, [&]() -> int32_t {
     return cv_set_folds(h, fold_of_row, K, out_count);
@@ -1799,4 +1814,5 @@ int32_t cdh_quad_coordinate_descent(cdh_quad q, const cdh_options* opt, cdh_stat
 // the start-stop chain of the Cox step, LAST: its kernels are emitted behind every other kernel (the reason is in the file)
 namespace {
 #include "cox_interval.hpp"
+#include "cox_efron_host.hpp"   // the Efron chain's host body: no kernel of its own (they are cox_efron.hip's, the second unit)
 }  // namespace

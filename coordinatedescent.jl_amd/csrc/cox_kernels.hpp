@@ -46,6 +46,12 @@
 //   k_cox_exp<true>  k_cox_gather  k_cox_offsets x2  k_cox_scan (T)  k_cox_scan (T2)  k_cox_hazard_iv  k_cox_offsets
 //   k_cox_scan (A, B)  k_cox_apply_iv  k_gram_reduce
 // The three kernels of its own and its launcher live in cox_interval.hpp, which cdhip.hip includes LAST (the reason is there).
+//
+// Efron ties (cdh_glm_set_cox_ties; survival::coxph's default, right-censored data only): a fourth chain, always segmented and
+// weighted like the interval chain, in which the sums over a tie group -- an event's rank, the group's events, their ev and dv
+// -- are scans that restart at the tie groups' bounds: k_cox_scan<., ., true> with `first` or `last` as its heads.  Its three
+// kernels are compiled in a translation unit of their own, cox_efron.hip (the mathematics and the chain are described there),
+// so that this unit's code object stays what it was; its launcher, cox_efron_host.hpp, is included after cox_interval.hpp.
 
 // One position's share of the step, every quantity in double and every operation rounded on its own (tests/_cox_numpy.py
 // writes the same lines).  eta_lin = yw - r is X beta: the offset is NOT part of the stored working response.
@@ -446,7 +452,10 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
     const double* wt = (const double*)host_weights;
     const double* sta = (const double*)host_start;
     const bool iv = sta != nullptr;
-    const bool sw = host_strata != nullptr || wt != nullptr || iv;
+    // the tie rule stays (cdh_glm_set_cox_ties) unless start times come: an Efron handle stores absent strata and weights as
+    // their defaults, like an interval handle; its Efron pair is already there
+    const bool ef = h->glm.set && h->glm.family == GlmData::Cox && h->glm.cox.efron && !iv;
+    const bool sw = host_strata != nullptr || wt != nullptr || iv || ef;
     char buf[160];
     if (!cox_check(h->n, tm, st, off, buf, sizeof buf, wt)) return fail(h, CDH_BAD_ARG, buf);
     if (iv && !cox_check_interval(h->n, sta, tm, buf, sizeof buf)) return fail(h, CDH_BAD_ARG, buf);
@@ -531,6 +540,7 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
     h->glm.has_offset = off != nullptr;
     h->glm.cox.strata = sw;
     h->glm.cox.interval = iv;
+    h->glm.cox.efron = ef;
     h->glm.weighted = false;             // (the weights of cdh_glm_set_weights go with the labels or counts they came with)
     h->glm.set = true;
     return CDH_OK;
@@ -584,6 +594,66 @@ int32_t cox_get_survival_strata(cdh_handle h, int32_t* host_strata, void* host_w
     return CDH_OK;
 }
 
+// cdh_glm_set_cox_ties: 0 Breslow, 1 Efron (cox_efron.hip).  Efron's chain is segmented and weighted, so a handle without strata
+// and weights gets the second pair here, filled with the defaults cox_set_survival would store (one stratum over the rows, one
+// over the pads, the ids zero, the weights one: cox_order_strata without ids IS cox_order, so order, first and last stay), and
+// the Efron pair; all of it allocated before the handle changes.  Back at Breslow such a handle runs the segmented chain over
+// its defaults, whose bits are the plain chain's.  The rows' y, w and r are not touched.
+int32_t cox_set_ties(cdh_handle h, int32_t ties) {
+    if (!h->glm.set || h->glm.family != GlmData::Cox)
+        return fail(h, CDH_BAD_ARG, "no survival data are set: call cdh_glm_set_survival first");
+    if (ties != 0 && ties != 1) return fail(h, CDH_BAD_ARG, "ties must be 0 (Breslow) or 1 (Efron)");
+    if (ties == 1 && h->glm.cox.interval)
+        return fail(h, CDH_BAD_ARG, "Efron ties are not offered with start-stop times: the handle holds start times");
+    if (ties == 0 || h->glm.cox.efron) {
+        h->glm.cox.efron = ties == 1;
+        return CDH_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const CoxLayout lay = cox_layout(h->ld);
+    const CoxEfronLayout el = cox_efron_layout(h->ld);
+    const bool fill = !h->glm.cox.strata;
+    DevBuf<double> fresh_sd, fresh_ed;
+    DevBuf<int32_t> fresh_si, fresh_ei;
+    if (fill && !h->glm.cox.sd) {
+        HIPCHK(h, fresh_sd.alloc((size_t)lay.strata_doubles * sizeof(double)));
+        HIPCHK(h, fresh_si.alloc((size_t)lay.strata_ints * sizeof(int32_t)));
+    }
+    if (!h->glm.cox.ed) {
+        HIPCHK(h, fresh_ed.alloc((size_t)el.doubles * sizeof(double)));
+        HIPCHK(h, fresh_ei.alloc((size_t)el.ints * sizeof(int32_t)));
+        HIPCHK(h, hipMemsetAsync(fresh_ed, 0, (size_t)el.doubles * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(fresh_ei, 0, (size_t)el.ints * sizeof(int32_t), h->stream));
+    }
+    if (fill) {
+        double* sd = fresh_sd ? (double*)fresh_sd : (double*)h->glm.cox.sd;
+        int32_t* si = fresh_si ? (int32_t*)fresh_si : (int32_t*)h->glm.cox.si;
+        std::vector<int32_t> sfirst, slast;
+        cox_one_stratum(h->n, h->ld, sfirst, slast);
+        std::vector<double> ones((size_t)h->ld, 0.0);
+        std::fill_n(ones.begin(), (size_t)h->n, 1.0);
+        const size_t idxbytes = (size_t)h->ld * sizeof(int32_t);
+        HIPCHK(h, hipMemsetAsync(si, 0, (size_t)lay.strata_ints * sizeof(int32_t), h->stream));
+        HIPCHK(h, hipMemcpyAsync(si + lay.sfirst, sfirst.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(si + lay.slast, slast.data(), idxbytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(sd + lay.weight, ones.data(), (size_t)h->ld * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));      // (the host vectors are pageable: the copies are done here)
+    }
+    if (fresh_sd) { h->glm.cox.sd = std::move(fresh_sd); h->glm.cox.si = std::move(fresh_si); }
+    if (fresh_ed) { h->glm.cox.ed = std::move(fresh_ed); h->glm.cox.ei = std::move(fresh_ei); }
+    h->glm.cox.strata = true;
+    h->glm.cox.efron = true;
+    return CDH_OK;
+}
+
+int32_t cox_get_ties(cdh_handle h, int32_t* ties) {
+    NEED_P(h, ties);
+    if (!h->glm.set || h->glm.family != GlmData::Cox)
+        return fail(h, CDH_BAD_ARG, "no survival data are set: call cdh_glm_set_survival first");
+    *ties = h->glm.cox.efron ? 1 : 0;
+    return CDH_OK;
+}
+
 // The Cox family as glm_step sees it: what its export refuses, in cdh_glm_poisson_irls' order and words.
 struct GlmCox {
     static constexpr int kVals = kCoxVals;
@@ -615,6 +685,8 @@ int32_t glm_check<GlmCox>(cdh_handle h, int32_t k, int32_t apply, const GlmParam
 
 // the chain of a handle with start times, up to the partials (cox_interval.hpp, at the end of cdhip.hip)
 int32_t cox_launch_interval(cdh_handle h, int32_t k, bool apply, const GlmParams& pm);
+// the chain of a handle set to Efron ties, up to the partials (cox_efron_host.hpp, at the end of cdhip.hip)
+int32_t cox_launch_efron(cdh_handle h, int32_t k, bool apply, const GlmParams& pm);
 
 // the chain and its record: out holds the kCoxVals doubles, added over the workgroups in block order; k = -1: no row is held
 // out and the fold ids are not read
@@ -662,7 +734,8 @@ int32_t glm_launch<GlmCox>(cdh_handle h, int32_t k, bool apply, const GlmParams&
         HIPCHK(h, hipGetLastError());
         return CDH_OK;
     };
-    if (h->glm.cox.interval) CHK(cox_launch_interval(h, k, apply, pm));      // cox_interval.hpp
+    if (h->glm.cox.efron) CHK(cox_launch_efron(h, k, apply, pm));            // cox_efron_host.hpp
+    else if (h->glm.cox.interval) CHK(cox_launch_interval(h, k, apply, pm));      // cox_interval.hpp
     else if (h->glm.cox.strata) CHK(chain(std::true_type{})); else CHK(chain(std::false_type{}));
     hipLaunchKernelGGL(k_gram_reduce, dim3((kCoxVals + kReduceVals - 1) / kReduceVals), dim3(64 * kReduceWaves), 0, h->stream,
                        (const double*)h->d_partials, (int)pl.records, (int)kCoxVals, (double*)h->d_red);

@@ -85,6 +85,26 @@ constexpr CoxLayout cox_layout(int64_t ld) {
                      0, ld, 2 * ld, 3 * ld, 3 * ld + kCoxMaxGrid, 0, ld, 2 * ld, 2 * ld + kCoxMaxGrid};
 }
 
+// A handle set to Efron ties (cdh_glm_set_cox_ties) holds the second pair AND a pair of its own, which no other handle
+// allocates.  Doubles, ld each: cnt and Dv (the event indicator and ev at the events, then their prefix scans inside the tie
+// group: an event's rank l + 1, and d_g and D_g at the group's last position), Sdv (dv, then its SUFFIX scan inside the tie
+// group: sum dv of the group at its first position), hc and hc2 (the event's own-group terms m c / den and m c^2 / den^2, then
+// their prefix scans inside the tie group), lg and mm (log den and m at an event that counts, else 0: the nll's terms); then
+// the runs' sums of the five scans, kCoxMaxGrid each, in the order cnt, Dv, Sdv, hc, hc2.  cnt and Dv, and hc and hc2, are ld
+// apart and their sums kCoxMaxGrid apart: each pair is ONE launch of k_cox_scan<2, false, true>.  int32: the head-seen flags
+// of the runs for the scans whose heads are the tie groups' first positions (heads_p) and last positions (heads_s),
+// kCoxMaxGrid each.
+struct CoxEfronLayout {
+    int64_t cnt, Dv, Sdv, hc, hc2, lg, mm, sums;   // offsets in doubles; sums + i kCoxMaxGrid: cnt, Dv, Sdv, hc, hc2
+    int64_t doubles;
+    int64_t heads_p, heads_s;                      // offsets in int32s
+    int64_t ints;
+};
+constexpr CoxEfronLayout cox_efron_layout(int64_t ld) {
+    return CoxEfronLayout{0, ld, 2 * ld, 3 * ld, 4 * ld, 5 * ld, 6 * ld, 7 * ld, 7 * ld + 5 * kCoxMaxGrid,
+                          0, kCoxMaxGrid, 2 * kCoxMaxGrid};
+}
+
 // ---- the time order and its tie groups ---------------------------------------------------------------------------------------
 // What cdh_glm_set_survival refuses of its data, the row named in msg (at least 128 chars): a time or an offset that is not
 // finite, a status other than 0 or 1, a weight (cdh_glm_set_survival_strata; NULL: none) that is not finite or not > 0, no
@@ -170,6 +190,15 @@ inline void cox_order_strata(int64_t n, int64_t ld, const double* time, const in
         first[s] = (int32_t)s; last[s] = (int32_t)s;
         sfirst[s] = (int32_t)n; slast[s] = (int32_t)(ld - 1);
     }
+}
+
+// The strata's bounds of a handle WITHOUT strata, as cox_order_strata(.., strata = nullptr, ..) gives them -- the rows one
+// stratum, the pads another -- without sorting again: what cdh_glm_set_cox_ties stores when a plain handle turns to Efron, whose
+// chain is segmented (order, first and last are then cox_order's and stay).
+inline void cox_one_stratum(int64_t n, int64_t ld, std::vector<int32_t>& sfirst, std::vector<int32_t>& slast) {
+    sfirst.assign((size_t)ld, 0);
+    slast.assign((size_t)ld, (int32_t)(n - 1));
+    for (int64_t s = n; s < ld; ++s) { sfirst[(size_t)s] = (int32_t)n; slast[(size_t)s] = (int32_t)(ld - 1); }
 }
 
 // ---- start-stop times: the second order and the two lookups --------------------------------------------------------------------

@@ -324,7 +324,8 @@ int32_t glm_set_observations(cdh_handle h, GlmData family, const void* host_obs,
     h->glm.family = family;
     h->glm.has_offset = off != nullptr;  // (a Poisson handle turned binomial drops its offset)
     h->glm.cox.strata = false;           // (and a Cox handle its strata and observation weights,
-    h->glm.cox.interval = false;         //  and its start times)
+    h->glm.cox.interval = false;         //  its start times
+    h->glm.cox.efron = false;            //  and its tie rule)
     h->glm.weighted = false;             // (and every handle the weights of cdh_glm_set_weights)
     h->glm.set = true;
     return CDH_OK;

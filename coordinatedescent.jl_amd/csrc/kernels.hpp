@@ -21,9 +21,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_sum.hpp"   // kBlock, wave_sum, block_sum: shared with the second translation unit
+
 namespace cdk {
 
-constexpr int kBlock = 256;   // 4 waves
 constexpr int kUnroll = 4;    // independent 16-B loads per stream per thread
 constexpr int kNSum = 4;      // a, b, q (+pad) per partial record
 
@@ -97,36 +98,10 @@ __device__ __forceinline__ void visit_vec(const fvec4& xc, fvec4& r, const fvec4
     r = fvec4{(float)r0, (float)r1, (float)r2, (float)r3};
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
     return v;
-}
-
-// Sum NV per-thread values over a kBlock-thread block; result valid in thread 0.
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double* lds /* [NV * 4] */) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        v[i] = wave_sum(v[i]);
-        if (lane == 0) lds[i * (kBlock / 64) + wid] = v[i];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int w = 0; w < kBlock / 64; ++w) s += lds[i * (kBlock / 64) + w];
-            v[i] = s;
-        }
-    }
 }
 
 // Sum NV per-thread values over the block and store them VALUE-MAJOR: out[v * G + block]

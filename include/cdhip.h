@@ -380,7 +380,8 @@ int32_t cdh_glm_get_weights(cdh_handle h, void *host_weights);
  * P(u) the sum of dv / S(t) over the event times t <= u, B_i the same with dv / S^2 -- the prefix scans read at two positions.
  * The subtractions are inherent (glmnet and survival::coxph subtract too): the error of S is relative to the two sums of its
  * stratum, about n U (T + T2), not to S, and that of A and B to P(stop) + P(start); nothing crosses a stratum's boundary.  An
- * event whose computed S is not > 0 is skipped, a w_raw driven negative is clamped at wmin.  Efron ties are not offered. */
+ * event whose computed S is not > 0 is skipped, a w_raw driven negative is clamped at wmin.  Efron ties are offered for right-censored data; not yet with
+ * start-stop times (cdh_glm_set_cox_ties). */
 /* cdh_glm_set_survival (no reference counterpart; the loss is that of cd_differentiable_function.jl:118-194 per round)
  * stands in for cdh_set_y: it stores n statuses where cdh_glm_set_labels stores labels, n offsets (when not NULL) where
  * cdh_glm_set_counts stores them, sorts the times on the host (stable, ascending) and keeps the order, the tie groups' bounds,
@@ -397,7 +398,8 @@ int32_t cdh_glm_set_survival(cdh_handle h, const void *host_time, const void *ho
 int32_t cdh_glm_get_survival(cdh_handle h, void *host_time, void *host_status);
 /* cdh_glm_set_survival_strata (no reference counterpart; see cdh_glm_set_survival, cd_differentiable_function.jl:118-194):
  * cdh_glm_set_survival with n int32 stratum ids and n weights, either of which may be NULL (one stratum; unit weights).
- * With both NULL it IS cdh_glm_set_survival, call for call and bit for bit.  Otherwise the order is a stable ascending sort
+ * With both NULL it IS cdh_glm_set_survival, call for call and bit for bit (on a handle set to Efron ties, cdh_glm_set_cox_ties,
+ * either call stores one stratum and unit weights: the Efron chain is segmented and weighted).  Otherwise the order is a stable ascending sort
  * by (stratum id, time) -- every int32 is a valid id -- and the bounds of every position's stratum, the ids and the weights
  * live in a second group of buffers, allocated all-or-nothing with the rest before the handle changes.  The weights are stored
  * as given: the library does not normalise them.  CDH_BAD_ARG, the handle unchanged: what cdh_glm_set_survival refuses; a
@@ -441,6 +443,28 @@ int32_t cdh_glm_get_survival_strata(cdh_handle h, int32_t *host_strata, void *ho
  * survival data set; apply not in {0, 1}; wmin not finite or not > 0; eta_max outside (0, 700]; k < -1; k >= 0 without
  * folds; k >= K; out5 NULL. */
 int32_t cdh_glm_cox_irls(cdh_handle h, int32_t k, int32_t apply, double wmin, double eta_max, double *out5);
+/* cdh_glm_set_cox_ties (no reference counterpart; the tie rule of the Cox steps' sums, a round's solve stays the weighted lasso
+ * of cd_differentiable_function.jl:118-194): ties = 0 Breslow (the default of every fresh set of survival data), 1 Efron, the
+ * default of survival::coxph.  Among the TRAINING rows of a tie group g (one stratum, one time) let d be the number of events,
+ * D = sum of ev and m = (sum of dv) / d over them, S the risk-set sum; for l = 0 .. d - 1, den_l = S - (l / d) D.  Then
+ * n nll = sum_g [m sum_l log den_l - sum over the events of g of dv eta], A_i = sum over the groups at or before i's of
+ * m sum_l c / den_l and B_i the same with c^2 / den_l^2, where c = 1 - l / d if i is an event of g itself and 1 otherwise;
+ * the rest of the step is cdh_glm_cox_irls' (d = dv - ev A, w_raw = ev A - ev^2 B, the clamp, z, r, the five-slot record).
+ * The weights follow survival::coxph's convention: every event of a group enters with the group's MEAN event weight m.
+ * d = 1 is Breslow; a group whose events are all held out adds nothing; an event whose den is not > 0 is skipped.  The sums
+ * over a group are scans that restart at the group's bounds: constant work per row whatever the groups' sizes, no atomics,
+ * bit-identical run to run.  An Efron handle always runs the segmented, weighted arithmetic (absent strata and weights are
+ * stored as one stratum and unit weights) and holds a group of scratch buffers of its own, allocated all-or-nothing before
+ * the handle changes; a handle that never asks for Efron allocates nothing.  With Breslow set, cdh_glm_cox_irls is what it
+ * was, launch for launch and bit for bit.  cdh_glm_set_survival and cdh_glm_set_survival_strata keep the rule, and so does
+ * cdh_glm_set_survival_interval without start times; WITH start times it puts the handle back to Breslow (Efron with
+ * start-stop times is not offered yet); cdh_glm_set_labels and cdh_glm_set_counts drop it with the rest of the Cox state.  The
+ * handle's y, w and r are not touched.  CDH_BAD_ARG, the handle unchanged: no survival data set; ties not 0 or 1; Efron on a
+ * handle with start times (the message says so). */
+int32_t cdh_glm_set_cox_ties(cdh_handle h, int32_t ties);
+/* cdh_glm_get_cox_ties (no reference counterpart; see cdh_glm_set_cox_ties, cd_differentiable_function.jl:118-194): the
+ * handle's rule, 0 Breslow or 1 Efron.  CDH_BAD_ARG: ties NULL; no survival data set. */
+int32_t cdh_glm_get_cox_ties(cdh_handle h, int32_t *ties);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects

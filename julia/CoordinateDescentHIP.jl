@@ -594,18 +594,33 @@ end
 
 "glm_set_survival! with stratum ids (Int32; nothing: one stratum) and observation weights (stored as given; nothing: ones); with neither it is glm_set_survival!"
 function glm_set_survival_strata!(X::HipMatrix{Float64}, time::Vector{Float64}, status::Vector{Float64}, offset::Union{Nothing,Vector{Float64}}=nothing;
-                                  strata::Union{Nothing,Vector{Int32}}=nothing, weights::Union{Nothing,Vector{Float64}}=nothing)
+                                  strata::Union{Nothing,Vector{Int32}}=nothing, weights::Union{Nothing,Vector{Float64}}=nothing,
+                                  ties::Symbol=:breslow)
   length(time) == X.n && length(status) == X.n || throw(DimensionMismatch())
   for v in (offset, strata, weights)
     v === nothing || length(v) == X.n || throw(DimensionMismatch())
   end
+  ties in (:breslow, :efron) || throw(ArgumentError("ties must be :breslow or :efron"))
   set_loss!(X, CDH_WLS)
   check(X.handle, ccall((:cdh_glm_set_survival_strata, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cvoid}),
                         X.handle, time, status, offset === nothing ? C_NULL : pointer(offset),
                         strata === nothing ? C_NULL : pointer(strata), weights === nothing ? C_NULL : pointer(weights)))
   X.owner = nothing
   X.synced = false
+  glm_set_cox_ties!(X, ties)
+end
+
+"the tie rule of a Cox handle's steps: :breslow (the default) or :efron (survival::coxph's default; refused with start times). The setters of survival data keep it, except that start times put it back to :breslow."
+function glm_set_cox_ties!(X::HipMatrix{Float64}, ties::Symbol)
+  ties in (:breslow, :efron) || throw(ArgumentError("ties must be :breslow or :efron"))
+  check(X.handle, ccall((:cdh_glm_set_cox_ties, libcdhip), Int32, (Ptr{Cvoid}, Int32), X.handle, Int32(ties === :efron)))
   X
+end
+
+function glm_get_cox_ties(X::HipMatrix{Float64})
+  out = Ref{Int32}(0)
+  check(X.handle, ccall((:cdh_glm_get_cox_ties, libcdhip), Int32, (Ptr{Cvoid}, Ptr{Int32}), X.handle, out))
+  out[] == 1 ? :efron : :breslow
 end
 
 "the stratum ids (zeros without strata) and the observation weights (ones without weights) of a Cox handle, in the caller's row order"

@@ -35,8 +35,20 @@ start order 20 (pos2 4, ev in 8, T2 out 8), T2's suffix scan 20 (16 and the stra
 apply launch 32 (lo and enter 8, T2 8, the hazards' prefix sums at the entry 16).  Of these pos2 and enter are gathers in random
 order whatever the rows' order; lo is monotone inside a stratum.  The line gains the key "interval".
 
-Environment: N, REPS, ROUNDS, N2, P2, M2, PROUNDS, STEP_TIMEOUT, PATH_TIMEOUT, STRATA, INTERVAL, OUT (a file that receives the
-line too)."""
+EFRON=1 (default 0; not with INTERVAL) sets the handle to Efron ties (cdh_glm_set_cox_ties) after the survival data: the step
+measured is Efron's, and the Breslow step OF THE SAME HANDLE is timed beside it call by call ("breslow_apply1": the rule is set
+before each call, a host-side flag once the Efron scratch exists), so the line carries "efron_over_breslow" next to
+"efron_bytes_over_breslow_bytes", the ratio the byte counts predict.  Efron's chain always runs the segmented, weighted
+arithmetic; over the strata step's 252 bytes a row it moves 260 more, 512: the mark launch 48 (ev, dv, first, last in; cnt, Dv,
+Sdv out), the three tie-group scans 56 (16 each and their bounds 4 + 4), the hazard launch 68 (last, cnt twice, Dv, Sdv in; hc,
+hc2, lg, mm out), the scan of (hc, hc2) 36, the apply launch 52 (sfirst, the prefix sums in front of the group 16, hc and hc2 at
+its end 16, lg, mm -- less S, which it no longer reads, 8 -- the count takes the event rows' reads for every row).  DECIMALS
+(default 3) is the rounding of the times: 4 ties about half of the events at n = 2 000 000 with 100 strata; the line reports the
+fraction that is tied ("tied_events").  The host's step is then the Efron twin's (tests/_cox_efron_numpy.py) in its
+cumulative-sum form, the tie groups' sums as differences of cumulative sums.
+
+Environment: N, REPS, ROUNDS, N2, P2, M2, PROUNDS, STEP_TIMEOUT, PATH_TIMEOUT, STRATA, INTERVAL, EFRON, DECIMALS, OUT (a file that
+receives the line too)."""
 import ctypes as C
 import json
 import os
@@ -89,7 +101,11 @@ PD = C.POINTER(C.c_double)
 WMIN, ETA_MAX = 1e-5, 50.0
 STRATA = env("STRATA", 0)
 INTERVAL = env("INTERVAL", 0)
-BYTES = 336 if INTERVAL else (252 if STRATA else 228)
+EFRON = env("EFRON", 0)
+DECIMALS = env("DECIMALS", 3)
+BRESLOW_BYTES = 336 if INTERVAL else (252 if STRATA else 228)
+BYTES = 512 if EFRON else BRESLOW_BYTES
+assert not (EFRON and INTERVAL), "Efron ties are not offered with start-stop times"
 
 
 def timed(fn):
@@ -148,8 +164,44 @@ class HostStep:
         c = np.cumsum(a)
         return c if self.sfirst is None else c - np.r_[0.0, c[:-1]][self.sfirst]
 
+    def _efron(self, e):
+        """The Efron twin's A and B per row (tests/_cox_efron_numpy.py, scans): a sum over a tie group is the difference of a
+        cumulative sum at its bounds."""
+        first, last = self.first, self.last
+        es, ds = e[self.order], self.ds
+        event = ds != 0.0
+
+        def group_prefix(a):
+            c = np.cumsum(a)
+            return c - np.r_[0.0, c[:-1]][first]
+
+        cnt, Dv, Sdv = group_prefix(event.astype(np.float64)), group_prefix(np.where(event, es, 0.0)), group_prefix(ds)
+        d, D, S = cnt[last], Dv[last], self._suffix(es)[first]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m = Sdv[last] / d
+            frac = (cnt - 1.0) / d
+            den = S - frac * D
+            ok = event & (den > 0.0)
+            cf = 1.0 - frac
+            h = np.where(ok, m / den, 0.0)
+            h2 = np.where(ok, h / den, 0.0)
+            hc, hc2 = np.where(ok, cf * h, 0.0), np.where(ok, (cf * cf) * h2, 0.0)
+        if self.sfirst is None:
+            cA, cB, some = np.cumsum(h), np.cumsum(h2), first > 0
+        else:
+            cA, cB, some = self._prefix(h), self._prefix(h2), first > self.sfirst
+        before = np.maximum(first - 1, 0)
+        A = np.where(event, np.where(some, cA[before], 0.0) + group_prefix(hc)[last], cA[last])
+        B = np.where(event, np.where(some, cB[before], 0.0) + group_prefix(hc2)[last], cB[last])
+        return A[self.inv], B[self.inv]
+
     def __call__(self, eta_lin):
         e = self.v * np.exp(np.minimum(eta_lin + self.off, ETA_MAX))
+        if EFRON:
+            A, B = self._efron(e)
+            eA = e * A
+            w = np.maximum(eA - e * (e * B), WMIN)
+            return eta_lin + (self.dv - eA) / w, w
         Ss = self._suffix(e[self.order])[self.first]
         if self.order2 is not None:
             Ss = Ss - np.where(self.has_lo, self._suffix(e[self.order2])[self.lo], 0.0)
@@ -172,7 +224,7 @@ def survival(f, seed, presorted):
     rng = np.random.default_rng(seed)
     sig = f.y
     off = rng.uniform(-0.5, 0.5, n)
-    t = np.round(rng.exponential(1.0, n) / np.exp(0.5 * sig / np.std(sig) + off), 3)
+    t = np.round(rng.exponential(1.0, n) / np.exp(0.5 * sig / np.std(sig) + off), DECIMALS)
     status = (rng.random(n) >= 0.3).astype(np.float64)
     if INTERVAL:
         t = np.maximum(t, 0.001)
@@ -202,6 +254,20 @@ def survival(f, seed, presorted):
 
 
 def set_survival(f, t, status, off, g, v, start=None):
+    _set_survival(f, t, status, off, g, v, start)
+    if EFRON:                                                   # (the setters keep the rule; the first call allocates its scratch)
+        cd.check(f._L.cdh_glm_set_cox_ties(f._h, 1), f._h)
+
+
+def tied_events(t, status, g):
+    """The fraction of the events that share their time (and stratum) with another event."""
+    ev = status != 0
+    key = t[ev] if g is None else np.stack([g[ev].astype(np.float64), t[ev]], axis=1)
+    _, inv, cnt = np.unique(key, axis=0 if g is not None else None, return_inverse=True, return_counts=True)
+    return float((cnt[inv.ravel()] > 1).mean())
+
+
+def _set_survival(f, t, status, off, g, v, start=None):
     if start is not None:
         cd.check(f._L.cdh_glm_set_survival_interval(f._h, vp(start), vp(t), vp(status), vp(off), None if g is None else vp(g),
                                                     None if v is None else vp(v)), f._h)
@@ -229,6 +295,11 @@ def measure_step(presorted):
     def dev0():
         cd.check(L.cdh_glm_cox_irls(h, -1, 0, WMIN, ETA_MAX, out5.ctypes.data_as(PD)), h)
 
+    def breslow1():                                             # the Breslow step of the same handle, the rule restored after it
+        cd.check(L.cdh_glm_set_cox_ties(h, 0), h)
+        cd.check(L.cdh_glm_cox_irls(h, -1, 1, WMIN, ETA_MAX, out5.ctypes.data_as(PD)), h)
+        cd.check(L.cdh_glm_set_cox_ties(h, 1), h)
+
     def composed():
         nonlocal z
         cd.check(L.cdh_get_residual(h, vp(r)), h)
@@ -244,6 +315,8 @@ def measure_step(presorted):
         torch.cuda.synchronize()
 
     names, fns = ("cox_apply1", "cox_apply0", "copy_%d_bytes_a_row" % BYTES), (dev1, dev0, copy)
+    if EFRON:
+        names, fns = names + ("breslow_apply1",), fns + (breslow1,)
     for fn in fns:
         fn()
     per = {k: [] for k in names}
@@ -268,6 +341,11 @@ def measure_step(presorted):
                   "TBps_of_%dn" % BYTES: BYTES * n / min(v) / 1e12}
     res["host_composed_ms"] = [1e3 * a for a in comp]
     res["cox_over_copy"] = min(per[names[0]]) / min(per[names[2]])
+    res["efron"] = EFRON
+    res["tied_events"] = tied_events(t, status, g)
+    if EFRON:
+        res["efron_over_breslow"] = min(per["cox_apply1"]) / min(per["breslow_apply1"])
+        res["efron_bytes_over_breslow_bytes"] = BYTES / BRESLOW_BYTES
     res["host_composed_over_cox"] = min(comp) / min(per[names[0]])
     f.close()
     return res
@@ -285,7 +363,7 @@ def measure_path():
     L, h = f._L, f._h
 
     def device_route(lams):
-        return cd.CoxLassoPath(f, None, lams, opts, irls, standardizeX=False)
+        return cd.CoxLassoPath(f, None, lams, opts, irls, standardizeX=False, **({"ties": "efron"} if EFRON else {}))
 
     def composed_route(lams):
         x, betas, rounds_, r = cd.SparseIterate(p), [], [], np.zeros(n)
@@ -333,7 +411,7 @@ def measure_path():
         tt, (betas, crounds) = timed(lambda: composed_route(lam))
         t_com.append(tt)
     diff = max(float(np.max(np.abs(b.dense() - c))) for b, c in zip(path.betapath, betas))
-    res = {"n": n, "p": p, "lambdas": m, "strata": STRATA, "weighted": bool(STRATA), "interval": INTERVAL, "CoxLassoPath_s": t_dev, "composed_s": t_com,
+    res = {"n": n, "p": p, "lambdas": m, "strata": STRATA, "weighted": bool(STRATA), "interval": INTERVAL, "efron": EFRON, "CoxLassoPath_s": t_dev, "composed_s": t_com,
            "min_s": {"CoxLassoPath": min(t_dev), "composed": min(t_com)},
            "composed_over_CoxLassoPath": min(t_com) / min(t_dev),
            "irls_rounds": {"CoxLassoPath": int(sum(path.rounds)), "composed": int(sum(crounds))},
