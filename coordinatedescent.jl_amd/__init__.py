@@ -24,6 +24,7 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   PoissonLassoPathResult, cvPoissonLassoPath, CVPoissonLassoPathResult,
                   CDCoxLoss, coxLasso_, coxLasso, coxLambdaMax, CoxLassoPath, CoxLassoSolution,
                   CoxLassoPathResult, cvCoxLassoPath, CVCoxLassoPathResult,
+                  CoxBaseline, coxResiduals, coxBaselineHazard, coxSurvival,
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
                   get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
                   getSigma, findInitResiduals_,

@@ -787,6 +787,7 @@ class CDCoxLoss(_GLMLoss):
         self._strata, self._weights = _strata_weights(strata, weights, len(status))
         self._weighted = self._weights is not None
         self._interval = self._start is not None
+        self._n_events = int(np.count_nonzero(status))           # baseline_hazard's capacity, without a download
         super().__init__(status, X, offset, device=device)
         del self._start, self._time, self._strata, self._weights
 
@@ -893,6 +894,60 @@ class CDCoxLoss(_GLMLoss):
         res["held_deviance"] = 2.0 * (float(every[0]) - float(train[0]))
         res["held_events"] = self._events(every[4]) - self._events(train[4])
         return res
+
+    def residuals(self, type="martingale", eta_max=50.0):
+        """The residuals of the model at the iterate the handle holds (cdh_glm_cox_residuals), an n-vector in the caller's row
+        order; no row is held out.  type: "martingale" -- M_i = δ_i - e^η_i A_i, survival's residuals(coxph, "martingale"),
+        unweighted (v_i M_i is the gradient's term); "deviance" -- sign(M_i) sqrt(-2 (M_i + δ_i log(e^η_i A_i))),
+        residuals(coxph, "deviance"); "cumhaz" -- A_i itself, the baseline cumulative hazard accrued over the row's time at
+        risk: H0 at the row's time (less H0 at its start with start-stop times) -- the A of the handle's own step, read where the
+        baseline table reads it, so that it equals baseline_hazard()'s step function at the row's time with ==.
+        The baseline is uncentred (x = 0, offset 0).  η is capped at eta_max as in irls_step; y, w, r and β are not touched."""
+        if type not in _COX_RESIDUALS:
+            raise ArgumentError('type must be "martingale", "deviance" or "cumhaz", not %r' % (type,))
+        out = np.zeros(self.n)
+        ptrs = [_vp(out) if t == type else None for t in _COX_RESIDUALS]
+        check(self._L.cdh_glm_cox_residuals(self._h, float(eta_max), *ptrs), self._h)
+        return out
+
+    def baseline_hazard(self, eta_max=50.0):
+        """The cumulative baseline hazard of the model at the iterate the handle holds (cdh_glm_cox_baseline; R's basehaz(fit,
+        centered = FALSE) and glmnet's survfit.coxnet at x = 0): a CoxBaseline with one entry per (stratum, event time), in
+        (stratum id, time) ascending order.  Breslow's estimate, or Efron's on a loss set to Efron ties; uncentred (x = 0,
+        offset 0).  The tie groups are compacted on the device; `hazard` is the per-stratum first difference of `cumhaz`,
+        taken here.  y, w, r and β are not touched."""
+        cap = getattr(self, "_n_events", None)                   # a table row holds at least one event: one call suffices
+        if cap is None:                                          # (a loss whose survival data did not come through __init__)
+            cap = int(np.count_nonzero(self.status))
+        stratum = np.zeros(cap, dtype=np.int32)
+        cols = [np.zeros(cap) for _ in range(5)]
+        count = C.c_int64()
+        check(self._L.cdh_glm_cox_baseline(self._h, float(eta_max), cap, _vp(stratum), *[_vp(c) for c in cols], C.byref(count)),
+              self._h)
+        m = count.value
+        stratum = stratum[:m].copy()
+        time, n_event, risk_sum, cumhaz, cumvar = (c[:m].copy() for c in cols)
+        head = np.r_[True, stratum[1:] != stratum[:-1]] if m else np.zeros(0, dtype=bool)
+        hazard = np.where(head, cumhaz, cumhaz - np.r_[0.0, cumhaz[:-1]]) if m else np.zeros(0)
+        return CoxBaseline(stratum, time, n_event, risk_sum, hazard, cumhaz, cumvar)
+
+
+_COX_RESIDUALS = ("cumhaz", "martingale", "deviance")      # cdh_glm_cox_residuals' three outputs, in its order
+
+
+@dataclass
+class CoxBaseline:
+    """The cumulative baseline hazard of a Cox model (CDCoxLoss.baseline_hazard; R's basehaz, uncentred), one entry per tie
+    group -- one stratum, one time -- that holds an event, in (stratum, time) ascending order: the stratum id, the time, n_event
+    (Σ v δ over the group), risk_sum (Σ v e^η over the rows at risk), hazard (the increment of cumhaz inside the stratum),
+    cumhaz (H0 of the stratum at that time, the group included) and cumvar (the same sum of hazard / risk_sum)."""
+    stratum: np.ndarray
+    time: np.ndarray
+    n_event: np.ndarray
+    risk_sum: np.ndarray
+    hazard: np.ndarray
+    cumhaz: np.ndarray
+    cumvar: np.ndarray
 
 
 # --------------------------------------------------------------------------------------
@@ -2534,6 +2589,51 @@ def coxLambdaMax(f, omega=None):
     out = C.c_double()
     check(f._L.cdh_lambda_max(f._h, C.byref(out)), f._h)
     return out.value
+
+
+def coxResiduals(f, type="martingale", eta_max=50.0):
+    """residuals(coxph, type) of a fitted CDCoxLoss at the iterate its handle holds: CDCoxLoss.residuals."""
+    if not isinstance(f, CDCoxLoss):
+        raise TypeError("MethodError: coxResiduals takes a CDCoxLoss")
+    return f.residuals(type, eta_max)
+
+
+def coxBaselineHazard(f, eta_max=50.0):
+    """basehaz(fit, centered = FALSE) of a fitted CDCoxLoss at the iterate its handle holds: CDCoxLoss.baseline_hazard,
+    uncentred (x = 0, offset 0)."""
+    if not isinstance(f, CDCoxLoss):
+        raise TypeError("MethodError: coxBaselineHazard takes a CDCoxLoss")
+    return f.baseline_hazard(eta_max)
+
+
+def coxSurvival(baseline, eta_new, times, strata_new=None):
+    """Survival curves of new rows (survfit.coxph / glmnet's survfit.coxnet with newx): the m x len(times) array
+    exp(-H0_g(t) exp(eta_new)), eta_new = x_new'β + offset of the m new rows and g their strata (strata_new; None: every row
+    in the table's only stratum).  H0_g is the right-continuous step function of the CoxBaseline table, which is uncentred
+    (x = 0, offset 0): 0 before the stratum's first event time, and its value at an event time includes that time's events.
+    Plain numpy on the compact table; a stratum that the table does not hold is refused."""
+    eta = np.atleast_1d(np.asarray(eta_new, dtype=np.float64))
+    tt = np.atleast_1d(np.asarray(times, dtype=np.float64))
+    if eta.ndim != 1 or tt.ndim != 1:
+        raise DimensionMismatch("eta_new and times must be vectors")
+    ids = np.unique(baseline.stratum)
+    if strata_new is None:
+        if len(ids) > 1:
+            raise ArgumentError("the baseline holds %d strata: strata_new must name the stratum of every new row" % len(ids))
+        g = np.full(len(eta), ids[0] if len(ids) else 0, dtype=np.int64)
+    else:
+        g = np.atleast_1d(np.asarray(strata_new)).astype(np.int64)
+        if g.shape != eta.shape:
+            raise DimensionMismatch("length(strata_new) != length(eta_new)")
+    H = np.zeros((len(eta), len(tt)))
+    for s in np.unique(g):
+        rows = baseline.stratum == s
+        if not rows.any():
+            raise ArgumentError("stratum %d is not in the baseline table" % int(s))
+        ts, cs = baseline.time[rows], baseline.cumhaz[rows]
+        at = np.searchsorted(ts, tt, side="right")              # the event times <= t
+        H[g == s] = np.where(at > 0, cs[np.maximum(at - 1, 0)], 0.0)[None, :]
+    return np.exp(-H * np.exp(eta)[:, None])
 
 
 def CoxLassoPath(X, y, lambdapath, options=None, irls=None, max_hat_s=np.inf, standardizeX=True, offset=None, strata=None,

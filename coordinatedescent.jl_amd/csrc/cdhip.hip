@@ -303,6 +303,7 @@ struct CvState {
 #include "glm_plan.hpp"
 #include "cox_plan.hpp"   // the Cox step's tiles, runs and scratch layout; the time order and its tie groups: host-only arithmetic
 #include "cox_efron.hpp"  // the three launches of the Efron chain that the second translation unit (cox_efron.hip) defines
+#include "cox_post.hpp"   // the post-estimation exports' launches that the third translation unit (cox_post.hip) defines
 enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
 // The Cox group (cox_kernels.hpp; cox_layout): d -- the scans' scratch, the runs' sums and the times; i -- order and the tie
 // groups' bounds.  Allocated together by the first cdh_glm_set_survival, or not at all.  sd, si -- the second pair, of a handle
@@ -312,7 +313,8 @@ enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
 // (then `strata` is set too; every setter without start times clears it).  ed, ei -- the Efron pair (cox_efron_layout), of a
 // handle set to Efron ties: allocated together by the first cdh_glm_set_cox_ties that asks for them, and in use while `efron`
 // is set (then `strata` is set too: the Efron chain is segmented and weighted; a setter with start times, the label and the
-// count setters clear it).
+// count setters clear it).  pd, pi -- the post group (cox_post_layout), of a handle that was asked for residuals or a baseline
+// hazard: allocated together by the first cdh_glm_cox_residuals or cdh_glm_cox_baseline, scratch of those calls alone.
 struct CoxState {
     DevBuf<double> d;
     DevBuf<int32_t> i;
@@ -322,6 +324,8 @@ struct CoxState {
     DevBuf<int32_t> vi;
     DevBuf<double> ed;
     DevBuf<int32_t> ei;
+    DevBuf<double> pd;
+    DevBuf<int32_t> pi;
     bool strata = false;
     bool interval = false;
     bool efron = false;
@@ -711,6 +715,7 @@ int32_t rebuild_residual(cdh_handle h) { return rebuild_residual_from(h, h->x, t
 #include "cv_path.hpp"      // k_fold_weights, k_path_sse: the folds of a cross-validated path and its errors in one pass
 #include "glm_kernels.hpp"  // k_glm_step: the step between two IRLS rounds of a GLM family
 #include "cox_kernels.hpp"  // the Cox family's step: risk-set scans in time order, a chain of launches
+#include "cox_post_host.hpp"  // residuals and the baseline hazard of a fitted Cox model: host bodies, the kernels are cox_post.hip's
 
 #include "solve.hpp"       // screened_full_pass, run_pass, solve; the bodies of cdh_descend, cdh_pass, cdh_solve, cdh_coordinate_descent
 
@@ -1228,6 +1233,15 @@ int32_t cdh_glm_set_cox_ties(cdh_handle h, int32_t ties) { return guarded(h, [&]
 
 int32_t cdh_glm_get_cox_ties(cdh_handle h, int32_t* ties) { return guarded(h, [&]() -> int32_t {
     return cox_get_ties(h, ties);
+}); }
+
+// what survival work is done with, at the iterate the handle holds (cox_post_host.hpp, cox_post.hip)
+int32_t cdh_glm_cox_residuals(cdh_handle h, double eta_max, void* host_cumhaz_or_null, void* host_martingale_or_null, void* host_deviance_or_null) { return guarded(h, [&]() -> int32_t {
+    return cox_post_residuals(h, eta_max, host_cumhaz_or_null, host_martingale_or_null, host_deviance_or_null);
+}); }
+
+int32_t cdh_glm_cox_baseline(cdh_handle h, double eta_max, int64_t capacity, int32_t* host_stratum, void* host_time, void* host_n_event, void* host_risk_sum, void* host_cumhaz, void* host_cumvar, int64_t* count) { return guarded(h, [&]() -> int32_t {
+    return cox_post_baseline(h, eta_max, capacity, host_stratum, host_time, host_n_event, host_risk_sum, host_cumhaz, host_cumvar, count);
 }); }
 
 // ---- cross-validation of a lasso path (cv_path.hpp; the solves are lasso.jl:229-260 on 0/1 weights, utils.jl:140-151) ------

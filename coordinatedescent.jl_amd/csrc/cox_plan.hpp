@@ -2,10 +2,11 @@
 // a scan, how the tiles are dealt to the workgroups, the layout of the step's scratch, and the time order with its tie groups
 // as cdh_glm_set_survival uploads them -- and, for cdh_glm_set_survival_strata, the order by (stratum, time) with the bounds of
 // every position's stratum; for cdh_glm_set_survival_interval, the second order by (stratum, start) and the two static lookups
-// that turn the scans into the sums over (start, stop].  No HIP in here: tests/test_cox_plan_host.py,
-// tests/test_cox_strata_plan_host.py and tests/test_cox_interval_plan_host.py compile it with g++ (tests/cox_plan_main.cpp,
-// tests/cox_strata_plan_main.cpp, tests/cox_interval_plan_main.cpp).  cox_kernels.hpp calls these functions and nothing else
-// decides the sizes.
+// that turn the scans into the sums over (start, stop]; and the scratch of the post-estimation exports (cox_post_layout).  No HIP
+// in here: tests/test_cox_plan_host.py, tests/test_cox_strata_plan_host.py, tests/test_cox_interval_plan_host.py,
+// tests/test_cox_efron_plan_host.py and tests/test_cox_post_plan_host.py compile it with g++ (tests/cox_plan_main.cpp,
+// tests/cox_strata_plan_main.cpp, tests/cox_interval_plan_main.cpp, tests/cox_efron_plan_main.cpp, tests/cox_post_plan_main.cpp).
+// cox_kernels.hpp calls these functions and nothing else decides the sizes.
 //
 // The tie groups are kept as TWO int32 vectors, not as head flags: first[s] and last[s] are the first and the last sorted
 // position of the group that sorted position s belongs to.  The risk-set sum of a row is the suffix scan read at first[s], its
@@ -103,6 +104,26 @@ struct CoxEfronLayout {
 constexpr CoxEfronLayout cox_efron_layout(int64_t ld) {
     return CoxEfronLayout{0, ld, 2 * ld, 3 * ld, 4 * ld, 5 * ld, 6 * ld, 7 * ld, 7 * ld + 5 * kCoxMaxGrid,
                           0, kCoxMaxGrid, 2 * kCoxMaxGrid};
+}
+
+// A handle that was asked for a post-estimation export (cdh_glm_cox_residuals, cdh_glm_cox_baseline; cox_post.hip) holds a pair
+// of its own, allocated by the first such call and by no other.  Doubles, ld each: dv (v delta in sorted order, then its prefix
+// scan inside the tie group: the group's n_event at its last position), flag (1 at the last position of a tie group that holds
+// an event, then its plain prefix scan: the group's slot in the table, plus one), and kCoxPostCols = 5 output vectors -- the
+// table's columns time, n_event, risk_sum, cumhaz, cumvar (a table has at most n rows), or the rows' export cumhaz, martingale,
+// deviance in the first three; then the runs' sums of the two scans, kCoxMaxGrid each, and ONE double: the table's length.
+// int32: the table's stratum column and slotpos (the last sorted position of every table row's tie group: where the rows'
+// export reads hA), ld each, and the head-seen flags of the runs for the scan of dv, kCoxMaxGrid.
+constexpr int kCoxPostCols = 5;
+struct CoxPostLayout {
+    int64_t dv, flag, out, sums, total;   // offsets in doubles; out + c ld: column c; sums + i kCoxMaxGrid: dv (0), flag (1)
+    int64_t doubles;
+    int64_t stratum, slotpos, heads;      // offsets in int32s
+    int64_t ints;
+};
+constexpr CoxPostLayout cox_post_layout(int64_t ld) {
+    return CoxPostLayout{0, ld, 2 * ld, (2 + kCoxPostCols) * ld, (2 + kCoxPostCols) * ld + 2 * kCoxMaxGrid,
+                         (2 + kCoxPostCols) * ld + 2 * kCoxMaxGrid + 1, 0, ld, 2 * ld, 2 * ld + kCoxMaxGrid};
 }
 
 // ---- the time order and its tie groups ---------------------------------------------------------------------------------------

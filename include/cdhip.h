@@ -465,6 +465,43 @@ int32_t cdh_glm_set_cox_ties(cdh_handle h, int32_t ties);
 /* cdh_glm_get_cox_ties (no reference counterpart; see cdh_glm_set_cox_ties, cd_differentiable_function.jl:118-194): the
  * handle's rule, 0 Breslow or 1 Efron.  CDH_BAD_ARG: ties NULL; no survival data set. */
 int32_t cdh_glm_get_cox_ties(cdh_handle h, int32_t *ties);
+/* cdh_glm_cox_residuals (no reference counterpart; the model is the one whose rounds solve the weighted lasso of
+ * cd_differentiable_function.jl:118-194): per row, in the caller's row order, at the iterate the handle holds and with no row
+ * held out (fold ids are not read).  eta = X beta + offset capped at eta_max as in cdh_glm_cox_irls, e = exp(eta) WITHOUT
+ * the weight, delta the status.
+ *   cumhaz_i     = A_i, the baseline cumulative hazard accrued over the row's time at risk.  Breslow: the stratum's
+ *                  cumulative hazard at the row's time, less that at its start on a handle with start times.  Efron: the
+ *                  same for a row that is not an event; an event's own group enters with c = 1 - l / d.  It is the A the
+ *                  handle's own step forms for the row, read from the step's scans at the positions where
+ *                  cdh_glm_cox_baseline reads them.  So a row's cumhaz == the table's cumhaz at the last event time <= its
+ *                  time (0 if there is none), and with start times == the one rounded difference of two such entries.
+ *                  Where the row's own tie group holds an event, that position is the step's own and cumhaz is the step's
+ *                  A bit for bit.  In an event-free group the step reads its scan further on, past zeros only, and may
+ *                  differ from cumhaz in the last bits (the same sum along another association);
+ *   martingale_i = delta_i - e_i A_i   (survival's residuals(coxph, "martingale"); v_i times it is the step's d_i);
+ *   deviance_i   = sign(M_i) sqrt(-2 (M_i + delta_i log(e_i A_i))), the delta log term 0 where delta = 0; a radicand that rounds
+ *                  below 0 (e A within rounding of 1) is taken as 0; an event with e A = 0 gives +inf.
+ * A NULL output is skipped; each of the others receives n doubles.  The call runs the read-only step of cdh_glm_cox_irls
+ * (k = -1, apply = 0, its catch-up of r included), then the table's launches of cdh_glm_cox_baseline, then one kernel over
+ * the scratch.  y, w, r and beta are not touched; the results are bit-identical run to run.  The first call allocates a group of scratch buffers of its own, all-or-nothing
+ * before anything else; a handle that never asks allocates nothing.  CDH_BAD_ARG, the handle unchanged: no survival data set;
+ * eta_max outside (0, 700]; all three outputs NULL. */
+int32_t cdh_glm_cox_residuals(cdh_handle h, double eta_max, void *host_cumhaz_or_null,
+                              void *host_martingale_or_null, void *host_deviance_or_null);
+/* cdh_glm_cox_baseline (no reference counterpart; R's basehaz and glmnet's survfit.coxnet at x = 0, offset 0 -- uncentred; the
+ * model is the one whose rounds solve the weighted lasso of cd_differentiable_function.jl:118-194): one table row per tie
+ * group (one stratum, one time) that holds at least one event, in (stratum id, time) ascending order, evaluated as
+ * cdh_glm_cox_residuals evaluates.  Columns: stratum (int32 id; 0 without strata), time, n_event (sum of dv = v delta over
+ * the group), risk_sum (S of the group: the sum of v e over the rows at risk), cumhaz (the stratum's cumulative baseline
+ * hazard H0 at that time, the group included; under Efron with sum_l m / den_l) and cumvar (the same sum of h / S, B of the
+ * step).  A group whose events were all skipped (S or den not > 0) still has a row.  *count is always written; the columns
+ * are written, count entries each, only when count <= capacity (count never exceeds the number of events); a NULL column is
+ * skipped.  The groups are compacted on the device by scans in a fixed order: the table is bit-identical run to run; y, w, r
+ * and beta are not touched.  CDH_BAD_ARG, the handle unchanged: no survival data set; eta_max outside (0, 700]; count NULL;
+ * capacity negative; count > capacity (the message names both numbers). */
+int32_t cdh_glm_cox_baseline(cdh_handle h, double eta_max, int64_t capacity, int32_t *host_stratum,
+                             void *host_time, void *host_n_event, void *host_risk_sum,
+                             void *host_cumhaz, void *host_cumvar, int64_t *count);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects

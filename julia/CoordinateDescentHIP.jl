@@ -663,6 +663,26 @@ function glm_cox_irls!(X::HipMatrix{Float64}, k::Integer=-1; apply::Bool=true, w
   (nll = out[1] / X.n, sum_w = out[2], clamped = Int(out[3]), capped = Int(out[4]), events = isinteger(out[5]) ? Int(out[5]) : out[5])   # the sum of v delta: the event count, an Int, without weights
 end
 
+"residuals of the Cox model at the iterate the handle holds, in the caller's row order: (cumhaz, martingale, deviance); survival's residuals(coxph, type = \"martingale\" / \"deviance\"), cumhaz the baseline cumulative hazard over the row's time at risk (uncentred)"
+function glm_cox_residuals(X::HipMatrix{Float64}; eta_max::Float64=50.0)
+  cumhaz, martingale, deviance = (Vector{Float64}(undef, X.n) for _ in 1:3)
+  check(X.handle, ccall((:cdh_glm_cox_residuals, libcdhip), Int32, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                        X.handle, eta_max, cumhaz, martingale, deviance))
+  (cumhaz = cumhaz, martingale = martingale, deviance = deviance)
+end
+
+"the cumulative baseline hazard of the Cox model at the iterate the handle holds (R's basehaz, uncentred): one entry per (stratum, event time) in that order; events: an upper bound of the table's length, the number of events"
+function glm_cox_baseline(X::HipMatrix{Float64}, events::Integer; eta_max::Float64=50.0)
+  stratum = Vector{Int32}(undef, events)
+  time, n_event, risk_sum, cumhaz, cumvar = (Vector{Float64}(undef, events) for _ in 1:5)
+  count = Ref{Int64}(0)
+  check(X.handle, ccall((:cdh_glm_cox_baseline, libcdhip), Int32,
+                        (Ptr{Cvoid}, Float64, Int64, Ptr{Int32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}),
+                        X.handle, eta_max, Int64(events), stratum, time, n_event, risk_sum, cumhaz, cumvar, count))
+  m = Int(count[])
+  (stratum = stratum[1:m], time = time[1:m], n_event = n_event[1:m], risk_sum = risk_sum[1:m], cumhaz = cumhaz[1:m], cumvar = cumvar[1:m])
+end
+
 # ---- locpolyl1 with the design expanded on the device (src/varying_coefficient_lasso.jl:30-79) ----------------
 # The reference rebuilds w, expandX and stdX on the host for every z0 (:63-65).  A HipVaryingDesign keeps the base
 # design and z in HBM; cdh_vc_set_point regenerates all three there, and the refit (:71-76) reads its weighted normal
