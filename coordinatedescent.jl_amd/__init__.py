@@ -25,6 +25,7 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   CDCoxLoss, coxLasso_, coxLasso, coxLambdaMax, CoxLassoPath, CoxLassoSolution,
                   CoxLassoPathResult, cvCoxLassoPath, CVCoxLassoPathResult,
                   CoxBaseline, coxResiduals, coxBaselineHazard, coxSurvival,
+                  CoxConcordance, coxConcordance, CVCoxConcordancePathResult,
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
                   get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
                   getSigma, findInitResiduals_,

@@ -931,6 +931,25 @@ class CDCoxLoss(_GLMLoss):
         hazard = np.where(head, cumhaz, cumhaz - np.r_[0.0, cumhaz[:-1]]) if m else np.zeros(0)
         return CoxBaseline(stratum, time, n_event, risk_sum, hazard, cumhaz, cumvar)
 
+    def concordance(self, fold=None):
+        """Harrell's concordance index of the model at the iterate the handle holds (cdh_glm_cox_concordance; R's
+        survival::concordance, glmnet's Cindex): a CoxConcordance.  fold=None: over all rows; fold=k (after set_folds): over the
+        rows of fold k alone, the held-out rows.  Rows i != j of one stratum are comparable, i the earlier, iff i is an event
+        and t_j > t_i, or t_j == t_i and j is censored; the pair is concordant if η_i > η_j, discordant if η_i < η_j, tied if
+        they are equal, and counts v_i v_j.  η = Xβ + offset is NOT capped.  The counts come from a merge sort of η on the
+        device; without weights they are exact.  The tie rule does not enter; not offered with start-stop times.  y, w, r and β
+        are not touched.  A NaN among the η of the rows that take part is refused."""
+        k = -1 if fold is None else int(fold)
+        if k < 0 and fold is not None:
+            raise ArgumentError("fold must be a fold id")
+        out = np.zeros(4)
+        check(self._L.cdh_glm_cox_concordance(self._h, k, out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        if out[3] > 0:
+            raise ArgumentError("eta is NaN in %d of the rows that take part: the concordance index is undefined" % int(out[3]))
+        c, d, t = float(out[0]), float(out[1]), float(out[2])
+        comparable = c + d + t
+        return CoxConcordance(c, d, t, comparable, (c + t / 2.0) / comparable if comparable > 0 else float("nan"))
+
 
 _COX_RESIDUALS = ("cumhaz", "martingale", "deviance")      # cdh_glm_cox_residuals' three outputs, in its order
 
@@ -948,6 +967,17 @@ class CoxBaseline:
     hazard: np.ndarray
     cumhaz: np.ndarray
     cumvar: np.ndarray
+
+
+@dataclass
+class CoxConcordance:
+    """Harrell's concordance index (CDCoxLoss.concordance): the weighted numbers of concordant, discordant and tied pairs,
+    comparable = their sum, and C = (concordant + tied / 2) / comparable -- nan when nothing is comparable."""
+    concordant: float
+    discordant: float
+    tied: float
+    comparable: float
+    C: float
 
 
 # --------------------------------------------------------------------------------------
@@ -2038,6 +2068,15 @@ class CVCoxLassoPathResult:
     fold_events: np.ndarray = None
 
 
+@dataclass
+class CVCoxConcordancePathResult(CVCoxLassoPathResult):
+    """What cvCoxLassoPath(measure="C") returns: CVCoxLassoPathResult with fold_concordance[k, j], Harrell's C of the held-out
+    rows of fold k at the β of λ_j fitted without them.  cvm, cvsd and the two selections are taken from it, the folds
+    weighted by their held-out Σ v (their sizes without weights): index_min is the position of the LARGEST cvm, index_1se the
+    largest λ whose cvm is at least that maximum less its cvsd."""
+    fold_concordance: np.ndarray = None
+
+
 def _penalty_value(g, beta):
     return g.lambda0 * float(np.sum(np.abs(beta) * (1.0 if g.lam is None else g.lam)))
 
@@ -2279,7 +2318,8 @@ def _glm_path_on(fam, f, lambdapath, options, irls, max_hat_s, standardizeX, fit
 
 
 def _cv_glm_path(fam, X, y, lambdapath, K, folds, options, irls, standardizeX, fit_intercept, seed, measure, offset,
-                 full_path, keep_fold_paths, extra=None):
+                 full_path, keep_fold_paths, extra=None, after_solve=None):
+    """after_solve(f, k, j): called after the solve of fold k at λ_j, at the β it left (None: nothing is called)."""
     front = "cv%sLassoPath" % fam.name.capitalize()
     if measure not in fam.cv_measures:
         raise ArgumentError("measure must be " + " or ".join('"%s"' % m for m in fam.cv_measures))
@@ -2301,14 +2341,14 @@ def _cv_glm_path(fam, X, y, lambdapath, K, folds, options, irls, standardizeX, f
     f, owned = _glm_loss(fam, X, y, fit_intercept, offset, extra)
     try:
         return _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, obs, off,
-                               measure, full_path, keep_fold_paths)
+                               measure, full_path, keep_fold_paths, after_solve)
     finally:
         if owned:
             f.close()                  # the handle this call made goes with it, also when a fold raises
 
 
 def _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standardizeX, fit_intercept, obs, off, measure,
-                    full_path, keep_fold_paths):
+                    full_path, keep_fold_paths, after_solve=None):
     n, K, m = f.n, len(sizes), lam.size
     if f.n_total != f.n:
         raise ArgumentError("%s does not run on row-sharded handles" % front)
@@ -2361,6 +2401,8 @@ def _cv_glm_path_on(fam, front, f, owned, lam, ids, sizes, options, irls, standa
                     wts[k] = fam.cv_weight(sol)
                 if keep_fold_paths:
                     _glm_keep(fam, res, sol, x, p, fit_intercept, nll=sol.nll * n / vk)
+                if after_solve is not None:
+                    after_solve(f, k, j)
             if keep_fold_paths:
                 fold_paths.append(res)
     finally:
@@ -2606,6 +2648,14 @@ def coxBaselineHazard(f, eta_max=50.0):
     return f.baseline_hazard(eta_max)
 
 
+def coxConcordance(f, fold=None):
+    """Harrell's concordance index of a fitted CDCoxLoss at the iterate its handle holds (survival::concordance, glmnet's
+    Cindex): CDCoxLoss.concordance."""
+    if not isinstance(f, CDCoxLoss):
+        raise TypeError("MethodError: coxConcordance takes a CDCoxLoss")
+    return f.concordance(fold)
+
+
 def coxSurvival(baseline, eta_new, times, strata_new=None):
     """Survival curves of new rows (survfit.coxph / glmnet's survfit.coxnet with newx): the m x len(times) array
     exp(-H0_g(t) exp(eta_new)), eta_new = x_new'β + offset of the m new rows and g their strata (strata_new; None: every row
@@ -2659,9 +2709,16 @@ def cvCoxLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, 
     of the risk sets and the event sums and keeps them at w = 0, z = Xβ.  The Cox lasso on the n_k training rows of fold k
     alone, at λ, has the iterates of that loop at λ·sqrt(n_k / n) with ω = _stdX!(w, X) of the 0/1 weights
     (standardizeX=False: ω = 1 and λ·n_k / n): the loss is (1/n) Σ here and (1/n_k) Σ there.  The read-only steps that end
-    every solve give fold_deviance[k, j] = -2 (ℓ_all - ℓ_train) / (held-out events of fold k), the only measure; cvm and cvsd
+    every solve give fold_deviance[k, j] = -2 (ℓ_all - ℓ_train) / (held-out events of fold k), the default measure; cvm and cvsd
     weight the folds by those event counts.  A fold without a held-out event, or without a training event, is refused
     before the upload.  Nothing n-sized moves after the upload.
+
+    measure="C" (glmnet's type.measure = "C"): after every solve of fold k the held-out rows' concordance index at that β
+    (CDCoxLoss.concordance(fold=k): counted on the device, four doubles come back) goes into fold_concordance[k, j] of a
+    CVCoxConcordancePathResult; cvm and cvsd weight the folds by their held-out Σ v (their sizes without weights), index_min
+    is the position of the LARGEST cvm and index_1se the largest λ whose cvm is at least that maximum less its cvsd.
+    fold_deviance and the rest are filled as under "deviance", whose calls the handle sees unchanged.  A fold whose held-out
+    rows hold no comparable pair is refused.  Not offered with start-stop times.
 
     strata and weights: CDCoxLoss's (refused, like offset, when a loss is passed in: they are then its own).  The folds keep
     the λ scaling above and the unweighted penalty scales; "events" are then Σ v_i δ_i, floats: a fold is weighted by its
@@ -2679,11 +2736,17 @@ def cvCoxLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, 
     ties: coxLasso's.  With "efron" a fold's tie groups count their TRAINING rows only (d, D and m), the held-out deviance is
     2 (ℓ_all - ℓ_train) of Efron's likelihood, and the λ scaling of the folds is the same: all three follow from the step."""
     _cox_ties(ties, X, y)
+    if measure not in ("deviance", "C"):
+        raise ArgumentError('measure must be "deviance" or "C"')
+    if measure == "C" and (X._interval if isinstance(X, CDCoxLoss) else np.ndim(y) == 2 and np.shape(y)[1] == 3):
+        raise ArgumentError('measure="C": concordance with start-stop times is not offered yet')     # (before the upload)
     extra = dict(strata=strata, weights=weights, ties=ties)
+    v = None
     if isinstance(X, CDCoxLoss):
         _glm_loss(_COX, X, y, False, offset, extra)               # (its refusals of what belongs to the loss)
         status = X.status
-        dv = status * X.weights if X._weighted else None
+        v = X.weights if X._weighted else None
+        dv = status * v if X._weighted else None
     elif isinstance(X, CoordinateDifferentiableFunction):
         raise TypeError("MethodError: cvCoxLassoPath takes a matrix or a CDCoxLoss")
     else:
@@ -2698,10 +2761,31 @@ def cvCoxLassoPath(X, y, lambdapath, K=10, folds=None, options=None, irls=None, 
             raise ArgumentError("fold %d holds no event: its held-out deviance is undefined" % k)
         if count[k] == count.sum():
             raise ArgumentError("fold %d holds every event: its training rows have none" % k)
-    res = _cv_glm_path(_COX, X, y, lambdapath, K, folds, options, irls, standardizeX, False, seed, measure, offset,
-                       full_path, keep_fold_paths, extra)
-    res.fold_events = events
-    return res
+    if measure == "deviance":
+        res = _cv_glm_path(_COX, X, y, lambdapath, K, folds, options, irls, standardizeX, False, seed, measure, offset,
+                           full_path, keep_fold_paths, extra)
+        res.fold_events = events
+        return res
+    lam = np.array(list(lambdapath), dtype=np.float64)
+    conc = np.zeros((len(sizes), lam.size))
+
+    def held_out_c(f, k, j):
+        c = f.concordance(fold=k)
+        if not c.comparable > 0:
+            raise ArgumentError("fold %d holds no comparable pair: its concordance index is undefined" % k)
+        conc[k, j] = c.C
+
+    res = _cv_glm_path(_COX, X, y, lam, K, folds, options, irls, standardizeX, False, seed, "deviance", offset,
+                       full_path, keep_fold_paths, extra, held_out_c)
+    held_v = sizes.astype(np.float64) if v is None else np.bincount(ids, weights=v, minlength=len(sizes))
+    cvm, cvsd, _, _ = _cv_select(lam, held_v, conc)
+    imax = int(np.argmax(cvm))
+    ok = np.nonzero(cvm >= cvm[imax] - cvsd[imax])[0]
+    i1se = int(ok[np.argmax(lam[ok])])           # the largest λ within one standard error of the best
+    kept = {k: getattr(res, k) for k in CVCoxLassoPathResult.__dataclass_fields__}
+    kept.update(measure="C", cvm=cvm, cvsd=cvsd, index_min=imax, lambda_min=float(lam[imax]), index_1se=i1se,
+                lambda_1se=float(lam[i1se]), fold_events=events)
+    return CVCoxConcordancePathResult(**kept, fold_concordance=conc)
 
 
 # --------------------------------------------------------------------------------------

@@ -304,6 +304,7 @@ struct CvState {
 #include "cox_plan.hpp"   // the Cox step's tiles, runs and scratch layout; the time order and its tie groups: host-only arithmetic
 #include "cox_efron.hpp"  // the three launches of the Efron chain that the second translation unit (cox_efron.hip) defines
 #include "cox_post.hpp"   // the post-estimation exports' launches that the third translation unit (cox_post.hip) defines
+#include "cox_concordance.hpp"   // the concordance index's launches that the fourth translation unit (cox_concordance.hip) defines
 enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
 // The Cox group (cox_kernels.hpp; cox_layout): d -- the scans' scratch, the runs' sums and the times; i -- order and the tie
 // groups' bounds.  Allocated together by the first cdh_glm_set_survival, or not at all.  sd, si -- the second pair, of a handle
@@ -315,6 +316,8 @@ enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
 // is set (then `strata` is set too: the Efron chain is segmented and weighted; a setter with start times, the label and the
 // count setters clear it).  pd, pi -- the post group (cox_post_layout), of a handle that was asked for residuals or a baseline
 // hazard: allocated together by the first cdh_glm_cox_residuals or cdh_glm_cox_baseline, scratch of those calls alone.
+// cd, ci -- the concordance group (cox_conc_layout): allocated together by the first cdh_glm_cox_concordance, which also fills
+// its order; every setter of survival data drops it, since the order is the data's.
 struct CoxState {
     DevBuf<double> d;
     DevBuf<int32_t> i;
@@ -326,6 +329,8 @@ struct CoxState {
     DevBuf<int32_t> ei;
     DevBuf<double> pd;
     DevBuf<int32_t> pi;
+    DevBuf<double> cd;
+    DevBuf<int32_t> ci;
     bool strata = false;
     bool interval = false;
     bool efron = false;
@@ -716,6 +721,7 @@ int32_t rebuild_residual(cdh_handle h) { return rebuild_residual_from(h, h->x, t
 #include "glm_kernels.hpp"  // k_glm_step: the step between two IRLS rounds of a GLM family
 #include "cox_kernels.hpp"  // the Cox family's step: risk-set scans in time order, a chain of launches
 #include "cox_post_host.hpp"  // residuals and the baseline hazard of a fitted Cox model: host bodies, the kernels are cox_post.hip's
+#include "cox_concordance_host.hpp"  // Harrell's concordance index: the host body, the kernels are cox_concordance.hip's
 
 #include "solve.hpp"       // screened_full_pass, run_pass, solve; the bodies of cdh_descend, cdh_pass, cdh_solve, cdh_coordinate_descent
 
@@ -1242,6 +1248,11 @@ int32_t cdh_glm_cox_residuals(cdh_handle h, double eta_max, void* host_cumhaz_or
 
 int32_t cdh_glm_cox_baseline(cdh_handle h, double eta_max, int64_t capacity, int32_t* host_stratum, void* host_time, void* host_n_event, void* host_risk_sum, void* host_cumhaz, void* host_cumvar, int64_t* count) { return guarded(h, [&]() -> int32_t {
     return cox_post_baseline(h, eta_max, capacity, host_stratum, host_time, host_n_event, host_risk_sum, host_cumhaz, host_cumvar, count);
+}); }
+
+// what a survival model is judged by: the concordance index of the held-out rows, or of all (cox_concordance_host.hpp)
+int32_t cdh_glm_cox_concordance(cdh_handle h, int32_t k, double* out4) { return guarded(h, [&]() -> int32_t {
+    return cox_concordance(h, k, out4);
 }); }
 
 // ---- cross-validation of a lasso path (cv_path.hpp; the solves are lasso.jl:229-260 on 0/1 weights, utils.jl:140-151) ------

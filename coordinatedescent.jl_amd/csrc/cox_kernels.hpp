@@ -502,6 +502,8 @@ int32_t cox_set_survival(cdh_handle h, const void* host_time, const void* host_s
     if (!h->glm.cox.d) { h->glm.cox.d = std::move(fresh_d); h->glm.cox.i = std::move(fresh_i); }
     if (sw && !h->glm.cox.sd) { h->glm.cox.sd = std::move(fresh_sd); h->glm.cox.si = std::move(fresh_si); }
     if (iv && !h->glm.cox.vd) { h->glm.cox.vd = std::move(fresh_vd); h->glm.cox.vi = std::move(fresh_vi); }
+    h->glm.cox.cd = DevBuf<double>();    // the concordance group goes with the order it was derived from (cox_concordance_host.hpp)
+    h->glm.cox.ci = DevBuf<int32_t>();
     double* d = h->glm.cox.d;
     int32_t* ii = h->glm.cox.i;
     HIPCHK(h, hipMemcpyAsync(h->glm.labels, st, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));

@@ -2,10 +2,13 @@
 // a scan, how the tiles are dealt to the workgroups, the layout of the step's scratch, and the time order with its tie groups
 // as cdh_glm_set_survival uploads them -- and, for cdh_glm_set_survival_strata, the order by (stratum, time) with the bounds of
 // every position's stratum; for cdh_glm_set_survival_interval, the second order by (stratum, start) and the two static lookups
-// that turn the scans into the sums over (start, stop]; and the scratch of the post-estimation exports (cox_post_layout).  No HIP
+// that turn the scans into the sums over (start, stop]; the scratch of the post-estimation exports (cox_post_layout); and, for
+// cdh_glm_cox_concordance, the concordance order with every event's range of comparable positions, the level arithmetic of the
+// merge sort the counts are read off, and that call's scratch (cox_conc_layout).  No HIP
 // in here: tests/test_cox_plan_host.py, tests/test_cox_strata_plan_host.py, tests/test_cox_interval_plan_host.py,
-// tests/test_cox_efron_plan_host.py and tests/test_cox_post_plan_host.py compile it with g++ (tests/cox_plan_main.cpp,
-// tests/cox_strata_plan_main.cpp, tests/cox_interval_plan_main.cpp, tests/cox_efron_plan_main.cpp, tests/cox_post_plan_main.cpp).
+// tests/test_cox_efron_plan_host.py, tests/test_cox_post_plan_host.py and tests/test_cox_concordance_plan_host.py compile it with
+// g++ (tests/cox_plan_main.cpp, tests/cox_strata_plan_main.cpp, tests/cox_interval_plan_main.cpp, tests/cox_efron_plan_main.cpp,
+// tests/cox_post_plan_main.cpp, tests/cox_concordance_plan_main.cpp).
 // cox_kernels.hpp calls these functions and nothing else decides the sizes.
 //
 // The tie groups are kept as TWO int32 vectors, not as head flags: first[s] and last[s] are the first and the last sorted
@@ -283,4 +286,87 @@ inline void cox_order_interval(int64_t n, int64_t ld, const double* start, const
         }
         enter[s] = l > a ? (int32_t)(l - 1) : -1;
     }
+}
+
+// ---- the concordance index (cdh_glm_cox_concordance; cox_concordance.hip) ------------------------------------------------------
+// The concordance order: the Cox order with every tie group stably partitioned, its events before its censored rows -- a stable
+// sort by (stratum, time, events before censored).  For a position s that holds an event the rows it is comparable with (a
+// later time in its stratum, or the same time and censored) are then ONE range of positions [qa[s], qb[s]): qa is the first
+// censored position of s's tie group (the group's end when it has none), qb the end of s's stratum.  Every other position, the
+// pads included, has qa = qb = 0.  order, last, slast: the handle's (slast == nullptr: one stratum, 0 .. n - 1);
+// status: by row.  corder, qa, qb get N entries, N >= ld the positions the kernels plan (cox_conc_layout); the pads stay in
+// place and the positions beyond ld hold row -1, which no kernel reads.
+inline void cox_conc_order(int64_t n, int64_t ld, int64_t N, const int32_t* order, const int32_t* last, const int32_t* slast, const double* status, std::vector<int32_t>& corder, std::vector<int32_t>& qa,
+                           std::vector<int32_t>& qb) {
+    corder.assign((size_t)N, -1);
+    qa.assign((size_t)N, 0);
+    qb.assign((size_t)N, 0);
+    for (int64_t s = n; s < ld; ++s) corder[(size_t)s] = (int32_t)s;
+    for (int64_t g = 0; g < n;) {
+        const int64_t e = (int64_t)last[g] + 1;
+        int64_t at = g;
+        for (int64_t s = g; s < e; ++s)
+            if (status[order[s]] == 1.0) corder[(size_t)at++] = order[s];
+        const int64_t censored = at;
+        for (int64_t s = g; s < e; ++s)
+            if (status[order[s]] != 1.0) corder[(size_t)at++] = order[s];
+        const int64_t end = slast ? (int64_t)slast[g] + 1 : n;
+        for (int64_t s = g; s < censored; ++s) { qa[(size_t)s] = (int32_t)censored; qb[(size_t)s] = (int32_t)end; }
+        g = e;
+    }
+}
+
+// The level arithmetic.  At level lev the positions are cut into the runs [m 2^lev, (m + 1) 2^lev), each sorted by eta.  A range
+// [a, b) is the disjoint union of at most two WHOLE runs per level, the iterative segment-tree walk: with l = ceil(a / 2^lev)
+// and r = floor(b / 2^lev), while l < r, run l is taken if l is odd and run r - 1 if r is odd (l odd and r odd never name the
+// same run: then r - 1 is even).  Both are closed forms of lev, so a kernel that holds level lev alone can answer its part.
+struct CoxConcTake { int64_t run[2]; int count; };
+constexpr CoxConcTake cox_conc_take(int64_t a, int64_t b, int lev) {
+    const int64_t l = (a + ((int64_t)1 << lev) - 1) >> lev, r = b >> lev;
+    CoxConcTake t{{0, 0}, 0};
+    if (l < r) {
+        if (l & 1) t.run[t.count++] = l;
+        if (r & 1) t.run[t.count++] = r - 1;
+    }
+    return t;
+}
+
+// The levels below the tile are not kept: what the walk takes of them is exactly the two FRINGES of the range, [a, a1) and
+// [b0, b) with a1 = a rounded up and b0 = b rounded down to a multiple of the tile (both clipped so that a <= a1 <= b0 <= b: a
+// range inside two neighbouring tiles is all fringe), and a fringe is counted position by position.  The levels from the tile's
+// up then tile [a1, b0).
+constexpr int kCoxTileLog = 10;
+static_assert(((int64_t)1 << kCoxTileLog) == kCoxTile, "the first level the level kernel reads is the tile's");
+struct CoxConcFringe { int64_t a1, b0; };
+constexpr CoxConcFringe cox_conc_fringe(int64_t a, int64_t b) {
+    int64_t a1 = (a + kCoxTile - 1) / kCoxTile * kCoxTile;
+    if (a1 > b) a1 = b;
+    int64_t b0 = b / kCoxTile * kCoxTile;
+    if (b0 < a1) b0 = a1;
+    return CoxConcFringe{a1, b0};
+}
+// the last level: the first whose one run holds all N positions (N a multiple of the tile, so top >= kCoxTileLog)
+constexpr int cox_conc_top(int64_t N) {
+    int lev = kCoxTileLog;
+    while (((int64_t)1 << lev) < N) ++lev;
+    return lev;
+}
+
+// A handle that was asked for the concordance index holds a FIFTH pair, allocated whole by the first cdh_glm_cox_concordance
+// after a setter of survival data and dropped by that setter (the order is the data's).  N: ld rounded up to whole tiles.
+// Doubles, N each: key0 and v0 (eta and the weight by position; +inf and 0 outside the subset and on the pads), two ping-pong
+// pairs (ka, pa) and (kb, pb) -- a level's keys and the inclusive prefix sums of the weights inside its runs -- and the rows'
+// three sums L (smaller eta), E (smaller or equal) and G (all) over their ranges; then 4 doubles per tile (the tiles' partial
+// concordant, discordant, tied and NaN counts) and the 4 of the result.  int32, N each: corder, qa, qb.
+struct CoxConcLayout {
+    int64_t N, tiles;
+    int64_t key0, v0, ka, pa, kb, pb, L, E, G, part, out;   // offsets in doubles
+    int64_t doubles;
+    int64_t order, qa, qb;                                   // offsets in int32s
+    int64_t ints;
+};
+constexpr CoxConcLayout cox_conc_layout(int64_t ld) {
+    const int64_t tiles = ld > 0 ? (ld + kCoxTile - 1) / kCoxTile : 1, N = tiles * kCoxTile;
+    return CoxConcLayout{N, tiles, 0, N, 2 * N, 3 * N, 4 * N, 5 * N, 6 * N, 7 * N, 8 * N, 9 * N, 9 * N + 4 * tiles,
+                         9 * N + 4 * tiles + 4, 0, N, 2 * N, 3 * N};
 }

@@ -502,6 +502,23 @@ int32_t cdh_glm_cox_residuals(cdh_handle h, double eta_max, void *host_cumhaz_or
 int32_t cdh_glm_cox_baseline(cdh_handle h, double eta_max, int64_t capacity, int32_t *host_stratum,
                              void *host_time, void *host_n_event, void *host_risk_sum,
                              void *host_cumhaz, void *host_cumvar, int64_t *count);
+/* cdh_glm_cox_concordance (no reference counterpart; R's survival::concordance and glmnet's Cindex -- Harrell's C; the model
+ * is the one whose rounds solve the weighted lasso of cd_differentiable_function.jl:118-194): the weighted numbers of
+ * concordant, discordant and tied pairs at the iterate the handle holds.  k == -1: all rows take part and the fold ids are
+ * not read; k >= 0: the rows with fold id == k, the held-out rows, after cdh_set_folds.  Rows i != j that take part, in the
+ * same stratum, are a comparable pair with i the earlier iff i is an event and t_j > t_i, or t_j == t_i and j is censored (a
+ * row censored at an event's time outlived it; two events at one time are not comparable).  eta = X beta + offset, formed as
+ * cdh_glm_cox_residuals forms it but NOT capped: only its order matters.  The pair is concordant if eta_i > eta_j, discordant
+ * if eta_i < eta_j, tied if eta_i == eta_j (doubles: -0.0 == 0.0), and counts with weight v_i v_j (1 without weights).
+ * out4 = {concordant, discordant, tied, number of rows taking part whose eta is NaN}; C = (concordant + tied / 2) /
+ * (concordant + discordant + tied).  When out4[3] > 0 the first three are unspecified.  On a handle without weights the first
+ * three are exact integers while their sum is below 2^53.  The tie rule does not enter.  Read-only: r first catches up as for
+ * cdh_glm_cox_irls; y, w, r, beta and the step's scratch stay as they are; the results are bit-identical run to run.  The first
+ * call after a setter of survival data allocates a group of scratch buffers of its own (9 doubles and 3 int32 per row,
+ * rounded up to tiles of 1024 rows), all-or-nothing, and derives its order; the survival setters drop it.  CDH_BAD_ARG, the
+ * handle unchanged: row shards and whatever else the GLM exports refuse of the handle; no survival data set; k < -1, k >= 0
+ * without folds, k >= K; out4 NULL; a handle with start times ("concordance with start-stop times is not offered yet"). */
+int32_t cdh_glm_cox_concordance(cdh_handle h, int32_t k, double *out4);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects

@@ -683,6 +683,15 @@ function glm_cox_baseline(X::HipMatrix{Float64}, events::Integer; eta_max::Float
   (stratum = stratum[1:m], time = time[1:m], n_event = n_event[1:m], risk_sum = risk_sum[1:m], cumhaz = cumhaz[1:m], cumvar = cumvar[1:m])
 end
 
+"Harrell's concordance index of the Cox model at the iterate the handle holds (survival::concordance, glmnet's Cindex): over all rows (k = -1) or over the held-out rows of fold k (0-based, after set_folds!); the pair counts carry the weights v_i v_j"
+function glm_cox_concordance(X::HipMatrix{Float64}, k::Integer=-1)
+  out = Vector{Float64}(undef, 4)
+  check(X.handle, ccall((:cdh_glm_cox_concordance, libcdhip), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}), X.handle, Int32(k), out))
+  out[4] > 0 && throw(ArgumentError("eta is NaN in $(Int(out[4])) rows"))
+  comparable = out[1] + out[2] + out[3]
+  (concordant = out[1], discordant = out[2], tied = out[3], comparable = comparable, C = comparable > 0 ? (out[1] + out[3] / 2) / comparable : NaN)
+end
+
 # ---- locpolyl1 with the design expanded on the device (src/varying_coefficient_lasso.jl:30-79) ----------------
 # The reference rebuilds w, expandX and stdX on the host for every z0 (:63-65).  A HipVaryingDesign keeps the base
 # design and z in HBM; cdh_vc_set_point regenerates all three there, and the refit (:71-76) reads its weighted normal
