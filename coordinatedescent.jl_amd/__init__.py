@@ -26,6 +26,8 @@ from .api import (CDOptions, IterLassoOptions, ProxL1, SparseIterate, CDLeastSqu
                   CoxLassoPathResult, cvCoxLassoPath, CVCoxLassoPathResult,
                   CoxBaseline, coxResiduals, coxBaselineHazard, coxSurvival,
                   CoxConcordance, coxConcordance, CVCoxConcordancePathResult,
+                  CoxSchoenfeld, CoxInference, coxScoreResiduals, coxSchoenfeldResiduals, coxInformation, coxInference,
+                  coxInferenceFrom,
                   SmoothingKernel, GaussianKernel, EpanechnikovKernel, createKernel, evaluate,
                   get_nonzero_coordinates, CDVaryingCoefficientLoss, locpolyl1, lvocv_locpolyl1,
                   getSigma, findInitResiduals_,

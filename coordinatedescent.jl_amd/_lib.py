@@ -73,15 +73,17 @@ def needs_build() -> bool:
 
 
 def build(force: bool = False) -> str:
-    """hipcc --offload-arch=gfx950 csrc/cdhip.hip csrc/cox_efron.hip csrc/cox_post.hip csrc/cox_concordance.hip ->
-    csrc/libcdhip.so (in-tree).  Four translation units, four code objects in the one library: the Efron kernels, the
-    post-estimation kernels and the concordance kernels stay out of the code object whose layout the sweep is sensitive to
-    (csrc/cox_efron.hip, csrc/cox_post.hip, csrc/cox_concordance.hip)."""
+    """hipcc --offload-arch=gfx950 csrc/cdhip.hip csrc/cox_efron.hip csrc/cox_post.hip csrc/cox_concordance.hip
+    csrc/cox_score.hip -> csrc/libcdhip.so (in-tree).  Five translation units, five code objects in the one library: the
+    Efron kernels, the post-estimation kernels, the concordance kernels and the score kernels stay out of the code object
+    whose layout the sweep is sensitive to (csrc/cox_efron.hip, csrc/cox_post.hip, csrc/cox_concordance.hip,
+    csrc/cox_score.hip)."""
     if not force and not needs_build():
         return SO_PATH
     cmd = ["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-Wall",
            "-o", SO_PATH, os.path.join(CSRC, "cdhip.hip"), os.path.join(CSRC, "cox_efron.hip"),
-           os.path.join(CSRC, "cox_post.hip"), os.path.join(CSRC, "cox_concordance.hip"), "-ldl"]
+           os.path.join(CSRC, "cox_post.hip"), os.path.join(CSRC, "cox_concordance.hip"),
+           os.path.join(CSRC, "cox_score.hip"), "-ldl"]
     subprocess.run(cmd, check=True)
     return SO_PATH
 
@@ -144,6 +146,7 @@ def lib():
         "cdh_glm_cox_residuals": [vp, f64, vp, vp, vp],
         "cdh_glm_cox_baseline": [vp, f64, i64, vp, vp, vp, vp, vp, vp, P(i64)],
         "cdh_glm_cox_concordance": [vp, i32, P(f64)],
+        "cdh_glm_cox_score": [vp, f64, i64, vp, vp, vp, vp, vp, vp],
         "cdh_generate": [vp, C.c_uint64, i64, f64, vp],
         "cdh_set_penalty": [vp, f64, vp, i64],
         "cdh_num_coordinates": [vp, P(i64)],

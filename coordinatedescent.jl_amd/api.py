@@ -950,6 +950,96 @@ class CDCoxLoss(_GLMLoss):
         comparable = c + d + t
         return CoxConcordance(c, d, t, comparable, (c + t / 2.0) / comparable if comparable > 0 else float("nan"))
 
+    def _score_columns(self, columns):
+        """The 1-based columns of a score call: the given ones, or the support of the handle's β."""
+        if columns is None:
+            idx = np.zeros(max(self.p, 1), dtype=np.int64)
+            nnz = C.c_int64()
+            check(self._L.cdh_get_support(self._h, _vp(idx), C.byref(nnz)), self._h)
+            cols = idx[: nnz.value].copy()
+            if len(cols) == 0:
+                raise ArgumentError("the support of β is empty: name the columns")
+        else:
+            cols = np.atleast_1d(np.asarray(columns))
+            if cols.ndim != 1 or len(cols) == 0 or not np.issubdtype(cols.dtype, np.integer):
+                raise ArgumentError("columns must be a non-empty vector of 1-based column indices")
+            cols = np.ascontiguousarray(cols, dtype=np.int64)
+        if len(cols) > COX_SCORE_MAX_COLS:
+            raise ArgumentError("%d columns: score residuals and the information matrix are offered for at most %d columns"
+                                % (len(cols), COX_SCORE_MAX_COLS))
+        if cols.min() < 1 or cols.max() > self.p:
+            raise ArgumentError("a column index lies outside 1 .. p")
+        return cols
+
+    def _score(self, columns, eta_max, schoenfeld=False, score=False, info=False, centre=None):
+        """cdh_glm_cox_score -> (columns, schoenfeld n x m or None, score n x m or None, info m x m or None, the centres used)."""
+        cols = self._score_columns(columns)
+        m = len(cols)
+        mu = None if centre is None else np.ascontiguousarray(centre, dtype=np.float64)
+        if mu is not None and mu.shape != (m,):
+            raise DimensionMismatch("centre must hold one value per column")
+        used = np.zeros(m)
+        sch = np.zeros((self.n, m), order="F") if schoenfeld else None
+        L = np.zeros((self.n, m), order="F") if score else None
+        I = np.zeros((m, m)) if info else None
+        check(self._L.cdh_glm_cox_score(self._h, float(eta_max), m, _vp(cols), _vp(mu), _vp(used), _vp(sch), _vp(L), _vp(I)), self._h)
+        return cols, sch, L, I, used
+
+    def score_residuals(self, columns=None, weighted=False, eta_max=50.0):
+        """The score residuals of the model at the iterate the handle holds (cdh_glm_cox_score; R's residuals(coxph, "score")),
+        n x m in the caller's row order, for the 1-based `columns` (None: the support of the handle's β; at most 64), Breslow
+        ties: L_ic = δ_i (x_ic - x̄_c(t_i)) - e^η_i Σ_{event times t <= t_i} h(t) (x_ic - x̄_c(t)), x̄_c(t) the risk-set mean
+        Σ v e^η x_c / S.  weighted=True multiplies row i by v_i; the column sums of the weighted form are the gradient
+        X_c'(vδ - v e^η A).  Not offered with Efron ties or start-stop times yet.  y, w, r and β are not touched."""
+        _, _, L, _, _ = self._score(columns, eta_max, score=True)
+        return L * self.weights[:, None] if weighted else L
+
+    def schoenfeld_residuals(self, columns=None, eta_max=50.0):
+        """The Schoenfeld residuals x_ic - x̄_c(t_i) of the events (cdh_glm_cox_score; R's residuals(coxph, "schoenfeld")): a
+        CoxSchoenfeld with the event rows in (stratum, time) ascending order, ties in the handle's order, which is the
+        caller's.  An event whose risk-set sum is not > 0 has a zero row.  What a proportional-hazards check needs."""
+        cols, sch, _, _, _ = self._score(columns, eta_max, schoenfeld=True)
+        status, time, strata = self.status, self.time, self.strata
+        rows = np.nonzero(status != 0)[0]
+        rows = rows[np.lexsort((time[rows], strata[rows]))]       # stable: ties keep the caller's order
+        return CoxSchoenfeld(rows, strata[rows], time[rows], np.ascontiguousarray(sch[rows]), cols)
+
+    def information(self, columns=None, eta_max=50.0):
+        """The information matrix of the model at the iterate the handle holds (cdh_glm_cox_score), m x m: the Hessian of the
+        un-normalised negative log partial likelihood in β_columns, Σ_events vδ [Σ_risk v e^η x̃x̃'/S - x̄x̄'], formed on the
+        device from centred columns; symmetric.  Its inverse is coxph's var."""
+        return self._score(columns, eta_max, info=True)[3]
+
+
+COX_SCORE_MAX_COLS = 64     # include/cdhip.h: cdh_glm_cox_score's cap; kCoxScoreMaxCols in csrc/cox_plan.hpp
+
+
+@dataclass
+class CoxSchoenfeld:
+    """The Schoenfeld residuals of a Cox model (CDCoxLoss.schoenfeld_residuals): `rows` -- the event rows' indices in (stratum,
+    time) ascending order; `stratum` and `time` of those rows; `resid` -- n_events x m, x_ic - x̄_c(t_i); `columns` -- the
+    1-based columns."""
+    rows: np.ndarray
+    stratum: np.ndarray
+    time: np.ndarray
+    resid: np.ndarray
+    columns: np.ndarray
+
+
+@dataclass
+class CoxInference:
+    """Standard errors of a fitted Cox model (coxInference): `columns` (1-based), `beta` on them, `var` = I⁻¹, `se`, `z` =
+    beta / se; with robust=True also `dfbeta` = diag(v) L I⁻¹ (n x m; R's residuals(type = "dfbeta", weighted = TRUE)),
+    `robust_var` = D'D with D = dfbeta summed over the cluster ids, and `robust_se` -- else None."""
+    columns: np.ndarray
+    beta: np.ndarray
+    var: np.ndarray
+    se: np.ndarray
+    z: np.ndarray
+    dfbeta: np.ndarray = None
+    robust_var: np.ndarray = None
+    robust_se: np.ndarray = None
+
 
 _COX_RESIDUALS = ("cumhaz", "martingale", "deviance")      # cdh_glm_cox_residuals' three outputs, in its order
 
@@ -2654,6 +2744,82 @@ def coxConcordance(f, fold=None):
     if not isinstance(f, CDCoxLoss):
         raise TypeError("MethodError: coxConcordance takes a CDCoxLoss")
     return f.concordance(fold)
+
+
+def coxScoreResiduals(f, columns=None, weighted=False, eta_max=50.0):
+    """residuals(coxph, "score") of a fitted CDCoxLoss at the iterate its handle holds: CDCoxLoss.score_residuals."""
+    if not isinstance(f, CDCoxLoss):
+        raise TypeError("MethodError: coxScoreResiduals takes a CDCoxLoss")
+    return f.score_residuals(columns, weighted, eta_max)
+
+
+def coxSchoenfeldResiduals(f, columns=None, eta_max=50.0):
+    """residuals(coxph, "schoenfeld") of a fitted CDCoxLoss at the iterate its handle holds: CDCoxLoss.schoenfeld_residuals."""
+    if not isinstance(f, CDCoxLoss):
+        raise TypeError("MethodError: coxSchoenfeldResiduals takes a CDCoxLoss")
+    return f.schoenfeld_residuals(columns, eta_max)
+
+
+def coxInformation(f, columns=None, eta_max=50.0):
+    """The information matrix of a fitted CDCoxLoss at the iterate its handle holds, on `columns`: CDCoxLoss.information."""
+    if not isinstance(f, CDCoxLoss):
+        raise TypeError("MethodError: coxInformation takes a CDCoxLoss")
+    return f.information(columns, eta_max)
+
+
+def coxInferenceFrom(columns, beta, info, score=None, weights=None, cluster=None):
+    """CoxInference from the device's answers, in plain numpy: var = info⁻¹, se, z; with `score` (the n x m unweighted score
+    residuals) also dfbeta = diag(weights) score var, robust_var = D'D with D = dfbeta summed over the `cluster` ids (None:
+    every row its own cluster) and robust_se -- R's coxph(robust = TRUE).  A singular information matrix is refused."""
+    cols = np.atleast_1d(np.asarray(columns, dtype=np.int64))
+    b = np.atleast_1d(np.asarray(beta, dtype=np.float64))
+    I = np.asarray(info, dtype=np.float64)
+    m = len(cols)
+    if I.shape != (m, m) or b.shape != (m,):
+        raise DimensionMismatch("info must be m x m and beta of length m for the m columns")
+    if not np.all(np.isfinite(I)) or np.linalg.matrix_rank(I) < m:
+        raise ArgumentError("the information matrix is singular on these columns: no variance")
+    var = np.linalg.inv(I)
+    var = (var + var.T) / 2.0
+    if np.any(np.diag(var) <= 0.0):
+        raise ArgumentError("the information matrix is singular on these columns: no variance")
+    se = np.sqrt(np.diag(var))
+    out = CoxInference(cols, b, var, se, b / se)
+    if score is not None:
+        L = np.asarray(score, dtype=np.float64)
+        v = np.ones(L.shape[0]) if weights is None else np.asarray(weights, dtype=np.float64)
+        if L.ndim != 2 or L.shape[1] != m or v.shape != (L.shape[0],):
+            raise DimensionMismatch("score must be n x m and weights of length n")
+        out.dfbeta = (v[:, None] * L) @ var
+        D = out.dfbeta
+        if cluster is not None:
+            ids = np.asarray(cluster)
+            if ids.shape != (L.shape[0],):
+                raise DimensionMismatch("cluster must hold one id per row")
+            _, inverse = np.unique(ids, return_inverse=True)
+            D = np.zeros((inverse.max() + 1, m))
+            np.add.at(D, inverse, out.dfbeta)
+        out.robust_var = D.T @ D
+        out.robust_se = np.sqrt(np.diag(out.robust_var))
+    return out
+
+
+def coxInference(f, columns=None, robust=False, cluster=None, eta_max=50.0):
+    """Standard errors of a fitted CDCoxLoss at the iterate its handle holds, on `columns` (1-based; None: the support of β):
+    a CoxInference with var = I⁻¹ (coxph's var on those columns, the others held at their values), se and z; robust=True adds
+    the sandwich of R's coxph(robust = TRUE): dfbeta, robust_var and robust_se, clustered by `cluster` ids when given.  One
+    device call (cdh_glm_cox_score) and plain numpy on its m x m and n x m answers.  After an l1-penalised fit these are the
+    usual post-selection quantities: the penalty is not accounted for.  Breslow ties; no start-stop times yet."""
+    if not isinstance(f, CDCoxLoss):
+        raise TypeError("MethodError: coxInference takes a CDCoxLoss")
+    if cluster is not None and not robust:
+        raise ArgumentError("cluster needs robust=True")
+    if cluster is not None and np.shape(cluster) != (f.n,):
+        raise DimensionMismatch("cluster must hold one id per row")
+    cols, _, L, I, _ = f._score(columns, eta_max, score=bool(robust), info=True)
+    beta = np.zeros(f.p)
+    check(f._L.cdh_get_beta(f._h, _vp(beta)), f._h)
+    return coxInferenceFrom(cols, beta[cols - 1], I, L, f.weights if robust else None, cluster)
 
 
 def coxSurvival(baseline, eta_new, times, strata_new=None):

@@ -305,6 +305,7 @@ struct CvState {
 #include "cox_efron.hpp"  // the three launches of the Efron chain that the second translation unit (cox_efron.hip) defines
 #include "cox_post.hpp"   // the post-estimation exports' launches that the third translation unit (cox_post.hip) defines
 #include "cox_concordance.hpp"   // the concordance index's launches that the fourth translation unit (cox_concordance.hip) defines
+#include "cox_score.hpp"   // the score residuals' and the information matrix's launches that the fifth translation unit (cox_score.hip) defines
 enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
 // The Cox group (cox_kernels.hpp; cox_layout): d -- the scans' scratch, the runs' sums and the times; i -- order and the tie
 // groups' bounds.  Allocated together by the first cdh_glm_set_survival, or not at all.  sd, si -- the second pair, of a handle
@@ -317,7 +318,9 @@ enum class GlmData : int { Binomial = 0, Poisson = 1, Cox = 2 };
 // count setters clear it).  pd, pi -- the post group (cox_post_layout), of a handle that was asked for residuals or a baseline
 // hazard: allocated together by the first cdh_glm_cox_residuals or cdh_glm_cox_baseline, scratch of those calls alone.
 // cd, ci -- the concordance group (cox_conc_layout): allocated together by the first cdh_glm_cox_concordance, which also fills
-// its order; every setter of survival data drops it, since the order is the data's.
+// its order; every setter of survival data drops it, since the order is the data's.  qd, qi -- the score group
+// (cox_score_layout) for score_cols columns: allocated together by the first cdh_glm_cox_score and regrown together, never
+// shrunk, when a later call asks for more columns; scratch of that call alone, which fills it anew every time.
 struct CoxState {
     DevBuf<double> d;
     DevBuf<int32_t> i;
@@ -331,6 +334,9 @@ struct CoxState {
     DevBuf<int32_t> pi;
     DevBuf<double> cd;
     DevBuf<int32_t> ci;
+    DevBuf<double> qd;
+    DevBuf<int32_t> qi;
+    int64_t score_cols = 0;
     bool strata = false;
     bool interval = false;
     bool efron = false;
@@ -722,6 +728,7 @@ int32_t rebuild_residual(cdh_handle h) { return rebuild_residual_from(h, h->x, t
 #include "cox_kernels.hpp"  // the Cox family's step: risk-set scans in time order, a chain of launches
 #include "cox_post_host.hpp"  // residuals and the baseline hazard of a fitted Cox model: host bodies, the kernels are cox_post.hip's
 #include "cox_concordance_host.hpp"  // Harrell's concordance index: the host body, the kernels are cox_concordance.hip's
+#include "cox_score_host.hpp"  // score and Schoenfeld residuals, the information matrix: the host body, the kernels are cox_score.hip's
 
 #include "solve.hpp"       // screened_full_pass, run_pass, solve; the bodies of cdh_descend, cdh_pass, cdh_solve, cdh_coordinate_descent
 
@@ -1253,6 +1260,11 @@ int32_t cdh_glm_cox_baseline(cdh_handle h, double eta_max, int64_t capacity, int
 // what a survival model is judged by: the concordance index of the held-out rows, or of all (cox_concordance_host.hpp)
 int32_t cdh_glm_cox_concordance(cdh_handle h, int32_t k, double* out4) { return guarded(h, [&]() -> int32_t {
     return cox_concordance(h, k, out4);
+}); }
+
+// what inference after a Cox fit is made of: score and Schoenfeld residuals, the information matrix (cox_score_host.hpp, cox_score.hip)
+int32_t cdh_glm_cox_score(cdh_handle h, double eta_max, int64_t m, const int64_t* idx1, const double* host_centre_or_null, double* host_centre_out_or_null, void* host_schoenfeld_or_null, void* host_score_or_null, double* host_info_or_null) { return guarded(h, [&]() -> int32_t {
+    return cox_score(h, eta_max, m, idx1, host_centre_or_null, host_centre_out_or_null, host_schoenfeld_or_null, host_score_or_null, host_info_or_null);
 }); }
 
 // ---- cross-validation of a lasso path (cv_path.hpp; the solves are lasso.jl:229-260 on 0/1 weights, utils.jl:140-151) ------

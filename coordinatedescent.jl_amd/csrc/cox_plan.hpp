@@ -4,11 +4,13 @@
 // every position's stratum; for cdh_glm_set_survival_interval, the second order by (stratum, start) and the two static lookups
 // that turn the scans into the sums over (start, stop]; the scratch of the post-estimation exports (cox_post_layout); and, for
 // cdh_glm_cox_concordance, the concordance order with every event's range of comparable positions, the level arithmetic of the
-// merge sort the counts are read off, and that call's scratch (cox_conc_layout).  No HIP
+// merge sort the counts are read off, and that call's scratch (cox_conc_layout); and, for cdh_glm_cox_score, that call's scratch
+// (cox_score_layout), the pair tiles of its matrix and the regrowth of the group.  No HIP
 // in here: tests/test_cox_plan_host.py, tests/test_cox_strata_plan_host.py, tests/test_cox_interval_plan_host.py,
-// tests/test_cox_efron_plan_host.py, tests/test_cox_post_plan_host.py and tests/test_cox_concordance_plan_host.py compile it with
+// tests/test_cox_efron_plan_host.py, tests/test_cox_post_plan_host.py, tests/test_cox_concordance_plan_host.py and
+// tests/test_cox_score_plan_host.py compile it with
 // g++ (tests/cox_plan_main.cpp, tests/cox_strata_plan_main.cpp, tests/cox_interval_plan_main.cpp, tests/cox_efron_plan_main.cpp,
-// tests/cox_post_plan_main.cpp, tests/cox_concordance_plan_main.cpp).
+// tests/cox_post_plan_main.cpp, tests/cox_concordance_plan_main.cpp, tests/cox_score_plan_main.cpp).
 // cox_kernels.hpp calls these functions and nothing else decides the sizes.
 //
 // The tie groups are kept as TWO int32 vectors, not as head flags: first[s] and last[s] are the first and the last sorted
@@ -127,6 +129,48 @@ struct CoxPostLayout {
 constexpr CoxPostLayout cox_post_layout(int64_t ld) {
     return CoxPostLayout{0, ld, 2 * ld, (2 + kCoxPostCols) * ld, (2 + kCoxPostCols) * ld + 2 * kCoxMaxGrid,
                          (2 + kCoxPostCols) * ld + 2 * kCoxMaxGrid + 1, 0, ld, 2 * ld, 2 * ld + kCoxMaxGrid};
+}
+
+// A handle that was asked for score or Schoenfeld residuals or the information matrix (cdh_glm_cox_score; cox_score.hip) holds a
+// SIXTH pair, allocated whole by the first such call for the m columns it asks for and regrown whole, never shrunk, when a later
+// call asks for more (cox_score_grow); no other call allocates it and no setter needs to drop it: every call fills it again.
+// Doubles: e, ev, h, dvk and wA by sorted position (exp(eta); v e; the hazard term dv / S at an event that counts, else 0; dv at
+// such an event, else 0; ev A), ld each; then per column, ld apart: xt (the centred column in sorted order), N (ev xt, then
+// its suffix scan inside the stratum) and Q (h xbar, then its prefix scan inside the stratum); the runs' sums of the two scans,
+// kCoxMaxGrid per column each; the kCoxScoreMaxCols centres; the two residual outputs, ld m each (stored n apart); the
+// information matrix's partials, kCoxMaxGrid runs x pair tiles x 2 sums x kCoxScorePair^2 entries; and the m x m matrix.
+// int32: the head-seen flags of the runs for the suffix scan and the prefix scan, kCoxMaxGrid each, and the kCoxScoreMaxCols
+// column indices (0-based).
+constexpr int kCoxScoreMaxCols = 64;                      // cdh_vc_gram's cap
+constexpr int kCoxScorePair = 4;                          // the information matrix is computed in pair tiles of 4 x 4 columns
+constexpr int kCoxScoreCentreRuns = 256;                  // workgroups that share a column's rows for its mean; their partials,
+                                                          // kCoxScoreCentreRuns a column, lie at the head of the matrix's partials
+constexpr int64_t cox_score_col_tiles(int64_t m) { return (m + kCoxScorePair - 1) / kCoxScorePair; }
+constexpr int64_t cox_score_pair_tiles(int64_t m) { return cox_score_col_tiles(m) * (cox_score_col_tiles(m) + 1) / 2; }
+// pair tile t of ct column tiles -> its column tiles (ci <= di), row by row of the upper triangle; and back
+struct CoxScorePair { int64_t ci, di; };
+constexpr CoxScorePair cox_score_pair(int64_t ct, int64_t t) {
+    int64_t ci = 0;
+    while (t >= ct - ci) { t -= ct - ci; ++ci; }
+    return CoxScorePair{ci, ci + t};
+}
+constexpr int64_t cox_score_pair_index(int64_t ct, int64_t ci, int64_t di) { return ci * ct - ci * (ci - 1) / 2 + (di - ci); }
+// the columns the group holds room for after a call that asks for m: never fewer than before
+constexpr int64_t cox_score_grow(int64_t have, int64_t m) { return m > have ? m : have; }
+struct CoxScoreLayout {
+    int64_t e, ev, h, dvk, wA, xt, N, Q, sums, mu, out, part, info;   // offsets in doubles; sums + (a m + c) kCoxMaxGrid: scan a
+    int64_t doubles;
+    int64_t heads, idx;                                                // offsets in int32s; heads + a kCoxMaxGrid
+    int64_t ints;
+};
+constexpr CoxScoreLayout cox_score_layout(int64_t ld, int64_t m) {
+    static_assert(kCoxMaxGrid * 2 * kCoxScorePair * kCoxScorePair >= (int64_t)kCoxScoreCentreRuns * kCoxScorePair * 2,
+                  "the partials of the matrix hold the centres' partials: pair tiles >= column tiles / 2, 4 columns a tile");
+    const int64_t xt = 5 * ld, sums = xt + 3 * m * ld, mu = sums + 2 * m * kCoxMaxGrid, out = mu + kCoxScoreMaxCols,
+                  part = out + 2 * m * ld,
+                  info = part + kCoxMaxGrid * cox_score_pair_tiles(m) * 2 * kCoxScorePair * kCoxScorePair;
+    return CoxScoreLayout{0, ld, 2 * ld, 3 * ld, 4 * ld, xt, xt + m * ld, xt + 2 * m * ld, sums, mu, out, part, info,
+                          info + m * m, 0, 2 * kCoxMaxGrid, 2 * kCoxMaxGrid + kCoxScoreMaxCols};
 }
 
 // ---- the time order and its tie groups ---------------------------------------------------------------------------------------

@@ -519,6 +519,36 @@ int32_t cdh_glm_cox_baseline(cdh_handle h, double eta_max, int64_t capacity, int
  * handle unchanged: row shards and whatever else the GLM exports refuse of the handle; no survival data set; k < -1, k >= 0
  * without folds, k >= K; out4 NULL; a handle with start times ("concordance with start-stop times is not offered yet"). */
 int32_t cdh_glm_cox_concordance(cdh_handle h, int32_t k, double *out4);
+/* cdh_glm_cox_score (no reference counterpart; R's residuals(coxph, "score") and "schoenfeld" and the inverse of coxph's
+ * var -- the model is the one whose rounds solve the weighted lasso of cd_differentiable_function.jl:118-194): what standard
+ * errors, robust variances and a check of proportional hazards are made of, for m <= 64 columns idx1 (1-based like cdh_gram;
+ * duplicates allowed: equal columns give equal bits) of the resident design, at the iterate the handle holds, Breslow ties, no
+ * row held out.  With e, ev = v e, dv = v delta, S, h and A as cdh_glm_cox_residuals forms them, xt_c = x_c - centre_c,
+ * N_c the stratum's suffix scan of ev xt_c, xbar_c = N_c / S at the tie group's first position (the risk-set mean) and Q_c
+ * the stratum's prefix scan of h xbar_c read at the group's last position:
+ *   schoenfeld[i, c] = xt_ic - xbar_c    at an event that counts (S > 0), exactly 0 on every other row
+ *   score[i, c]      = delta_i schoenfeld[i, c] - e_i (xt_ic A_i - Q_ic)      R's unweighted score residual; v_i times it is
+ *                      the weighted one, and its column sums over v are the gradient X_c'(dv - ev A)
+ *   info[c, d]       = sum_i ev_i A_i xt_ic xt_id - sum over the events that count of dv xbar_c xbar_d
+ *                      the Hessian of the un-normalised negative log partial likelihood in beta_idx; symmetric by construction
+ * The centres are the columns' unweighted means over the rows, formed on the device in a fixed order, unless
+ * host_centre_or_null gives m of them; host_centre_out_or_null receives the m used.  No output depends on the centres in exact
+ * arithmetic, but info, a difference of two positive semidefinite sums, loses digits without centring.  Each residual output
+ * is n x m doubles, column-major with leading dimension n, in the caller's row order; host_info is m x m.  A NULL output is
+ * skipped.  The call runs the read-only step of cdh_glm_cox_irls (k = -1, apply = 0, its catch-up of r included), then a
+ * fixed number of launches whatever m is: one gather of X per (row, column) through the time order, one segmented suffix scan
+ * and one segmented prefix scan per column, the rows, and the matrix in pair tiles of columns with per-run partials added in
+ * run order.  No atomics: every output is bit-identical run to run, and a column's residuals are the same bits whether it is
+ * asked for alone or in any list.  y, w, r and beta are not touched.  The first call allocates a group of scratch buffers of its
+ * own, all-or-nothing ((5 + 5 m) doubles per row and the partials of the matrix); a later call with a larger m regrows it,
+ * all-or-nothing; a handle that never asks allocates nothing.  CDH_BAD_ARG, the handle unchanged: no survival data set;
+ * eta_max outside (0, 700]; m < 1 or m > 64; idx1 NULL or an index outside 1 .. p; all three outputs NULL; a centre that is
+ * not finite; a handle with start times ("cdh_glm_cox_score is not offered with start-stop times yet"); a handle set to Efron
+ * ties ("cdh_glm_cox_score is not offered with Efron ties yet" -- a handle put back to Breslow is served). */
+int32_t cdh_glm_cox_score(cdh_handle h, double eta_max, int64_t m, const int64_t *idx1,
+                          const double *host_centre_or_null, double *host_centre_out_or_null,
+                          void *host_schoenfeld_or_null, void *host_score_or_null,
+                          double *host_info_or_null);
 /* Which loss the resident X serves from now on.  The reference builds a new loss object around the
  * same matrix for every front-end call (lasso.jl:33,48,71,93,117,245: CDLeastSquaresLoss(y, X),
  * CDSqrtLassoLoss(y, X), CDWeightedLSLoss(y, X, w)); the binding keeps X in HBM across those objects

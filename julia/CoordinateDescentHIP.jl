@@ -692,6 +692,17 @@ function glm_cox_concordance(X::HipMatrix{Float64}, k::Integer=-1)
   (concordant = out[1], discordant = out[2], tied = out[3], comparable = comparable, C = comparable > 0 ? (out[1] + out[3] / 2) / comparable : NaN)
 end
 
+"score residuals (n x m), Schoenfeld residuals (n x m, zero off the events) and the information matrix (m x m) of the Cox model at the iterate the handle holds, for the 1-based columns idx (at most 64), Breslow ties; centre: the columns' centres, or nothing for their means"
+function glm_cox_score(X::HipMatrix{Float64}, idx::Vector{Int64}; centre::Union{Nothing,Vector{Float64}}=nothing, eta_max::Float64=50.0)
+  n, m = size(X, 1), length(idx)
+  sch, score = Matrix{Float64}(undef, n, m), Matrix{Float64}(undef, n, m)
+  info, used = Matrix{Float64}(undef, m, m), Vector{Float64}(undef, m)
+  check(X.handle, ccall((:cdh_glm_cox_score, libcdhip), Int32,
+                        (Ptr{Cvoid}, Float64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}),
+                        X.handle, eta_max, Int64(m), idx, centre === nothing ? C_NULL : centre, used, sch, score, info))
+  (schoenfeld = sch, score = score, info = info, centre = used)
+end
+
 # ---- locpolyl1 with the design expanded on the device (src/varying_coefficient_lasso.jl:30-79) ----------------
 # The reference rebuilds w, expandX and stdX on the host for every z0 (:63-65).  A HipVaryingDesign keeps the base
 # design and z in HBM; cdh_vc_set_point regenerates all three there, and the refit (:71-76) reads its weighted normal
